@@ -37,8 +37,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# one hardware queue per in-flight batch: ROCm's default of 4 would make engine streams share queues
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -99,10 +97,18 @@ def parse():
     ap.add_argument("--extras-gib", type=float, default=None, help="bytes per device batch of the short legs (tests)")
     ap.add_argument("--extras-file-mib", type=float, default=64.0)
     ap.add_argument("--seed", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step as DIR/<name>.npy (float64 / float32; "
+                         "a fixed, seeded sample of rows above 64 MB); ring workloads")
     a = ap.parse_args()
     a.brief = False
     if a.steps is None:
         a.steps = 48 if a.workload == "hostfeed" else 20
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and not a.workload.startswith("ring"):
+        ap.error("--dump-outputs: the ring workloads only (a step of the batch, hostfeed and verify paths is not one fixed "
+                 "set of records)")
     if a.file_mib is None:
         a.file_mib = 1.0 if a.workload == "verify" else 64.0
     return a
@@ -642,6 +648,43 @@ def _copy_args(a, **kw):
     return b
 
 
+DUMP_CAP_BYTES = 64_000_000 - (64 << 10)   # --dump-outputs: 64 MB in all, with room for the .npy headers
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def record_arrays(recs, file_index=None):
+    """What a caller of the ring receives per chunk (pbsgpu_record), as exact floats: end offset and size (float64, exact
+    below 2^53) and the SHA-256 digest bytes (float32, one column per byte); `file_index`: the file of every record."""
+    out = {"records_end": recs["end"].astype(np.float64), "records_size": recs["size"].astype(np.float64),
+           "records_digest": recs["digest"].astype(np.float32)}
+    if file_index is not None:
+        out["records_file"] = np.asarray(file_index, dtype=np.float64)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write `arrays` (float32 / float64, one row per record) as <path>/<name>.npy. Above DUMP_CAP_BYTES in all, the same
+    fixed, seeded sample of rows is taken from every array and its row numbers go to sample_rows.npy. Returns the manifest
+    that goes into the JSON line."""
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v.itemsize * int(np.prod(v.shape[1:], dtype=np.int64)) for v in arrays.values())
+    rows = None
+    if n * row_bytes > DUMP_CAP_BYTES:
+        k = DUMP_CAP_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+        arrays = dict({name: v[rows] for name, v in arrays.items()}, sample_rows=rows.astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    stale = os.path.join(path, "sample_rows.npy")
+    if rows is None and os.path.exists(stale):
+        os.remove(stale)
+    files = {}
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64) and len(v) == len(arrays["records_end"]), name
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v))
+        files[name] = {"dtype": str(v.dtype), "shape": list(v.shape)}
+    return {"dir": path, "records": int(n), "sampled": rows is not None, "files": files}
+
+
 def cu_time_budget(regime):
     """Where the CU-seconds of one GiB go: the pair service's figure is THIS run's (regime probe), scan and refill are static
     (profiles/r06_kernel_trace_bench_default.csv.gz: kernel time x the cut side's 64 CUs / bytes, one box)."""
@@ -686,6 +729,7 @@ def extras(a, rank, local_rank, world, ctx, with_batch=False):
     driver's clock sees them too (each at its full single-GPU shape, a few steps, its own oracle check). A leg that fails
     reports the error instead of taking the headline line down."""
     import copy
+    a = _copy_args(a, dump_outputs=None)
     res = {}
     t_all = time.perf_counter()
     legs = [x.strip() for x in a.extras.split(",") if x.strip()]
@@ -728,9 +772,9 @@ def extras(a, rank, local_rank, world, ctx, with_batch=False):
                          "results": o.get("results"), "leg_seconds": round(time.perf_counter() - t0, 1)}
         except BaseException as exc:  # noqa: BLE001
             res[name] = {"error": repr(exc)}
-    # (The host-fed legs ran last for a reason until round 4: with GPU_MAX_HW_QUEUES=24 a process that had used more than ~20
-    # hardware queues was time-sliced by the hardware scheduler from then on and every later leg lost 20-30 %,
-    # profiles/r03_extras_leg_order.log. With 20 the effect is gone and the order is free.)
+    # (The host-fed legs ran last for a reason until round 4: a process that had used more than ~20 hardware queues was
+    # time-sliced by the hardware scheduler from then on and every later leg lost 20-30 %, profiles/r03_extras_leg_order.log.
+    # The process's queue count is the host's setting; within the scheduler's limit the order is free.)
     for label, key, producers, gib_steps, archives in (("hostfeed_1_writer", "hostfeed1", 1, 96, 1),
                                                        ("hostfeed_1_writer_4_archives", "hostfeed1", 1, 96, 4),
                                                        ("hostfeed_8_writers", "hostfeed8", 8, 32, 1)):
@@ -1151,6 +1195,8 @@ def ring_run(a, rank, local_rank, world, ctx):
         }
         if extra:
             out["results"] = extra
+        if a.dump_outputs:   # the last timed step = the last timed file (its records, whole)
+            out["dump_outputs"] = dump_outputs(a.dump_outputs, record_arrays(kept[state["first_timed"] + a.steps - 1]))
         if not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = ring_cpu_baseline(a, kept, single, file_bytes, kind, seed_of)
     if not a.no_cpu_baseline and world > 1:
@@ -1394,6 +1440,10 @@ def ring_files_run(a, rank, local_rank, world, ctx, mode):
                                          f"their seeds, oracle chunk_and_digest on {len(ths)} threads",
                                "records_match_gpu": bool(res["ok"] and tiles), "records_checked": res["records"],
                                "first_bad_file": res["bad"], "every_file_tiled_by_its_records": bool(tiles)}
+    if a.dump_outputs and rank == 0:   # the last timed step = its files_per_step files, in file order
+        last = range(per_step * (a.steps - 1), per_step * a.steps)
+        out["dump_outputs"] = dump_outputs(a.dump_outputs, record_arrays(
+            np.concatenate([recs_of[g] for g in last]), np.concatenate([np.full(recs_of[g].size, g) for g in last])))
     ring.close()
     eng.close()
     return out

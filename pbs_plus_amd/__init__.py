@@ -13,16 +13,8 @@ pbs-plus reference uses for its pxar stream path:
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
-import os as _os
-
-# The engine overlaps batches on separate HIP streams (up to 16 slots + copy streams); ROCm's default of 4
-# hardware queues would make them share queues, and with 8 two of eight slots still collide (measured: a
-# pair of batches then runs back to back). Must be set before the HIP runtime initialises (import this
-# package first).
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
-
-from . import buzhash  # noqa: F401,E402
-from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401,E402
-from .engine import Chunker, Comm, Engine, PageRing, PayloadStream  # noqa: F401,E402
+from . import buzhash  # noqa: F401
+from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
+from .engine import Chunker, Comm, Engine, PageRing, PayloadStream  # noqa: F401
 
 __all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "RECORD_DTYPE", "PbsGpuError"]

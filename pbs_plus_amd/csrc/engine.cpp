@@ -10,11 +10,8 @@
 #include <cstdio>
 #include <cstdlib>
 
-// The engine runs up to 16 batches on separate HIP streams; ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues
-// (default 4) and reads the variable when the HIP runtime initialises, i.e. at the first HIP call of the process.
-// Setting a default when this library is loaded covers hosts that bind the C ABI directly (cgo, JNI, ctypes)
-// without going through the Python package; an explicit setting of the host always wins.
-__attribute__((constructor)) static void pbsgpu_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "20", 0); }
+// The engine runs up to 16 batches on separate HIP streams; ROCm maps them onto the hardware queues the process may open.
+// That count is the host's setting (GPU_MAX_HW_QUEUES): the library never changes it.
 
 namespace pbse {
 std::atomic<int> g_last_hip_error{0};

@@ -11,7 +11,6 @@ import traceback
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 os.environ.setdefault("PBSGPU_RING_IDLE_TIMEOUT_S", "4")
 
 import numpy as np  # noqa: E402

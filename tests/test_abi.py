@@ -144,25 +144,25 @@ def test_product_never_touches_the_oracle():
     assert not bad, bad
 
 
-def test_library_load_sets_hw_queue_default_but_never_overrides():
-    """libpbsgpu.so's load-time constructor exports GPU_MAX_HW_QUEUES=20 for hosts that bind the C ABI directly
-    (the engine overlaps up to 16 batches on separate HIP streams; ROCm's default of 4 queues serialises them),
-    and leaves an explicit setting of the host alone."""
+def test_library_load_leaves_hw_queue_setting_to_the_host():
+    """The hardware queues a process may open are the host's setting: neither loading libpbsgpu.so (hosts that bind the
+    C ABI directly) nor importing the package sets GPU_MAX_HW_QUEUES, and an explicit setting of the host is kept."""
     import subprocess
     import sys
 
     from pbs_plus_amd._lib import LIB_PATH
 
-    code = ("import ctypes, sys\n"
-            "ctypes.CDLL(%r)\n"
-            "g = ctypes.CDLL(None).getenv; g.restype = ctypes.c_char_p\n"
-            "print((g(b'GPU_MAX_HW_QUEUES') or b'').decode())\n" % LIB_PATH)
+    probe = ("g = ctypes.CDLL(None).getenv; g.restype = ctypes.c_char_p\n"
+             "print(repr(g(b'GPU_MAX_HW_QUEUES')), repr(os.environ.get('GPU_MAX_HW_QUEUES')))\n")
+    codes = {"library": "import ctypes, os\nctypes.CDLL(%r)\n" % LIB_PATH + probe,
+             "package": "import ctypes, os, sys\nsys.path.insert(0, %r)\nimport pbs_plus_amd\n" % ROOT + probe}
     env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-    assert out.stdout.strip() == "20", out.stdout + out.stderr
-    out = subprocess.run([sys.executable, "-c", code], env=dict(env, GPU_MAX_HW_QUEUES="6"), capture_output=True,
-                         text=True, timeout=120)
-    assert out.stdout.strip() == "6", out.stdout + out.stderr
+    for what, code in codes.items():
+        out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0 and out.stdout.strip() == "None None", (what, out.stdout + out.stderr)
+        out = subprocess.run([sys.executable, "-c", code], env=dict(env, GPU_MAX_HW_QUEUES="1"), capture_output=True,
+                             text=True, timeout=120)
+        assert out.returncode == 0 and out.stdout.strip() == "b'1' '1'", (what, out.stdout + out.stderr)
 
 
 def test_option_structs_have_the_layout_the_bindings_assume(L, tmp_path):

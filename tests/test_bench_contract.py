@@ -562,3 +562,85 @@ def test_bench_gpus_flag_spawns_its_own_ranks_and_every_rank_is_checked():
     bad = subprocess.run([sys.executable, "-c", code], env=dict(env, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0"),
                          capture_output=True, text=True, timeout=120)
     assert bad.returncode == 2 and "WORLD_SIZE=3" in bad.stderr
+
+
+def _ring_dump_args(extra=()):
+    return ["--gib", str(24 / 1024), "--avg", "65536", "--steps", "3", "--warmup", "1", "--ring-streams", "2",
+            "--no-cpu-baseline", "--no-extras", *extra]
+
+
+def test_bench_dump_outputs_writes_the_records_of_the_last_step(monkeypatch, tmp_path):
+    """--dump-outputs DIR: after the timed steps, the records of the last timed file (what a caller of the ring receives) as
+    float64 / float32 .npy files, bit for bit the oracle's records of that file's bytes; the same arguments give the same
+    files, so two builds can be compared output for output."""
+    from oracle import oracle as O
+
+    _patch(monkeypatch)
+    d = _run(monkeypatch, _ring_dump_args(["--dump-outputs", str(tmp_path / "a")]))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    m = d["dump_outputs"]
+    assert m["sampled"] is False and set(m["files"]) == {"records_end", "records_size", "records_digest"}
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in m["files"]}
+    assert got["records_end"].dtype == np.float64 and got["records_size"].dtype == np.float64
+    assert got["records_digest"].dtype == np.float32 and got["records_digest"].shape == (m["records"], 32)
+    # the last timed file: warm-up file 0, timed files 1..3; bench.py's seed_of(3) on rank 0, generator kind 4
+    n = (24 << 20) & ~15
+    want = O.chunk_and_digest(O.new_config(65536), O.fill(n, 2 + 7919 * 3, 4), [(0, n)])
+    assert m["records"] == want.size > 100
+    assert np.array_equal(got["records_end"], want["end"].astype(np.float64))
+    assert np.array_equal(got["records_size"], want["size"].astype(np.float64))
+    assert np.array_equal(got["records_digest"], want["digest"].astype(np.float32))
+    d2 = _run(monkeypatch, _ring_dump_args(["--dump-outputs", str(tmp_path / "b")]))
+    assert d2["dump_outputs"]["files"] == m["files"]
+    for k in m["files"]:
+        assert (tmp_path / "a" / (k + ".npy")).read_bytes() == (tmp_path / "b" / (k + ".npy")).read_bytes(), k
+
+
+def test_bench_dump_outputs_samples_rows_above_the_cap(monkeypatch, tmp_path):
+    """Above the size cap every array keeps the same fixed, seeded sample of rows, and the rows go to sample_rows.npy."""
+    import bench
+
+    _patch(monkeypatch)
+    _run(monkeypatch, _ring_dump_args(["--dump-outputs", str(tmp_path / "full")]))
+    full = {k: np.load(tmp_path / "full" / (k + ".npy")) for k in ("records_end", "records_size", "records_digest")}
+    cap = 40 * (8 + 8 + 128 + 8)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", cap)
+    m = _run(monkeypatch, _ring_dump_args(["--dump-outputs", str(tmp_path / "s")]))["dump_outputs"]
+    assert m["sampled"] is True and m["records"] == full["records_end"].size
+    rows = np.load(tmp_path / "s" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and rows.size == 40 and np.all(np.diff(rows) > 0)
+    total = 0
+    for k, v in full.items():
+        s = np.load(tmp_path / "s" / (k + ".npy"))
+        assert np.array_equal(s, v[rows.astype(np.int64)]), k
+        total += s.nbytes
+    assert total + rows.nbytes <= cap
+    m2 = _run(monkeypatch, _ring_dump_args(["--dump-outputs", str(tmp_path / "s2")]))["dump_outputs"]
+    assert m2 == dict(m, dir=str(tmp_path / "s2"))
+    assert np.array_equal(np.load(tmp_path / "s2" / "sample_rows.npy"), rows)
+
+
+def test_bench_dump_outputs_of_the_many_file_ring_workload(monkeypatch, tmp_path):
+    """ring_manyfiles: the last timed step is files_per_step files; their records in file order, with the file of each."""
+    _patch(monkeypatch)
+    d = _run(monkeypatch, ["--workload", "ring_manyfiles", "--gib", str(12 / 1024), "--file-mib", "0.5", "--avg", "16384",
+                           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
+    per_step = d["config"]["files_per_step"]
+    f = np.load(tmp_path / "records_file.npy")
+    end = np.load(tmp_path / "records_end.npy")
+    size = np.load(tmp_path / "records_size.npy")
+    assert set(np.unique(f).astype(int)) == set(range(per_step, 2 * per_step)) and np.all(np.diff(f) >= 0)
+    for g in range(per_step, 2 * per_step):       # every file of the step tiled by its records
+        assert end[f == g][-1] == 512 << 10 and size[f == g].sum() == 512 << 10
+
+
+@pytest.mark.parametrize("argv", [["--workload", "stream64g", "--dump-outputs", "x"], ["--steps", "0"]])
+def test_bench_rejects_what_it_cannot_honour(monkeypatch, argv):
+    """--steps is the number of timed steps (at least one); --dump-outputs is for the ring workloads, whose step is one fixed
+    set of records."""
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.parse()
+    assert e.value.code == 2
