@@ -146,3 +146,13 @@ func (r *Ring) Stats() (RingStats, error)                                       
 func (r *Ring) Express() (uint32, uint64, error)                                 { return 0, 0, ErrNotBuilt }
 func (r *Ring) Probe() (RingProbe, error)                                        { return RingProbe{}, ErrNotBuilt }
 func (r *Ring) Close()                                                           {}
+
+// KnownChunks is the known-chunk set of an incremental session.
+type KnownChunks struct{}
+
+func (e *Engine) NewKnownChunks(uint64) (*KnownChunks, error)                 { return nil, ErrNotBuilt }
+func (k *KnownChunks) Add([]ChunkInfo) error                                  { return ErrNotBuilt }
+func (k *KnownChunks) AddDynamicIndex([]byte) error                           { return ErrNotBuilt }
+func (k *KnownChunks) Classify([]ChunkInfo, bool) ([]bool, DedupStats, error) { return nil, DedupStats{}, ErrNotBuilt }
+func (k *KnownChunks) Len() int                                               { return 0 }
+func (k *KnownChunks) Close()                                                 {}

@@ -963,6 +963,92 @@ func (c *Comm) Close() {
 	c.eng = nil
 }
 
+// ---- known-chunk set (incremental dedup) --------------------------------------------------------------------------
+
+// KnownChunks is the device-resident known-chunk set of an incremental session (pbsgpu_known_*): the digests of the
+// previous snapshot's indexes (PreviousBackup, internal/pxarmount/commit_orchestrate.go:127-158) plus every chunk already
+// sent or injected (InjectChunks refs, commit_reuse.go:315-341). Classify says, per polled record, whether the server
+// already has the chunk; only the rest is uploaded. The set keeps its engine alive; one goroutine per set at a time.
+type KnownChunks struct {
+	h   *C.pbsgpu_known
+	eng *Engine
+}
+
+// NewKnownChunks creates an empty set sized for `capacity` digests (0 = default); it grows by itself.
+func (e *Engine) NewKnownChunks(capacity uint64) (*KnownChunks, error) {
+	defer runtime.KeepAlive(e)
+	k := &KnownChunks{eng: e}
+	if err := check(C.pbsgpu_known_create(e.h, C.uint64_t(capacity), &k.h), "known_create"); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(k, (*KnownChunks).Close)
+	return k, nil
+}
+
+// Add inserts every digest of recs (idempotent).
+func (k *KnownChunks) Add(recs []ChunkInfo) error {
+	defer runtime.KeepAlive(k)
+	if len(recs) == 0 {
+		return nil
+	}
+	cr := toRecords(recs)
+	return check(C.pbsgpu_known_add_host(k.h, &cr[0], C.uint64_t(len(cr))), "known_add_host")
+}
+
+// AddDynamicIndex inserts the digests of a .didx image (a previous snapshot's .mpxar.didx / .ppxar.didx). It validates
+// what ParseDynamicIndex validates and, like it, does not verify the index checksum.
+func (k *KnownChunks) AddDynamicIndex(blob []byte) error {
+	defer runtime.KeepAlive(k)
+	if len(blob) == 0 {
+		return errors.New("pbsgpu: empty index")
+	}
+	return check(C.pbsgpu_known_add_didx(k.h, (*C.uint8_t)(unsafe.Pointer(&blob[0])), C.uint64_t(len(blob))), "known_add_didx")
+}
+
+// Classify reports known[i] = true when the set held the digest of recs[i] or an earlier record of this call carries it;
+// false marks the first occurrence of a new chunk (upload it). With insert, the new digests are in the set afterwards.
+// Stats: Records / TotalBytes over all records, Unique / UniqueBytes over the new ones.
+func (k *KnownChunks) Classify(recs []ChunkInfo, insert bool) ([]bool, DedupStats, error) {
+	defer runtime.KeepAlive(k)
+	if len(recs) == 0 {
+		return nil, DedupStats{}, nil
+	}
+	cr := toRecords(recs)
+	flags := make([]C.uint8_t, len(recs))
+	ins := C.int(0)
+	if insert {
+		ins = 1
+	}
+	var st C.pbsgpu_dedup_stats
+	if err := check(C.pbsgpu_known_classify_host(k.h, &cr[0], C.uint64_t(len(cr)), ins, &flags[0], &st), "known_classify_host"); err != nil {
+		return nil, DedupStats{}, err
+	}
+	out := make([]bool, len(recs))
+	for i := range out {
+		out[i] = flags[i] != 0
+	}
+	return out, DedupStats{uint64(st.nrecords), uint64(st.nunique), uint64(st.total_bytes), uint64(st.unique_bytes)}, nil
+}
+
+// Len is the number of digests in the set.
+func (k *KnownChunks) Len() int {
+	defer runtime.KeepAlive(k)
+	var n C.uint64_t
+	if C.pbsgpu_known_count(k.h, &n) != C.PBSGPU_OK {
+		return 0
+	}
+	return int(n)
+}
+
+func (k *KnownChunks) Close() {
+	runtime.SetFinalizer(k, nil)
+	if k.h != nil {
+		C.pbsgpu_known_destroy(k.h)
+		k.h = nil
+	}
+	k.eng = nil
+}
+
 // DedupDevice flags duplicates among n records that already are in device memory (the receive buffer of an RCCL
 // all-gather): the digest-set reduce without a host round trip of the set.
 func (e *Engine) DedupDevice(drecs uintptr, n uint64) ([]bool, DedupStats, error) {

@@ -495,6 +495,39 @@ int pbsgpu_dedup_host(pbsgpu_engine *eng, const pbsgpu_record *recs, uint64_t n,
 int pbsgpu_dedup_device(pbsgpu_engine *eng, const void *drecs, uint64_t n, uint8_t *dup /* n, may be NULL */,
                         pbsgpu_dedup_stats *stats);
 
+/* ---- known-chunk set (incremental dedup) ---------------------------------------------
+ * The "known-chunk check" of the writer's inner loop (scan -> cut -> SHA-256 -> known-chunk check ->
+ * upload -> DIDX append). A session starts from the previous snapshot's indexes (PreviousBackup,
+ * commit_orchestrate.go:127-158): every digest in them, and every chunk already sent in this session, is known; only the
+ * rest is uploaded, and InjectChunks refs (commit_reuse.go:315-341) are known by construction. The set lives in device
+ * memory (a hash table the library grows by itself, load factor <= 1/2: 80-160 bytes per digest) and keeps its engine alive.
+ * One thread per set at a time (the engine's rule); different sets may be used concurrently. A classify call beside a
+ * running page-ring service does not wait for the service: its work runs on a leased stream of the engine.
+ * Limits: n < 2^32 per call; the set holds fewer than 2^32 digests (PBSGPU_E_CAPACITY on an insert that would reach it). */
+#define PBSGPU_HAS_KNOWN_SET 1
+typedef struct pbsgpu_known pbsgpu_known;
+/* `capacity` = digests expected (0 = default, 64 Ki); only sizes the first table, the set grows past it. */
+int pbsgpu_known_create(pbsgpu_engine *eng, uint64_t capacity, pbsgpu_known **out);
+void pbsgpu_known_destroy(pbsgpu_known *k); /* NULL: no-op */
+int pbsgpu_known_count(const pbsgpu_known *k, uint64_t *n);
+/* Insert every digest (idempotent): a previous snapshot's index, InjectChunks refs. Growth that fails to allocate
+ * returns PBSGPU_E_NOMEM and leaves the set exactly as it was. */
+int pbsgpu_known_add_host(pbsgpu_known *k, const pbsgpu_record *recs, uint64_t n);
+int pbsgpu_known_add_device(pbsgpu_known *k, const void *drecs, uint64_t n); /* device records, 8-byte aligned */
+/* The digests of a .didx image (datastore.ParseDynamicIndex, commit_orchestrate.go:127-158). Validates exactly what
+ * pbsgpu_didx_decode validates — magic, body a multiple of 40 bytes, ascending ends — and, like it, does NOT verify the
+ * index checksum. */
+int pbsgpu_known_add_didx(pbsgpu_known *k, const uint8_t *didx, uint64_t nbytes);
+/* known[i] = 1 when the digest of record i was in the set before the call, or an earlier record of the SAME call (j < i)
+ * carries it; 0 = new (the first occurrence of a digest the set lacked: the chunk to upload). insert != 0: every new
+ * digest is in the set afterwards; insert = 0: the set is unchanged. Exact (all 32 bytes) and deterministic.
+ * stats: nrecords / total_bytes over all records, nunique / unique_bytes over the new ones. `known` (host) may be NULL. */
+int pbsgpu_known_classify_host(pbsgpu_known *k, const pbsgpu_record *recs, uint64_t n, int insert,
+                               uint8_t *known /* n, may be NULL */, pbsgpu_dedup_stats *stats);
+/* The same on records in device memory (e.g. what a ring delivered into a device buffer); a host pointer: E_INVALID. */
+int pbsgpu_known_classify_device(pbsgpu_known *k, const void *drecs, uint64_t n, int insert,
+                                 uint8_t *known /* host, n, may be NULL */, pbsgpu_dedup_stats *stats);
+
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or
  * several engines in one process) ingests its own streams. The one exchange step is the digest-set reduce for cross-file

@@ -85,6 +85,70 @@ struct KnownChunkRef {
     uint64_t Size = 0;
 };
 
+// The known-chunk set of an incremental session (pbsgpu_known_*, device resident): the digests of the previous
+// snapshot's indexes (PreviousBackup, commit_orchestrate.go:127-158) plus every chunk already sent or injected
+// (InjectChunks refs, commit_reuse.go:315-341). Classify flags, per record, the chunks the server already has; the rest
+// is uploaded. Keeps its engine alive; one thread per set at a time.
+class KnownChunks {
+  public:
+    static Result<std::unique_ptr<KnownChunks>> New(pbsgpu_engine *eng, uint64_t capacity = 0) {
+        Result<std::unique_ptr<KnownChunks>> r;
+        pbsgpu_known *k = nullptr;
+        const int st = pbsgpu_known_create(eng, capacity, &k);
+        if (st != PBSGPU_OK) {
+            r.err = errorf("known chunks", st);
+            return r;
+        }
+        r.value.reset(new KnownChunks(k));
+        return r;
+    }
+    ~KnownChunks() { pbsgpu_known_destroy(k_); }
+    KnownChunks(const KnownChunks &) = delete;
+    KnownChunks &operator=(const KnownChunks &) = delete;
+
+    std::string Add(const std::vector<KnownChunkRef> &refs) {
+        std::vector<pbsgpu_record> recs(refs.size());
+        for (size_t i = 0; i < refs.size(); ++i) {
+            std::memcpy(recs[i].digest, refs[i].Digest_.data(), 32);
+            recs[i].size = (uint32_t)refs[i].Size;
+        }
+        return AddRecords(recs);
+    }
+    std::string AddRecords(const std::vector<pbsgpu_record> &recs) {
+        const int st = pbsgpu_known_add_host(k_, recs.data(), recs.size());
+        return st == PBSGPU_OK ? std::string() : errorf("known chunks add", st);
+    }
+    // the bytes of a previous snapshot's .didx (validated as ParseDynamicIndex does; the index checksum is not verified)
+    std::string AddDynamicIndex(const std::vector<uint8_t> &didx) {
+        const int st = pbsgpu_known_add_didx(k_, didx.data(), didx.size());
+        return st == PBSGPU_OK ? std::string() : errorf("known chunks add dynamic index", st);
+    }
+    // known[i]: the set held the digest, or an earlier record of this call carries it; false = upload this chunk
+    Result<std::vector<bool>> Classify(const std::vector<pbsgpu_record> &recs, bool insert,
+                                       pbsgpu_dedup_stats *stats = nullptr) {
+        Result<std::vector<bool>> r;
+        std::vector<uint8_t> flags(recs.size());
+        pbsgpu_dedup_stats st{};
+        const int s = pbsgpu_known_classify_host(k_, recs.data(), recs.size(), insert ? 1 : 0, flags.data(), &st);
+        if (s != PBSGPU_OK) {
+            r.err = errorf("known chunks classify", s);
+            return r;
+        }
+        if (stats) *stats = st;
+        r.value.assign(flags.begin(), flags.end());
+        return r;
+    }
+    uint64_t Len() const {
+        uint64_t n = 0;
+        pbsgpu_known_count(k_, &n);
+        return n;
+    }
+
+  private:
+    explicit KnownChunks(pbsgpu_known *k) : k_(k) {}
+    pbsgpu_known *k_;
+};
+
 // datastore.DynamicIndexReader
 class DynamicIndexReader {
   public:

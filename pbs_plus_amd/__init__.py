@@ -10,11 +10,12 @@ pbs-plus reference uses for its pxar stream path:
 * ``PageRing`` — many streams, page-granular memory release, persistent SHA-256 service
 * ``Chunker`` — upstream-style ``scan`` compatibility
 * ``didx`` / ``dedup`` / ``Comm`` — dynamic index records and the cross-GPU digest-set reduce (RCCL, behind the C ABI)
+* ``KnownChunks`` — the device-resident known-chunk set of an incremental session (which chunks to upload)
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
 from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
-from .engine import Chunker, Comm, Engine, PageRing, PayloadStream  # noqa: F401
+from .engine import Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
 
-__all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "RECORD_DTYPE", "PbsGpuError"]
+__all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError"]

@@ -209,6 +209,14 @@ SYMBOLS = {
     "pbsgpu_xxh3_many_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
     "pbsgpu_dedup_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(DedupStats)]),
     "pbsgpu_dedup_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.POINTER(DedupStats)]),
+    "pbsgpu_known_create": (C.c_int, [_P, C.c_uint64, C.POINTER(_P)]),
+    "pbsgpu_known_destroy": (None, [_P]),
+    "pbsgpu_known_count": (C.c_int, [_P, _U64P]),
+    "pbsgpu_known_add_host": (C.c_int, [_P, _P, C.c_uint64]),
+    "pbsgpu_known_add_device": (C.c_int, [_P, _P, C.c_uint64]),
+    "pbsgpu_known_add_didx": (C.c_int, [_P, _P, C.c_uint64]),
+    "pbsgpu_known_classify_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.POINTER(DedupStats)]),
+    "pbsgpu_known_classify_device": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.POINTER(DedupStats)]),
     "pbsgpu_comm_unique_id": (C.c_int, [_P]),
     "pbsgpu_comm_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "pbsgpu_comm_destroy": (None, [_P]),

@@ -310,6 +310,76 @@ def didx_decode(blob: bytes):
     return out[: n.value], ct.value, bytes(cs)
 
 
+class KnownChunks:
+    """Device-resident known-chunk set of an incremental session (pbsgpu_known_*): the previous snapshot's digests
+    (PreviousBackup, commit_orchestrate.go:127-158) plus every chunk sent so far. ``classify`` says per record whether
+    the server already has the chunk (1) or it is the first occurrence of a new one (0: upload it). The set keeps its
+    engine alive; one thread per set at a time."""
+
+    def __init__(self, eng: Engine, capacity: int = 0):
+        self._eng = eng
+        self._L = eng._L
+        h = C.c_void_p()
+        check(self._L.pbsgpu_known_create(eng._h, int(capacity), C.byref(h)), "known_create")
+        self._h = h
+
+    def add(self, records: np.ndarray) -> None:
+        """Insert every digest (idempotent)."""
+        recs = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        check(self._L.pbsgpu_known_add_host(self._h, recs.ctypes.data if recs.size else None, recs.size), "known_add_host")
+
+    def add_device(self, dptr: int, n: int) -> None:
+        """add() on n records in device memory."""
+        check(self._L.pbsgpu_known_add_device(self._h, int(dptr) if n else None, int(n)), "known_add_device")
+
+    def add_didx(self, blob: bytes) -> None:
+        """Insert the digests of a .didx image (its index checksum is not verified)."""
+        a = np.frombuffer(blob, dtype=np.uint8)
+        check(self._L.pbsgpu_known_add_didx(self._h, a.ctypes.data, a.size), "known_add_didx")
+
+    def classify(self, records: np.ndarray, insert: bool = True, want_flags: bool = True):
+        """(known flags, stats): known[i] = 1 when the set held the digest or an earlier record of this call carries it.
+        stats as Engine.dedup(), with nunique / unique_bytes counting the new records."""
+        recs = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+        known = np.zeros(max(recs.size, 1), dtype=np.uint8) if want_flags else None
+        st = _lib.DedupStats()
+        check(self._L.pbsgpu_known_classify_host(self._h, recs.ctypes.data if recs.size else None, recs.size, int(insert),
+                                                 known.ctypes.data if want_flags else None, C.byref(st)),
+              "known_classify_host")
+        return (known[: recs.size] if want_flags else None), {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
+
+    def classify_device(self, dptr: int, n: int, insert: bool = True, want_flags: bool = True):
+        """classify() on n records in device memory."""
+        known = np.zeros(max(n, 1), dtype=np.uint8) if want_flags else None
+        st = _lib.DedupStats()
+        check(self._L.pbsgpu_known_classify_device(self._h, int(dptr) if n else None, int(n), int(insert),
+                                                   known.ctypes.data if want_flags else None, C.byref(st)),
+              "known_classify_device")
+        return (known[:n] if want_flags else None), {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
+
+    def __len__(self) -> int:
+        n = C.c_uint64()
+        check(self._L.pbsgpu_known_count(self._h, C.byref(n)), "known_count")
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pbsgpu_known_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class PayloadStream:
     """The payload-stream seam ``WriteEntryReader`` feeds (transfer.ArchiveWriter,
     internal/pxarmount/commit_test.go:33-67): append bytes, get (end, digest) records."""
