@@ -221,9 +221,35 @@ struct alignas(64) RingCtl {   // device memory, one 64-byte line
     uint32_t pad[4];
 };
 static_assert(sizeof(RingCtl) == 64, "RingCtl is one 64-byte line");
+// A queue position of the ring (RingSource::desc, ldesc, sdesc) holds one chunk's descriptor, 2 x uint4:
+// {p1.lo, p1.hi, len, len1} {p2v.lo, p2v.hi, cell, pages}. p1 = address of the chunk's first byte; the chunk's bytes from
+// len1 on lie in a second physical page, chunk byte `off` at p2v + off (p2v = p1 for a chunk in one page); cell = its record
+// cell; pages = the physical pages it holds a reference on (low and high 16 bits, 0xffff = none).
+struct RingDesc {
+    uint64_t p1, p2v;
+    uint32_t len, len1, cell, pages;
+};
+__host__ __device__ inline void ring_desc_encode(uint4 *q, const uint32_t slot, const RingDesc &d) {
+    q[2u * slot] = make_uint4((uint32_t)d.p1, (uint32_t)(d.p1 >> 32), d.len, d.len1);
+    q[2u * slot + 1u] = make_uint4((uint32_t)d.p2v, (uint32_t)(d.p2v >> 32), d.cell, d.pages);
+}
+__host__ __device__ inline RingDesc ring_desc_decode(const uint4 e0, const uint4 e1) {
+    return RingDesc{((uint64_t)e0.y << 32) | e0.x, ((uint64_t)e1.y << 32) | e1.x, e0.z, e0.w, e1.z, e1.w};
+}
+
+// A 64-byte record cell (RingSource::cells, mapped pinned), in 32-bit words. The cut side writes end, segment, size and the
+// tier tag; a SHA-256 service writes the digest and then raises the flag; the host copies the first 48 bytes out as a
+// pbsgpu_record once the flag is up.
+constexpr uint32_t kCellBytes = 64;
+enum : uint32_t { kCellEnd = 0, kCellDigest = 2, kCellSegment = 10, kCellSize = 11, kCellFlag = 12, kCellTier = 13 };
+static_assert(offsetof(pbsgpu_record, end) == 4 * kCellEnd && offsetof(pbsgpu_record, digest) == 4 * kCellDigest &&
+                  offsetof(pbsgpu_record, segment) == 4 * kCellSegment && offsetof(pbsgpu_record, size) == 4 * kCellSize,
+              "a record cell starts with a pbsgpu_record");
+static_assert(sizeof(pbsgpu_record) == 4 * kCellFlag, "the cell's flag sits right behind its record, at byte 48");
+
 struct RingSource {
     static constexpr bool kRing = true;
-    const uint4 *desc;         // ring of positions, 2 x uint4 each: {p1.lo, p1.hi, len, len1} {p2v.lo, p2v.hi, cell, pages}
+    const uint4 *desc;         // ring of positions, 2 x uint4 each (RingDesc)
     uint32_t qmask;            // positions - 1 (power of two)
     // Which regime did a run land in? ONE producer wave of each service (workgroup 0, first producer) samples clock64() (the
     // shader clock) and wall_clock64() (100 MHz) once per kRingProbeSteps block steps and, if it carried a block in EVERY step
@@ -249,7 +275,7 @@ struct RingSource {
     uint32_t short_bytes;      // 0 = no lanes service
     uint32_t short_room;
     RingCtl *ctl;
-    uint8_t *cells;            // mapped pinned: 64-byte record cells {end, digest[32], segment, size, flag, pad}
+    uint8_t *cells;            // mapped pinned: 64-byte record cells (kCell*)
     uint32_t *pending;         // per physical page: chunks not yet loaded + holds of open chunks
     unsigned long long *free_fifo;  // mapped pinned: (sequence << 32) | page
     uint32_t free_mask;

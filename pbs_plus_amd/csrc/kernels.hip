@@ -1246,6 +1246,113 @@ __device__ __forceinline__ void ring_probe_step(const RingSource &src, RingProbe
     pb.w0 = w;
 }
 
+// ---- the queue protocol the services share with the cut side (k_ring_control) and the host (ring.cpp) --------------------
+// Every helper is called with the same arguments in every lane of a wave (per-lane values go in as predicates).
+// * Queue words are read RELAXED at device scope: a poll must not invalidate the cache. Only a lane that goes on to read
+//   what a position holds pays ONE acquire fence, behind which the descriptor and the chunk's bytes (written by other
+//   kernels while the service runs) are visible; the cut side publishes a tail with release.
+// * A page reference is dropped with RELEASE once the chunk's last block is in registers: every load of the chunk has
+//   completed before the page can go back to the host and be refilled.
+// * The record cell's flag and the free-page FIFO live in mapped pinned memory the host polls: system scope, and the
+//   digest is fenced out (system) before its flag.
+
+// rank of this lane among the lanes of m
+__device__ __forceinline__ uint32_t wave_rank(const unsigned long long m, const int lane) {
+    return (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// batch queue: the wave's leader claims n positions with one atomicAdd; the first of them, in every lane
+__device__ __forceinline__ uint32_t wave_claim(uint32_t *queue, const unsigned long long m, const uint32_t n, const int lane) {
+    uint32_t first = 0;
+    const int leader = __ffsll((long long)m) - 1;
+    if (lane == leader) first = atomicAdd(queue, n);
+    return __shfl(first, leader, 64);
+}
+
+// published, not yet taken positions of a compare-and-swap queue word {tail, head} (RingCtl::lq, sq), and its head
+__device__ __forceinline__ int32_t ring_queue_avail(const unsigned long long *q, uint32_t &head) {
+    const unsigned long long v = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    head = (uint32_t)(v >> 32);
+    return (int32_t)((uint32_t)v - head);
+}
+
+// Compare-and-swap claim on such a queue: the leader of the lanes in m moves `head` from h to h + cnt, and only over published
+// positions (0 < cnt <= what ring_queue_avail saw), so no lane ever waits at a position of this queue. Returns the first position
+// claimed, in every lane; ~0u when another wave moved `head` first (nothing claimed: look again next time). The lane of rank i
+// in m (i < cnt) owns position first + i. (`h` by reference: as a by-value argument it would tell the optimiser that the
+// queue word is never undef, which drops a freeze and moves the pair service's long-queue test from scalar to vector code.)
+__device__ __forceinline__ uint32_t ring_cas_claim(uint32_t *head, const uint32_t &h, const uint32_t cnt, const unsigned long long m,
+                                                   const int lane) {
+    const int leader = __ffsll((long long)m) - 1;
+    uint32_t first = 0xffffffffu;
+    if (lane == leader && atomicCAS(head, h, h + cnt) == h) first = h;
+    first = __shfl(first, leader, 64);
+    if (first != 0xffffffffu) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return first;
+}
+
+// the descriptor at queue slot `slot`, loaded by the lanes of `pred` only (zero elsewhere)
+__device__ __forceinline__ void ring_desc_load(const uint4 *q, const uint32_t slot, const bool pred, uint4 &e0, uint4 &e1) {
+    e0 = make_uint4(0, 0, 0, 0);
+    e1 = make_uint4(0, 0, 0, 0);
+    if (pred) {
+        e0 = q[2u * slot];
+        e1 = q[2u * slot + 1u];
+    }
+}
+
+// lanes of `take` make the descriptor their chunk: both piece addresses, length, first-piece length, digest destination in
+// the record cell, page references. (Selects, not conditional stores: two flags set in sibling branches get their stores
+// merged through a selected pointer by the optimiser, which moves both into scratch memory.)
+__device__ __forceinline__ void ring_desc_take(const RingSource &src, const bool take, const uint4 e0, const uint4 e1,
+                                               const uint8_t *&base, const uint8_t *&base2, uint64_t &len, uint32_t &len1,
+                                               uint8_t *&dst, uint32_t &pages) {
+    const RingDesc d = ring_desc_decode(e0, e1);
+    base = take ? reinterpret_cast<const uint8_t *>(d.p1) : base;
+    base2 = take ? reinterpret_cast<const uint8_t *>(d.p2v) : base2;
+    len = take ? (uint64_t)d.len : len;
+    len1 = take ? d.len1 : len1;
+    dst = take ? src.cells + (uint64_t)d.cell * kCellBytes + 4u * kCellDigest : dst;
+    pages = take ? d.pages : pages;
+}
+
+// `stop` is raised (release) behind the last publish of every queue. Once a lane has seen it (relaxed), the queue word q is
+// looked at once more behind an acquire fence: true = q is empty as well, the lane may leave. No lane leaves while positions
+// are unclaimed.
+__device__ __forceinline__ bool ring_drained_after_stop(const unsigned long long *q) {
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    uint32_t h;
+    return ring_queue_avail(q, h) <= 0;
+}
+__device__ __forceinline__ bool ring_stop_raised(const RingSource &src) {
+    return (uint32_t)(__hip_atomic_load(&src.ctl->tail_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) != 0u;
+}
+
+// a page has no reference left: hand it to the host through the free FIFO ((sequence << 32) | page)
+__device__ __forceinline__ void ring_report_free(const RingSource &q, const uint32_t page) {
+    const uint32_t fs = atomicAdd(&q.ctl->free_count, 1u);
+    __hip_atomic_store(&q.free_fifo[fs & q.free_mask], ((unsigned long long)(fs + 1u) << 32) | page, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// drop one reference on a page; whoever brings it to zero reports it free
+__device__ __forceinline__ void ring_release_page(const RingSource &q, const uint32_t page) {
+    if (__hip_atomic_fetch_sub(&q.pending[page], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) == 1u) ring_report_free(q, page);
+}
+// ... the references of a chunk (RingDesc::pages)
+__device__ __forceinline__ void ring_release_pages(const RingSource &q, const uint32_t pages) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const uint32_t pi = h ? (pages >> 16) : (pages & 0xffffu);
+        if (pi != 0xffffu) ring_release_page(q, pi);
+    }
+}
+
+// the digest is in the record cell (dst = its digest words): raise the cell's flag behind it
+__device__ __forceinline__ void ring_cell_publish(PBSK_GLOBAL uint32_t *dst) {
+    __threadfence_system();
+    __hip_atomic_store(dst + (kCellFlag - kCellDigest), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // Each lane streams one byte range through SHA-256. Per loop trip every busy lane consumes
 // one 64-byte block: the raw dwords of the NEXT block are requested before the current
 // block is compressed, so the HBM/L2 latency of a lane's private stream hides behind the
@@ -1303,12 +1410,9 @@ __global__ __launch_bounds__(64) void k_sha256(Source src, const uint32_t *nitem
     auto acquire = [&](bool need) {
         const unsigned long long m = __ballot(need);
         if (m == 0) return;
-        uint32_t first = 0;
-        const int leader = __ffsll((long long)m) - 1;
-        if (lane == leader) first = atomicAdd(queue, (uint32_t)__popcll(m));
-        first = __shfl(first, leader, 64);
+        const uint32_t first = wave_claim(queue, m, (uint32_t)__popcll(m), lane);
         if (need) {
-            const uint32_t i = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t i = first + wave_rank(m, lane);
             if (i < nitems) {
                 src.get(i, base, len, dst);
                 blk = 0;
@@ -1384,44 +1488,24 @@ __global__ __launch_bounds__(512) void k_sha256_lanes(RingSource src) {
     auto acquire = [&](bool need) {
         if (__ballot(need) == 0) return;
         if (__ballot(have) != 0 && ((++poll_ctr) & src.poll_mask) != 0u) return;
-        const unsigned long long sq = __hip_atomic_load(&src.ctl->sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t st = (uint32_t)sq, sh = (uint32_t)(sq >> 32);
-        const int32_t avail = (int32_t)(st - sh);
+        uint32_t sh;
+        const int32_t avail = ring_queue_avail(&src.ctl->sq, sh);
         const unsigned long long mn = __ballot(need);
         if (avail > 0) {
             const uint32_t cnt = min((uint32_t)__popcll(mn), (uint32_t)avail);
-            const int leader = __ffsll((long long)mn) - 1;
-            uint32_t got0 = 0xffffffffu;
-            if (lane == leader && atomicCAS(&src.ctl->shead, sh, sh + cnt) == sh) got0 = sh;
-            got0 = __shfl(got0, leader, 64);
-            if (got0 != 0xffffffffu) {
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                const uint32_t rank = (uint32_t)__popcll(mn & ((1ull << lane) - 1ull));
+            const uint32_t first = ring_cas_claim(&src.ctl->shead, sh, cnt, mn, lane);
+            if (first != 0xffffffffu) {
+                const uint32_t rank = wave_rank(mn, lane);
                 const bool got = need && rank < cnt;
-                uint4 e0 = make_uint4(0, 0, 0, 0), e1 = make_uint4(0, 0, 0, 0);
-                if (got) {
-                    e0 = src.sdesc[2u * ((got0 + rank) & src.smask)];
-                    e1 = src.sdesc[2u * ((got0 + rank) & src.smask) + 1u];
-                }
-                base = got ? reinterpret_cast<const uint8_t *>(((uint64_t)e0.y << 32) | e0.x) : base;
-                base2 = got ? reinterpret_cast<const uint8_t *>(((uint64_t)e1.y << 32) | e1.x) : base2;
-                len = got ? (uint64_t)e0.z : len;
-                len1 = got ? e0.w : len1;
-                dst = got ? src.cells + (uint64_t)e1.z * 64u + 8u : dst;
-                pages = got ? e1.w : pages;
+                uint4 e0, e1;
+                ring_desc_load(src.sdesc, (first + rank) & src.smask, got, e0, e1);
+                ring_desc_take(src, got, e0, e1, base, base2, len, len1, dst, pages);
                 blk = got ? 0ull : blk;
                 nblk = got ? ((uint64_t)e0.z + 8u) / 64u + 1u : nblk;
                 have = have | got;
             }
-        } else {
-            // nothing published: has the service been told to stop? (stop is raised behind the last publish; the queue is looked
-            // at again behind the fence, so no lane leaves while short chunks are unclaimed)
-            const unsigned long long ts = __hip_atomic_load(&src.ctl->tail_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((uint32_t)(ts >> 32) != 0u) {
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                const unsigned long long sq2 = __hip_atomic_load(&src.ctl->sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((int32_t)((uint32_t)sq2 - (uint32_t)(sq2 >> 32)) <= 0) exhausted = exhausted | need;
-            }
+        } else if (ring_stop_raised(src) && ring_drained_after_stop(&src.ctl->sq)) {
+            exhausted = exhausted | need;
         }
     };
 
@@ -1464,21 +1548,7 @@ __global__ __launch_bounds__(512) void k_sha256_lanes(RingSource src) {
         if (have) {
             if (!cur_last) ++blk; else have = false;
         }
-        if (cur_last) {  // the chunk's last block is in registers: drop its page references (k_sha256_pair)
-            const uint32_t pg = pages;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t pi = h ? (pg >> 16) : (pg & 0xffffu);
-                if (pi != 0xffffu) {
-                    const uint32_t old = __hip_atomic_fetch_sub(&src.pending[pi], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                    if (old == 1u) {
-                        const uint32_t fs = atomicAdd(&src.ctl->free_count, 1u);
-                        __hip_atomic_store(&src.free_fifo[fs & src.free_mask], ((unsigned long long)(fs + 1u) << 32) | pi,
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
-                }
-            }
-        }
+        if (cur_last) ring_release_pages(src, pages);  // the chunk's last block is in registers
         acquire(!have && !exhausted);
         if (have) load_block();
         if (cur) sha256_compress(H, W);
@@ -1486,8 +1556,7 @@ __global__ __launch_bounds__(512) void k_sha256_lanes(RingSource src) {
             PBSK_GLOBAL uint32_t *o = (PBSK_GLOBAL uint32_t *)cur_dst;
 #pragma unroll
             for (int j = 0; j < 8; ++j) o[j] = __builtin_bswap32(H[j]);
-            __threadfence_system();
-            __hip_atomic_store(o + 10, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            ring_cell_publish(o);
             sha256_iv(H);
         }
     }
@@ -1601,8 +1670,7 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                 // chunk: 0.02 % of a 4 MiB chunk's chain); a wave with no work at all polls every step, as before.
                 if (__ballot(need) == 0) return;
                 if (__ballot(have) != 0 && ((++poll_ctr) & src.poll_mask) != 0u) return;
-                // (0) LONG chunks first (see RingSource::ldesc): one relaxed load of {ltail, lhead}; the wave's leader moves
-                // lhead forward by compare-and-swap only over published positions, so no lane ever waits on this queue
+                // (0) LONG chunks first (see RingSource::ldesc; a CAS queue: ring_cas_claim)
                 // Who may take a long chunk: a lane that holds NO claim on the main queue — one that has just finished a
                 // chunk, or one of the few lanes (1 in 16) that never claim there. A lane that waits at a claimed, not yet
                 // published position must not: the chunk published at its position later would then wait for the whole
@@ -1610,9 +1678,9 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                 const bool long_only = src.long_bytes != 0u && src.xp == 0u && (lane & 15) == 0;
                 const bool elig = need && claimed == 0u;
                 if (src.long_bytes && __ballot(elig)) {
-                    const unsigned long long lq = __hip_atomic_load(&src.ctl->lq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const uint32_t lt = (uint32_t)lq, lh = (uint32_t)(lq >> 32);
-                    int32_t avail = (int32_t)(lt - lh) - (int32_t)src.long_spill;  // (spill: what the express service's lanes are left)
+                    uint32_t lh;
+                    // (spill: what the express service's lanes are left)
+                    int32_t avail = ring_queue_avail(&src.ctl->lq, lh) - (int32_t)src.long_spill;
                     // with an express service: only while ALL its lane pairs are busy — a long chunk that waited for one would
                     // finish later than on a pair lane that is free now (configs[2]: half the bytes are 16 MiB chunks)
                     // (safety valve: more long chunks waiting than the express service has pairs — e.g. its workgroups have not
@@ -1623,25 +1691,13 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                     if (avail > 0) {
                         const unsigned long long mn = __ballot(elig);
                         const uint32_t cnt = min((uint32_t)__popcll(mn), (uint32_t)avail);
-                        const int leader = __ffsll((long long)mn) - 1;
-                        uint32_t got0 = 0xffffffffu;
-                        if (lane == leader && atomicCAS(&src.ctl->lhead, lh, lh + cnt) == lh) got0 = lh;
-                        got0 = __shfl(got0, leader, 64);
-                        if (got0 != 0xffffffffu) {
-                            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                            const uint32_t rank = (uint32_t)__popcll(mn & ((1ull << lane) - 1ull));
+                        const uint32_t first = ring_cas_claim(&src.ctl->lhead, lh, cnt, mn, lane);
+                        if (first != 0xffffffffu) {
+                            const uint32_t rank = wave_rank(mn, lane);
                             const bool tk = elig && rank < cnt;
-                            uint4 e0 = make_uint4(0, 0, 0, 0), e1 = make_uint4(0, 0, 0, 0);
-                            if (tk) {
-                                e0 = src.ldesc[2u * ((got0 + rank) & src.lmask)];
-                                e1 = src.ldesc[2u * ((got0 + rank) & src.lmask) + 1u];
-                            }
-                            base = tk ? reinterpret_cast<const uint8_t *>(((uint64_t)e0.y << 32) | e0.x) : base;
-                            base2 = tk ? reinterpret_cast<const uint8_t *>(((uint64_t)e1.y << 32) | e1.x) : base2;
-                            len = tk ? (uint64_t)e0.z : len;
-                            len1 = tk ? e0.w : len1;
-                            dst = tk ? src.cells + (uint64_t)e1.z * 64u + 8u : dst;
-                            pages = tk ? e1.w : pages;
+                            uint4 e0, e1;
+                            ring_desc_load(src.ldesc, (first + rank) & src.lmask, tk, e0, e1);
+                            ring_desc_take(src, tk, e0, e1, base, base2, len, len1, dst, pages);
                             blk = tk ? 0ull : blk;
                             nblk = tk ? ((uint64_t)e0.z + 8u) / 64u + 1u : nblk;
                             have = have | tk;
@@ -1666,69 +1722,49 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                     }
                     first = __shfl(first, leader, 64);
                     if (want) {
-                        claim = first + (uint32_t)__popcll(mw & ((1ull << lane) - 1ull));
+                        claim = first + wave_rank(mw, lane);
                         claimed = 1u;
                     }
                 }
-                // (2) has the queue reached the lane's position? A relaxed device-scope load of {tail, stop} (no cache
-                // invalidate per poll); only a lane that really takes a descriptor pays the acquire fence behind which
-                // the descriptor and the chunk's bytes (written by other kernels while this one runs) are read.
+                // (2) has the queue reached the lane's position? {tail, stop} in one relaxed load; the acquire fence only
+                // when some lane takes a descriptor
                 if (__ballot(need) == 0) return;
                 const unsigned long long ts = __hip_atomic_load(&src.ctl->tail_stop,
                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t tail = (uint32_t)ts, stop = (uint32_t)(ts >> 32);
                 const bool ready = need && claimed != 0u && (int32_t)(tail - claim) > 0;
                 if (__ballot(ready)) __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                uint4 d0 = make_uint4(0, 0, 0, 0), d1 = make_uint4(0, 0, 0, 0);
-                if (ready) {
-                    d0 = src.desc[2u * (claim & src.qmask)];
-                    d1 = src.desc[2u * (claim & src.qmask) + 1u];
-                }
-                // size 0 = a void position (the open chunk of a round): the lane takes another one next time.
-                // (selects and or-updates, no conditional stores: two flags set in sibling branches get their stores merged
-                // through a selected pointer by the optimiser, which moves both flags into scratch memory)
+                uint4 d0, d1;
+                ring_desc_load(src.desc, claim & src.qmask, ready, d0, d1);
+                // size 0 = a void position (the open chunk of a round): the lane takes another one next time
                 const bool got = ready && d0.z != 0u;
                 claimed = ready ? 0u : claimed;
-                base = got ? reinterpret_cast<const uint8_t *>(((uint64_t)d0.y << 32) | d0.x) : base;
-                base2 = got ? reinterpret_cast<const uint8_t *>(((uint64_t)d1.y << 32) | d1.x) : base2;
-                len = got ? (uint64_t)d0.z : len;
-                len1 = got ? d0.w : len1;
-                dst = got ? src.cells + (uint64_t)d1.z * 64u + 8u : dst;
-                pages = got ? d1.w : pages;
+                ring_desc_take(src, got, d0, d1, base, base2, len, len1, dst, pages);
                 blk = got ? 0ull : blk;
                 nblk = got ? ((uint64_t)d0.z + 8u) / 64u + 1u : nblk;
                 have = have | got;
-                // stop: nothing will ever be published at this position. (stop is raised behind the last publish of BOTH queues;
-                // the long queue is looked at again after the fence, so a lane never leaves while long chunks are unclaimed)
+                // stop: nothing will ever be published at this position (without an express service the long queue is
+                // this service's too: looked at once more)
                 bool leave = need && !ready && stop != 0u;
-                if (src.long_bytes && src.xp == 0u && __ballot(leave)) {
-                    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                    const unsigned long long lq2 = __hip_atomic_load(&src.ctl->lq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((int32_t)((uint32_t)lq2 - (uint32_t)(lq2 >> 32)) > 0) leave = false;
-                }
+                if (src.long_bytes && src.xp == 0u && __ballot(leave) && !ring_drained_after_stop(&src.ctl->lq)) leave = false;
                 exhausted = exhausted | leave;
                 return;
             }
             const unsigned long long m = __ballot(need);
             if (m == 0) return;
             uint32_t first = 0;
-            const int leader = __ffsll((long long)m) - 1;
             uint32_t avail = 0;
             if constexpr (DENSE) {
                 const uint32_t cnt = (uint32_t)__popcll(m);
                 avail = res_end - res_next;
-                if (cnt > avail) {
-                    if (lane == leader) first = atomicAdd(queue, cnt - avail + kReserve);
-                    first = __shfl(first, leader, 64);
-                }
+                if (cnt > avail) first = wave_claim(queue, m, cnt - avail + kReserve, lane);
             } else {
-                if (lane == leader) first = atomicAdd(queue, (uint32_t)__popcll(m));
-                first = __shfl(first, leader, 64);
+                first = wave_claim(queue, m, (uint32_t)__popcll(m), lane);
             }
             if (need) {
-                uint32_t i = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                uint32_t i = first + wave_rank(m, lane);
                 if constexpr (DENSE) {
-                    const uint32_t r = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                    const uint32_t r = wave_rank(m, lane);
                     i = r < avail ? res_next + r : first + (r - avail);
                 }
                 if (i < nitems) {
@@ -1811,28 +1847,11 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                     uint8_t *cur_dst = dstv[s];
                     if constexpr (Source::kRing) {
                         // The chunk's LAST block has arrived in registers: nothing of the chunk will be read from HBM
-                        // again. Drop its page references (release: all earlier loads of this lane have completed);
-                        // whoever brings a page to zero hands it back to the host, which may refill it at once.
+                        // again, its pages may go back to the host at once.
                         // (Round 4 tried letting go of a two-page chunk's FIRST page as soon as its last block there was
                         // in: no gain — a max-size chunk lives almost entirely in ONE 16.2 MiB page, which it holds for
                         // its whole 0.46 s either way; configs[2] through the ring 412 vs 422 GiB/s. Removed again.)
-                        if (c & 2u) {
-                            const uint32_t pg = pagesv[s];
-#pragma unroll
-                            for (int h = 0; h < 2; ++h) {
-                                const uint32_t pi = h ? (pg >> 16) : (pg & 0xffffu);
-                                if (pi != 0xffffu) {
-                                    const uint32_t old = __hip_atomic_fetch_sub(&src.pending[pi], 1u, __ATOMIC_RELEASE,
-                                                                                __HIP_MEMORY_SCOPE_AGENT);
-                                    if (old == 1u) {
-                                        const uint32_t fs = atomicAdd(&src.ctl->free_count, 1u);
-                                        __hip_atomic_store(&src.free_fifo[fs & src.free_mask],
-                                                           ((unsigned long long)(fs + 1u) << 32) | pi, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_SYSTEM);
-                                    }
-                                }
-                            }
-                        }
+                        if (c & 2u) ring_release_pages(src, pagesv[s]);
                     }
                     prep(s);  // refill the slot: the block D iterations ahead
                     const bool any_cur = __any(c & 1u);
@@ -1955,10 +1974,7 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                     PBSK_GLOBAL uint32_t *o = (PBSK_GLOBAL uint32_t *)x.d;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) o[j] = __builtin_bswap32(H[j]);
-                    if constexpr (Source::kRing) {  // record cell in mapped pinned memory: digest first, then its flag
-                        __threadfence_system();
-                        __hip_atomic_store(o + 10, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
+                    if constexpr (Source::kRing) ring_cell_publish(o);  // record cell in mapped pinned memory: digest, then flag
                     sha256_iv(H);
                 }
             }
@@ -2121,54 +2137,31 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
             if (__ballot(need) == 0) return;
             bool got = false;
             if constexpr (Source::kRing) {
-                // the ring's LONG-chunk queue only (RingSource::ldesc): no claims, no waiting at positions — the wave's
-                // leader moves lhead forward by compare-and-swap over published positions
+                // the ring's LONG-chunk queue only (RingSource::ldesc)
                 if (__ballot(have) != 0 && ((++poll_ctr) & src.poll_mask) != 0u) return;
-                const unsigned long long lq = __hip_atomic_load(&src.ctl->lq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t lt = (uint32_t)lq, lh = (uint32_t)(lq >> 32);
-                const int32_t avail = (int32_t)(lt - lh);
+                uint32_t lh;
+                const int32_t avail = ring_queue_avail(&src.ctl->lq, lh);
                 const unsigned long long mn = __ballot(need);
                 if (avail > 0) {
                     const uint32_t cnt = min((uint32_t)__popcll(mn), (uint32_t)avail);
-                    const int leader = __ffsll((long long)mn) - 1;
-                    uint32_t got0 = 0xffffffffu;
-                    if (lane == leader && atomicCAS(&src.ctl->lhead, lh, lh + cnt) == lh) got0 = lh;
-                    got0 = __shfl(got0, leader, 64);
-                    if (got0 != 0xffffffffu) {
-                        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                        const uint32_t rank = (uint32_t)__popcll(mn & ((1ull << lane) - 1ull));
+                    const uint32_t first = ring_cas_claim(&src.ctl->lhead, lh, cnt, mn, lane);
+                    if (first != 0xffffffffu) {
+                        const uint32_t rank = wave_rank(mn, lane);
                         got = need && rank < cnt;
-                        uint4 e0 = make_uint4(0, 0, 0, 0), e1 = make_uint4(0, 0, 0, 0);
-                        if (got) {
-                            e0 = src.ldesc[2u * ((got0 + rank) & src.lmask)];
-                            e1 = src.ldesc[2u * ((got0 + rank) & src.lmask) + 1u];
-                        }
-                        base = got ? reinterpret_cast<const uint8_t *>(((uint64_t)e0.y << 32) | e0.x) : base;
-                        base2 = got ? reinterpret_cast<const uint8_t *>(((uint64_t)e1.y << 32) | e1.x) : base2;
-                        len = got ? (uint64_t)e0.z : len;
-                        len1 = got ? e0.w : len1;
-                        dst = got ? src.cells + (uint64_t)e1.z * 64u + 8u : dst;
-                        pages = got ? e1.w : pages;
-                        if (lane == leader) atomicAdd(&src.ctl->xp_busy, cnt);  // (given back when the chunk's last block is in)
+                        uint4 e0, e1;
+                        ring_desc_load(src.ldesc, (first + rank) & src.lmask, got, e0, e1);
+                        ring_desc_take(src, got, e0, e1, base, base2, len, len1, dst, pages);
+                        // (given back when the chunk's last block is in)
+                        if (lane == __ffsll((long long)mn) - 1) atomicAdd(&src.ctl->xp_busy, cnt);
                     }
-                } else {
-                    // nothing published: has the service been told to stop? (stop is raised behind the last publish; the
-                    // queue is looked at again behind the fence, so no lane leaves while long chunks are unclaimed)
-                    const unsigned long long ts = __hip_atomic_load(&src.ctl->tail_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if ((uint32_t)(ts >> 32) != 0u) {
-                        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-                        const unsigned long long lq2 = __hip_atomic_load(&src.ctl->lq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if ((int32_t)((uint32_t)lq2 - (uint32_t)(lq2 >> 32)) <= 0) exhausted = exhausted | need;
-                    }
+                } else if (ring_stop_raised(src) && ring_drained_after_stop(&src.ctl->lq)) {
+                    exhausted = exhausted | need;
                 }
             } else {
                 const unsigned long long m = __ballot(need);
-                uint32_t first = 0;
-                const int leader = __ffsll((long long)m) - 1;
-                if (lane == leader) first = atomicAdd(queue, (uint32_t)__popcll(m));
-                first = __shfl(first, leader, 64);
+                const uint32_t first = wave_claim(queue, m, (uint32_t)__popcll(m), lane);
                 if (need) {
-                    const uint32_t i = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+                    const uint32_t i = first + wave_rank(m, lane);
                     if (i < nitems) {
                         src.get(i, base, len, dst);
                         got = true;
@@ -2270,23 +2263,7 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
                             const unsigned long long mdone = __ballot((c & 2u) != 0u);
                             if (mdone && lane == (__ffsll((long long)mdone) - 1)) atomicSub(&src.ctl->xp_busy, (uint32_t)__popcll(mdone));
                         }
-                        if (c & 2u) {
-                            const uint32_t pg = pagesv[s];
-#pragma unroll
-                            for (int h = 0; h < 2; ++h) {
-                                const uint32_t pi = h ? (pg >> 16) : (pg & 0xffffu);
-                                if (pi != 0xffffu) {
-                                    const uint32_t old = __hip_atomic_fetch_sub(&src.pending[pi], 1u, __ATOMIC_RELEASE,
-                                                                                __HIP_MEMORY_SCOPE_AGENT);
-                                    if (old == 1u) {
-                                        const uint32_t fs = atomicAdd(&src.ctl->free_count, 1u);
-                                        __hip_atomic_store(&src.free_fifo[fs & src.free_mask],
-                                                           ((unsigned long long)(fs + 1u) << 32) | pi, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_SYSTEM);
-                                    }
-                                }
-                            }
-                        }
+                        if (c & 2u) ring_release_pages(src, pagesv[s]);
                     }
                     prep(s);
                     const bool any_cur = __any(c & 1u);
@@ -2364,10 +2341,7 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
                     PBSK_GLOBAL uint32_t *o = (PBSK_GLOBAL uint32_t *)x.d + (roleB ? 0 : 4);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = __builtin_bswap32(HR[j]);
-                    if constexpr (Source::kRing) {  // record cell in mapped pinned memory: both halves first, then the flag
-                        __threadfence_system();
-                        __hip_atomic_store((PBSK_GLOBAL uint32_t *)x.d + 10, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    }
+                    if constexpr (Source::kRing) ring_cell_publish((PBSK_GLOBAL uint32_t *)x.d);  // both halves, then the flag
 #pragma unroll
                     for (int j = 0; j < 4; ++j) HR[j] = ivr[j];
                 }

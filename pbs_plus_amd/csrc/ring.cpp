@@ -128,15 +128,16 @@ void ring_reap_rounds(pbsgpu_ring *r) {
             const uint8_t *cells = r->cells.as<uint8_t>();
             for (uint32_t i = 0; i < n; ++i) {
                 const uint32_t c = (uint32_t)((ri.cell_base + i) & (r->ncells - 1));
-                const uint32_t *cw = reinterpret_cast<const uint32_t *>(cells + (size_t)c * 64);
-                if (cw[11] == 0) continue;  // the round's open chunk: no record
-                const uint32_t slot = cw[10];
+                const uint32_t *cw = reinterpret_cast<const uint32_t *>(cells + (size_t)c * pbsk::kCellBytes);
+                if (cw[pbsk::kCellSize] == 0) continue;  // the round's open chunk: no record
+                const uint32_t slot = cw[pbsk::kCellSegment];
                 if (slot >= r->slots.size()) continue;
                 r->slots[slot].cells.push_back(CellRef{c, ri.seq});
                 ri.live_cells++;
                 r->st.chunks++;
-                r->obs_bytes += (double)cw[11];
-                if (r->long_bytes && cw[11] >= r->long_bytes) r->obs_long_bytes += (double)cw[11];
+                const uint32_t size = cw[pbsk::kCellSize];
+                r->obs_bytes += (double)size;
+                if (r->long_bytes && size >= r->long_bytes) r->obs_long_bytes += (double)size;
             }
             r->st.candidates += hs->ncand;
             r->pub_positions += (uint32_t)(hs->tail - r->tail_seen);
@@ -400,7 +401,7 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     r->cell_cursor += cells_needed;
     uint8_t *cells = r->cells.as<uint8_t>();
     for (uint64_t i = 0; i < cells_needed; ++i)
-        std::memset(cells + (size_t)((ri.cell_base + i) & (r->ncells - 1)) * 64, 0, 64);
+        std::memset(cells + (size_t)((ri.cell_base + i) & (r->ncells - 1)) * pbsk::kCellBytes, 0, pbsk::kCellBytes);
     ri.seq = r->next_seq++;
     ri.input = (uint32_t)in;
     pbsk::RingRoundStatus *hs = r->in_status((uint32_t)in);
@@ -681,14 +682,14 @@ void ring_pop_records(pbsgpu_ring *r, uint32_t slot, pbsgpu_record *out, uint64_
     const uint8_t *cells = r->cells.as<uint8_t>();
     while (*n < cap && !s.cells.empty()) {
         const CellRef cr = s.cells.front();
-        const uint8_t *c = cells + (size_t)cr.cell * 64;
-        const volatile uint32_t *flag = reinterpret_cast<const volatile uint32_t *>(c + 48);
-        if (*flag != 1u) break;  // its chunk is still being hashed: records come out in stream order
+        const uint8_t *c = cells + (size_t)cr.cell * pbsk::kCellBytes;
+        const volatile uint32_t *cw = reinterpret_cast<const volatile uint32_t *>(c);
+        if (cw[pbsk::kCellFlag] != 1u) break;  // its chunk is still being hashed: records come out in stream order
         std::atomic_thread_fence(std::memory_order_acquire);
         pbsgpu_record rec;
         std::memcpy(&rec, c, sizeof(rec));
         rec.segment = slot;
-        if (r->tier_tag) rec.segment |= (reinterpret_cast<const uint32_t *>(c)[13] & 3u) << 28;  // PBSGPU_RING_F_TIER_TAG
+        if (r->tier_tag) rec.segment |= (cw[pbsk::kCellTier] & 3u) << 28;  // PBSGPU_RING_F_TIER_TAG
         out[(*n)++] = rec;
         s.cells.pop_front();
         s.records_out++;
@@ -912,7 +913,7 @@ int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool 
         CHK(r->seg_ecand_in.ensure((size_t)r->max_streams * 8 + 16));
         CHK(r->seg_ecand.ensure((size_t)r->max_streams * 8 + 16));
         CHK(r->recs.ensure((size_t)r->rec_cap * sizeof(pbsgpu_record) + 64));
-        CHK(r->cells.ensure((size_t)r->ncells * 64));
+        CHK(r->cells.ensure((size_t)r->ncells * pbsk::kCellBytes));
         CHK(r->heartbeat.ensure(256));
         std::memset(r->heartbeat.p, 0, 256);
         CHK(r->free_fifo.ensure((size_t)r->nfree * 8));
@@ -1398,11 +1399,11 @@ int pbsgpu_ring_debug(pbsgpu_ring *r, char *buf, uint64_t cap) {
             s.ready.size(), s.cells.size(), (unsigned long long)s.records_out, (unsigned long long)sts[i].c,
             (unsigned long long)sts[i].end);
         if (!s.cells.empty()) {
-            const uint8_t *c = r->cells.as<uint8_t>() + (size_t)s.cells.front().cell * 64;
+            const uint8_t *c = r->cells.as<uint8_t>() + (size_t)s.cells.front().cell * pbsk::kCellBytes;
             pbsgpu_record rec;
             std::memcpy(&rec, c, sizeof(rec));
             put("  waiting for cell %u: end=%llu size=%u flag=%u\n", s.cells.front().cell, (unsigned long long)rec.end, rec.size,
-                *reinterpret_cast<const uint32_t *>(c + 48));
+                reinterpret_cast<const uint32_t *>(c)[pbsk::kCellFlag]);
         }
     }
     return PBSGPU_OK;

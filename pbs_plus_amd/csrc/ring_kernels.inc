@@ -19,20 +19,12 @@
 // walk asks such a tile for the first candidate behind a position by re-scanning the stretch on demand (DenseTiles, kernels.h).
 // No input fails a stream (rounds 3-5 failed the stream that owned the tile: PBSGPU_E_DENSITY, retired with ABI v5).
 
-__device__ __forceinline__ void ring_report_free(const RingSource &q, uint32_t page) {
-    const uint32_t fs = atomicAdd(&q.ctl->free_count, 1u);
-    __hip_atomic_store(&q.free_fifo[fs & q.free_mask], ((unsigned long long)(fs + 1u) << 32) | page, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // a ticket for the short queue: true (and the entry written) while the round's allowance lasts. Tickets beyond it are simply
 // not used: the tail step publishes min(tickets, allowance) entries, and every ticket below the allowance has written its entry.
-__device__ __forceinline__ bool ring_short_ticket(const RingRound &r, const uint4 e0, const uint4 e1) {
+__device__ __forceinline__ bool ring_short_ticket(const RingRound &r, const RingDesc &d) {
     const uint32_t idx = atomicAdd(&r.scalars[kRsNshort], 1u);
     if (idx >= r.scalars[kRsShortRoom]) return false;
-    const uint32_t sp = (r.q.ctl->stail + idx) & r.q.smask;
-    r.sdesc_w[2u * sp] = e0;
-    r.sdesc_w[2u * sp + 1u] = e1;
+    ring_desc_encode(r.sdesc_w, (r.q.ctl->stail + idx) & r.q.smask, d);
     return true;
 }
 
@@ -174,9 +166,9 @@ __device__ __forceinline__ void ring_order_one(const RingRound &r, const uint32_
     const uint64_t Aoff = r.segs[s].offset & kRingOffMask;
     const uint64_t endl = Aoff + rec.end, start = endl - rec.size;
     const uint32_t cell = (r.cell_base + i) & r.cell_mask;
-    uint32_t *cw = reinterpret_cast<uint32_t *>(r.q.cells + (uint64_t)cell * 64u);
+    uint32_t *cw = reinterpret_cast<uint32_t *>(r.q.cells + (uint64_t)cell * kCellBytes);
     if (is_last && r.seg_open[s]) {  // the still-open chunk (resolve_walk decided): no record, no work
-        cw[11] = 0;                  // void cell (size 0): the host skips it
+        cw[kCellSize] = 0;           // void cell (size 0): the host skips it
         return;
     }
     const uint64_t G = r.page_bytes;
@@ -193,13 +185,12 @@ __device__ __forceinline__ void ring_order_one(const RingRound &r, const uint32_
         atomicAdd(&r.q.pending[ph2], 1u);
         pages = ph1 | (ph2 << 16);
     }
-    // record cell {end u64, digest[32], segment u32, size u32, flag u32}: the service adds digest and flag
-    cw[0] = (uint32_t)endl;
-    cw[1] = (uint32_t)(endl >> 32);
-    cw[10] = sg.slot;
-    cw[11] = rec.size;
-    const uint4 e0 = make_uint4((uint32_t)p1, (uint32_t)(p1 >> 32), rec.size, len1);
-    const uint4 e1 = make_uint4((uint32_t)p2v, (uint32_t)(p2v >> 32), cell, pages);
+    // record cell: the service adds digest and flag
+    cw[kCellEnd] = (uint32_t)endl;
+    cw[kCellEnd + 1] = (uint32_t)(endl >> 32);
+    cw[kCellSegment] = sg.slot;
+    cw[kCellSize] = rec.size;
+    const RingDesc d{p1, p2v, rec.size, len1, cell, pages};
     bool go_long = r.q.long_bytes && rec.size >= r.q.long_bytes;
     if (!go_long && r.q.long_lo && rec.size >= r.q.long_lo) {  // light load: see RingSource::long_lo
         const unsigned long long lq = __hip_atomic_load(&r.q.ctl->lq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -208,23 +199,19 @@ __device__ __forceinline__ void ring_order_one(const RingRound &r, const uint32_
                               __hip_atomic_load(&r.scalars[kRsNlong], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         go_long = 4u * busy < 3u * r.q.xp_pairs;
     }
-    cw[13] = 0;  // which queue the chunk went to (0 main, 1 long, 2 short): PBSGPU_RING_F_TIER_TAG, diagnostics
+    cw[kCellTier] = 0;  // which queue the chunk went to (0 main, 1 long, 2 short): PBSGPU_RING_F_TIER_TAG, diagnostics
     if (go_long) {
-        cw[13] = 1;
+        cw[kCellTier] = 1;
         // a long chunk goes to the queue idle lanes look at first
-        const uint32_t lp = (r.q.ctl->ltail + atomicAdd(&r.scalars[kRsNlong], 1u)) & r.q.lmask;
-        r.ldesc_w[2u * lp] = e0;
-        r.ldesc_w[2u * lp + 1u] = e1;
+        ring_desc_encode(r.ldesc_w, (r.q.ctl->ltail + atomicAdd(&r.scalars[kRsNlong], 1u)) & r.q.lmask, d);
     } else if (r.q.short_bytes && rec.size <= r.q.short_bytes &&
                __hip_atomic_load(&r.scalars[kRsNshort], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < r.scalars[kRsShortRoom] &&
-               ring_short_ticket(r, e0, e1)) {
+               ring_short_ticket(r, d)) {
         // a short chunk for the lanes service (while it has room: RingSource::sdesc)
-        cw[13] = 2;
+        cw[kCellTier] = 2;
     } else {
         // only the publish step (same HIP stream) moves the tail
-        const uint32_t pos = (r.q.ctl->tail + atomicAdd(&r.scalars[kRsNmain], 1u)) & r.q.qmask;
-        r.desc_w[2u * pos] = e0;
-        r.desc_w[2u * pos + 1u] = e1;
+        ring_desc_encode(r.desc_w, (r.q.ctl->tail + atomicAdd(&r.scalars[kRsNmain], 1u)) & r.q.qmask, d);
     }
 }
 
@@ -258,9 +245,7 @@ __device__ __forceinline__ void ring_publish_subs(const RingRound &r, const uint
             const uint64_t last_old = (end_old - 1u) / G;
             for (uint64_t k = c_old / G; k <= last_old; ++k) {
                 if (open_new && k >= c_new / G) break;
-                const uint32_t ph = st->pt[k % kRingPT];
-                if (__hip_atomic_fetch_sub(&r.q.pending[ph], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT) == 1u)
-                    ring_report_free(r.q, ph);
+                ring_release_page(r.q, st->pt[k % kRingPT]);
             }
         }
         st->c = c_new;
