@@ -84,6 +84,9 @@ SMALL = dict(page_bytes=65536, max_streams=8, sha_cus=4, round_pages=6)
 def test_ring_streams_match_the_oracle(gpu_lib, O, name, avg, opt, jobs, conc):
     from pbs_plus_amd import PageRing
 
+    lanes = opt.get("lanes_cus", 0)
+    if lanes:   # PBSGPU_RING_F_TIER_TAG: bits 28-29 of `segment` name the queue a chunk went through (2 = the lanes service's)
+        opt = dict(opt, flags=opt.get("flags", 0) | 256)
     eng = _engine(avg)
     ring = PageRing(eng, **opt)
     got = ring.ingest_synthetic(jobs, timeout_s=60.0, concurrent=conc)
@@ -92,6 +95,11 @@ def test_ring_streams_match_the_oracle(gpu_lib, O, name, avg, opt, jobs, conc):
     want = _oracle_records(O, avg, jobs)
     for i, (g, w) in enumerate(zip(got, want)):
         _assert_same(g, w, (name, i, jobs[i]))
+    if lanes:   # the lanes service really took chunks, and only short ones
+        tier = np.concatenate([(g["segment"] >> 28) & 3 for g in got])
+        size = np.concatenate([g["size"] for g in got])
+        assert set(tier.tolist()) <= {0, 2} and (tier == 2).sum() > 0, (name, np.bincount(tier))
+        assert (size[tier == 2] <= opt["short_bytes"]).all(), name
     # every page came back, exactly once per use
     assert st["pages_free"] == st["pages_total"] and st["pages_recycled"] == st["pages_enqueued"], st
     assert st["service_launches"] == 1

@@ -85,7 +85,14 @@ RING_CODE = (
     "        w = O.chunk_and_digest(cfg, O.fill(n, seed, kind), [(0, n)]) if n else np.zeros(0, dtype=O.RECORD_DTYPE)\n"
     "        same(got[i], w, (avg, i))\n"
     "    assert st['pages_free'] == st['pages_total'] and st['pages_recycled'] == st['pages_enqueued'], st\n"
-    "    long_chunks = sum(int((g['size'] >= LONG).sum()) for g in got)\n"
+    # PBSGPU_RING_TIER_TAG: bits 28-29 of `segment` name the queue a chunk went through (1 = long: the express service's);
+    # with the light-load rule off (PBSGPU_RING_LONG_LO_BYTES=0) exactly the chunks of at least LONG take it
+    "    assert ring.express() == (XP_CUS, LONG), ring.express()\n"
+    "    tier = np.concatenate([(g['segment'] >> 28) & 3 for g in got])\n"
+    "    size = np.concatenate([g['size'] for g in got])\n"
+    "    assert set(tier.tolist()) <= {0, 1}, set(tier.tolist())\n"
+    "    long_chunks = int((tier == 1).sum())\n"
+    "    assert long_chunks == int((size >= LONG).sum()), (long_chunks, int((size >= LONG).sum()))\n"
     "    ring.close(); eng.close()\n"
     "    return long_chunks\n" % ROOT)
 
@@ -95,23 +102,25 @@ def test_ring_with_an_express_service_small_pages(gpu_lib):
     zero / periodic streams go through the express service (2 CUs) — many of them crossing pages — while the pair service
     (4 CUs) takes the rest; the arena of 24 pages turns over many times."""
     code = RING_CODE + (
-        "LONG = 10240\n"
+        "LONG, XP_CUS = 10240, 2\n"
         "nl = run(4096, dict(arena_bytes=24 * (65536 + 256), page_bytes=65536, max_streams=8, sha_cus=4, round_pages=6),\n"
         "         [(21, 0, (1 << 20) + 5), (22, 1, 300 * 1024), (23, 3, 700 * 1024 + 3), (24, 0, 0), (25, 0, 63), (26, 2, 65536),\n"
         "          (27, 0, 65536 * 3), (28, 4, 65536 * 2 + 1), (29, 0, 1), (30, 1, 1 << 20)])\n"
         "assert nl > 50, nl\n"
         "print('xp-ok', nl)\n")
-    _run(code, dict(PBSGPU_RING_XP_CUS="2", PBSGPU_RING_LONG_BYTES="10240", PBSGPU_RING_IDLE_TIMEOUT_S="5"))
+    _run(code, dict(PBSGPU_RING_XP_CUS="2", PBSGPU_RING_LONG_BYTES="10240", PBSGPU_RING_LONG_LO_BYTES="0", PBSGPU_RING_TIER_TAG="1",
+                    PBSGPU_RING_IDLE_TIMEOUT_S="5"))
 
 
 def test_ring_with_an_express_service_production_chunker(gpu_lib):
-    """avg 4 MiB: default pages (16.2 MiB), long = 10 MiB (the default 5/8 of the maximum): random, 30 % zero extents and an
-    all-zero stream (every chunk 16 MiB = express) through 3 GiB of pages."""
+    """avg 4 MiB: default pages (16.2 MiB), long = 10 MiB (set: the default is 13/16 of the maximum): random, 30 % zero extents
+    and an all-zero stream (every chunk 16 MiB = express) through 3 GiB of pages."""
     code = RING_CODE + (
-        "LONG = 10 << 20\n"
+        "LONG, XP_CUS = 10 << 20, 16\n"
         "G = 1 << 30\n"
         "nl = run(4 << 20, dict(arena_bytes=3 * G, max_streams=4, sha_cus=48, round_pages=64),\n"
         "         [(51, 0, 3 * G // 2 + 56), (52, 3, 3 * G // 2), (53, 1, G // 2 + 4096), (54, 4, G + 24)])\n"
         "assert nl > 30, nl\n"
         "print('xp-ok', nl)\n")
-    _run(code, dict(PBSGPU_RING_XP_CUS="16", PBSGPU_RING_IDLE_TIMEOUT_S="5"))
+    _run(code, dict(PBSGPU_RING_XP_CUS="16", PBSGPU_RING_LONG_BYTES=str(10 << 20), PBSGPU_RING_LONG_LO_BYTES="0",
+                    PBSGPU_RING_TIER_TAG="1", PBSGPU_RING_IDLE_TIMEOUT_S="5"))
