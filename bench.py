@@ -25,8 +25,11 @@ Workloads (BASELINE.json configs):
 N > 1 (torch.distributed.run, one rank per GPU, RCCL): every rank owns its own batches (segments and
 streams are independent, no data-path collective); the only exchange is the digest-set all-gather.
 
-Prints ONE JSON line on rank 0 with `roofline` and `cpu_baseline` (the C oracle, SHA-NI, one host
-thread, on a bounded sample of the same workload, which also re-checks the GPU records bit for bit).
+Prints ONE JSON line on rank 0 with `roofline`. A plain run of the default workload sets up, warms up, times its steps,
+writes --dump-outputs and prints the line, nothing more. `--full` adds what the headline figure does not need: the
+`cpu_baseline` (the C oracle, SHA-NI, one host thread, on a bounded sample of the same workload, which also re-checks the
+GPU records bit for bit, and the host's many-core figure), the single-file pass, the short legs of the other workloads
+(`workloads`) and, at N > 1, the cross-check of the digest-set reduce.
 """
 import argparse
 import json
@@ -85,15 +88,18 @@ def parse():
     ap.add_argument("--archives", type=int, default=1,
                     help="hostfeed: archives per producer, written back to back (finish_begin: an archive's last chunks are "
                          "hashed while the next one is being written)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the ring's CPU baseline + oracle re-check, its "
+                         "single-file pass and (N > 1) reduce cross-check, and the short legs of the other workloads")
     ap.add_argument("--cpu-sample-gib", type=float, default=2.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-spread-check", action="store_true", help="skip the whole-batch restart-point parity check")
     ap.add_argument("--spread-points", type=int, default=40, help="restart points per resident slot")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default workload only: skip the short configs[2..4] / host-fed legs folded into the line")
+                    help="with --full: skip the short configs[2..4] / host-fed legs folded into the line")
     ap.add_argument("--extras", default="batch,manyfiles,corpus_dup,rechunk,ring_manyfiles,ring_corpus_dup,ring_rechunk,hostfeed1,hostfeed8",
-                    help="which short legs the default line carries (they run when --gib is left at its default, or when "
-                         "--extras-gib names a reduced shape)")
+                    help="which short legs a --full line of the default workload carries (they run when --gib is left at its "
+                         "default, or when --extras-gib names a reduced shape)")
     ap.add_argument("--extras-gib", type=float, default=None, help="bytes per device batch of the short legs (tests)")
     ap.add_argument("--extras-file-mib", type=float, default=64.0)
     ap.add_argument("--seed", type=int, default=2)
@@ -605,7 +611,7 @@ def main():
     if a.workload == "ring":
         out = ring_run(a, rank, local_rank, world, ctx)
         if rank == 0:
-            if world == 1 and not a.no_extras and (a.gib is None or a.extras_gib is not None):
+            if world == 1 and a.full and not a.no_extras and (a.gib is None or a.extras_gib is not None):
                 out["workloads"] = extras(_copy_args(a, workload="stream64g"), rank, local_rank, world, ctx, with_batch=True)
                 mc = (out.get("cpu_baseline") or {}).get("many_core") or {}
                 if mc.get("value"):
@@ -629,7 +635,7 @@ def main():
     else:
         out = run_batch(a, rank, local_rank, world, ctx)
         if rank == 0:
-            if (a.workload == "stream64g" and world == 1 and not a.no_extras and not a.reread
+            if (a.workload == "stream64g" and world == 1 and a.full and not a.no_extras and not a.reread
                     and (a.gib is None or a.extras_gib is not None)):
                 out["workloads"] = extras(a, rank, local_rank, world, ctx)
             print(json.dumps(out), flush=True)
@@ -707,7 +713,7 @@ def regime_block(ring, p0, p_fed, p1, p2, pair_cus, xp_cus):
     try:
         D = type(ring).probe_delta
         out = {"feed_phase": D(p0, p_fed) if p_fed else None, "drain": D(p_fed, p1) if p_fed else None,
-               "timed_region": D(p0, p1), "single_file": D(p1, p2)}
+               "timed_region": D(p0, p1), "single_file": D(p1, p2) if p2 else None}
         pr = (out["timed_region"] or {}).get("pair")
         if pr:   # a pair-service CU carries 128 chains: 128 x 64 B per block step
             out["pair_GiBps_per_cu"] = round(128 * 64 / pr["ns_per_block_step"] * 1e9 / GiB, 3)
@@ -1102,25 +1108,27 @@ def ring_run(a, rank, local_rank, world, ctx):
         ctx.dist.all_reduce(tb, op=ctx.dist.ReduceOp.SUM)
         total_bytes = float(tb.item())
     state["timed"] = False
-    if ctx.dist is not None:
+    if ctx.dist is not None and a.full:
         # the reduce of the timed region once more on the last timed file of every rank, and (when it went through the C ABI)
         # the torch.distributed path beside it: both must report the same union
         ctx.cabi = reduce_cross_check(ctx, eng, kept[max(kept)])
-    # one file alone through an idle ring: single-file latency (outside the timed region)
-    ts0 = time.perf_counter()
-    s_saved, state["S"] = state["S"], 1
-    single = run_files(1, True)
-    single_fed_s = marks.get("t_fed", ts0) - ts0     # every byte of the file in a cut round (then: the chains of its last chunks)
-    ring.quiesce()
-    single_s = time.perf_counter() - ts0
-    probe2 = ring.probe()
+    single, probe2 = {}, None
+    if a.full:
+        # one file alone through an idle ring: single-file latency (outside the timed region)
+        ts0 = time.perf_counter()
+        s_saved, state["S"] = state["S"], 1
+        single = run_files(1, True)
+        single_fed_s = marks.get("t_fed", ts0) - ts0   # every byte of the file in a cut round (then: its last chunks' chains)
+        ring.quiesce()
+        single_s = time.perf_counter() - ts0
+        probe2 = ring.probe()
+        state["S"] = s_saved
     if os.environ.get("PBS_BENCH_RING_DEBUG"):
         dbg = ring.debug().splitlines()
         sys.stderr.write("[ring debug] " + dbg[1] + "\n")
         for ln in dbg:
             if ln.startswith("control kernel"):
                 sys.stderr.write("[ring debug] " + ln + "\n")
-    state["S"] = s_saved
     out = None
     if rank == 0:
         value = total_bytes / GiB / elapsed
@@ -1187,19 +1195,21 @@ def ring_run(a, rank, local_rank, world, ctx):
                 "traffic": None if tr is None else int(tr["ratio"] * svc_bytes),
                 "traffic_note": None if tr is None else tr["note"],
                 "algorithmic_bytes_per_launch": int(svc_bytes),
-                "single_file": {"ms": round(single_s * 1e3, 1), "GiBps": round(file_bytes / GiB / single_s, 1),
-                                "cut_ms": round(single_fed_s * 1e3, 1),
-                                "note": "one file alone through an idle ring, first page filled to last record delivered"},
             },
-            "serial_value": round(file_bytes / GiB / single_s, 2),
         }
+        if a.full:
+            out["roofline"]["single_file"] = {"ms": round(single_s * 1e3, 1), "GiBps": round(file_bytes / GiB / single_s, 1),
+                                              "cut_ms": round(single_fed_s * 1e3, 1),
+                                              "note": "one file alone through an idle ring, first page filled to last record "
+                                                      "delivered"}
+            out["serial_value"] = round(file_bytes / GiB / single_s, 2)
         if extra:
             out["results"] = extra
         if a.dump_outputs:   # the last timed step = the last timed file (its records, whole)
             out["dump_outputs"] = dump_outputs(a.dump_outputs, record_arrays(kept[state["first_timed"] + a.steps - 1]))
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = ring_cpu_baseline(a, kept, single, file_bytes, kind, seed_of)
-    if not a.no_cpu_baseline and world > 1:
+    if a.full and not a.no_cpu_baseline and world > 1:
         # N ranks: EVERY rank checks its own files against the oracle (prefix + restart points, regenerated from the files'
         # seeds), the verdicts meet on rank 0 — an N-GPU line carries parity evidence for all N GPUs' records. The one-core
         # CPU figure is rank 0's (the contract times it at N = 1; here it is context only).

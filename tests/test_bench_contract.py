@@ -306,7 +306,7 @@ def test_bench_default_line_carries_the_other_configs(monkeypatch):
     _patch(monkeypatch)
     d = _run(monkeypatch, ["--workload", "stream64g", "--gib", str(16 / 1024), "--avg", "65536", "--steps", "4", "--warmup", "1", "--cpu-sample-gib",
                            str(8 / 1024), "--extras-gib", str(32 / 1024), "--extras-file-mib", "1",
-                           "--extras", "manyfiles,corpus_dup,rechunk"])
+                           "--extras", "manyfiles,corpus_dup,rechunk", "--full"])
     _check_common(d, 4, 1)
     w = d["workloads"]
     assert set(w) == {"manyfiles", "corpus_dup", "rechunk", "total_seconds"}
@@ -326,7 +326,7 @@ def test_bench_ring_workload_is_the_default_and_keeps_the_contract(monkeypatch):
     _patch(monkeypatch)
     d = _run(monkeypatch, ["--gib", str(24 / 1024), "--avg", "65536", "--steps", "5", "--warmup", "2", "--cpu-sample-gib",
                            str(8 / 1024), "--ring-streams", "3", "--extras-gib", str(16 / 1024), "--extras-file-mib", "1",
-                           "--extras", "batch,manyfiles"])
+                           "--extras", "batch,manyfiles", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -349,6 +349,39 @@ def test_bench_ring_workload_is_the_default_and_keeps_the_contract(monkeypatch):
     w = d["workloads"]
     assert "error" not in w["batch_path_stream64g"] and w["batch_path_stream64g"]["value"] > 0
     assert w["batch_path_stream64g"]["records_match_gpu"] is True and w["manyfiles"]["records_match_gpu"] is True
+
+
+def test_bench_plain_run_only_times_its_steps(monkeypatch):
+    """Without --full the default line is the headline alone: the ring carries the warm-up and timed files and nothing
+    else (no single-file pass), no oracle or CPU figure is computed, no other workload runs."""
+    import bench
+
+    opened = []
+
+    class _CountingRing(_FakeRing):
+        def open(self):
+            opened.append(1)
+            return super().open()
+
+    def _no_oracle(*a, **k):
+        raise AssertionError("a plain run computed a CPU baseline")
+
+    _patch(monkeypatch)
+    import pbs_plus_amd
+    monkeypatch.setattr(pbs_plus_amd, "PageRing", _CountingRing)
+    monkeypatch.setattr(bench, "ring_cpu_baseline", _no_oracle)
+    monkeypatch.setattr(bench, "extras", _no_oracle)
+    d = _run(monkeypatch, ["--gib", str(24 / 1024), "--avg", "65536", "--steps", "3", "--warmup", "2", "--ring-streams", "2",
+                           "--extras-gib", str(16 / 1024)])
+    assert len(opened) == 2 + 3
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["metric"] == "GiB/s ingested through CDC+SHA-256" and d["unit"] == "GiB/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u32" and d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 3 * (24 << 20) / (1 << 30) / (d["ms_per_step"] * 3e-3)) <= 0.005 + 1e-3 * d["value"]   # (rounding)
+    assert not {"cpu_baseline", "workloads", "serial_value"} & set(d)
+    assert "single_file" not in d["roofline"] and d["roofline"]["regime"]["single_file"] is None
+    assert d["roofline"]["service_launch_bytes"] == 3 * (24 << 20)
 
 
 def test_bench_reread_protocol_is_labelled(monkeypatch):
@@ -501,7 +534,7 @@ def test_bench_two_ranks_time_the_reduce_of_the_c_abi_communicator():
     gloo with a stand-in communicator that keeps the collective contract: every timed reduce and the first contact go through
     it, the line says so, and both paths report the same union."""
     d = _two_ranks(["--gpus", "2", "--gib", str(12 / 1024), "--avg", "65536", "--steps", "4", "--warmup", "1",
-                    "--ring-streams", "2", "--no-cpu-baseline"], extra_env={"PBS_BENCH_REDUCE": "cabi"})
+                    "--ring-streams", "2", "--no-cpu-baseline", "--full"], extra_env={"PBS_BENCH_REDUCE": "cabi"})
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] > 0
     c = d["results"]["c_abi_digest_reduce"]
     assert c["ok"] is True and c["timed_through_c_abi"] is True and c["equals_torch_path"] is True, c
@@ -542,7 +575,7 @@ def test_bench_gpus_flag_spawns_its_own_ranks_and_every_rank_is_checked():
     import subprocess
 
     args = ["--gpus", "2", "--gib", str(12 / 1024), "--avg", "65536", "--steps", "3", "--warmup", "1", "--ring-streams", "2",
-            "--cpu-sample-gib", str(4 / 1024)]
+            "--cpu-sample-gib", str(4 / 1024), "--full"]
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "from test_bench_contract import _patched_main\n"
             "_patched_main(%r)\n" % (ROOT, os.path.join(ROOT, "tests"), args))

@@ -266,7 +266,7 @@ def test_bench_ring_workload_small_scale(gpu_lib, extra):
     """bench.py's default workload (the ring) end to end at a size the oracle re-checks completely enough: 1.5 GiB files
     through a 6 GiB arena, prefix + restart points over every timed file."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gib", "1.5", "--arena-gib", "6", "--steps", "5",
-                          "--warmup", "2", "--cpu-sample-gib", "0.5", "--no-extras", "--ring-sha-cus", "128"] + extra,
+                          "--warmup", "2", "--cpu-sample-gib", "0.5", "--no-extras", "--ring-sha-cus", "128", "--full"] + extra,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

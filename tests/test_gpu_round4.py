@@ -269,7 +269,7 @@ def test_bench_ring_forced_dist_runs_the_c_abi_reduce_beside_torch(gpu_lib):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gib", "0.25", "--steps", "3", "--warmup", "1",
-                          "--avg", str(1 << 20), "--arena-gib", "1.5", "--ring-streams", "2", "--no-cpu-baseline"],
+                          "--avg", str(1 << 20), "--arena-gib", "1.5", "--ring-streams", "2", "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
