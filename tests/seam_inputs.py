@@ -77,25 +77,46 @@ class Planter:
         lo = max(0, e - 128)
         return self.O.candidates(self.cfg, data[lo:e + 64]).astype(np.int64) + lo
 
-    def plant(self, data: np.ndarray, e: int) -> None:
+    def plant(self, data: np.ndarray, e: int, pair: bool = False) -> None:
         """Make a candidate end at exactly `e` (window data[e-64:e]) without creating any other one; `data` is candidate-free
-        around `e` but for candidates planted at least 64 bytes in front of it, which stay."""
+        around `e` but for candidates planted at least 64 bytes in front of it, which stay.
+
+        pair: candidates at e - 1 AND e. h(e) = rotl(h(e - 1), 1) ^ T[b[e - 1]] ^ T[b[e - 65]] (rotl by 64 is the identity),
+        so with b[e - 1] = b[e - 65] and the low bits of h(e - 1) all ones, the low bits of h(e) are all ones but bit 0 (which
+        is bit 31 of h(e - 1)): both pass the break test. The plant then aims at e - 1 with the value `mask` alone."""
+        keep = set()
+        if pair:
+            assert 69 <= e <= data.size, e
+            keep.add(e)
+            e -= 1
+        keep |= set(int(x) for x in self._local(data, e))
+        if pair:
+            data[e] = data[e - 64]
         assert 68 <= e <= data.size, e
         mask = np.uint64(self.mask)
-        keep = sorted(set(int(x) for x in self._local(data, e)) | {e})
+        keep = sorted(keep | {e})
         for attempt in range(16):
             if attempt:
                 # h(e + 32) takes the four bytes in front of e at the same rotations as h(e) (rotl by k and k + 32 agree):
                 # for some bytes around e every hit here is a hit there too. A byte that only h(e) sees breaks the tie.
                 q = e - 36 - int(self.rng.integers(0, 24))
                 data[q] = self.rng.integers(0, 256)
+                if pair:
+                    # h(e + 64) sees b[e] but none of the bytes the search sets: the pair's shared byte is re-drawn too; and
+                    # h(e + 2) = rotl(h(e), 2) passes as well when b[e + 1] = b[e - 63]: that byte is re-drawn as well
+                    data[e - 64] = data[e] = self.rng.integers(0, 256)
+                    data[e - 63] = self.rng.integers(0, 256)
             w = data[e - 64:e].copy()
             rest = window_hash(self.T, w)
             for j in range(60, 64):
                 rest ^= int(_rotl(self.T[int(w[j])], 63 - j))
             for _ in range(4):
-                r = self.rng.integers(0, 65536, 256)
+                # 256 right halves meet one of 65 536 left halves with probability 2^(24 - bits) each: enough up to 20 bits;
+                # wider masks (up to 29 bits at avg 2^28) search every right half (~2^(32 - bits) hits)
+                r = self.rng.integers(0, 65536, 256) if self.mask < (1 << 20) else self.rng.permutation(65536)
                 v = np.uint64(self.mask - int(self.rng.integers(0, 3)))      # mask, mask - 1 or mask - 2: the break test passes
+                if pair:
+                    v = np.uint64(self.mask)
                 want = (np.uint64(rest) ^ self.right[r] ^ v) & mask
                 pos = np.searchsorted(self.lsorted, want)
                 pos[pos >= self.lsorted.size] = 0
