@@ -479,9 +479,10 @@ int pbsgpu_xxh3_many_host(pbsgpu_engine *eng, const void *hptr, uint64_t nbytes,
                           const pbsgpu_segment *segs, uint32_t nseg, uint64_t *out);
 
 /* ---- digest-set operations (cross-file duplicate detection) -----------------
- * Sort records by digest on the device and flag duplicates: dup[i] = 1 when
- * an earlier record (lower index) carries the same digest. Used on the
- * all-gathered (digest, size) set of all ranks. */
+ * Flag duplicates on the device: dup[i] = 1 when an earlier record (lower index)
+ * carries the same digest; exact (all 32 bytes) and deterministic. This is the
+ * known-chunk set's classify (below) against an empty set, with insert = 0.
+ * Used on the all-gathered (digest, size) set of all ranks. */
 typedef struct pbsgpu_dedup_stats {
     uint64_t nrecords;
     uint64_t nunique;

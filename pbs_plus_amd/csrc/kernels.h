@@ -442,12 +442,6 @@ hipError_t launch_ring_service_lanes(const RingSource &q, unsigned workgroups, h
 hipError_t launch_ring_stop(RingCtl *ctl, hipStream_t st);
 hipError_t launch_ring_reset(RingCtl *ctl, hipStream_t st);
 
-// digest-set: sort keys/index pairs by the first 8 digest bytes (big-endian) and flag duplicates
-hipError_t launch_dedup(const pbsgpu_record *recs, uint64_t n, uint64_t *keys, uint32_t *idx,
-                        uint64_t *keys_alt, uint32_t *idx_alt, uint8_t *dup, uint64_t *stats4,
-                        void *tmp, size_t tmp_bytes, hipStream_t st);
-size_t dedup_tmp_bytes(uint64_t n);
-
 // payload-stream assembly: kind 0 = copy len bytes from src_base+src_off; kind 1 = 16-byte
 // {type = src_off, size = len} header at dst_off
 struct PackItem {

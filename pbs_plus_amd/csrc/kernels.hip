@@ -16,8 +16,6 @@
 #include <cstring>
 #include <type_traits>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 namespace pbsk {
 
 __device__ __forceinline__ void wave_sync() {
@@ -2641,87 +2639,6 @@ hipError_t launch_fill(void *dptr, uint64_t stream_off, uint64_t nbytes, uint64_
     if (blocks == 0) blocks = 1;
     hipLaunchKernelGGL(k_fill, dim3((unsigned)blocks), dim3(256), 0, st, (uint64_t *)dptr, stream_off >> 3, nwords,
                        seed, kind, (uint8_t *)dptr + nwords * 8, tail);
-    return hipGetLastError();
-}
-
-// =====================================================================================
-// digest-set duplicate detection (cross-file dedup over the all-gathered record set)
-// =====================================================================================
-// Sort (first 8 digest bytes, index) pairs with a stable radix sort, then a record is a
-// duplicate iff an earlier entry of its equal-prefix run carries the same 32-byte digest.
-__global__ __launch_bounds__(256) void k_dedup_keys(const pbsgpu_record *recs, uint64_t n, uint64_t *keys,
-                                                    uint32_t *idx) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint8_t *d = recs[i].digest;
-    uint64_t k = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) k = (k << 8) | d[b];
-    keys[i] = k;
-    idx[i] = (uint32_t)i;
-}
-
-__device__ __forceinline__ bool digest_eq(const pbsgpu_record *a, const pbsgpu_record *b) {
-    const uint32_t *x = reinterpret_cast<const uint32_t *>(a->digest);
-    const uint32_t *y = reinterpret_cast<const uint32_t *>(b->digest);
-    bool eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (x[i] == y[i]);
-    return eq;
-}
-
-__global__ __launch_bounds__(256) void k_dedup_mark(const pbsgpu_record *recs, uint64_t n, const uint64_t *keys,
-                                                    const uint32_t *idx, uint8_t *dup, uint64_t *stats4) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool is_dup = false;
-    uint64_t size = 0;
-    if (j < n) {
-        const pbsgpu_record *me = recs + idx[j];
-        size = me->size;
-        const uint64_t key = keys[j];
-        for (uint64_t q = j; q > 0 && keys[q - 1] == key; --q) {
-            if (digest_eq(me, recs + idx[q - 1])) {  // stable sort: idx[q-1] < idx[j]
-                is_dup = true;
-                break;
-            }
-        }
-        if (dup) dup[idx[j]] = is_dup ? 1 : 0;
-    }
-    // stats: [0] records, [1] unique, [2] total bytes, [3] unique bytes (wave-reduced atomics)
-    uint64_t c_all = (j < n) ? 1 : 0, c_uni = (j < n && !is_dup) ? 1 : 0;
-    uint64_t b_all = size, b_uni = is_dup ? 0 : size;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        c_all += __shfl_xor(c_all, d, 64);
-        c_uni += __shfl_xor(c_uni, d, 64);
-        b_all += __shfl_xor(b_all, d, 64);
-        b_uni += __shfl_xor(b_uni, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0 && c_all) {
-        atomicAdd(reinterpret_cast<unsigned long long *>(stats4 + 0), (unsigned long long)c_all);
-        atomicAdd(reinterpret_cast<unsigned long long *>(stats4 + 1), (unsigned long long)c_uni);
-        atomicAdd(reinterpret_cast<unsigned long long *>(stats4 + 2), (unsigned long long)b_all);
-        atomicAdd(reinterpret_cast<unsigned long long *>(stats4 + 3), (unsigned long long)b_uni);
-    }
-}
-
-size_t dedup_tmp_bytes(uint64_t n) {
-    size_t bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                    (uint32_t *)nullptr, (size_t)n, 0, 64, (hipStream_t)0);
-    return bytes + 256;
-}
-
-hipError_t launch_dedup(const pbsgpu_record *recs, uint64_t n, uint64_t *keys, uint32_t *idx, uint64_t *keys_alt,
-                        uint32_t *idx_alt, uint8_t *dup, uint64_t *stats4, void *tmp, size_t tmp_bytes,
-                        hipStream_t st) {
-    hipError_t e = hipMemsetAsync(stats4, 0, 4 * sizeof(uint64_t), st);
-    if (e != hipSuccess || n == 0) return e;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_dedup_keys, dim3(nb), dim3(256), 0, st, recs, n, keys, idx);
-    e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_alt, idx, idx_alt, (size_t)n, 0, 64, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_dedup_mark, dim3(nb), dim3(256), 0, st, recs, n, keys_alt, idx_alt, dup, stats4);
     return hipGetLastError();
 }
 

@@ -21,6 +21,9 @@
 //      occupied slot and claims an empty one with a 64-bit device-scope CAS on the tag, then writes the 32 bytes.
 //   Every read of a slot written by another workgroup happens in a LATER kernel on the same stream: the kernel boundary
 //   is the only ordering (no in-kernel acquire / release across the XCDs' L2s).
+//
+// The batch dedup (pbsgpu_dedup_host / _device) is the same marking with no table: k_known_keys in place of the lookup,
+// so every before[i] = 0 and known[i] = dup[i] — an earlier record of the batch carries the same digest.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "engine_internal.h"
@@ -53,6 +56,9 @@ __device__ __forceinline__ void known_load(const uint8_t *base, uint32_t stride,
     w[3] = q[3];
 }
 
+// 32-bit sort key: a mix of all 32 digest bytes (h = known_home(w))
+__device__ __forceinline__ uint32_t known_key(uint64_t h, const uint64_t w[4]) { return (uint32_t)known_mix(h ^ w[0]); }
+
 __device__ __forceinline__ bool known_slot_eq(const uint64_t *digs, uint64_t slot, const uint64_t w[4]) {
     const uint64_t *d = digs + slot * 4;
     return d[0] == w[0] && d[1] == w[1] && d[2] == w[2] && d[3] == w[3];
@@ -77,7 +83,19 @@ __global__ __launch_bounds__(256) void k_known_lookup(const uint8_t *base, uint3
         }
     }
     before[i] = found;
-    keys[i] = (uint32_t)known_mix(h ^ w[0]);
+    keys[i] = known_key(h, w);
+    idx[i] = (uint32_t)i;
+}
+
+// k_known_lookup without a table (the batch dedup): nothing is known before the call
+__global__ __launch_bounds__(256) void k_known_keys(const uint8_t *base, uint32_t stride, uint64_t n, uint32_t *keys,
+                                                    uint32_t *idx, uint8_t *before) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t w[4];
+    known_load(base, stride, i, w);
+    before[i] = 0;
+    keys[i] = known_key(known_home(w), w);
     idx[i] = (uint32_t)i;
 }
 
@@ -230,12 +248,11 @@ int grow(pbsgpu_known *k, uint64_t want, hipStream_t st) {
 }
 
 // Records (stride 48) or .didx entries (stride 40), host or device; `known` (host, may be NULL) and `stats` (may be NULL
-// for the add paths) as pbsgpu_known_classify_*.
-int known_common(pbsgpu_known *k, const uint8_t *src, uint32_t stride, bool on_device, uint64_t n, bool insert,
-                 uint8_t *known, pbsgpu_dedup_stats *stats) {
+// for the add paths) as pbsgpu_known_classify_*. k = NULL: no table, and insert is false — the batch dedup.
+int known_common(pbsgpu_engine *e, pbsgpu_known *k, const uint8_t *src, uint32_t stride, bool on_device, uint64_t n,
+                 bool insert, uint8_t *known, pbsgpu_dedup_stats *stats) {
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n == 0) return PBSGPU_OK;
-    pbsgpu_engine *e = k->eng;
     CHK(set_device(e));
     AuxLease lease(e);
     Slot *s = lease.s;
@@ -267,8 +284,11 @@ int known_common(pbsgpu_known *k, const uint8_t *src, uint32_t stride, bool on_d
     const uint64_t *hs = s->h_scalars.as<uint64_t>();
     const unsigned nb = blocks_for(n);
     HIPCHK(hipMemsetAsync(d_stats, 0, 32, st));
-    hipLaunchKernelGGL(pbsk::k_known_lookup, dim3(nb), dim3(256), 0, st, base, stride, n, k->tags.as<uint64_t>(),
-                       k->digs.as<uint64_t>(), k->slots - 1, keys, idx, d_before);
+    if (k)
+        hipLaunchKernelGGL(pbsk::k_known_lookup, dim3(nb), dim3(256), 0, st, base, stride, n, k->tags.as<uint64_t>(),
+                           k->digs.as<uint64_t>(), k->slots - 1, keys, idx, d_before);
+    else
+        hipLaunchKernelGGL(pbsk::k_known_keys, dim3(nb), dim3(256), 0, st, base, stride, n, keys, idx, d_before);
     HIPCHK(hipGetLastError());
     HIPCHK(rocprim::radix_sort_pairs(s->scan_tmp.p, tmp_bytes, keys, keys_alt, idx, idx_alt, (size_t)n, 0, 32, st));
     hipLaunchKernelGGL(pbsk::k_known_mark, dim3(nb), dim3(256), 0, st, base, stride, n, keys_alt, idx_alt, d_before,
@@ -350,13 +370,15 @@ int pbsgpu_known_count(const pbsgpu_known *k, uint64_t *n) {
 
 int pbsgpu_known_add_host(pbsgpu_known *k, const pbsgpu_record *recs, uint64_t n) {
     if (!k || (!recs && n) || n >= kMaxCount) return PBSGPU_E_INVALID;
-    return known_common(k, reinterpret_cast<const uint8_t *>(recs), sizeof(pbsgpu_record), false, n, true, nullptr, nullptr);
+    return known_common(k->eng, k, reinterpret_cast<const uint8_t *>(recs), sizeof(pbsgpu_record), false, n, true, nullptr,
+                        nullptr);
 }
 
 int pbsgpu_known_add_device(pbsgpu_known *k, const void *drecs, uint64_t n) {
     if (!k || (!drecs && n) || n >= kMaxCount) return PBSGPU_E_INVALID;
     if (n && !is_device_pointer(drecs)) return PBSGPU_E_INVALID;
-    return known_common(k, static_cast<const uint8_t *>(drecs), sizeof(pbsgpu_record), true, n, true, nullptr, nullptr);
+    return known_common(k->eng, k, static_cast<const uint8_t *>(drecs), sizeof(pbsgpu_record), true, n, true, nullptr,
+                        nullptr);
 }
 
 int pbsgpu_known_add_didx(pbsgpu_known *k, const uint8_t *didx, uint64_t nbytes) {
@@ -376,21 +398,37 @@ int pbsgpu_known_add_didx(pbsgpu_known *k, const uint8_t *didx, uint64_t nbytes)
         prev = end;
     }
     // the 40-byte entries go to the device as they are: the kernels read the digest at offset 8 of either layout
-    return known_common(k, ent, 40, false, n, true, nullptr, nullptr);
+    return known_common(k->eng, k, ent, 40, false, n, true, nullptr, nullptr);
+}
+
+int pbsgpu_dedup_host(pbsgpu_engine *e, const pbsgpu_record *recs, uint64_t n, uint8_t *dup,
+                      pbsgpu_dedup_stats *stats) {
+    if (!e || (!recs && n) || !stats || n >= kMaxCount) return PBSGPU_E_INVALID;
+    return known_common(e, nullptr, reinterpret_cast<const uint8_t *>(recs), sizeof(pbsgpu_record), false, n, false,
+                        dup, stats);
+}
+
+// the records are already in device memory (e.g. the output of an RCCL all-gather): no host round trip of the set
+int pbsgpu_dedup_device(pbsgpu_engine *e, const void *drecs, uint64_t n, uint8_t *dup, pbsgpu_dedup_stats *stats) {
+    if (!e || (!drecs && n) || !stats || n >= kMaxCount) return PBSGPU_E_INVALID;
+    if (n && !is_device_pointer(drecs)) return PBSGPU_E_INVALID;
+    return known_common(e, nullptr, static_cast<const uint8_t *>(drecs), sizeof(pbsgpu_record), true, n, false, dup,
+                        stats);
 }
 
 int pbsgpu_known_classify_host(pbsgpu_known *k, const pbsgpu_record *recs, uint64_t n, int insert, uint8_t *known,
                                pbsgpu_dedup_stats *stats) {
     if (!k || (!recs && n) || !stats || n >= kMaxCount) return PBSGPU_E_INVALID;
-    return known_common(k, reinterpret_cast<const uint8_t *>(recs), sizeof(pbsgpu_record), false, n, insert != 0, known,
-                        stats);
+    return known_common(k->eng, k, reinterpret_cast<const uint8_t *>(recs), sizeof(pbsgpu_record), false, n,
+                        insert != 0, known, stats);
 }
 
 int pbsgpu_known_classify_device(pbsgpu_known *k, const void *drecs, uint64_t n, int insert, uint8_t *known,
                                  pbsgpu_dedup_stats *stats) {
     if (!k || (!drecs && n) || !stats || n >= kMaxCount) return PBSGPU_E_INVALID;
     if (n && !is_device_pointer(drecs)) return PBSGPU_E_INVALID;
-    return known_common(k, static_cast<const uint8_t *>(drecs), sizeof(pbsgpu_record), true, n, insert != 0, known, stats);
+    return known_common(k->eng, k, static_cast<const uint8_t *>(drecs), sizeof(pbsgpu_record), true, n, insert != 0,
+                        known, stats);
 }
 
 }  // extern "C"

@@ -6,9 +6,9 @@
 //    (end, digest) records fall out in order, exactly what the module appends to the .didx.
 //    A client of the engine's page ring (ring.cpp) since round 4.
 //  * pbsgpu_chunker_* — upstream `scan(data) -> pos` compatibility (buzhash.Config's chunker).
-//  * pbsgpu_dedup_host — digest-set duplicate detection on the device.
 //  * pbsgpu_didx_*    — dynamic index encode/decode (commit_bottleneck_test.go:773-793).
 // All byte-stream work runs through the same HIP kernels as the batch path.
+// The batch dedup (pbsgpu_dedup_*) is in known.hip: the known-chunk set's marking with no table.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -1224,63 +1224,6 @@ int pbsgpu_gather_device(pbsgpu_engine *e, const void *src, uint64_t src_bytes, 
     HIPCHK(pbsk::launch_pack(static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst),
                              s->tile_slots.as<pbsk::PackItem>(), (uint32_t)items.size(), s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
-    return PBSGPU_OK;
-}
-
-// ---- digest-set duplicate detection ---------------------------------------------------------
-static int dedup_common(pbsgpu_engine *e, const pbsgpu_record *recs, bool on_device, uint64_t n, uint8_t *dup,
-                        pbsgpu_dedup_stats *stats);
-
-int pbsgpu_dedup_host(pbsgpu_engine *e, const pbsgpu_record *recs, uint64_t n, uint8_t *dup,
-                      pbsgpu_dedup_stats *stats) {
-    return dedup_common(e, recs, false, n, dup, stats);
-}
-
-// the records are already in device memory (e.g. the output of an RCCL all-gather): no host round trip of the set
-int pbsgpu_dedup_device(pbsgpu_engine *e, const void *drecs, uint64_t n, uint8_t *dup, pbsgpu_dedup_stats *stats) {
-    if (n && !is_device_pointer(drecs)) return PBSGPU_E_INVALID;
-    return dedup_common(e, static_cast<const pbsgpu_record *>(drecs), true, n, dup, stats);
-}
-
-static int dedup_common(pbsgpu_engine *e, const pbsgpu_record *recs, bool on_device, uint64_t n, uint8_t *dup,
-                        pbsgpu_dedup_stats *stats) {
-    if (!e || (!recs && n) || !stats) return PBSGPU_E_INVALID;
-    if (n >= (1ull << 32)) return PBSGPU_E_INVALID;
-    std::memset(stats, 0, sizeof(*stats));
-    if (n == 0) return PBSGPU_OK;
-    CHK(set_device(e));
-    AuxLease lease(e);
-    Slot *s = lease.s;
-    const size_t tmp_bytes = pbsk::dedup_tmp_bytes(n);
-    // layout inside slot buffers: recs | keys | keys_alt | idx | idx_alt | dup | stats | tmp
-    if (!on_device) CHK(s->recs.ensure((size_t)n * sizeof(pbsgpu_record)));
-    CHK(s->dense.ensure((size_t)n * 16 + 64));
-    CHK(s->tile_slots.ensure((size_t)n * 8 + 64));
-    CHK(s->tile_cnt.ensure((size_t)n + 64));
-    CHK(s->scalars.ensure(SC_COUNT * 4 + 64));
-    CHK(s->scan_tmp.ensure(tmp_bytes));
-    CHK(s->h_scalars.ensure(64));
-    const pbsgpu_record *drecs = recs;
-    if (!on_device) {
-        CHK(staged_h2d(*s, s->recs.p, recs, n * sizeof(pbsgpu_record), s->stream));
-        drecs = s->recs.as<pbsgpu_record>();
-    }
-    uint64_t *keys = s->dense.as<uint64_t>();
-    uint64_t *keys_alt = keys + n;
-    uint32_t *idx = s->tile_slots.as<uint32_t>();
-    uint32_t *idx_alt = idx + n;
-    uint8_t *d_dup = s->tile_cnt.as<uint8_t>();
-    uint64_t *d_stats = reinterpret_cast<uint64_t *>(s->scalars.as<uint8_t>() + 32);
-    HIPCHK(pbsk::launch_dedup(drecs, n, keys, idx, keys_alt, idx_alt, d_dup, d_stats,
-                              s->scan_tmp.p, tmp_bytes, s->stream));
-    HIPCHK(hipMemcpyAsync(s->h_scalars.p, d_stats, 32, hipMemcpyDeviceToHost, s->stream));
-    if (dup) HIPCHK(hipMemcpyAsync(dup, d_dup, (size_t)n, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    const uint64_t *hs = s->h_scalars.as<uint64_t>();
-    stats->nrecords = hs[0];
-    stats->nunique = hs[1];
-    stats->total_bytes = hs[2];
-    stats->unique_bytes = hs[3];
     return PBSGPU_OK;
 }
 

@@ -217,6 +217,51 @@ def test_host_and_device_variants_agree():
     eng.close()
 
 
+def test_batch_dedup_is_classify_against_an_empty_set():
+    """Engine.dedup / dedup_device (pbsgpu_dedup_*) give the flags and stats of classify(insert=False) on a fresh set,
+    and of the sequential model."""
+    from pbs_plus_amd import KnownChunks
+
+    rng = np.random.default_rng(17)
+    eng = _engine()
+    pre = _rand(rng, 40)
+    pre[:, :8] = pre[0, :8]                                        # 40 records sharing one 8-byte prefix ...
+    pre[[9, 17, 33]] = pre[[2, 5, 2]]                              # ... with repeated digests among them
+    n = 1 << 20
+    root = np.arange(n)
+    rep = rng.random(n) < 0.4                                      # ~40 % repeat a random earlier record
+    rep[0] = False
+    root[rep] = (rng.random(n) * np.arange(n)).astype(np.int64)[rep]
+    while not np.array_equal(root[root], root):
+        root = root[root]
+    k = KnownChunks(eng)
+    for batch in (_recs(_rand(rng, 0)), _recs(_rand(rng, 1)), _recs(pre), _recs(_rand(rng, n)[root], seed=3)):
+        want, wst, _ = _model(set(), batch, insert=False)
+        dup, st = eng.dedup(batch)
+        assert np.array_equal(dup, want) and st == wst, batch.size
+        buf = eng.alloc(batch.nbytes) if batch.size else None
+        if buf:
+            buf.upload(batch.view(np.uint8))
+        dptr = buf.ptr if buf else 0
+        dup_d, st_d = eng.dedup_device(dptr, batch.size)
+        assert np.array_equal(dup_d, want) and st_d == wst, batch.size
+        none, st_n = eng.dedup_device(dptr, batch.size, want_flags=False)
+        assert none is None and st_n == wst
+        kf, kst = k.classify(batch, insert=False)
+        assert np.array_equal(kf, want) and kst == wst, batch.size
+        if buf:
+            kf, kst = k.classify_device(buf.ptr, batch.size, insert=False)
+            assert np.array_equal(kf, want) and kst == wst, batch.size
+            buf.free()
+        if batch.size == 40:
+            assert wst["nunique"] == 37
+        if batch.size == n:
+            assert 0.35 < 1 - wst["nunique"] / n < 0.45, wst
+    assert len(k) == 0
+    k.close()
+    eng.close()
+
+
 def test_add_didx_loads_an_index_and_rejects_bad_images():
     from pbs_plus_amd import KnownChunks, PbsGpuError
 

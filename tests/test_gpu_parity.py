@@ -565,8 +565,8 @@ def test_incremental_rechunk_after_edits_keeps_boundaries_local(engines, O):
 
 
 def test_dedup_digest_prefix_collisions_are_not_duplicates(engines):
-    """The device dedup sorts by the first 8 digest bytes: records that share that prefix but differ
-    later are NOT duplicates (domain 'collision' case), true duplicates inside the same run are."""
+    """Records that share the first 8 digest bytes but differ later are NOT duplicates (domain 'collision'
+    case); true duplicates among them are. The device dedup compares all 32 bytes."""
     from pbs_plus_amd import RECORD_DTYPE
 
     eng = engines(4096)

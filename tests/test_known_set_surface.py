@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNOWN_SYMBOLS = ("pbsgpu_known_create", "pbsgpu_known_destroy", "pbsgpu_known_count", "pbsgpu_known_add_host",
                  "pbsgpu_known_add_device", "pbsgpu_known_add_didx", "pbsgpu_known_classify_host",
                  "pbsgpu_known_classify_device")
-KERNELS = ("k_known_lookup", "k_known_mark", "k_known_insert", "k_known_rehash")
+KERNELS = ("k_known_lookup", "k_known_keys", "k_known_mark", "k_known_insert", "k_known_rehash")
 
 
 @pytest.fixture(scope="module")
@@ -110,6 +110,28 @@ def test_argument_checks_need_no_device(L):
     # a host pointer handed to the _device variants
     assert L.pbsgpu_known_add_device(C.cast(fake, C.c_void_p), rec.ctypes.data, 1) == E
     assert L.pbsgpu_known_classify_device(C.cast(fake, C.c_void_p), rec.ctypes.data, 1, 0, None, C.byref(st)) == E
+
+
+def test_dedup_argument_checks_need_no_device(L):
+    """pbsgpu_dedup_host / _device (the set's marking with no table): E_INVALID for a NULL engine, NULL stats, NULL
+    records with n > 0, n >= 2^32 and a host pointer to the _device variant; n = 0 is OK with zeroed stats and touches
+    neither the engine nor the device."""
+    from pbs_plus_amd import _lib
+
+    E = _lib.E_INVALID
+    rec = np.zeros(1, dtype=_lib.RECORD_DTYPE)
+    st = _lib.DedupStats()
+    fake = C.cast(C.create_string_buffer(256), C.c_void_p)
+    for fn in (L.pbsgpu_dedup_host, L.pbsgpu_dedup_device):
+        assert fn(None, rec.ctypes.data, 1, None, C.byref(st)) == E
+        assert fn(None, None, 0, None, C.byref(st)) == E
+        assert fn(fake, rec.ctypes.data, 1, None, None) == E
+        assert fn(fake, None, 3, None, C.byref(st)) == E
+        assert fn(fake, rec.ctypes.data, 1 << 32, None, C.byref(st)) == E
+        st.nrecords = st.nunique = st.total_bytes = st.unique_bytes = 7
+        assert fn(fake, None, 0, None, C.byref(st)) == 0
+        assert (st.nrecords, st.nunique, st.total_bytes, st.unique_bytes) == (0, 0, 0, 0)
+    assert L.pbsgpu_dedup_device(fake, rec.ctypes.data, 1, None, C.byref(st)) == E
 
 
 def _didx_parts(ends, digests):
