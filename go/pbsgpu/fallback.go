@@ -156,3 +156,38 @@ func (k *KnownChunks) AddDynamicIndex([]byte) error                           { 
 func (k *KnownChunks) Classify([]ChunkInfo, bool) ([]bool, DedupStats, error) { return nil, DedupStats{}, ErrNotBuilt }
 func (k *KnownChunks) Len() int                                               { return 0 }
 func (k *KnownChunks) Close()                                                 {}
+
+// Blob kinds and VerifyBlobs statuses (PBSGPU_BLOB_*).
+const (
+	BlobUncompressed        = 0
+	BlobCompressed          = 1
+	BlobEncrypted           = 2
+	BlobEncryptedCompressed = 3
+
+	BlobOK        = 0
+	BlobBadMagic  = 1
+	BlobBadCRC    = 2
+	BlobBadSize   = 3
+	BlobBadDigest = 4
+	BlobCRCOnly   = 5
+)
+
+// BlobStats counts VerifyBlobs' statuses and the bytes checked.
+type BlobStats struct {
+	Count                            [6]uint64
+	BlobBytes, CRCBytes, SHA256Bytes uint64
+}
+
+func BlobMagic(int) ([8]byte, error)             { return [8]byte{}, ErrNotBuilt }
+func CRC32Combine(uint32, uint32, uint64) uint32 { return 0 }
+func BlobEncodedSize([]uint64) (uint64, error)   { return 0, ErrNotBuilt }
+func (e *Engine) CRC32Files([]byte, []uint64, []uint64) ([]uint32, error) { return nil, ErrNotBuilt }
+func (e *Engine) EncodeBlobsDevice(unsafe.Pointer, uint64, []uint64, []uint64, unsafe.Pointer, uint64) ([]uint64, []uint32, error) {
+	return nil, nil, ErrNotBuilt
+}
+func (e *Engine) VerifyBlobs([]byte, []uint64, []uint64, [][32]byte, []uint32) ([]uint8, BlobStats, error) {
+	return nil, BlobStats{}, ErrNotBuilt
+}
+func (e *Engine) VerifyBlobsDevice(unsafe.Pointer, uint64, []uint64, []uint64, [][32]byte, []uint32) ([]uint8, BlobStats, error) {
+	return nil, BlobStats{}, ErrNotBuilt
+}

@@ -1067,3 +1067,152 @@ func (e *Engine) DedupDevice(drecs uintptr, n uint64) ([]bool, DedupStats, error
 	}
 	return out, DedupStats{uint64(st.nrecords), uint64(st.nunique), uint64(st.total_bytes), uint64(st.unique_bytes)}, nil
 }
+
+// ---- data blobs: CRC-32, upload framing, chunk verification -------------------------------------------------------
+
+// Blob kinds (PBSGPU_BLOB_*) and the status VerifyBlobs reports per blob, in the order the checks run.
+const (
+	BlobUncompressed        = 0
+	BlobCompressed          = 1
+	BlobEncrypted           = 2
+	BlobEncryptedCompressed = 3
+
+	BlobOK        = 0 // every check passed
+	BlobBadMagic  = 1 // unknown magic, or shorter than its header
+	BlobBadCRC    = 2
+	BlobBadSize   = 3 // uncompressed: data length differs from the expected size
+	BlobBadDigest = 4 // uncompressed: SHA-256 differs from the expected digest
+	BlobCRCOnly   = 5 // compressed or encrypted with a good CRC: the content needs zstd / AES
+)
+
+// BlobStats counts VerifyBlobs' statuses (indexed by Blob*) and the bytes checked.
+type BlobStats struct {
+	Count                            [6]uint64
+	BlobBytes, CRCBytes, SHA256Bytes uint64
+}
+
+// BlobMagic is the 8-byte magic of a blob kind: the first 8 bytes of SHA-256 of its name (PBS data_blob.rs).
+func BlobMagic(kind int) ([8]byte, error) {
+	var out [8]byte
+	err := check(C.pbsgpu_blob_magic(C.int(kind), (*C.uint8_t)(unsafe.Pointer(&out[0]))), "blob_magic")
+	return out, err
+}
+
+// CRC32Combine is zlib's crc32_combine: crc32.ChecksumIEEE(A || B) from the checksums of A and B and len(B).
+func CRC32Combine(crcA, crcB uint32, lenB uint64) uint32 {
+	var out C.uint32_t
+	C.pbsgpu_crc32_combine(C.uint32_t(crcA), C.uint32_t(crcB), C.uint64_t(lenB), &out)
+	return uint32(out)
+}
+
+// BlobEncodedSize is the size of the uncompressed blobs of chunks of these lengths: the sum of 12 + length.
+func BlobEncodedSize(lengths []uint64) (uint64, error) {
+	segs, err := toSegments(make([]uint64, len(lengths)), lengths)
+	if err != nil {
+		return 0, err
+	}
+	var n C.uint64_t
+	var p *C.pbsgpu_segment
+	if len(segs) > 0 {
+		p = &segs[0]
+	}
+	err = check(C.pbsgpu_blob_encoded_size(p, C.uint32_t(len(segs)), &n), "blob_encoded_size")
+	return uint64(n), err
+}
+
+// CRC32Files is crc32.ChecksumIEEE of many chunks of one host buffer: the CRC an uploader puts into each chunk's blob
+// header (compress=false, internal/pxarmount/commit_orchestrate.go:137-149).
+func (e *Engine) CRC32Files(buf []byte, offsets, lengths []uint64) ([]uint32, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 {
+		return nil, errors.New("pbsgpu: CRC32Files needs matching, non-empty offsets/lengths")
+	}
+	out := make([]uint32, len(segs))
+	var base unsafe.Pointer
+	if len(buf) > 0 {
+		base = unsafe.Pointer(&buf[0])
+	}
+	err = check(C.pbsgpu_crc32_many_host(e.h, base, C.uint64_t(len(buf)), &segs[0], C.uint32_t(len(segs)),
+		(*C.uint32_t)(unsafe.Pointer(&out[0]))), "crc32_many_host")
+	runtime.KeepAlive(buf)
+	return out, err
+}
+
+// EncodeBlobsDevice writes the uncompressed blobs of the chunks (offsets, lengths) of device memory src back to back
+// into device memory dst. It returns each blob's offset in dst (one more entry: the total) and the chunks' CRCs; a dst
+// smaller than BlobEncodedSize is an error and nothing is written.
+func (e *Engine) EncodeBlobsDevice(src unsafe.Pointer, srcBytes uint64, offsets, lengths []uint64, dst unsafe.Pointer,
+	dstCap uint64) ([]uint64, []uint32, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 {
+		return nil, nil, errors.New("pbsgpu: EncodeBlobsDevice needs matching, non-empty offsets/lengths")
+	}
+	offs := make([]uint64, len(segs)+1)
+	crcs := make([]uint32, len(segs))
+	var total C.uint64_t
+	err = check(C.pbsgpu_blob_encode_device(e.h, src, C.uint64_t(srcBytes), &segs[0], C.uint32_t(len(segs)), dst,
+		C.uint64_t(dstCap), &total, (*C.uint64_t)(unsafe.Pointer(&offs[0])), (*C.uint32_t)(unsafe.Pointer(&crcs[0]))),
+		"blob_encode_device")
+	if err != nil {
+		return nil, nil, err
+	}
+	return offs, crcs, nil
+}
+
+func (e *Engine) verifyBlobs(device bool, base unsafe.Pointer, nbytes uint64, offsets, lengths []uint64,
+	digests [][32]byte, sizes []uint32) ([]uint8, BlobStats, error) {
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 || (digests != nil && len(digests) != len(segs)) || (sizes != nil && len(sizes) != len(segs)) {
+		return nil, BlobStats{}, errors.New("pbsgpu: VerifyBlobs needs matching, non-empty offsets/lengths/digests/sizes")
+	}
+	var dg *C.uint8_t
+	if digests != nil {
+		dg = (*C.uint8_t)(unsafe.Pointer(&digests[0][0]))
+	}
+	var sz *C.uint32_t
+	if sizes != nil {
+		sz = (*C.uint32_t)(unsafe.Pointer(&sizes[0]))
+	}
+	status := make([]uint8, len(segs))
+	var st C.pbsgpu_blob_stats
+	if device {
+		err = check(C.pbsgpu_blob_verify_device(e.h, base, C.uint64_t(nbytes), &segs[0], C.uint32_t(len(segs)), dg, sz,
+			(*C.uint8_t)(unsafe.Pointer(&status[0])), &st), "blob_verify_device")
+	} else {
+		err = check(C.pbsgpu_blob_verify_host(e.h, base, C.uint64_t(nbytes), &segs[0], C.uint32_t(len(segs)), dg, sz,
+			(*C.uint8_t)(unsafe.Pointer(&status[0])), &st), "blob_verify_host")
+	}
+	if err != nil {
+		return nil, BlobStats{}, err
+	}
+	var out BlobStats
+	for i := range out.Count {
+		out.Count[i] = uint64(st.count[i])
+	}
+	out.BlobBytes, out.CRCBytes, out.SHA256Bytes = uint64(st.blob_bytes), uint64(st.crc_bytes), uint64(st.sha_bytes)
+	return status, out, nil
+}
+
+// VerifyBlobs checks whole blobs of a host buffer as a chunk-store read does (datastore.NewChunkStore,
+// internal/server/verification/job.go:931): magic, CRC, then for uncompressed blobs the size and SHA-256 against the
+// index (digests and sizes may be nil: that check is skipped). The SHA-256 follows HashFiles' policy: one GPU lane per
+// chunk, so it pays with thousands of chunks per call.
+func (e *Engine) VerifyBlobs(buf []byte, offsets, lengths []uint64, digests [][32]byte, sizes []uint32) ([]uint8, BlobStats, error) {
+	defer runtime.KeepAlive(e)
+	var base unsafe.Pointer
+	if len(buf) > 0 {
+		base = unsafe.Pointer(&buf[0])
+	}
+	status, st, err := e.verifyBlobs(false, base, uint64(len(buf)), offsets, lengths, digests, sizes)
+	runtime.KeepAlive(buf)
+	return status, st, err
+}
+
+// VerifyBlobsDevice is VerifyBlobs on blobs in device memory.
+func (e *Engine) VerifyBlobsDevice(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, digests [][32]byte,
+	sizes []uint32) ([]uint8, BlobStats, error) {
+	defer runtime.KeepAlive(e)
+	return e.verifyBlobs(true, dptr, nbytes, offsets, lengths, digests, sizes)
+}

@@ -529,6 +529,74 @@ int pbsgpu_known_classify_host(pbsgpu_known *k, const pbsgpu_record *recs, uint6
 int pbsgpu_known_classify_device(pbsgpu_known *k, const void *drecs, uint64_t n, int insert,
                                  uint8_t *known /* host, n, may be NULL */, pbsgpu_dedup_stats *stats);
 
+/* ---- data blobs: CRC-32, upload framing and chunk verification -----------------------------------
+ * The "upload" step of the writer's inner loop and the chunk check of the read side. A PBS server takes
+ * a chunk as a data blob; the commit path uploads uncompressed ones (compress=false, commit_orchestrate.go:137-149):
+ *   [8-byte magic | CRC-32 of the bytes after the header, little endian | chunk bytes]        (12-byte header)
+ * The encrypted kinds add a 16-byte IV and a 16-byte tag (44-byte header). Each magic is the first 8 bytes of SHA-256 of
+ * the kind's name ("Proxmox Backup uncompressed blob v1.0", ...); the layout is recalled from PBS data_blob.rs [EXTERNAL].
+ * The read side (datastore.NewChunkStore / NewChunkStoreSource: internal/server/verification/job.go:931,
+ * internal/pxar/format.go:101, commit_orchestrate.go:356) checks a chunk as PBS verification does: CRC, decoded size
+ * against the index, SHA-256 against the index digest.
+ * The CRC is CRC-32/ISO-HDLC (zlib crc32, Go crc32.ChecksumIEEE): reflected 0xEDB88320, init and final xor 0xFFFFFFFF.
+ * Device work runs on a leased stream of the engine, so a call beside a running page-ring service does not wait for it. */
+#define PBSGPU_HAS_BLOB 1
+#define PBSGPU_BLOB_UNCOMPRESSED 0
+#define PBSGPU_BLOB_COMPRESSED 1          /* zstd */
+#define PBSGPU_BLOB_ENCRYPTED 2
+#define PBSGPU_BLOB_ENCRYPTED_COMPRESSED 3
+#define PBSGPU_BLOB_HEADER_SIZE 12u           /* uncompressed and compressed kinds */
+#define PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE 44u /* + IV[16] + tag[16] */
+/* verify status per blob, in the order the checks run */
+#define PBSGPU_BLOB_OK 0
+#define PBSGPU_BLOB_BAD_MAGIC 1   /* unknown magic, or shorter than its header */
+#define PBSGPU_BLOB_BAD_CRC 2
+#define PBSGPU_BLOB_BAD_SIZE 3    /* uncompressed: data length != sizes[i] */
+#define PBSGPU_BLOB_BAD_DIGEST 4  /* uncompressed: SHA-256 of the data != digests[i] */
+#define PBSGPU_BLOB_CRC_ONLY 5    /* compressed or encrypted, CRC good: the content needs zstd / AES (not done here) */
+#define PBSGPU_BLOB_NSTATUS 6
+typedef struct pbsgpu_blob_stats {
+    uint64_t count[PBSGPU_BLOB_NSTATUS]; /* blobs per status */
+    uint64_t blob_bytes;                 /* sum of the blob lengths */
+    uint64_t crc_bytes;                  /* bytes the CRC was computed over (every blob with a known magic and header) */
+    uint64_t sha_bytes;                  /* bytes hashed (uncompressed blobs, when digests are given) */
+} pbsgpu_blob_stats;
+/* out = the magic of `kind` (PBSGPU_BLOB_*); host only. */
+int pbsgpu_blob_magic(int kind, uint8_t out[8]);
+/* zlib's crc32_combine: *out = CRC-32(A || B) from crc_a = CRC-32(A), crc_b = CRC-32(B), len_b = |B|; host only. */
+int pbsgpu_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t *out);
+/* out[i] = CRC-32 of base[segs[i].offset .. +length) (any length, 0 included; any alignment; ranges may overlap): the
+ * header CRC of each chunk the commit path uploads (commit_orchestrate.go:137-149). The _host variant stages the bytes
+ * through pinned memory (the Go uploader's chunks live on the host). */
+int pbsgpu_crc32_many_device(pbsgpu_engine *eng, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                             uint32_t nseg, uint32_t *out /* nseg */);
+int pbsgpu_crc32_many_host(pbsgpu_engine *eng, const void *hptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                           uint32_t nseg, uint32_t *out);
+/* *nbytes = sum over segs of (12 + length): the size of their uncompressed blobs. E_INVALID on overflow; host only. */
+int pbsgpu_blob_encoded_size(const pbsgpu_segment *segs, uint32_t nseg, uint64_t *nbytes);
+/* The upload framing of the commit path (compress=false, commit_orchestrate.go:137-149):
+ * uncompressed blob i of the chunk segs[i] of device buffer src, written to device memory dst at offsets[i]
+ * (offsets[0] = 0, offsets[i + 1] = offsets[i] + 12 + length): [uncompressed magic | CRC-32 LE | bytes]. One pass: each
+ * chunk byte is read once, copied and folded into its CRC. *out_len = the encoded size, always; when dst_cap is smaller,
+ * E_CAPACITY and nothing is written. offsets (nseg + 1) and crcs (nseg) are host arrays and may be NULL. */
+int pbsgpu_blob_encode_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *segs,
+                              uint32_t nseg, void *dst, uint64_t dst_cap, uint64_t *out_len,
+                              uint64_t *offsets /* nseg + 1, may be NULL */, uint32_t *crcs /* nseg, may be NULL */);
+/* The chunk check of a chunk-store read (NewChunkStore: internal/server/verification/job.go:931,
+ * internal/pxar/format.go:101, commit_orchestrate.go:356). Verify whole blobs blobs[i] (offset, length) inside a buffer:
+ * magic and header length, then the CRC, then for uncompressed blobs the data length against sizes[i] and its SHA-256
+ * against digests[32 i] (either may be NULL: that check is skipped). status[i] = the first check that failed
+ * (PBSGPU_BLOB_*); stats (may be NULL) counts them.
+ * The SHA-256 runs through the pbsgpu_sha256_many_* kernels and their policy applies unchanged
+ * (pbsgpu_sha256_many_pays): one lane per chunk, so the batch wins with thousands of chunks, not with a handful. */
+int pbsgpu_blob_verify_device(pbsgpu_engine *eng, const void *dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                              uint32_t nblob, const uint8_t *digests /* 32 * nblob, may be NULL */,
+                              const uint32_t *sizes /* nblob, may be NULL */, uint8_t *status /* nblob */,
+                              pbsgpu_blob_stats *stats);
+int pbsgpu_blob_verify_host(pbsgpu_engine *eng, const void *hptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                            uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
+                            pbsgpu_blob_stats *stats);
+
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or
  * several engines in one process) ingests its own streams. The one exchange step is the digest-set reduce for cross-file

@@ -149,6 +149,85 @@ class KnownChunks {
     pbsgpu_known *k_;
 };
 
+// Data blobs (pbsgpu_crc32_* / pbsgpu_blob_*): the CRC-32 of the uploader's chunks, the uncompressed blobs of chunks in
+// device memory, and the chunk check of the read side (datastore.NewChunkStore: internal/server/verification/job.go:931).
+// Thin wrappers; the Go module's own blob types are not mirrored.
+namespace blob {
+
+// the 8-byte magic of a blob kind (PBSGPU_BLOB_UNCOMPRESSED ...)
+inline Result<std::array<uint8_t, 8>> Magic(int kind) {
+    Result<std::array<uint8_t, 8>> r;
+    const int st = pbsgpu_blob_magic(kind, r.value.data());
+    if (st != PBSGPU_OK) r.err = errorf("blob magic", st);
+    return r;
+}
+
+// crc32.ChecksumIEEE(A || B) from the two checksums and len(B) (zlib's crc32_combine)
+inline uint32_t CRC32Combine(uint32_t crcA, uint32_t crcB, uint64_t lenB) {
+    uint32_t out = 0;
+    pbsgpu_crc32_combine(crcA, crcB, lenB, &out);
+    return out;
+}
+
+// CRC-32 of every range of a host buffer (the uploader's chunks live on the host) or of a device buffer
+inline Result<std::vector<uint32_t>> CRC32Many(pbsgpu_engine *eng, const void *buf, uint64_t nbytes,
+                                               const std::vector<pbsgpu_segment> &segs, bool device = false) {
+    Result<std::vector<uint32_t>> r;
+    r.value.resize(segs.size());
+    const int st = device ? pbsgpu_crc32_many_device(eng, buf, nbytes, segs.data(), (uint32_t)segs.size(), r.value.data())
+                          : pbsgpu_crc32_many_host(eng, buf, nbytes, segs.data(), (uint32_t)segs.size(), r.value.data());
+    if (st != PBSGPU_OK) r.err = errorf("crc32 many", st);
+    return r;
+}
+
+inline Result<uint64_t> EncodedSize(const std::vector<pbsgpu_segment> &segs) {
+    Result<uint64_t> r;
+    const int st = pbsgpu_blob_encoded_size(segs.data(), (uint32_t)segs.size(), &r.value);
+    if (st != PBSGPU_OK) r.err = errorf("blob encoded size", st);
+    return r;
+}
+
+struct Encoded {
+    uint64_t bytes = 0;              // blob bytes written to dst
+    std::vector<uint64_t> offsets;   // blob i = dst[offsets[i], offsets[i + 1])
+    std::vector<uint32_t> crcs;
+};
+
+// uncompressed blobs of the chunks segs of device buffer src, back to back in device buffer dst
+inline Result<Encoded> EncodeDevice(pbsgpu_engine *eng, const void *src, uint64_t srcBytes,
+                                    const std::vector<pbsgpu_segment> &segs, void *dst, uint64_t dstCap) {
+    Result<Encoded> r;
+    r.value.offsets.resize(segs.size() + 1);
+    r.value.crcs.resize(segs.size());
+    const int st = pbsgpu_blob_encode_device(eng, src, srcBytes, segs.data(), (uint32_t)segs.size(), dst, dstCap,
+                                             &r.value.bytes, r.value.offsets.data(), r.value.crcs.data());
+    if (st != PBSGPU_OK) r.err = errorf("blob encode", st);
+    return r;
+}
+
+struct Verified {
+    std::vector<uint8_t> status;  // PBSGPU_BLOB_* per blob
+    pbsgpu_blob_stats stats{};
+};
+
+// check whole blobs of a host (or device) buffer; digests (32 per blob) and sizes may be empty: that check is skipped
+inline Result<Verified> Verify(pbsgpu_engine *eng, const void *buf, uint64_t nbytes, const std::vector<pbsgpu_segment> &blobs,
+                               const std::vector<uint8_t> &digests, const std::vector<uint32_t> &sizes,
+                               bool device = false) {
+    Result<Verified> r;
+    r.value.status.resize(blobs.size());
+    const uint8_t *dg = digests.empty() ? nullptr : digests.data();
+    const uint32_t *sz = sizes.empty() ? nullptr : sizes.data();
+    const int st = device ? pbsgpu_blob_verify_device(eng, buf, nbytes, blobs.data(), (uint32_t)blobs.size(), dg, sz,
+                                                      r.value.status.data(), &r.value.stats)
+                          : pbsgpu_blob_verify_host(eng, buf, nbytes, blobs.data(), (uint32_t)blobs.size(), dg, sz,
+                                                    r.value.status.data(), &r.value.stats);
+    if (st != PBSGPU_OK) r.err = errorf("blob verify", st);
+    return r;
+}
+
+}  // namespace blob
+
 // datastore.DynamicIndexReader
 class DynamicIndexReader {
   public:

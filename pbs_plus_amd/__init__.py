@@ -11,11 +11,15 @@ pbs-plus reference uses for its pxar stream path:
 * ``Chunker`` — upstream-style ``scan`` compatibility
 * ``didx`` / ``dedup`` / ``Comm`` — dynamic index records and the cross-GPU digest-set reduce (RCCL, behind the C ABI)
 * ``KnownChunks`` — the device-resident known-chunk set of an incremental session (which chunks to upload)
+* ``Engine.crc32_many`` / ``blob_encode`` / ``blob_verify`` — data-blob framing of the uploads and the chunk check
+  (``chunk_ranges`` turns records into the byte ranges of their chunks)
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
 from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
 from .engine import Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
+from .engine import blob_magic, chunk_ranges, crc32_combine  # noqa: F401
 
-__all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError"]
+__all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError",
+           "blob_magic", "chunk_ranges", "crc32_combine"]

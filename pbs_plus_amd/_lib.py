@@ -131,6 +131,16 @@ class DedupStats(C.Structure):
     ]
 
 
+BLOB_UNCOMPRESSED, BLOB_COMPRESSED, BLOB_ENCRYPTED, BLOB_ENCRYPTED_COMPRESSED = range(4)
+BLOB_HEADER_SIZE, BLOB_ENCRYPTED_HEADER_SIZE = 12, 44
+BLOB_OK, BLOB_BAD_MAGIC, BLOB_BAD_CRC, BLOB_BAD_SIZE, BLOB_BAD_DIGEST, BLOB_CRC_ONLY = range(6)
+BLOB_STATUS_NAMES = ("ok", "bad_magic", "bad_crc", "bad_size", "bad_digest", "crc_only")
+
+
+class BlobStats(C.Structure):
+    _fields_ = [("count", C.c_uint64 * 6), ("blob_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("sha_bytes", C.c_uint64)]
+
+
 # pbsgpu_record: 48 bytes, same layout as a DIDX entry + (segment, size)
 RECORD_DTYPE = np.dtype([("end", "<u8"), ("digest", "u1", (32,)), ("segment", "<u4"), ("size", "<u4")])
 assert RECORD_DTYPE.itemsize == 48
@@ -217,6 +227,14 @@ SYMBOLS = {
     "pbsgpu_known_add_didx": (C.c_int, [_P, _P, C.c_uint64]),
     "pbsgpu_known_classify_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.POINTER(DedupStats)]),
     "pbsgpu_known_classify_device": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.POINTER(DedupStats)]),
+    "pbsgpu_blob_magic": (C.c_int, [C.c_int, _P]),
+    "pbsgpu_crc32_combine": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "pbsgpu_crc32_many_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "pbsgpu_crc32_many_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "pbsgpu_blob_encoded_size": (C.c_int, [_P, C.c_uint32, _U64P]),
+    "pbsgpu_blob_encode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _U64P, _P, _P]),
+    "pbsgpu_blob_verify_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
+    "pbsgpu_blob_verify_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
     "pbsgpu_comm_unique_id": (C.c_int, [_P]),
     "pbsgpu_comm_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "pbsgpu_comm_destroy": (None, [_P]),

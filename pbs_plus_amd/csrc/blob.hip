@@ -1,0 +1,586 @@
+// Data blobs (pbsgpu_crc32_* / pbsgpu_blob_*, include/pbsgpu.h): the CRC-32 of many byte ranges, the uncompressed blob a
+// PBS server takes as a chunk upload, and the chunk check of the read side (magic, CRC, size, SHA-256).
+//
+// CRC-32/ISO-HDLC in the reflected form: a 32-bit word c stands for a polynomial of degree < 32 with bit 31 - i the
+// coefficient of x^i (x^0 = 0x80000000). raw(M) is the register after M with init 0 and no final xor; it is linear:
+//   raw(A || B) = raw(A) * x^(8|B|) + raw(B)            (mod P, GF(2))
+//   crc(M)      = raw(M) + 0xFFFFFFFF * x^(8|M|) + 0xFFFFFFFF
+// and leading zero bytes do not change raw(). gfx950 has no carry-less multiply in the VALU: products are 32 conditional
+// xor-shift steps (mul below), and the byte-wise work is table lookups from LDS.
+//
+// Two kernels over a host plan (the shape of k_xxh3_sums + k_xxh3):
+//   k_crc_pieces  every segment is cut into pieces of kPiece = 64 KiB aligned at the segment's END (only the first piece
+//                 of a segment is short); one wave per piece. The piece is seen as rows of kRow = 1024 bytes, zero-padded
+//                 in FRONT to whole rows (raw() unchanged). In row r, lane l owns the 16 bytes at 1024 r + 16 l: one
+//                 coalesced 1 KiB load per row and wave. A lane runs slice-by-16 over the stream
+//                 S_l = blk(0,l) 0^1008 blk(1,l) 0^1008 ...: its 16 tables T_m[b] = raw(b) * x^(8 (m + 1008)) fold the
+//                 1008 bytes of the other lanes into the lookup, so a row costs a lane 16 LDS reads, as plain
+//                 slice-by-16 does. The piece is then raw(piece) = sum_l raw(S_l) * x^(-128 l) (x is invertible mod P):
+//                 one product per lane and a wave-wide xor.
+//                 The init value is folded in here too: the segment's first four bytes enter the CRC inverted, which
+//                 adds 0xFFFFFFFF * x^(8|M|) (segments of 1-3 bytes take that term in the fold instead).
+//   k_crc_fold    one wave per segment: its pieces right to left in blocks of 64 lanes, a 6-level xor tree whose left
+//                 halves are shifted by x^(8 kPiece 2^k) (the right half of every merge holds only whole pieces, since
+//                 the short piece is the segment's first), then Horner over the blocks; final xor; the blob header.
+// The encode pass is the same pair with a destination: the piece kernel stores every loaded row at the blob's data
+// position (arbitrary alignment, one row and lane at a time) and the fold writes the 12-byte header.
+// Memory instructions: global_* only (address-space-1 pointers); no scratch (tests/test_blob_surface.py).
+#include "engine_internal.h"
+
+using namespace pbse;
+
+namespace pbsk {
+namespace crc {
+
+constexpr uint32_t kPoly = 0xEDB88320u;
+constexpr uint32_t kOne = 0x80000000u;  // x^0
+constexpr uint32_t kXInv = ((kPoly << 1) & 0xffffffffu) | 1u;  // x^-1 = (P - 1) / x
+constexpr uint32_t kRow = 1024;
+constexpr uint32_t kGap = kRow - 16;
+constexpr uint32_t kPieceLog = 16;
+constexpr uint64_t kPiece = 1ull << kPieceLog;
+constexpr uint32_t kFoldLanes = 64;
+
+__host__ __device__ constexpr uint32_t mul(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+#pragma unroll
+    for (int i = 31; i >= 0; --i) {
+        p ^= b & (0u - ((a >> i) & 1u));
+        b = (b >> 1) ^ (kPoly & (0u - (b & 1u)));
+    }
+    return p;
+}
+
+struct Consts {
+    uint32_t x8[64];     // x^(8 * 2^j)
+    uint32_t klane[64];  // x^(-128 l): lane l's share of a piece
+    uint32_t small[4];   // x^(8 L), L < 4
+    uint32_t gap;        // x^(8 kGap)
+};
+
+__host__ __device__ constexpr uint32_t pow_from(const uint32_t (&x8)[64], uint64_t bytes) {  // x^(8 bytes)
+    uint32_t r = kOne;
+    for (int j = 0; j < 64; ++j)
+        if ((bytes >> j) & 1u) r = mul(r, x8[j]);
+    return r;
+}
+
+constexpr Consts make_consts() {
+    Consts c{};
+    uint32_t x = 1u << 30;  // x^1
+    for (int i = 0; i < 3; ++i) x = mul(x, x);  // x^8
+    for (int j = 0; j < 64; ++j) {
+        c.x8[j] = x;
+        x = mul(x, x);
+    }
+    uint32_t inv128 = kXInv;
+    for (int i = 0; i < 7; ++i) inv128 = mul(inv128, inv128);  // x^-128
+    c.klane[0] = kOne;
+    for (int l = 1; l < 64; ++l) c.klane[l] = mul(c.klane[l - 1], inv128);
+    for (int l = 0; l < 4; ++l) c.small[l] = pow_from(c.x8, (uint64_t)l);
+    c.gap = pow_from(c.x8, kGap);
+    return c;
+}
+
+__device__ constexpr Consts kDev = make_consts();
+constexpr Consts kHost = make_consts();
+
+// the plan one launch pair works on (host-built, device arrays)
+struct Plan {
+    const uint8_t *src;
+    const pbsgpu_segment *segs;  // nseg ranges of src
+    const uint64_t *pbase;       // nseg + 1: index of each segment's first piece
+    const uint32_t *pseg;        // npieces: segment of each piece
+    uint32_t *praw;              // npieces: raw CRC of each piece
+    uint32_t *crcs;              // nseg: the result
+    uint8_t *dst;                // encode: blobs (nullptr: CRC only)
+    const uint64_t *doff;        // encode: offset of blob i in dst
+    uint64_t npieces;
+    uint32_t nseg;
+    uint32_t magic_lo, magic_hi;  // encode: the header's magic (little endian words)
+};
+
+// every access goes through a global-address-space pointer: a generic one compiles to flat_* 
+#define CRC_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+typedef const CRC_GLOBAL uint8_t *gbyte_ptr;
+typedef const CRC_GLOBAL uint32_t *gword_ptr;
+typedef const CRC_GLOBAL uint64_t *gquad_ptr;
+typedef const CRC_GLOBAL u32x4_a4 *gvec4_ptr;
+typedef CRC_GLOBAL uint8_t *gbyte_out;
+typedef CRC_GLOBAL uint16_t *ghalf_out;
+typedef CRC_GLOBAL uint32_t *gword_out;
+typedef CRC_GLOBAL u32x3_a4 *gvec3_out;
+typedef CRC_GLOBAL u32x4_a4 *gvec4_out;
+
+// 16 bytes at q; s = q & 3 (wave-uniform: every lane's q has the same alignment). The dwords read are the ones that hold
+// a byte of [q, q + 16), so nothing outside the pages of the range is touched.
+__device__ __forceinline__ void load16(const uint8_t *q, uint32_t s, uint32_t (&w)[4]) {
+    const gvec4_ptr a = (gvec4_ptr)(q - s);
+    const u32x4_a4 t = a[0];
+    if (s == 0) {
+        w[0] = t.x;
+        w[1] = t.y;
+        w[2] = t.z;
+        w[3] = t.w;
+    } else {
+        const uint32_t e = ((gword_ptr)(q - s))[4];
+        w[0] = __builtin_amdgcn_alignbyte(t.y, t.x, s);
+        w[1] = __builtin_amdgcn_alignbyte(t.z, t.y, s);
+        w[2] = __builtin_amdgcn_alignbyte(t.w, t.z, s);
+        w[3] = __builtin_amdgcn_alignbyte(e, t.w, s);
+    }
+}
+
+// 16 bytes to o; s = o & 3 (wave-uniform): head bytes up to a dword boundary, three (or four) aligned dwords, tail bytes
+__device__ __forceinline__ void store16(uint8_t *o, uint32_t s, const uint32_t (&w)[4]) {
+    if (s == 0) {
+        u32x4_a4 v;
+        v.x = w[0];
+        v.y = w[1];
+        v.z = w[2];
+        v.w = w[3];
+        *(gvec4_out)o = v;
+        return;
+    }
+    const uint32_t h = 4 - s;  // head bytes
+    u32x3_a4 v;
+    v.x = __builtin_amdgcn_alignbyte(w[1], w[0], h);
+    v.y = __builtin_amdgcn_alignbyte(w[2], w[1], h);
+    v.z = __builtin_amdgcn_alignbyte(w[3], w[2], h);
+    if (h & 1) ((gbyte_out)o)[0] = (uint8_t)w[0];
+    if (h & 2) *(ghalf_out)(o + (h & 1)) = (uint16_t)(w[0] >> (8 * (h & 1)));
+    *(gvec3_out)(o + h) = v;
+    const uint32_t t = w[3] >> (8 * h);  // the last s bytes
+    if (s & 2) *(ghalf_out)(o + 12 + h) = (uint16_t)t;
+    if (s & 1) ((gbyte_out)o)[15] = (uint8_t)(t >> (8 * (s & 2)));
+}
+
+// one row of a lane's stream: c = raw(S) after 16 more bytes and the 1008 of the other lanes
+__device__ __forceinline__ uint32_t step(const uint32_t (*tab)[256], uint32_t c, const uint32_t (&w)[4]) {
+    const uint32_t t = c ^ w[0];
+    return tab[15][t & 255] ^ tab[14][(t >> 8) & 255] ^ tab[13][(t >> 16) & 255] ^ tab[12][t >> 24] ^
+           tab[11][w[1] & 255] ^ tab[10][(w[1] >> 8) & 255] ^ tab[9][(w[1] >> 16) & 255] ^ tab[8][w[1] >> 24] ^
+           tab[7][w[2] & 255] ^ tab[6][(w[2] >> 8) & 255] ^ tab[5][(w[2] >> 16) & 255] ^ tab[4][w[2] >> 24] ^
+           tab[3][w[3] & 255] ^ tab[2][(w[3] >> 8) & 255] ^ tab[1][(w[3] >> 16) & 255] ^ tab[0][w[3] >> 24];
+}
+
+// a lane's 16 bytes at piece position pos in the rows that need care: padding in front of the piece (pos < 0: zeros, the
+// lane that straddles the start goes byte by byte) and the segment's first four bytes, which enter inverted ([0, inv))
+struct Row {
+    uint32_t w[4];
+};
+__device__ __forceinline__ Row row_edge(const uint8_t *d, uint8_t *o, int32_t pos, uint32_t sd, uint32_t so, uint32_t inv) {
+    Row x{{0, 0, 0, 0}};
+    if (pos >= 0) {
+        load16(d + pos, sd, x.w);
+        if (o) store16(o + pos, so, x.w);
+    } else if (pos > -16) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {  // (fixed bounds: the words stay in registers)
+            if (pos + j < 0) continue;
+            const uint8_t v = ((gbyte_ptr)d)[pos + j];
+            x.w[j >> 2] |= (uint32_t)v << (8 * (j & 3));
+            if (o) ((gbyte_out)o)[pos + j] = v;
+        }
+    }
+    if (pos < (int32_t)inv) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (pos + j >= 0 && pos + j < (int32_t)inv) x.w[j >> 2] ^= 0xffu << (8 * (j & 3));
+    }
+    return x;
+}
+
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v ^= __shfl_xor(v, d, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_crc_pieces(Plan pl) {
+    // tab[m] = T_m (m = 0..15), tab[16] = the byte table raw(b)
+    __shared__ uint32_t tab[17][256];
+    {
+        const uint32_t b = threadIdx.x;
+        uint32_t c = b;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
+        tab[16][b] = c;
+        uint32_t t = mul(c, kDev.gap);
+        tab[0][b] = t;
+        __syncthreads();
+        for (int m = 1; m < 16; ++m) {  // one more zero byte: the plain CRC step
+            t = (t >> 8) ^ tab[16][t & 255];
+            tab[m][b] = t;
+        }
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t kl = kDev.klane[lane];
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    for (uint64_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.npieces; p += nw) {
+        const uint32_t i = ((gword_ptr)pl.pseg)[p];
+        const uint64_t b0 = ((gquad_ptr)pl.pbase)[i];
+        const uint64_t m = ((gquad_ptr)pl.pbase)[i + 1] - b0;
+        const pbsgpu_segment sg{((gquad_ptr)pl.segs)[2 * i], ((gquad_ptr)pl.segs)[2 * i + 1]};
+        const uint64_t hi = sg.length - (m - 1 - (p - b0)) * kPiece;  // piece = segment bytes [lo, hi)
+        const uint64_t lo = hi > kPiece ? hi - kPiece : 0;
+        const uint32_t n = (uint32_t)(hi - lo);
+        const uint32_t rows = (n + kRow - 1) / kRow;
+        const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
+        const uint8_t *d = pl.src + sg.offset + lo;
+        uint8_t *o = pl.dst ? pl.dst + ((gquad_ptr)pl.doff)[i] + PBSGPU_BLOB_HEADER_SIZE + lo : nullptr;
+        const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
+        const uint32_t so = (uint32_t)((uintptr_t)o - z) & 3u;
+        // bytes [0, inv) of the piece are the segment's first four: they enter inverted (the init value)
+        const uint32_t inv = (sg.length >= 4 && lo < 4) ? (uint32_t)((hi < 4 ? hi : 4) - lo) : 0u;
+        uint32_t c = step(tab, 0u, row_edge(d, o, (int32_t)(16 * lane) - (int32_t)z, sd, so, inv).w);
+        uint32_t r = 1;
+        if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
+            c = step(tab, c, row_edge(d, o, (int32_t)(kRow + 16 * lane) - (int32_t)z, sd, so, inv).w);
+            r = 2;
+        }
+        for (; r + 4 <= rows; r += 4) {
+            uint32_t w[4][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (o) store16(o + (r + k) * kRow + 16 * lane - z, so, w[k]);
+                c = step(tab, c, w[k]);
+            }
+        }
+        for (; r < rows; ++r) {
+            uint32_t w[4];
+            load16(d + r * kRow + 16 * lane - z, sd, w);
+            if (o) store16(o + r * kRow + 16 * lane - z, so, w);
+            c = step(tab, c, w);
+        }
+        const uint32_t v = wave_xor(mul(c, kl));
+        if (lane == 0) ((gword_out)pl.praw)[p] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_crc_fold(Plan pl) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < pl.nseg; i += nw) {
+        const uint64_t b0 = ((gquad_ptr)pl.pbase)[i];
+        const uint64_t m = ((gquad_ptr)pl.pbase)[i + 1] - b0;
+        const uint64_t len = ((gquad_ptr)pl.segs)[2 * i + 1];
+        const gword_ptr raw = (gword_ptr)pl.praw + b0;
+        uint32_t acc = 0;
+        if (m == 1) {
+            acc = raw[0];
+        } else if (m > 1) {
+            for (uint64_t blk = (m - 1) / kFoldLanes + 1; blk-- > 0;) {  // left to right: Horner over 64-piece blocks
+                const uint64_t q = blk * kFoldLanes + lane;              // q = pieces from the segment's end
+                uint32_t v = q < m ? raw[m - 1 - q] : 0u;
+#pragma unroll
+                for (int lv = 0; lv < 6; ++lv) {  // the lane with bit lv clear holds the right (later) half
+                    const uint32_t u = __shfl_xor(v, 1 << lv, 64);
+                    if (!(lane & (1u << lv))) v ^= mul(u, kDev.x8[kPieceLog + lv]);
+                }
+                acc = mul(acc, kDev.x8[kPieceLog + 6]) ^ __shfl(v, 0, 64);
+            }
+        }
+        const uint32_t crc = (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+        if (lane == 0) ((gword_out)pl.crcs)[i] = crc;
+        if (pl.dst && lane < PBSGPU_BLOB_HEADER_SIZE) {
+            const uint32_t word = lane < 4 ? pl.magic_lo : lane < 8 ? pl.magic_hi : crc;
+            ((gbyte_out)pl.dst)[((gquad_ptr)pl.doff)[i] + lane] = (uint8_t)(word >> (8 * (lane & 3)));
+        }
+    }
+}
+
+// the first min(len, 12) bytes of every blob (verify_device: the host parses the headers)
+__global__ __launch_bounds__(256) void k_blob_heads(const uint8_t *src, const pbsgpu_segment *blobs, uint32_t n,
+                                                    uint8_t *heads) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)n * PBSGPU_BLOB_HEADER_SIZE) return;
+    const uint32_t i = (uint32_t)(t / PBSGPU_BLOB_HEADER_SIZE), j = (uint32_t)(t % PBSGPU_BLOB_HEADER_SIZE);
+    const pbsgpu_segment b{((gquad_ptr)blobs)[2 * i], ((gquad_ptr)blobs)[2 * i + 1]};
+    ((gbyte_out)heads)[t] = j < b.length ? ((gbyte_ptr)src)[b.offset + j] : 0;
+}
+
+}  // namespace crc
+}  // namespace pbsk
+
+namespace {
+
+using namespace pbsk::crc;
+
+// SHA-256("Proxmox Backup ... blob v1.0")[0..8): uncompressed, zstd compressed, encrypted, zstd compressed encrypted
+constexpr uint8_t kMagic[4][8] = {{66, 171, 56, 7, 190, 131, 112, 161},
+                                  {49, 185, 88, 66, 111, 182, 163, 127},
+                                  {123, 103, 133, 190, 34, 45, 76, 240},
+                                  {230, 89, 27, 191, 11, 191, 216, 11}};
+
+int magic_kind(const uint8_t *h) {
+    for (int k = 0; k < 4; ++k)
+        if (std::memcmp(h, kMagic[k], 8) == 0) return k;
+    return -1;
+}
+
+uint64_t header_size(int kind) {
+    return kind >= PBSGPU_BLOB_ENCRYPTED ? PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE : PBSGPU_BLOB_HEADER_SIZE;
+}
+
+bool ranges_ok(const pbsgpu_segment *segs, uint32_t nseg, uint64_t nbytes) {
+    for (uint32_t i = 0; i < nseg; ++i)
+        if (segs[i].length > nbytes || segs[i].offset > nbytes - segs[i].length) return false;
+    return true;
+}
+
+uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+// CRC of the nseg ranges already in s->segs over device bytes d; optionally the encode destination. crcs_dev = the
+// device result array (nseg u32). Enqueued on the slot's stream, nothing synchronised.
+int enqueue_crc(pbsgpu_engine *e, Slot *s, const uint8_t *d, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *dst,
+                const uint64_t *offsets, uint32_t **crcs_dev) {
+    std::vector<uint64_t> pbase((size_t)nseg + 1);
+    uint64_t np = 0;
+    for (uint32_t i = 0; i < nseg; ++i) {
+        pbase[i] = np;
+        np += (segs[i].length + kPiece - 1) >> kPieceLog;
+    }
+    pbase[nseg] = np;
+    if (np >= (1ull << 32)) return PBSGPU_E_INVALID;  // > 256 TiB of pieces in one call
+    std::vector<uint32_t> pseg((size_t)np);
+    for (uint32_t i = 0; i < nseg; ++i)
+        for (uint64_t p = pbase[i]; p < pbase[i + 1]; ++p) pseg[p] = i;
+    CHK(s->seg_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
+    CHK(s->tile_cnt.ensure(np * sizeof(uint32_t) + 64));
+    CHK(s->dense.ensure(np * sizeof(uint32_t) + 64));
+    CHK(s->seg_cnt.ensure((size_t)nseg * sizeof(uint32_t) + 64));
+    CHK(staged_h2d(*s, s->seg_off.p, pbase.data(), (nseg + 1) * sizeof(uint64_t), s->stream));
+    if (np) CHK(staged_h2d(*s, s->tile_cnt.p, pseg.data(), np * sizeof(uint32_t), s->stream));
+    Plan pl{};
+    pl.src = d;
+    pl.segs = s->segs.as<pbsgpu_segment>();
+    pl.pbase = s->seg_off.as<uint64_t>();
+    pl.pseg = s->tile_cnt.as<uint32_t>();
+    pl.praw = s->dense.as<uint32_t>();
+    pl.crcs = s->seg_cnt.as<uint32_t>();
+    pl.npieces = np;
+    pl.nseg = nseg;
+    if (dst) {
+        CHK(s->tile_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
+        CHK(staged_h2d(*s, s->tile_off.p, offsets, (nseg + 1) * sizeof(uint64_t), s->stream));
+        pl.dst = dst;
+        pl.doff = s->tile_off.as<uint64_t>();
+        pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
+        pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
+    }
+    if (np) {
+        // 8 workgroups per CU (17 KiB of tables each); every workgroup builds its tables once
+        const uint64_t wg = std::min<uint64_t>((np + 3) / 4, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pbsk::crc::k_crc_pieces, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
+    const uint64_t wg = std::min<uint64_t>((nseg + 3) / 4, (uint64_t)e->num_cus * 16);
+    hipLaunchKernelGGL(pbsk::crc::k_crc_fold, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
+    HIPCHK(hipGetLastError());
+    *crcs_dev = pl.crcs;
+    return PBSGPU_OK;
+}
+
+int crc32_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs, uint32_t nseg,
+               uint32_t *out) {
+    if (!e || (!ptr && nbytes) || (nseg && (!segs || !out))) return PBSGPU_E_INVALID;
+    if (!ranges_ok(segs, nseg, nbytes)) return PBSGPU_E_INVALID;
+    if (nseg == 0) return PBSGPU_OK;
+    if (!host && nbytes && !is_device_pointer(ptr)) return PBSGPU_E_INVALID;
+    CHK(set_device(e));
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const uint8_t *d = nullptr;
+    CHK(stage_ranges(e, s, ptr, host, nbytes, segs, nseg, &d));
+    uint32_t *crcs = nullptr;
+    CHK(enqueue_crc(e, s, d, segs, nseg, nullptr, nullptr, &crcs));
+    return fetch_result(s, out, crcs, (size_t)nseg * 4);
+}
+
+int encoded_size(const pbsgpu_segment *segs, uint32_t nseg, uint64_t *nbytes, uint64_t *offsets) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nseg; ++i) {
+        if (offsets) offsets[i] = total;
+        const uint64_t b = segs[i].length + PBSGPU_BLOB_HEADER_SIZE;
+        if (b < segs[i].length || total + b < total) return PBSGPU_E_INVALID;
+        total += b;
+    }
+    if (offsets) offsets[nseg] = total;
+    *nbytes = total;
+    return PBSGPU_OK;
+}
+
+int blob_verify(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t n,
+                const uint8_t *digests, const uint32_t *sizes, uint8_t *status, pbsgpu_blob_stats *stats) {
+    if (!e || (!ptr && nbytes) || (n && (!blobs || !status))) return PBSGPU_E_INVALID;
+    if (!ranges_ok(blobs, n, nbytes)) return PBSGPU_E_INVALID;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return PBSGPU_OK;
+    if (!host && nbytes && !is_device_pointer(ptr)) return PBSGPU_E_INVALID;
+    CHK(set_device(e));
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    // 1. the headers, on the host
+    std::vector<uint8_t> heads((size_t)n * PBSGPU_BLOB_HEADER_SIZE);
+    if (host) {
+        const uint8_t *h = static_cast<const uint8_t *>(ptr);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t j = 0; j < PBSGPU_BLOB_HEADER_SIZE; ++j)
+                heads[(size_t)i * PBSGPU_BLOB_HEADER_SIZE + j] = j < blobs[i].length ? h[blobs[i].offset + j] : 0;
+    } else {
+        const uint8_t *d = nullptr;
+        CHK(stage_ranges(e, s, ptr, false, nbytes, blobs, n, &d));
+        CHK(s->tile_slots.ensure(heads.size() + 64));
+        const uint64_t threads = heads.size();
+        hipLaunchKernelGGL(pbsk::crc::k_blob_heads, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s->stream, d,
+                           s->segs.as<pbsgpu_segment>(), n, s->tile_slots.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+        CHK(fetch_result(s, heads.data(), s->tile_slots.p, heads.size()));  // (synchronises: the slot's tables are free)
+    }
+    // 2. data ranges of the blobs with a known magic and a whole header: uncompressed ones first (the SHA-256 batch is a
+    // prefix of the CRC batch)
+    std::vector<int> kind(n);
+    std::vector<pbsgpu_segment> data;
+    std::vector<uint32_t> which;
+    data.reserve(n);
+    which.reserve(n);
+    for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t i = 0; i < n; ++i) {
+            if (pass == 0) {
+                const int k = blobs[i].length >= 8 ? magic_kind(&heads[(size_t)i * PBSGPU_BLOB_HEADER_SIZE]) : -1;
+                kind[i] = (k >= 0 && blobs[i].length >= header_size(k)) ? k : -1;
+            }
+            if (kind[i] < 0 || (kind[i] == PBSGPU_BLOB_UNCOMPRESSED) != (pass == 0)) continue;
+            const uint64_t hdr = header_size(kind[i]);
+            data.push_back(pbsgpu_segment{blobs[i].offset + hdr, blobs[i].length - hdr});
+            which.push_back(i);
+        }
+    uint32_t nunc = 0;
+    while (nunc < which.size() && kind[which[nunc]] == PBSGPU_BLOB_UNCOMPRESSED) ++nunc;
+    const uint32_t nd = (uint32_t)data.size();
+    std::vector<uint32_t> crc(nd);
+    std::vector<uint8_t> dig(digests ? (size_t)nunc * 32 : 0);
+    if (nd) {
+        const uint8_t *d = nullptr;
+        CHK(stage_ranges(e, s, ptr, host, nbytes, data.data(), nd, &d));
+        uint32_t *crcs = nullptr;
+        CHK(enqueue_crc(e, s, d, data.data(), nd, nullptr, nullptr, &crcs));
+        if (digests && nunc) {
+            uint64_t total_blocks = 0, longest = 1;
+            for (uint32_t j = 0; j < nunc; ++j) {
+                const uint64_t blocks = (data[j].length + 8) / 64 + 1;
+                total_blocks += blocks;
+                longest = std::max(longest, blocks);
+            }
+            CHK(s->recs.ensure((size_t)nunc * 32 + 64));
+            HIPCHK(pbsk::launch_sha256_segments(d, s->segs.as<pbsgpu_segment>(), nunc, s->recs.as<uint8_t>(),
+                                                s->scalars.as<uint32_t>() + SC_QUEUE, e->num_cus,
+                                                pbsk::sha256_dense_pays(total_blocks, longest, e->num_cus, e->opt.sha_dense_pct),
+                                                (int)e->opt.sha_form, s->stream));
+        }
+        CHK(fetch_result(s, crc.data(), crcs, (size_t)nd * 4));
+        if (digests && nunc) CHK(fetch_result(s, dig.data(), s->recs.p, (size_t)nunc * 32));
+    }
+    // 3. the statuses, in the order of the checks
+    pbsgpu_blob_stats st{};
+    for (uint32_t i = 0; i < n; ++i) {
+        status[i] = PBSGPU_BLOB_BAD_MAGIC;
+        st.blob_bytes += blobs[i].length;
+    }
+    for (uint32_t j = 0; j < nd; ++j) {
+        const uint32_t i = which[j];
+        st.crc_bytes += data[j].length;
+        uint8_t r;
+        if (crc[j] != le32(&heads[(size_t)i * PBSGPU_BLOB_HEADER_SIZE + 8]))
+            r = PBSGPU_BLOB_BAD_CRC;
+        else if (kind[i] != PBSGPU_BLOB_UNCOMPRESSED)
+            r = PBSGPU_BLOB_CRC_ONLY;
+        else if (sizes && data[j].length != sizes[i])
+            r = PBSGPU_BLOB_BAD_SIZE;
+        else if (digests && std::memcmp(&dig[(size_t)j * 32], digests + (size_t)i * 32, 32) != 0)
+            r = PBSGPU_BLOB_BAD_DIGEST;
+        else
+            r = PBSGPU_BLOB_OK;
+        if (digests && j < nunc) st.sha_bytes += data[j].length;
+        status[i] = r;
+    }
+    for (uint32_t i = 0; i < n; ++i) st.count[status[i]]++;
+    if (stats) *stats = st;
+    return PBSGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbsgpu_blob_magic(int kind, uint8_t out[8]) {
+    if (!out || kind < 0 || kind > 3) return PBSGPU_E_INVALID;
+    std::memcpy(out, kMagic[kind], 8);
+    return PBSGPU_OK;
+}
+
+int pbsgpu_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t *out) {
+    if (!out) return PBSGPU_E_INVALID;
+    *out = mul(pow_from(kHost.x8, len_b), crc_a) ^ crc_b;
+    return PBSGPU_OK;
+}
+
+int pbsgpu_crc32_many_device(pbsgpu_engine *e, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                             uint32_t nseg, uint32_t *out) {
+    return crc32_many(e, dptr, false, nbytes, segs, nseg, out);
+}
+
+int pbsgpu_crc32_many_host(pbsgpu_engine *e, const void *hptr, uint64_t nbytes, const pbsgpu_segment *segs, uint32_t nseg,
+                           uint32_t *out) {
+    return crc32_many(e, hptr, true, nbytes, segs, nseg, out);
+}
+
+int pbsgpu_blob_encoded_size(const pbsgpu_segment *segs, uint32_t nseg, uint64_t *nbytes) {
+    if (!nbytes || (nseg && !segs)) return PBSGPU_E_INVALID;
+    return encoded_size(segs, nseg, nbytes, nullptr);
+}
+
+int pbsgpu_blob_encode_device(pbsgpu_engine *e, const void *src, uint64_t src_bytes, const pbsgpu_segment *segs,
+                              uint32_t nseg, void *dst, uint64_t dst_cap, uint64_t *out_len, uint64_t *offsets,
+                              uint32_t *crcs) {
+    if (!e || !out_len || (!src && src_bytes) || (nseg && !segs)) return PBSGPU_E_INVALID;
+    if (!ranges_ok(segs, nseg, src_bytes)) return PBSGPU_E_INVALID;
+    std::vector<uint64_t> offs((size_t)nseg + 1);
+    uint64_t total = 0;
+    CHK(encoded_size(segs, nseg, &total, offs.data()));
+    *out_len = total;
+    if (total > dst_cap) return PBSGPU_E_CAPACITY;
+    if (offsets) std::memcpy(offsets, offs.data(), offs.size() * sizeof(uint64_t));
+    if (nseg == 0) return PBSGPU_OK;
+    if (!dst || !is_device_pointer(dst) || (src_bytes && !is_device_pointer(src))) return PBSGPU_E_INVALID;
+    CHK(set_device(e));
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const uint8_t *d = nullptr;
+    CHK(stage_ranges(e, s, src, false, src_bytes, segs, nseg, &d));
+    uint32_t *dcrcs = nullptr;
+    CHK(enqueue_crc(e, s, d, segs, nseg, static_cast<uint8_t *>(dst), offs.data(), &dcrcs));
+    if (crcs) return fetch_result(s, crcs, dcrcs, (size_t)nseg * 4);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBSGPU_OK;
+}
+
+int pbsgpu_blob_verify_device(pbsgpu_engine *e, const void *dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                              uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
+                              pbsgpu_blob_stats *stats) {
+    return blob_verify(e, dptr, false, nbytes, blobs, nblob, digests, sizes, status, stats);
+}
+
+int pbsgpu_blob_verify_host(pbsgpu_engine *e, const void *hptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                            uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
+                            pbsgpu_blob_stats *stats) {
+    return blob_verify(e, hptr, true, nbytes, blobs, nblob, digests, sizes, status, stats);
+}
+
+}  // extern "C"

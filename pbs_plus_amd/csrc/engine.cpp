@@ -1055,9 +1055,13 @@ int pbsgpu_resolve_candidates(pbsgpu_engine *e, const uint64_t *cands, uint64_t 
     return PBSGPU_OK;
 }
 
+}  // extern "C"
+
+namespace pbse {
+
 // shared front half of the whole-range hash batches: segment table (+ host bytes) onto an aux slot
-static int stage_ranges(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs,
-                        uint32_t nseg, const uint8_t **d) {
+int stage_ranges(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs,
+                 uint32_t nseg, const uint8_t **d) {
     CHK(s->h_segs.ensure((size_t)nseg * sizeof(pbsgpu_segment)));
     std::memcpy(s->h_segs.p, segs, (size_t)nseg * sizeof(pbsgpu_segment));
     CHK(s->segs.ensure((size_t)nseg * sizeof(pbsgpu_segment)));
@@ -1075,13 +1079,17 @@ static int stage_ranges(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, u
 
 // results of a synchronous helper: device -> mapped pinned memory by kernel (not by the shared copy queue, which a
 // copy waiting behind a long hash kernel would block for every other stream), then a host memcpy to the caller
-static int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes) {
+int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes) {
     CHK(s->h_recs.ensure(nbytes + 64));
     HIPCHK(pbsk::launch_publish(s->h_recs.p, src_dev, nbytes, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     std::memcpy(dst, s->h_recs.p, nbytes);
     return PBSGPU_OK;
 }
+
+}  // namespace pbse
+
+extern "C" {
 
 static int sha256_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs,
                        uint32_t nseg, uint8_t *digests) {

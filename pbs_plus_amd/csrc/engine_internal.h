@@ -280,6 +280,12 @@ int enqueue_candidates(pbsgpu_engine *e, Slot &s, const uint8_t *dptr, uint64_t 
 int staged_h2d(Slot &s, void *dst, const void *src, uint64_t nbytes, hipStream_t st);
 int stage_segments(pbsgpu_engine *e, Slot &s, const pbsgpu_segment *segs, uint32_t nseg, uint64_t nbytes,
                    const SuggestedHost *sg);
+// front half of the whole-range batches (sha256_many, xxh3_many, crc32_many, the blob calls): the segment table (and, with
+// `host`, the bytes through the slot's pinned staging) onto the slot; *d = the device bytes; SC_* scalars zeroed
+int stage_ranges(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs,
+                 uint32_t nseg, const uint8_t **d);
+// results of a synchronous helper: device -> mapped pinned memory by kernel, stream synchronised, then a host memcpy to dst
+int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes);
 // synchronous helper for the upstream-style chunker (the caller owns the slot)
 int candidates_sync(pbsgpu_engine *e, Slot &s, const uint8_t *dptr, uint64_t nbytes, uint64_t *count);
 // Caller bytes -> pinned staging. One thread copies ~12 GB/s, the H2D engine moves 57 GB/s: a single writer (the

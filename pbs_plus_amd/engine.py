@@ -240,6 +240,64 @@ class Engine:
                                                 out.ctypes.data), "xxh3_many_host")
         return out[:nseg]
 
+    # ---- CRC-32 and data blobs (the upload step and the chunk check of the read side) -------------------
+    def crc32_many(self, data, segments, nbytes: int | None = None) -> np.ndarray:
+        """CRC-32 (zlib's crc32) of every (offset, length) range of device or host bytes."""
+        segs, nseg = _segs(segments)
+        out = np.zeros(max(nseg, 1), dtype=np.uint32)
+        ptr, n = self._dev(data, nbytes)
+        if ptr is not None:
+            check(self._L.pbsgpu_crc32_many_device(self._h, ptr, n, segs, nseg, out.ctypes.data), "crc32_many_device")
+        else:
+            a = _host_view(data)
+            check(self._L.pbsgpu_crc32_many_host(self._h, a.ctypes.data if a.size else None, a.size, segs, nseg,
+                                                 out.ctypes.data), "crc32_many_host")
+        return out[:nseg]
+
+    def blob_encode(self, src, chunks, nbytes: int | None = None):
+        """Uncompressed data blobs of the device byte ranges `chunks` = [(offset, length)], laid out back to back in a new
+        DeviceBuffer. Returns (buffer, offsets (n + 1, uint64: blob i = [offsets[i], offsets[i + 1])), CRCs (n, uint32))."""
+        segs, n = _segs(chunks)
+        sp, sn = self._dev(src, nbytes)
+        assert sp is not None, "blob_encode() wants device memory"
+        total = C.c_uint64()
+        check(self._L.pbsgpu_blob_encoded_size(segs, n, C.byref(total)), "blob_encoded_size")
+        dst = self.alloc(total.value)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        try:
+            check(self._L.pbsgpu_blob_encode_device(self._h, sp, sn, segs, n, dst.ptr, dst.nbytes, C.byref(total),
+                                                    offs.ctypes.data, crcs.ctypes.data), "blob_encode_device")
+        except Exception:
+            dst.free()
+            raise
+        return dst, offs, crcs[:n]
+
+    def blob_verify(self, data, blobs, digests=None, sizes=None, nbytes: int | None = None):
+        """Check whole blobs [(offset, length)] of device or host bytes: magic, CRC and, for uncompressed blobs, the data
+        length against `sizes` and its SHA-256 against `digests` ((n, 32) uint8; either may be None). Returns
+        (status per blob, uint8 BLOB_* codes; stats dict with a count per status name and the byte totals)."""
+        segs, n = _segs(blobs)
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        dg = None if digests is None else np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        sz = None if sizes is None else np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+        assert dg is None or dg.shape[0] == n
+        assert sz is None or sz.size == n
+        dp = dg.ctypes.data if dg is not None and n else None
+        zp = sz.ctypes.data if sz is not None and n else None
+        st = _lib.BlobStats()
+        ptr, nb = self._dev(data, nbytes)
+        if ptr is not None:
+            check(self._L.pbsgpu_blob_verify_device(self._h, ptr, nb, segs, n, dp, zp, status.ctypes.data, C.byref(st)),
+                  "blob_verify_device")
+        else:
+            a = _host_view(data)
+            check(self._L.pbsgpu_blob_verify_host(self._h, a.ctypes.data if a.size else None, a.size, segs, n, dp, zp,
+                                                  status.ctypes.data, C.byref(st)), "blob_verify_host")
+        stats = {name: int(st.count[k]) for k, name in enumerate(_lib.BLOB_STATUS_NAMES)}
+        stats.update(blob_bytes=int(st.blob_bytes), crc_bytes=int(st.crc_bytes), sha_bytes=int(st.sha_bytes))
+        return status[:n], stats
+
     # ---- payload-stream assembly (.ppxar layout: markers + 16-byte headers + file bodies) ----------
     def payload_pack(self, src, files, dst, with_start: bool = True, with_tail: bool = True):
         """Lay the file bodies `files` = [(offset, length)] of device buffer `src` out as the pxar
@@ -308,6 +366,39 @@ def didx_decode(blob: bytes):
     check(L.pbsgpu_didx_decode(a.ctypes.data, a.size, out.ctypes.data, n.value, C.byref(n), C.byref(ct), cs),
           "didx_decode")
     return out[: n.value], ct.value, bytes(cs)
+
+
+def blob_magic(kind: int) -> bytes:
+    """The 8-byte magic of a data blob kind (_lib.BLOB_UNCOMPRESSED ... BLOB_ENCRYPTED_COMPRESSED)."""
+    out = (C.c_uint8 * 8)()
+    check(_lib.lib().pbsgpu_blob_magic(int(kind), out), "blob_magic")
+    return bytes(out)
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """zlib.crc32(A + B) from zlib.crc32(A), zlib.crc32(B) and len(B)."""
+    out = C.c_uint32()
+    check(_lib.lib().pbsgpu_crc32_combine(int(crc_a), int(crc_b), int(len_b), C.byref(out)), "crc32_combine")
+    return int(out.value)
+
+
+def chunk_ranges(records: np.ndarray, segments=None, known=None) -> np.ndarray:
+    """(n, 2) uint64 (offset, length) of each record's chunk in the submitted buffer: a record's `end` is relative to its
+    segment, so the chunk is [segments[segment].offset + end - size, + size). segments = None: one segment at offset 0.
+    known (flags of KnownChunks.classify / Engine.dedup) keeps only the records flagged 0 — the chunks to upload."""
+    recs = np.asarray(records, dtype=RECORD_DTYPE).reshape(-1)
+    if known is not None:
+        recs = recs[np.asarray(known).reshape(-1)[: recs.size] == 0]
+    if segments is None or len(segments) == 0:
+        base = np.zeros(recs.size, dtype=np.uint64)
+    else:
+        segs = np.ascontiguousarray(segments, dtype=np.uint64).reshape(-1, 2)
+        base = segs[recs["segment"].astype(np.int64), 0]
+    out = np.empty((recs.size, 2), dtype=np.uint64)
+    size = recs["size"].astype(np.uint64)
+    out[:, 0] = base + recs["end"] - size
+    out[:, 1] = size
+    return out
 
 
 class KnownChunks:
