@@ -55,6 +55,7 @@ type (
 		BacklogMiB, LoneDeferMs, IdleTimeoutS, AutoparkMs                                float64
 		LanesCUs                                                                         uint32
 		ShortBytes                                                                       uint64
+		HoldPages                                                                        bool
 	}
 	EngineOptions struct {
 		Inflight, ShaForm, ShaSlackPct, ShaDensePct                      uint32
@@ -81,6 +82,7 @@ func NewEngine(int, Config, int) (*Engine, error) { return nil, ErrNotBuilt }
 func NewEngineOpt(int, Config, EngineOptions) (*Engine, error) { return nil, ErrNotBuilt }
 
 const RingOff = ^uint32(0)
+const RingAnyStream = ^uint32(0)
 func ParseDynamicIndex([]byte) ([]ChunkInfo, int64, [32]byte, error) {
 	return nil, 0, [32]byte{}, ErrNotBuilt
 }
@@ -139,6 +141,12 @@ func (r *Ring) Pump() error                                                     
 func (r *Ring) Poll(uint32, int) ([]ChunkInfo, bool, error)                      { return nil, false, ErrNotBuilt }
 func (r *Ring) PollAny(int, int) ([]ChunkInfo, []uint32, error)                  { return nil, nil, ErrNotBuilt }
 func (r *Ring) CloseStream(uint32) error                                         { return ErrNotBuilt }
+func (r *Ring) Release(uint32, uint64) error                                     { return ErrNotBuilt }
+func (r *Ring) Held(uint32) (uint64, uint32, error)                              { return 0, 0, ErrNotBuilt }
+func (r *Ring) EncodeBlobs(uint32, []ChunkInfo, []bool, unsafe.Pointer, uint64) ([]uint64, []uint32, uint64, error) {
+	return nil, nil, 0, ErrNotBuilt
+}
+func (r *Ring) Copy(uint32, uint64, uint64, unsafe.Pointer) error                { return ErrNotBuilt }
 func (r *Ring) Quiesce() error                                                   { return ErrNotBuilt }
 func (r *Ring) Park() error                                                      { return ErrNotBuilt }
 func (r *Ring) Suggest(uint32, uint64) error                                     { return ErrNotBuilt }

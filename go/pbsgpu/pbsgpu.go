@@ -682,6 +682,9 @@ type RingOptions struct {
 	// (0 = 3/2 of the average chunk size). Off by default: measured neutral on bulk rings (DESIGN.md 5.5).
 	LanesCUs   uint32
 	ShortBytes uint64
+	// HoldPages (PBSGPU_RING_F_HOLD_PAGES): pages the services are done with stay with their stream until Release, so
+	// that EncodeBlobs / Copy can still read the polled chunks' bytes. The holder must release, or the ring stalls (ErrBusy).
+	HoldPages bool
 }
 
 // RingOff expresses "none" for RingOptions fields whose zero value means "default" (PBSGPU_RING_OFF).
@@ -696,6 +699,9 @@ func (e *Engine) NewRing(o RingOptions) (*Ring, error) {
 		long_spill: C.uint32_t(o.LongSpill), poll_every: C.uint32_t(o.PollEvery), flags: C.uint32_t(o.Flags),
 		backlog_mib: C.double(o.BacklogMiB), lone_defer_ms: C.double(o.LoneDeferMs), idle_timeout_s: C.double(o.IdleTimeoutS),
 		autopark_ms: C.double(o.AutoparkMs), lanes_cus: C.uint32_t(o.LanesCUs), short_bytes: C.uint64_t(o.ShortBytes)}
+	if o.HoldPages {
+		co.flags |= C.PBSGPU_RING_F_HOLD_PAGES
+	}
 	r := &Ring{eng: e}
 	if err := check(C.pbsgpu_ring_create(e.h, &co, &r.h), "ring_create"); err != nil {
 		return nil, err
@@ -797,6 +803,65 @@ func (r *Ring) PollAny(max, maxFinished int) (recs []ChunkInfo, finished []uint3
 func (r *Ring) CloseStream(stream uint32) error {
 	defer runtime.KeepAlive(r)
 	return check(C.pbsgpu_ring_close(r.h, C.uint32_t(stream)), "ring_close")
+}
+
+// RingAnyStream as EncodeBlobs' stream: every entry's stream is its Segment, as PollAny reports it.
+const RingAnyStream = ^uint32(0)
+
+// Release tells a HoldPages ring that the stream's bytes below upto (at most the End of the last entry Poll has handed
+// out) are no longer needed: pages that lie wholly below go back to the free list. The watermark only moves forward.
+func (r *Ring) Release(stream uint32, upto uint64) error {
+	defer runtime.KeepAlive(r)
+	return check(C.pbsgpu_ring_release(r.h, C.uint32_t(stream), C.uint64_t(upto)), "ring_release")
+}
+
+// Held reports the stream offset from which bytes are still available and how many handed-back pages the stream holds.
+func (r *Ring) Held(stream uint32) (firstOffset uint64, pages uint32, err error) {
+	defer runtime.KeepAlive(r)
+	var f C.uint64_t
+	var p C.uint32_t
+	err = check(C.pbsgpu_ring_held(r.h, C.uint32_t(stream), &f, &p), "ring_held")
+	return uint64(f), uint32(p), err
+}
+
+// EncodeBlobs frames the polled entries recs whose skip flag is not set (skip may be nil; true = known, leave it out) as
+// uncompressed blobs, straight out of the ring's pages, back to back into device memory dst. It returns each kept
+// entry's offset in dst (0 for skipped ones), its CRC and the bytes used. A dst that is too small is an error that names
+// the size needed in used, and nothing is written. The loop of an incremental writer:
+// Poll -> KnownChunks.Classify -> EncodeBlobs(skip = isKnown) -> copy out / upload -> append to the index -> Release(last End).
+func (r *Ring) EncodeBlobs(stream uint32, recs []ChunkInfo, skip []bool, dst unsafe.Pointer, dstCap uint64) (offsets []uint64,
+	crcs []uint32, used uint64, err error) {
+	defer runtime.KeepAlive(r)
+	if len(recs) == 0 || (skip != nil && len(skip) != len(recs)) {
+		return nil, nil, 0, errors.New("pbsgpu: EncodeBlobs needs entries and, if given, one skip flag per entry")
+	}
+	cr := toRecords(recs)
+	var sk *C.uint8_t
+	if skip != nil {
+		flags := make([]uint8, len(skip))
+		for i, b := range skip {
+			if b {
+				flags[i] = 1
+			}
+		}
+		sk = (*C.uint8_t)(unsafe.Pointer(&flags[0]))
+	}
+	offsets = make([]uint64, len(recs))
+	crcs = make([]uint32, len(recs))
+	var u C.uint64_t
+	err = check(C.pbsgpu_ring_blob_encode_device(r.h, C.uint32_t(stream), &cr[0], C.uint64_t(len(cr)), sk, dst, C.uint64_t(dstCap),
+		(*C.uint64_t)(unsafe.Pointer(&offsets[0])), (*C.uint32_t)(unsafe.Pointer(&crcs[0])), &u), "ring_blob_encode_device")
+	if err != nil {
+		return nil, nil, uint64(u), err
+	}
+	return offsets, crcs, uint64(u), nil
+}
+
+// Copy writes the raw stream bytes [offset, offset + length), which polled entries must cover and no Release may have
+// passed, into device memory dst — for consumers that compress on the host or want the bytes unframed.
+func (r *Ring) Copy(stream uint32, offset, length uint64, dst unsafe.Pointer) error {
+	defer runtime.KeepAlive(r)
+	return check(C.pbsgpu_ring_copy_device(r.h, C.uint32_t(stream), C.uint64_t(offset), C.uint64_t(length), dst), "ring_copy_device")
 }
 
 // Quiesce waits until everything enqueued is hashed and stops the service kernel; the next Pump restarts it.

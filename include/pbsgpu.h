@@ -374,6 +374,7 @@ typedef struct pbsgpu_ring_options {
 #define PBSGPU_RING_F_DENSE_SERVICE 64u  /* the pair service with FOUR pairs (eight waves) per CU: more bytes per CU-second, every chain slower */
 #define PBSGPU_RING_F_DENSE_LANES 128u   /* the lanes service (lanes_cus) with EIGHT waves per CU: 84 instead of 77-81 chain-blocks per us and CU, 6 us per block */
 #define PBSGPU_RING_F_TIER_TAG 256u      /* diagnostics: pbsgpu_ring_poll* report the queue a chunk went through in bits 28-29 of `segment` (0 main, 1 long, 2 short) */
+#define PBSGPU_RING_F_HOLD_PAGES 512u    /* pages the services are done with stay with their stream until pbsgpu_ring_release (see "held pages" below) */
 typedef struct pbsgpu_ring_stats {
     uint64_t page_bytes, bytes_enqueued, chunks, candidates, pages_enqueued, pages_recycled, service_bytes_last;
     uint32_t pages_total, pages_free, sha_cus, rounds, rounds_done, rounds_in_flight, streams_opened, service_launches;
@@ -452,6 +453,44 @@ int pbsgpu_ring_get_probe(pbsgpu_ring *ring, pbsgpu_ring_probe *out);
 /* Diagnostic text snapshot of the ring's device-side state (queue words, page reference counts, stream states). Debugging
  * only: it copies from the device on the null stream, which may wait for a running service's idle time-out. */
 int pbsgpu_ring_debug(pbsgpu_ring *ring, char *buf, uint64_t cap);
+
+/* ---- held pages: upload the new chunks of a ring stream (PBSGPU_RING_F_HOLD_PAGES) -------------------------------
+ * Without the flag a page is free the moment the services have read every chunk that touches it: by the time a record has
+ * been polled and pbsgpu_known_classify has called its chunk new, the bytes may be another page's. With the flag a page
+ * the services are done with stays with its stream, under its logical index (page k = stream bytes [k * page_bytes,
+ * (k + 1) * page_bytes)), until the caller releases it. The loop of an incremental writer then never takes the payload
+ * off the device before it is known to be new:
+ *   poll -> pbsgpu_known_classify -> pbsgpu_ring_blob_encode_device(skip = known) -> copy out / upload -> release(last end)
+ * THE CALLER'S DUTY: held pages are arena pages. A holder that does not release makes reserve answer PBSGPU_E_BUSY and
+ * fill take 0 bytes, exactly like a full arena; that is no error state, releasing resumes the ring. The arena must hold
+ * what is between two releases (plus what is in flight). Without the flag every call below returns PBSGPU_E_STATE.
+ * Same thread rule as every pbsgpu_ring_* call. */
+#define PBSGPU_HAS_RING_UPLOAD 1
+#define PBSGPU_RING_ANY_STREAM 0xffffffffu
+/* The caller is done with the stream's bytes below offset `upto`: every page wholly below it — logical pages k with
+ * (k + 1) * page_bytes <= upto — goes back to the free list, at once if the services have handed it back, otherwise the
+ * moment they do. The watermark only moves forward (a lower value is a no-op) and may not pass the `end` of the last
+ * record pbsgpu_ring_poll* has handed out for the stream (PBSGPU_E_INVALID). A stream's last page, when it is short, and
+ * everything else it still holds go back with pbsgpu_ring_close. */
+int pbsgpu_ring_release(pbsgpu_ring *ring, uint32_t stream, uint64_t upto);
+/* Diagnostics: the stream offset from which bytes are still available (the watermark rounded down to a page) and the
+ * number of handed-back pages the stream is holding. */
+int pbsgpu_ring_held(pbsgpu_ring *ring, uint32_t stream, uint64_t *first_offset, uint32_t *pages_held);
+/* Uncompressed blobs (pbsgpu_blob_encode_device: magic, CRC-32 little endian, data) of polled records, straight out of
+ * the ring's pages, back to back into device memory dst. recs[i] as pbsgpu_ring_poll returned it (`end` absolute, `size`);
+ * with stream == PBSGPU_RING_ANY_STREAM every record's stream is the low 28 bits of its `segment`, as
+ * pbsgpu_ring_poll_any reports it. skip (n bytes, may be NULL): 1 = leave record i out (it is known). blob_off[i] = offset of
+ * record i's blob in dst and crcs[i] (may be NULL) its CRC-32; both untouched for skipped records. *used = bytes written.
+ * PBSGPU_E_CAPACITY when dst_cap is too small: *used is the size needed, nothing is written. PBSGPU_E_STATE, nothing
+ * written, when a selected record has not been polled yet or begins below the offset pbsgpu_ring_held reports.
+ * Runs on a leased stream of the engine and waits only for that: usable between pumps while the services run. */
+int pbsgpu_ring_blob_encode_device(pbsgpu_ring *ring, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
+                                   const uint8_t *skip, void *dst, uint64_t dst_cap, uint64_t *blob_off, uint32_t *crcs,
+                                   uint64_t *used);
+/* The raw bytes [offset, offset + length) of the stream into device memory dst, for consumers that compress on the host
+ * or want the bytes unframed; the range must be covered by polled records and begin at or above the offset
+ * pbsgpu_ring_held reports (PBSGPU_E_STATE otherwise). */
+int pbsgpu_ring_copy_device(pbsgpu_ring *ring, uint32_t stream, uint64_t offset, uint64_t length, void *dst);
 
 /* ---- whole-stream SHA-256 batch ---------------------------------------------
  * verification.HashFile (internal/agent/verification/handler.go:36-68) and

@@ -593,6 +593,45 @@ class PageRing {
         return p;
     }
 
+    // ---- held pages (a ring created with PBSGPU_RING_F_HOLD_PAGES in its options' flags): the upload side, beside
+    // datastore::blob. The holder must Release, or the ring stalls like a full arena.
+    // the stream's bytes below `upto` (at most the End of its last delivered entry) are no longer needed
+    std::string Release(uint32_t stream, uint64_t upto) {
+        const int st = pbsgpu_ring_release(r_, stream, upto);
+        return st == PBSGPU_OK ? std::string() : errorf("ring release", st);
+    }
+    // {stream offset from which bytes are still available, handed-back pages the stream is holding}
+    Result<std::pair<uint64_t, uint32_t>> Held(uint32_t stream) {
+        Result<std::pair<uint64_t, uint32_t>> r;
+        r.value = {0, 0};
+        const int st = pbsgpu_ring_held(r_, stream, &r.value.first, &r.value.second);
+        if (st != PBSGPU_OK) r.err = errorf("ring held", st);
+        return r;
+    }
+    // uncompressed blobs of the delivered entries recs (skip[i] != 0: entry i is known, leave it out; skip may be empty),
+    // straight out of the ring's pages, back to back in device buffer dst. offsets[i] / crcs[i] per kept entry; `bytes`
+    // is what was written — or, with a dst that is too small (an error, nothing written), what is needed.
+    // stream == PBSGPU_RING_ANY_STREAM: every entry's stream is its `segment`.
+    Result<datastore::blob::Encoded> EncodeBlobs(uint32_t stream, const std::vector<pbsgpu_record> &recs,
+                                                 const std::vector<uint8_t> &skip, void *dst, uint64_t dstCap) {
+        Result<datastore::blob::Encoded> r;
+        r.value.offsets.assign(recs.size(), 0);
+        r.value.crcs.assign(recs.size(), 0);
+        if (!skip.empty() && skip.size() != recs.size()) {
+            r.err = errorf("ring blob encode", PBSGPU_E_INVALID);
+            return r;
+        }
+        const int st = pbsgpu_ring_blob_encode_device(r_, stream, recs.data(), recs.size(), skip.empty() ? nullptr : skip.data(),
+                                                      dst, dstCap, r.value.offsets.data(), r.value.crcs.data(), &r.value.bytes);
+        if (st != PBSGPU_OK) r.err = errorf("ring blob encode", st);
+        return r;
+    }
+    // the raw stream bytes [offset, offset + length) into device buffer dst
+    std::string Copy(uint32_t stream, uint64_t offset, uint64_t length, void *dst) {
+        const int st = pbsgpu_ring_copy_device(r_, stream, offset, length, dst);
+        return st == PBSGPU_OK ? std::string() : errorf("ring copy", st);
+    }
+
   private:
     PageRing(std::shared_ptr<Engine> eng, pbsgpu_ring *r, Sink sink) : eng_(std::move(eng)), r_(r), sink_(std::move(sink)) {}
     PageRing(const PageRing &) = delete;

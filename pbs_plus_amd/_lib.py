@@ -88,6 +88,8 @@ RING_F_NO_OVERLAP, RING_F_NO_STAGE, RING_F_NO_CUT_PRIO, RING_F_NO_SPLIT_AUTO, RI
 RING_F_DENSE_SERVICE = 64
 RING_F_DENSE_LANES = 128
 RING_F_TIER_TAG = 256
+RING_F_HOLD_PAGES = 512
+RING_ANY_STREAM = 0xFFFFFFFF
 
 
 class RingOptions(C.Structure):
@@ -213,6 +215,10 @@ SYMBOLS = {
     "pbsgpu_ring_debug": (C.c_int, [_P, C.c_char_p, C.c_uint64]),
     "pbsgpu_ring_express": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "pbsgpu_ring_get_probe": (C.c_int, [_P, C.POINTER(RingProbe)]),
+    "pbsgpu_ring_release": (C.c_int, [_P, C.c_uint32, C.c_uint64]),
+    "pbsgpu_ring_held": (C.c_int, [_P, C.c_uint32, _U64P, C.POINTER(C.c_uint32)]),
+    "pbsgpu_ring_blob_encode_device": (C.c_int, [_P, C.c_uint32, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _U64P]),
+    "pbsgpu_ring_copy_device": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, _P]),
     "pbsgpu_sha256_many_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
     "pbsgpu_sha256_many_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
     "pbsgpu_xxh3_many_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),

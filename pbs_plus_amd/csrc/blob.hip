@@ -25,7 +25,7 @@
 // The encode pass is the same pair with a destination: the piece kernel stores every loaded row at the blob's data
 // position (arbitrary alignment, one row and lane at a time) and the fold writes the 12-byte header.
 // Memory instructions: global_* only (address-space-1 pointers); no scratch (tests/test_blob_surface.py).
-#include "engine_internal.h"
+#include "ring_internal.h"
 
 using namespace pbse;
 
@@ -305,6 +305,159 @@ __global__ __launch_bounds__(256) void k_blob_heads(const uint8_t *src, const pb
     ((gbyte_out)heads)[t] = j < b.length ? ((gbyte_ptr)src)[b.offset + j] : 0;
 }
 
+// ---- sources in up to two parts: the chunks of a page ring (pbsgpu_ring_blob_encode_device) ----------
+// A ring chunk lies in one page or straddles two that are not neighbours in the arena. Every PART is a segment of its
+// own for the piece pass (pieces aligned at the part's end, only its first piece short); a part knows how many of its
+// leading bytes are among the chunk's first four (`inv`: a first part of 1-3 bytes leaves the rest to the second part).
+// The fold joins the two parts with one more product: raw(A || B) = raw(A) * x^(8|B|) + raw(B), the constant from the
+// host plan. A pair of its own rather than a second form of k_crc_pieces / k_crc_fold: those stay exactly as measured.
+struct PartDesc {
+    uint64_t src;    // offset of the part's first byte from PartPlan::base
+    uint64_t dst;    // offset of where its bytes go in PartPlan::dst (behind the blob's header)
+    uint32_t len;    // <= a page: < 2^31
+    uint32_t inv;    // leading bytes that enter the CRC inverted (0..4)
+    uint32_t pbase;  // index of its first piece
+    uint32_t pad;
+};
+struct BlobDesc {
+    uint64_t hdr;     // offset of the blob (its header) in PartPlan::dst
+    uint32_t part0;   // its first part
+    uint32_t nparts;  // 0 (empty chunk), 1 or 2
+    uint32_t join;    // x^(8 |second part|)
+    uint32_t len;     // data bytes
+};
+struct PartPlan {
+    const uint8_t *base;
+    const PartDesc *parts;
+    const BlobDesc *blobs;   // nblob (nullptr for a plain copy)
+    const uint32_t *ppart;   // npieces: part of each piece
+    uint32_t *praw;          // npieces: raw CRC of each piece
+    uint32_t *crcs;          // nblob
+    uint8_t *dst;
+    uint32_t npieces, nparts, nblob;
+    uint32_t magic_lo, magic_hi;
+};
+typedef const CRC_GLOBAL PartDesc *gpart_ptr;
+typedef const CRC_GLOBAL BlobDesc *gblob_ptr;
+
+__global__ __launch_bounds__(256) void k_pagecrc_pieces(PartPlan pl) {
+    __shared__ uint32_t tab[17][256];  // as in k_crc_pieces
+    {
+        const uint32_t b = threadIdx.x;
+        uint32_t c = b;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
+        tab[16][b] = c;
+        uint32_t t = mul(c, kDev.gap);
+        tab[0][b] = t;
+        __syncthreads();
+        for (int m = 1; m < 16; ++m) {
+            t = (t >> 8) ^ tab[16][t & 255];
+            tab[m][b] = t;
+        }
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t kl = kDev.klane[lane];
+    const uint32_t nw = gridDim.x * 4;
+    for (uint32_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.npieces; p += nw) {
+        const uint32_t i = ((gword_ptr)pl.ppart)[p];
+        const gpart_ptr pd = (gpart_ptr)pl.parts + i;
+        const uint32_t len = pd->len, pinv = pd->inv;
+        const uint32_t m = (len + (uint32_t)kPiece - 1) >> kPieceLog;
+        const uint32_t hi = len - (m - 1 - (p - pd->pbase)) * (uint32_t)kPiece;  // piece = part bytes [lo, hi)
+        const uint32_t lo = hi > kPiece ? hi - (uint32_t)kPiece : 0;
+        const uint32_t n = hi - lo;
+        const uint32_t rows = (n + kRow - 1) / kRow;
+        const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
+        const uint8_t *d = pl.base + pd->src + lo;
+        uint8_t *o = pl.dst + pd->dst + lo;
+        const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
+        const uint32_t so = (uint32_t)((uintptr_t)o - z) & 3u;
+        const uint32_t inv = lo < pinv ? (hi < pinv ? hi : pinv) - lo : 0u;  // bytes [0, inv) of the piece enter inverted
+        uint32_t c = step(tab, 0u, row_edge(d, o, (int32_t)(16 * lane) - (int32_t)z, sd, so, inv).w);
+        uint32_t r = 1;
+        if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
+            c = step(tab, c, row_edge(d, o, (int32_t)(kRow + 16 * lane) - (int32_t)z, sd, so, inv).w);
+            r = 2;
+        }
+        for (; r + 4 <= rows; r += 4) {
+            uint32_t w[4][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                store16(o + (r + k) * kRow + 16 * lane - z, so, w[k]);
+                c = step(tab, c, w[k]);
+            }
+        }
+        for (; r < rows; ++r) {
+            uint32_t w[4];
+            load16(d + r * kRow + 16 * lane - z, sd, w);
+            store16(o + r * kRow + 16 * lane - z, so, w);
+            c = step(tab, c, w);
+        }
+        const uint32_t v = wave_xor(mul(c, kl));
+        if (lane == 0) ((gword_out)pl.praw)[p] = v;
+    }
+}
+
+// raw CRC of one part from its m >= 1 pieces (the fold of k_crc_fold: only the first piece is short)
+__device__ __forceinline__ uint32_t fold_part(gword_ptr raw, uint32_t m, uint32_t lane) {
+    if (m == 1) return raw[0];
+    uint32_t acc = 0;
+    for (uint32_t blk = (m - 1) / kFoldLanes + 1; blk-- > 0;) {
+        const uint32_t q = blk * kFoldLanes + lane;  // pieces from the part's end
+        uint32_t v = q < m ? raw[m - 1 - q] : 0u;
+#pragma unroll
+        for (int lv = 0; lv < 6; ++lv) {
+            const uint32_t u = __shfl_xor(v, 1 << lv, 64);
+            if (!(lane & (1u << lv))) v ^= mul(u, kDev.x8[kPieceLog + lv]);
+        }
+        acc = mul(acc, kDev.x8[kPieceLog + 6]) ^ __shfl(v, 0, 64);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void k_pagecrc_fold(PartPlan pl) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < pl.nblob; i += nw) {
+        const gblob_ptr bd = (gblob_ptr)pl.blobs + i;
+        const uint32_t np = bd->nparts, len = bd->len;
+        const gpart_ptr pd = (gpart_ptr)pl.parts + bd->part0;
+        uint32_t acc = 0;
+        if (np >= 1) acc = fold_part((gword_ptr)pl.praw + pd[0].pbase, (pd[0].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
+        if (np == 2)  // the part boundary: a join whose shift is no power of two of kPiece
+            acc = mul(acc, bd->join) ^
+                  fold_part((gword_ptr)pl.praw + pd[1].pbase, (pd[1].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
+        const uint32_t crc = (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+        if (lane == 0) ((gword_out)pl.crcs)[i] = crc;
+        if (lane < PBSGPU_BLOB_HEADER_SIZE) {
+            const uint32_t word = lane < 4 ? pl.magic_lo : lane < 8 ? pl.magic_hi : crc;
+            ((gbyte_out)pl.dst)[bd->hdr + lane] = (uint8_t)(word >> (8 * (lane & 3)));
+        }
+    }
+}
+
+// the parts' bytes, unframed (pbsgpu_ring_copy_device): blockIdx.y strides over the parts, x over a part's 16-byte units
+__global__ __launch_bounds__(256) void k_page_copy(PartPlan pl) {
+    for (uint32_t i = blockIdx.y; i < pl.nparts; i += gridDim.y) {
+        const gpart_ptr pd = (gpart_ptr)pl.parts + i;
+        const uint32_t len = pd->len, units = len >> 4;
+        const uint8_t *d = pl.base + pd->src;
+        uint8_t *o = pl.dst + pd->dst;
+        const uint32_t sd = (uint32_t)(uintptr_t)d & 3u, so = (uint32_t)(uintptr_t)o & 3u;
+        for (uint32_t u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+            uint32_t w[4];
+            load16(d + 16ull * u, sd, w);
+            store16(o + 16ull * u, so, w);
+        }
+        const uint32_t t = 16 * units + threadIdx.x;
+        if (blockIdx.x == 0 && t < len) ((gbyte_out)o)[t] = ((gbyte_ptr)d)[t];
+    }
+}
+
 }  // namespace crc
 }  // namespace pbsk
 
@@ -516,6 +669,126 @@ int blob_verify(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, c
 }
 
 }  // namespace
+
+namespace pbse {
+
+using namespace pbsk::crc;
+
+// the plan's tables onto the aux slot and the launch pair (or the copy kernel) behind them; nothing synchronised
+static int enqueue_parts(pbsgpu_engine *e, Slot *s, PartPlan &pl, const std::vector<PartDesc> &parts,
+                         const std::vector<BlobDesc> &blobs, const std::vector<uint32_t> &ppart) {
+    CHK(s->segs.ensure(parts.size() * sizeof(PartDesc) + 64));
+    CHK(staged_h2d(*s, s->segs.p, parts.data(), parts.size() * sizeof(PartDesc), s->stream));
+    pl.parts = s->segs.as<PartDesc>();
+    pl.nparts = (uint32_t)parts.size();
+    if (blobs.empty()) {
+        uint32_t longest = 0;
+        for (const PartDesc &p : parts) longest = std::max(longest, p.len);
+        const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((longest / 16 + 255) / 256, (uint32_t)e->num_cus * 8));
+        const uint32_t gy = std::min<uint32_t>(pl.nparts, 1024);
+        hipLaunchKernelGGL(pbsk::crc::k_page_copy, dim3(gx, gy), dim3(256), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+        return PBSGPU_OK;
+    }
+    CHK(s->seg_off.ensure(blobs.size() * sizeof(BlobDesc) + 64));
+    CHK(s->tile_cnt.ensure(ppart.size() * sizeof(uint32_t) + 64));
+    CHK(s->dense.ensure(ppart.size() * sizeof(uint32_t) + 64));
+    CHK(s->seg_cnt.ensure(blobs.size() * sizeof(uint32_t) + 64));
+    CHK(staged_h2d(*s, s->seg_off.p, blobs.data(), blobs.size() * sizeof(BlobDesc), s->stream));
+    if (!ppart.empty()) CHK(staged_h2d(*s, s->tile_cnt.p, ppart.data(), ppart.size() * sizeof(uint32_t), s->stream));
+    pl.blobs = s->seg_off.as<BlobDesc>();
+    pl.ppart = s->tile_cnt.as<uint32_t>();
+    pl.praw = s->dense.as<uint32_t>();
+    pl.crcs = s->seg_cnt.as<uint32_t>();
+    pl.npieces = (uint32_t)ppart.size();
+    pl.nblob = (uint32_t)blobs.size();
+    pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
+    pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
+    if (pl.npieces) {  // grids as in enqueue_crc
+        const uint64_t wg = std::min<uint64_t>(((uint64_t)pl.npieces + 3) / 4, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pbsk::crc::k_pagecrc_pieces, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
+    const uint64_t wg = std::min<uint64_t>(((uint64_t)pl.nblob + 3) / 4, (uint64_t)e->num_cus * 16);
+    hipLaunchKernelGGL(pbsk::crc::k_pagecrc_fold, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
+    HIPCHK(hipGetLastError());
+    return PBSGPU_OK;
+}
+
+int blob_encode_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart (*src)[2], uint32_t nblob, uint8_t *dst,
+                      const uint64_t *doff, uint32_t *crcs) {
+    if (nblob == 0) return PBSGPU_OK;
+    std::vector<PartDesc> parts;
+    std::vector<BlobDesc> blobs(nblob);
+    parts.reserve((size_t)nblob + nblob / 8 + 1);
+    uint64_t np = 0;
+    for (uint32_t i = 0; i < nblob; ++i) {
+        const uint64_t len = (uint64_t)src[i][0].len + src[i][1].len;
+        BlobDesc &b = blobs[i];
+        b.hdr = doff[i];
+        b.part0 = (uint32_t)parts.size();
+        b.nparts = 0;
+        b.len = (uint32_t)len;
+        b.join = src[i][1].len ? pow_from(kHost.x8, src[i][1].len) : kOne;
+        uint32_t done = 0;  // chunk bytes in front of the part
+        for (int k = 0; k < 2; ++k) {
+            const SrcPart &sp = src[i][k];
+            if (sp.len == 0) continue;
+            PartDesc p{};
+            p.src = sp.src;
+            p.dst = doff[i] + PBSGPU_BLOB_HEADER_SIZE + done;
+            p.len = sp.len;
+            p.inv = (len >= 4 && done < 4) ? std::min<uint32_t>(4 - done, sp.len) : 0u;
+            p.pbase = (uint32_t)np;
+            np += (sp.len + kPiece - 1) >> kPieceLog;
+            done += sp.len;
+            parts.push_back(p);
+            b.nparts++;
+        }
+        if (len >= (1ull << 32) || np >= (1ull << 32) || parts.size() >= (1ull << 32)) return PBSGPU_E_INVALID;
+    }
+    std::vector<uint32_t> ppart((size_t)np);
+    for (uint32_t j = 0; j < parts.size(); ++j) {
+        const uint32_t end = j + 1 < parts.size() ? parts[j + 1].pbase : (uint32_t)np;
+        for (uint32_t p = parts[j].pbase; p < end; ++p) ppart[p] = j;
+    }
+    CHK(set_device(e));
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    PartPlan pl{};
+    pl.base = base;
+    pl.dst = dst;
+    CHK(enqueue_parts(e, s, pl, parts, blobs, ppart));
+    if (crcs) return fetch_result(s, crcs, pl.crcs, (size_t)nblob * 4);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBSGPU_OK;
+}
+
+int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32_t nparts, uint8_t *dst) {
+    std::vector<PartDesc> parts;
+    uint64_t done = 0;
+    for (uint32_t j = 0; j < nparts; ++j) {
+        if (src[j].len == 0) continue;
+        PartDesc p{};
+        p.src = src[j].src;
+        p.dst = done;
+        p.len = src[j].len;
+        done += src[j].len;
+        parts.push_back(p);
+    }
+    if (parts.empty()) return PBSGPU_OK;
+    CHK(set_device(e));
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    PartPlan pl{};
+    pl.base = base;
+    pl.dst = dst;
+    CHK(enqueue_parts(e, s, pl, parts, {}, {}));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return PBSGPU_OK;
+}
+
+}  // namespace pbse
 
 extern "C" {
 

@@ -108,7 +108,8 @@ void ring_reap_free(pbsgpu_ring *r) {
     for (;;) {
         const unsigned long long e = f[r->free_read & (r->nfree - 1)];
         if ((uint32_t)(e >> 32) != r->free_read + 1u) break;
-        r->free_pages.push_back((uint32_t)e);
+        if (r->hold) r->held.handed_back((uint32_t)e, r->free_pages);  // (free only once its stream has released it)
+        else r->free_pages.push_back((uint32_t)e);
         r->free_read++;
         r->st.pages_recycled++;
     }
@@ -693,6 +694,7 @@ void ring_pop_records(pbsgpu_ring *r, uint32_t slot, pbsgpu_record *out, uint64_
         out[(*n)++] = rec;
         s.cells.pop_front();
         s.records_out++;
+        s.polled_end = rec.end;
         for (auto &ri : r->rounds)
             if (ri.seq == cr.round_idx) {
                 ri.live_cells--;
@@ -755,6 +757,7 @@ int ring_commit_dep(pbsgpu_ring *r, uint32_t stream, uint64_t nbytes, int final,
     q.valid = (uint32_t)nbytes;
     q.final = final != 0;
     q.dep = dep;
+    if (r->hold) r->held.assign(stream, q.k, q.phys);
     s.ready.push_back(q);
     r->ready_bytes += nbytes;
     s.reserved = -1;
@@ -982,6 +985,8 @@ int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool 
         r->piece_n.assign(r->max_streams, 0);
         r->free_pages.reserve(r->npages);
         for (uint32_t p = r->npages; p-- > 0;) r->free_pages.push_back(p);  // page 0 is handed out first
+        r->hold = (o.flags & PBSGPU_RING_F_HOLD_PAGES) != 0;
+        if (r->hold) r->held.init(r->npages, r->max_streams, r->page_bytes);
         r->st.pages_total = r->npages;
         r->st.page_bytes = r->page_bytes;
         r->st.sha_cus = r->sha_cus;
@@ -1112,6 +1117,7 @@ int pbsgpu_ring_open(pbsgpu_ring *r, uint32_t *stream) {
         if (!r->slots[i].open) {
             r->slots[i] = StreamSlot{};
             r->slots[i].open = true;
+            if (r->hold) r->held.open(i);
             if (i < r->piece_n.size()) r->piece_n[i] = 0;  // (a piece table left behind by the slot's previous stream is not this one's)
             *stream = i;
             r->st.streams_opened++;
@@ -1125,7 +1131,110 @@ int pbsgpu_ring_close(pbsgpu_ring *r, uint32_t stream) {
     StreamSlot &s = r->slots[stream];
     if (!s.final_done || !s.cells.empty()) return PBSGPU_E_STATE;  // finish it and poll its records first
     s.open = false;
+    if (r->hold) r->held.close(stream, r->free_pages);  // (what the services still have of it comes back as nobody's page)
     return PBSGPU_OK;
+}
+
+// ---- held pages: release, and the chunks' bytes while they are held (PBSGPU_RING_F_HOLD_PAGES) ----
+
+int pbsgpu_ring_release(pbsgpu_ring *r, uint32_t stream, uint64_t upto) {
+    if (!r) return PBSGPU_E_INVALID;
+    if (!r->hold) return PBSGPU_E_STATE;
+    if (stream >= r->slots.size() || !r->slots[stream].open) return PBSGPU_E_INVALID;
+    if (upto > r->slots[stream].polled_end) return PBSGPU_E_INVALID;  // only what poll has handed out can be done with
+    ring_heartbeat(r);
+    r->held.release(stream, upto, r->free_pages);
+    return PBSGPU_OK;
+}
+
+int pbsgpu_ring_held(pbsgpu_ring *r, uint32_t stream, uint64_t *first_offset, uint32_t *pages_held) {
+    if (!r || !first_offset || !pages_held) return PBSGPU_E_INVALID;
+    if (!r->hold) return PBSGPU_E_STATE;
+    if (stream >= r->slots.size() || !r->slots[stream].open) return PBSGPU_E_INVALID;
+    ring_reap_free(r);
+    *first_offset = r->held.first_offset(stream);
+    *pages_held = r->held.pages_held(stream);
+    return PBSGPU_OK;
+}
+
+// stream bytes [off, off + len) -> parts of the arena, one per page touched; false when a page is no longer (or not yet) there
+static bool ring_parts_of(const pbsgpu_ring *r, uint32_t stream, uint64_t off, uint64_t len, SrcPart *out, uint32_t cap,
+                          uint32_t *n) {
+    *n = 0;
+    uint64_t k = off / r->page_bytes, in = off - k * r->page_bytes;
+    for (; len; ++k, in = 0) {
+        const int64_t phys = r->held.phys_of(stream, k);
+        if (phys < 0 || *n == cap) return false;
+        const uint64_t take = std::min<uint64_t>(len, r->page_bytes - in);
+        out[(*n)++] = SrcPart{(uint64_t)phys * r->stride + 128u + in, (uint32_t)take};
+        len -= take;
+    }
+    return true;
+}
+
+// Why the encode kernel sees the pages' bytes: a record that poll has handed out was hashed, so the service
+// read its bytes — in a kernel that follows, in stream order or by event, the fill or the commit of its pages.
+int pbsgpu_ring_blob_encode_device(pbsgpu_ring *r, uint32_t stream, const pbsgpu_record *recs, uint64_t n, const uint8_t *skip,
+                                   void *dst, uint64_t dst_cap, uint64_t *blob_off, uint32_t *crcs, uint64_t *used) {
+    if (!r || !used || (n && (!recs || !blob_off)) || n >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (!r->hold) return PBSGPU_E_STATE;
+    std::vector<SrcPart> parts;  // two per selected record
+    std::vector<uint64_t> doff;
+    std::vector<uint32_t> which;
+    parts.reserve(2 * (size_t)n);
+    doff.reserve((size_t)n);
+    which.reserve((size_t)n);
+    uint64_t total = 0, first = 0, polled = 0;
+    uint32_t cur = PBSGPU_RING_ANY_STREAM;  // the stream `first` and `polled` belong to
+    for (uint64_t i = 0; i < n; ++i) {
+        if (skip && skip[i]) continue;
+        const pbsgpu_record &rc = recs[i];
+        const uint32_t sid = stream == PBSGPU_RING_ANY_STREAM ? (rc.segment & 0x0fffffffu) : stream;
+        if (sid != cur) {
+            if (sid >= r->slots.size() || !r->slots[sid].open) return PBSGPU_E_INVALID;
+            cur = sid;
+            first = r->held.first_offset(sid);
+            polled = r->slots[sid].polled_end;
+        }
+        if (rc.size > rc.end || rc.size > r->page_bytes) return PBSGPU_E_INVALID;  // (no chunk of this ring: it would touch three pages)
+        const uint64_t start = rc.end - rc.size;
+        if (rc.end > polled || start < first) return PBSGPU_E_STATE;
+        SrcPart two[2] = {};
+        uint32_t np = 0;
+        if (!ring_parts_of(r, sid, start, rc.size, two, 2, &np)) return PBSGPU_E_STATE;
+        parts.push_back(two[0]);
+        parts.push_back(two[1]);
+        doff.push_back(total);
+        which.push_back((uint32_t)i);
+        total += (uint64_t)rc.size + PBSGPU_BLOB_HEADER_SIZE;
+    }
+    *used = total;
+    if (total > dst_cap) return PBSGPU_E_CAPACITY;
+    for (size_t j = 0; j < which.size(); ++j) blob_off[which[j]] = doff[j];
+    if (which.empty()) return PBSGPU_OK;
+    CHK(set_device(r->eng));
+    if (!dst || !is_device_pointer(dst)) return PBSGPU_E_INVALID;
+    ring_heartbeat(r);
+    std::vector<uint32_t> got(crcs ? which.size() : 0);
+    CHK(blob_encode_parts(r->eng, r->arena.as<uint8_t>(), reinterpret_cast<const SrcPart(*)[2]>(parts.data()),
+                          (uint32_t)which.size(), static_cast<uint8_t *>(dst), doff.data(), crcs ? got.data() : nullptr));
+    for (size_t j = 0; j < got.size(); ++j) crcs[which[j]] = got[j];
+    return PBSGPU_OK;
+}
+
+int pbsgpu_ring_copy_device(pbsgpu_ring *r, uint32_t stream, uint64_t offset, uint64_t length, void *dst) {
+    if (!r || (length && !dst)) return PBSGPU_E_INVALID;
+    if (!r->hold) return PBSGPU_E_STATE;
+    if (stream >= r->slots.size() || !r->slots[stream].open || offset + length < offset) return PBSGPU_E_INVALID;
+    if (offset + length > r->slots[stream].polled_end || offset < r->held.first_offset(stream)) return PBSGPU_E_STATE;
+    if (length == 0) return PBSGPU_OK;
+    std::vector<SrcPart> parts((size_t)(length / r->page_bytes) + 2);
+    uint32_t np = 0;
+    if (!ring_parts_of(r, stream, offset, length, parts.data(), (uint32_t)parts.size(), &np)) return PBSGPU_E_STATE;
+    CHK(set_device(r->eng));
+    if (!is_device_pointer(dst)) return PBSGPU_E_INVALID;
+    ring_heartbeat(r);
+    return copy_parts(r->eng, r->arena.as<uint8_t>(), parts.data(), np, static_cast<uint8_t *>(dst));
 }
 
 int pbsgpu_ring_reserve(pbsgpu_ring *r, uint32_t stream, void **dptr, uint64_t *cap) {
@@ -1186,6 +1295,7 @@ int pbsgpu_ring_fill(pbsgpu_ring *r, uint32_t stream, uint64_t seed, uint32_t ki
         q.seed = seed;
         q.kind = kind;
         q.fill_off = s.bytes_committed;  // the generator's stream offset = the page's offset in its stream
+        if (r->hold) r->held.assign(stream, q.k, q.phys);
         s.ready.push_back(q);
         r->ready_bytes += n;
         s.bytes_committed += n;
@@ -1247,6 +1357,7 @@ int pbsgpu_ring_fill_pieces(pbsgpu_ring *r, uint32_t stream, const pbsgpu_fill_p
         q.tab = tab;
         q.ntab = nt;
         q.fill_off = s.bytes_committed;
+        if (r->hold) r->held.assign(stream, q.k, q.phys);
         s.ready.push_back(q);
         r->ready_bytes += n;
         s.bytes_committed += n;

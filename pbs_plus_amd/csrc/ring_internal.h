@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine_internal.h"
+#include "hold.h"
 
 namespace pbse {
 
@@ -48,6 +49,7 @@ struct StreamSlot {
     std::deque<PageReq> ready;
     std::deque<CellRef> cells;            // record cells in stream order (round results reaped)
     uint64_t records_out = 0;
+    uint64_t polled_end = 0;              // `end` of the last record handed out (what release / the ring-sourced encode may refer to)
     bool reported = false;                // poll_any has announced the end of this stream
     uint64_t origin = 0;                  // payload position of the stream's byte 0 (absolute reader grid of suggested boundaries)
     std::deque<uint64_t> sugg;            // suggested boundaries still of interest (stream offsets, ascending)
@@ -141,6 +143,8 @@ struct pbsgpu_ring {
     double park_wait_t0 = 0;              // since when a start has been waiting for the other rings of the device to let go (ring_start_service)
     bool parked_for_flush = false;        // ... and its service was parked for it: the next start waits for that service's END
     bool fill_serial = false;             // PBSGPU_RING_F_FILL_SERIAL
+    bool hold = false;                    // PBSGPU_RING_F_HOLD_PAGES: handed-back pages wait in `held` for pbsgpu_ring_release
+    pbse::HeldPages held;
     uint32_t opt_long_lo = 0, opt_long_spill = 0, opt_poll_every = 0;  // pbsgpu_ring_options (0 = the default rule)
     bool defer_service = false;           // PBSGPU_RING_F_DEFER_SERVICE (profiling): rounds only enqueue; quiesce runs the service ALONE
     double lone_defer_ms = 25.0;          // a lone bulk stream's rounds are cut ahead of the service start for at most this long (0 = off)
@@ -188,5 +192,16 @@ void ring_pop_records(pbsgpu_ring *r, uint32_t slot, pbsgpu_record *out, uint64_
 // stop the service behind everything enqueued so far WITHOUT waiting for it; the next round starts it again
 int ring_park(pbsgpu_ring *r);
 bool ring_idle(const pbsgpu_ring *r);
+
+// blob.hip: sources in up to two parts (a ring chunk in one or two pages). Offsets from `base`; a part of length 0 is none.
+struct SrcPart {
+    uint64_t src;
+    uint32_t len;
+};
+// blob i = header + src[i][0] + src[i][1] at dst + doff[i]; crcs (nblob, may be NULL). On a leased aux stream, synchronised.
+int blob_encode_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart (*src)[2], uint32_t nblob, uint8_t *dst,
+                      const uint64_t *doff, uint32_t *crcs);
+// the parts' bytes back to back at dst
+int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32_t nparts, uint8_t *dst);
 
 }  // namespace pbse

@@ -697,14 +697,17 @@ class PageRing:
     (internal/pxarmount/commit_reuse.go:457, internal/tapeio/converter.go:836) when bytes are in device memory."""
 
     def __init__(self, eng: Engine, arena_bytes: int = 0, page_bytes: int = 0, max_streams: int = 0, sha_cus: int = 0,
-                 round_pages: int = 0, express_cus: int = 0, **options):
-        """`options`: the other fields of pbsgpu_ring_options by name (flags=_lib.RING_F_NO_STAGE, lone_defer_ms=-1.0, ...)."""
+                 round_pages: int = 0, express_cus: int = 0, hold: bool = False, **options):
+        """`options`: the other fields of pbsgpu_ring_options by name (flags=_lib.RING_F_NO_STAGE, lone_defer_ms=-1.0, ...).
+        `hold`: PBSGPU_RING_F_HOLD_PAGES — pages stay with their stream until release(): see blob_encode() / copy()."""
         self._eng = eng
         self._L = eng._L
         opt = _lib.RingOptions(int(arena_bytes), int(page_bytes), int(max_streams), int(sha_cus), int(round_pages),
                                int(express_cus))
         for k, v in options.items():
             setattr(opt, k, v)
+        if hold:
+            opt.flags |= _lib.RING_F_HOLD_PAGES
         h = C.c_void_p()
         check(self._L.pbsgpu_ring_create(eng._h, C.byref(opt), C.byref(h)), "ring_create")
         self._h = h
@@ -768,6 +771,56 @@ class PageRing:
 
     def close_stream(self, stream: int) -> None:
         check(self._L.pbsgpu_ring_close(self._h, stream), "ring_close")
+
+    # ---- held pages (hold=True): the polled chunks' bytes stay in the ring until released ----------
+    def release(self, stream: int, upto: int) -> None:
+        """The stream's bytes below `upto` (at most the `end` of its last polled record) are no longer needed: pages that
+        lie wholly below go back to the free list. A holder that never releases stalls fill() / reserve()."""
+        check(self._L.pbsgpu_ring_release(self._h, stream, int(upto)), "ring_release")
+
+    def held(self, stream: int) -> tuple:
+        """(stream offset from which bytes are still available, handed-back pages the stream is holding)"""
+        first, pages = C.c_uint64(), C.c_uint32()
+        check(self._L.pbsgpu_ring_held(self._h, stream, C.byref(first), C.byref(pages)), "ring_held")
+        return int(first.value), int(pages.value)
+
+    def blob_encode(self, stream, recs: np.ndarray, skip=None):
+        """Uncompressed data blobs of the polled records `recs`, framed on the device straight out of the ring's pages,
+        back to back in a new DeviceBuffer. `stream` None: every record's stream is its `segment` (poll_any). `skip`
+        (n, truthy = leave the record out: it is known). Returns (buffer, offsets (n, uint64; untouched 0 for skipped
+        records), CRCs (n, uint32)); the bytes used are sum(size + 12) over the records kept."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        n = int(recs.size)
+        sid = _lib.RING_ANY_STREAM if stream is None else int(stream)
+        sk = None if skip is None else np.ascontiguousarray(np.asarray(skip) != 0, dtype=np.uint8)
+        assert sk is None or sk.size == n
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        used = C.c_uint64()
+        args = (self._h, sid, recs.ctypes.data if n else None, n, sk.ctypes.data if sk is not None and n else None)
+        st = self._L.pbsgpu_ring_blob_encode_device(*args, None, 0, offs.ctypes.data, None, C.byref(used))  # the size
+        if st != _lib.E_CAPACITY:
+            check(st, "ring_blob_encode_device")
+        dst = self._eng.alloc(max(int(used.value), 16))
+        try:
+            check(self._L.pbsgpu_ring_blob_encode_device(*args, dst.ptr, dst.nbytes, offs.ctypes.data, crcs.ctypes.data,
+                                                         C.byref(used)), "ring_blob_encode_device")
+        except Exception:
+            dst.free()
+            raise
+        dst.used = int(used.value)
+        return dst, offs[:n], crcs[:n]
+
+    def copy(self, stream: int, offset: int, length: int) -> DeviceBuffer:
+        """The raw stream bytes [offset, offset + length) out of the ring's pages into a new DeviceBuffer (the range must
+        be covered by polled records and not be released)."""
+        dst = self._eng.alloc(max(int(length), 16))
+        try:
+            check(self._L.pbsgpu_ring_copy_device(self._h, int(stream), int(offset), int(length), dst.ptr), "ring_copy_device")
+        except Exception:
+            dst.free()
+            raise
+        return dst
 
     def quiesce(self) -> None:
         check(self._L.pbsgpu_ring_quiesce(self._h), "ring_quiesce")

@@ -1,0 +1,171 @@
+"""Rates of the ring-sourced blob encode (pbsgpu_ring_blob_encode_device) and the cost of holding pages, on one GPU:
+
+* (a) the encode of polled chunks straight out of the pages of a holding ring, in GB/s of chunk bytes: one stream at
+  NewConfig(4 << 20) with the default pages and one at NewConfig(4096) with 64 KiB pages, every record of the stream in
+  one call (the ring is quiesced first: the figure is the encode alone);
+* (b) blob_encode_device over the same chunks, copied into one contiguous buffer with pbsgpu_ring_copy_device, in the same
+  run; and the ratio (a) / (b);
+* (c) the feed rate of a ring with the flag on whose consumer releases after every poll against the same ring with the flag
+  off (GiB/s from the first fill to the last record), and the share of the arena that was held on average.
+
+(a) and (b) are the median of a few synchronous calls timed with a host clock, after one warm-up call; (c) alternates the
+two rings and reports the median of its runs.
+
+    python tools/ring_upload_rate.py [--big-gib 2] [--small-mib 256] [--feed-gib 512] [--reps 5]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _median_s(fn, reps):
+    fn()  # warm-up (first-use allocation of the leased work buffers)
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts)
+
+
+def _ingest(ring, seed, kind, nbytes):
+    """one whole synthetic stream into a holding ring that releases nothing: (stream, records)"""
+    sid = ring.open()
+    left, recs, fin = nbytes, [], False
+    while not fin:
+        if left:
+            want = min(left, 64 * ring.page_bytes)
+            left -= ring.fill(sid, seed, kind, want, final=(want == left))
+        ring.pump()
+        r, fin = ring.poll(sid, cap=1 << 16)
+        recs.append(r.copy())
+    return sid, np.concatenate(recs)
+
+
+def encode_rates(a, name, avg, nbytes, ring_opt):
+    from pbs_plus_amd import Engine, PageRing, _lib, buzhash
+    from pbs_plus_amd.engine import _segs
+
+    eng = Engine(buzhash.NewConfig(avg), device=0)
+    L = _lib.lib()
+    ring = PageRing(eng, hold=True, **ring_opt)
+    page = ring.page_bytes
+    assert ring.stats()["pages_total"] * page >= nbytes + 4 * page, "the arena must hold the whole stream"
+    sid, recs = _ingest(ring, 0xB10B, 0, nbytes)
+    ring.quiesce()
+    n = int(recs.size)
+    data = int(recs["size"].astype(np.uint64).sum())
+    starts = recs["end"] - recs["size"]
+    two_pages = int((starts // page != (recs["end"] - 1) // page).sum())
+    dst = eng.alloc(data + 12 * n)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    crcs = np.zeros(n, dtype=np.uint32)
+    used = C.c_uint64()
+
+    def from_ring():
+        _lib.check(L.pbsgpu_ring_blob_encode_device(ring._h, sid, recs.ctypes.data, n, None, dst.ptr, dst.nbytes,
+                                                    offs.ctypes.data, crcs.ctypes.data, C.byref(used)), "ring_blob_encode_device")
+
+    t_ring = _median_s(from_ring, a.reps)
+    crc_ring = crcs.copy()
+    flat = ring.copy(sid, 0, nbytes)
+    segs, ns = _segs(list(zip(starts.tolist(), recs["size"].tolist())))
+
+    def contiguous():
+        _lib.check(L.pbsgpu_blob_encode_device(eng._h, flat.ptr, nbytes, segs, ns, dst.ptr, dst.nbytes, C.byref(used),
+                                               offs.ctypes.data, crcs.ctypes.data), "blob_encode_device")
+
+    t_flat = _median_s(contiguous, a.reps)
+    assert np.array_equal(crc_ring, crcs)
+    row = {"batch": name, "chunks": n, "bytes": data, "chunks_in_two_pages": two_pages, "page_bytes": page,
+           "ring_encode_GBps": data / t_ring / 1e9, "contiguous_encode_GBps": data / t_flat / 1e9,
+           "ring_over_contiguous": t_flat / t_ring, "ms": {"ring": t_ring * 1e3, "contiguous": t_flat * 1e3}}
+    print(json.dumps(row), flush=True)
+    flat.free()
+    dst.free()
+    ring.close_stream(sid)
+    ring.close()
+    eng.close()
+    return row
+
+
+def feed_once(eng, hold, total, nstreams, arena):
+    """(GiB/s from the first fill to the last record, mean share of the arena held by handed-back pages, arena bytes)"""
+    from pbs_plus_amd import PageRing
+
+    ring = PageRing(eng, hold=hold, arena_bytes=arena, max_streams=nstreams)  # arena 0: what is free minus 8 GiB
+    per = total // nstreams
+    left = {ring.open(): per for _ in range(nstreams)}
+    live = set(left)
+    pages = ring.stats()["pages_total"]
+    shares = []
+    t0 = time.perf_counter()
+    while live:
+        for sid in live:
+            if left[sid]:
+                want = min(left[sid], 64 * ring.page_bytes)
+                left[sid] -= ring.fill(sid, 1000 + sid, 4, want, final=(want == left[sid]))
+        ring.pump()
+        recs, fins = ring.poll_any()
+        if hold and recs.size:
+            sids = recs["segment"] & 0x0FFFFFFF
+            shares.append(sum(ring.held(s)[1] for s in live) / pages)   # before the release: what the consumer was keeping
+            for s in np.unique(sids):
+                ring.release(int(s), int(recs["end"][sids == s].max()))
+        for s in fins:
+            ring.close_stream(int(s))
+            live.discard(int(s))
+    dt = time.perf_counter() - t0
+    ring.quiesce()
+    ring.close()
+    return per * nstreams / dt / (1 << 30), (statistics.mean(shares) if shares else 0.0), pages * ring.page_bytes
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--big-gib", type=float, default=2.0, help="stream of the 4 MiB-average encode")
+    ap.add_argument("--small-mib", type=int, default=256, help="stream of the 4 KiB-average encode")
+    ap.add_argument("--feed-gib", type=float, default=512.0, help="bytes of one feed-rate run")
+    ap.add_argument("--feed-streams", type=int, default=8)
+    ap.add_argument("--feed-arena-gib", type=float, default=0.0, help="0 = the ring's default arena, as the benchmark's")
+    ap.add_argument("--feed-reps", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=5)
+    a = ap.parse_args()
+
+    from pbs_plus_amd import Engine, buzhash
+
+    big = int(a.big_gib * (1 << 30))
+    encode_rates(a, "4MiB-avg", 4 << 20, big, dict(arena_bytes=big + (256 << 20), max_streams=2))
+    small = a.small_mib << 20
+    encode_rates(a, "4KiB-avg", 4096, small,
+                 dict(arena_bytes=(small // 65536 + 64) * (65536 + 256), page_bytes=65536, max_streams=2, round_pages=256))
+    eng = Engine(buzhash.NewConfig(4 << 20), device=0)
+    total, arena = int(a.feed_gib * (1 << 30)), int(a.feed_arena_gib * (1 << 30))
+    feed_once(eng, False, total // 8, a.feed_streams, arena)  # warm-up
+    runs = {False: [], True: []}
+    share = []
+    for _ in range(a.feed_reps):
+        for hold in (False, True):
+            rate, sh, arena_used = feed_once(eng, hold, total, a.feed_streams, arena)
+            runs[hold].append(rate)
+            if hold:
+                share.append(sh)
+    row = {"batch": "feed", "bytes": total, "streams": a.feed_streams, "arena_bytes": arena_used,
+           "plain_GiBps": statistics.median(runs[False]), "holding_GiBps": statistics.median(runs[True]),
+           "plain_runs": [round(x, 1) for x in runs[False]], "holding_runs": [round(x, 1) for x in runs[True]],
+           "arena_share_held_mean": statistics.mean(share)}
+    print(json.dumps(row), flush=True)
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
