@@ -42,6 +42,13 @@ type (
 	Comm       struct{}
 	Ticket     uint64
 	DedupStats struct{ Records, Unique, TotalBytes, UniqueBytes uint64 }
+	Uploaded   struct {
+		Known   []bool
+		Offsets []uint64
+		CRCs    []uint32
+		Used    uint64
+		Stats   DedupStats
+	}
 	ReuseChunk struct {
 		Size, Padding, EndOffset uint64
 		Digest                   [32]byte
@@ -146,6 +153,9 @@ func (r *Ring) Held(uint32) (uint64, uint32, error)                             
 func (r *Ring) EncodeBlobs(uint32, []ChunkInfo, []bool, unsafe.Pointer, uint64) ([]uint64, []uint32, uint64, error) {
 	return nil, nil, 0, ErrNotBuilt
 }
+func (r *Ring) UploadNew(*KnownChunks, uint32, []ChunkInfo, bool, unsafe.Pointer, uint64) (Uploaded, error) {
+	return Uploaded{}, ErrNotBuilt
+}
 func (r *Ring) Copy(uint32, uint64, uint64, unsafe.Pointer) error                { return ErrNotBuilt }
 func (r *Ring) Quiesce() error                                                   { return ErrNotBuilt }
 func (r *Ring) Park() error                                                      { return ErrNotBuilt }
@@ -162,6 +172,9 @@ func (e *Engine) NewKnownChunks(uint64) (*KnownChunks, error)                 { 
 func (k *KnownChunks) Add([]ChunkInfo) error                                  { return ErrNotBuilt }
 func (k *KnownChunks) AddDynamicIndex([]byte) error                           { return ErrNotBuilt }
 func (k *KnownChunks) Classify([]ChunkInfo, bool) ([]bool, DedupStats, error) { return nil, DedupStats{}, ErrNotBuilt }
+func (k *KnownChunks) UploadNew(unsafe.Pointer, uint64, []ChunkInfo, []uint64, []uint64, bool, unsafe.Pointer, uint64) (Uploaded, error) {
+	return Uploaded{}, ErrNotBuilt
+}
 func (k *KnownChunks) Len() int                                               { return 0 }
 func (k *KnownChunks) Close()                                                 {}
 

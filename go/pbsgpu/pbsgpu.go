@@ -857,6 +857,53 @@ func (r *Ring) EncodeBlobs(stream uint32, recs []ChunkInfo, skip []bool, dst uns
 	return offsets, crcs, uint64(u), nil
 }
 
+// Uploaded is what UploadNew returns: the classify result and the blobs of the new chunks. Offsets and CRCs are per
+// entry and 0 for known ones; Used is the bytes written to dst — or, with a dst that is too small (an error: nothing is
+// written and the set is unchanged, while Known and Stats are valid), the bytes needed.
+type Uploaded struct {
+	Known   []bool
+	Offsets []uint64
+	CRCs    []uint32
+	Used    uint64
+	Stats   DedupStats
+}
+
+func uploadedFrom(flags []C.uint8_t, offsets []uint64, crcs []uint32, used C.uint64_t, st C.pbsgpu_dedup_stats) Uploaded {
+	known := make([]bool, len(flags))
+	for i := range known {
+		known[i] = flags[i] != 0
+	}
+	return Uploaded{known, offsets, crcs, uint64(used),
+		DedupStats{uint64(st.nrecords), uint64(st.nunique), uint64(st.total_bytes), uint64(st.unique_bytes)}}
+}
+
+// UploadNew is KnownChunks.Classify and EncodeBlobs(skip = isKnown) in one device-side call: the polled entries recs are
+// classified against known and the new ones framed straight out of the ring's pages into device memory dst. The flags
+// stay on the device in between and the encode plan is built there, so the call comes back to the host once. The loop of
+// an incremental writer: Poll -> UploadNew -> copy out / upload -> append to the index -> Release(last End).
+func (r *Ring) UploadNew(known *KnownChunks, stream uint32, recs []ChunkInfo, insert bool, dst unsafe.Pointer,
+	dstCap uint64) (Uploaded, error) {
+	defer runtime.KeepAlive(r)
+	defer runtime.KeepAlive(known)
+	if len(recs) == 0 || known == nil {
+		return Uploaded{}, errors.New("pbsgpu: UploadNew needs entries and a known-chunk set")
+	}
+	cr := toRecords(recs)
+	flags := make([]C.uint8_t, len(recs))
+	offsets := make([]uint64, len(recs))
+	crcs := make([]uint32, len(recs))
+	ins := C.int(0)
+	if insert {
+		ins = 1
+	}
+	var u C.uint64_t
+	var st C.pbsgpu_dedup_stats
+	err := check(C.pbsgpu_ring_upload_new_device(r.h, known.h, C.uint32_t(stream), &cr[0], C.uint64_t(len(cr)), ins, dst,
+		C.uint64_t(dstCap), &flags[0], (*C.uint64_t)(unsafe.Pointer(&offsets[0])), (*C.uint32_t)(unsafe.Pointer(&crcs[0])),
+		&u, &st), "ring_upload_new_device")
+	return uploadedFrom(flags, offsets, crcs, u, st), err
+}
+
 // Copy writes the raw stream bytes [offset, offset + length), which polled entries must cover and no Release may have
 // passed, into device memory dst — for consumers that compress on the host or want the bytes unframed.
 func (r *Ring) Copy(stream uint32, offset, length uint64, dst unsafe.Pointer) error {
@@ -1093,6 +1140,32 @@ func (k *KnownChunks) Classify(recs []ChunkInfo, insert bool) ([]bool, DedupStat
 		out[i] = flags[i] != 0
 	}
 	return out, DedupStats{uint64(st.nrecords), uint64(st.nunique), uint64(st.total_bytes), uint64(st.unique_bytes)}, nil
+}
+
+// UploadNew is Classify and Engine.EncodeBlobsDevice over the new chunks in one device-side call: chunk i =
+// src[offsets[i], offsets[i]+lengths[i]) of device memory carries the digest of recs[i]; the blobs of the new ones go
+// back to back into device memory dst.
+func (k *KnownChunks) UploadNew(src unsafe.Pointer, srcBytes uint64, recs []ChunkInfo, offsets, lengths []uint64, insert bool,
+	dst unsafe.Pointer, dstCap uint64) (Uploaded, error) {
+	defer runtime.KeepAlive(k)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 || len(segs) != len(recs) {
+		return Uploaded{}, errors.New("pbsgpu: UploadNew needs entries and one (offset, length) per entry")
+	}
+	cr := toRecords(recs)
+	flags := make([]C.uint8_t, len(recs))
+	boff := make([]uint64, len(recs))
+	crcs := make([]uint32, len(recs))
+	ins := C.int(0)
+	if insert {
+		ins = 1
+	}
+	var u C.uint64_t
+	var st C.pbsgpu_dedup_stats
+	err = check(C.pbsgpu_known_upload_new_device(k.h, src, C.uint64_t(srcBytes), &cr[0], &segs[0], C.uint64_t(len(cr)), ins,
+		dst, C.uint64_t(dstCap), &flags[0], (*C.uint64_t)(unsafe.Pointer(&boff[0])), (*C.uint32_t)(unsafe.Pointer(&crcs[0])),
+		&u, &st), "known_upload_new_device")
+	return uploadedFrom(flags, boff, crcs, u, st), err
 }
 
 // Len is the number of digests in the set.

@@ -461,6 +461,7 @@ int pbsgpu_ring_debug(pbsgpu_ring *ring, char *buf, uint64_t cap);
  * (k + 1) * page_bytes)), until the caller releases it. The loop of an incremental writer then never takes the payload
  * off the device before it is known to be new:
  *   poll -> pbsgpu_known_classify -> pbsgpu_ring_blob_encode_device(skip = known) -> copy out / upload -> release(last end)
+ * (pbsgpu_ring_upload_new_device, below the blob calls, is the two calls in the middle as one device-side call)
  * THE CALLER'S DUTY: held pages are arena pages. A holder that does not release makes reserve answer PBSGPU_E_BUSY and
  * fill take 0 bytes, exactly like a full arena; that is no error state, releasing resumes the ring. The arena must hold
  * what is between two releases (plus what is in flight). Without the flag every call below returns PBSGPU_E_STATE.
@@ -635,6 +636,38 @@ int pbsgpu_blob_verify_device(pbsgpu_engine *eng, const void *dptr, uint64_t nby
 int pbsgpu_blob_verify_host(pbsgpu_engine *eng, const void *hptr, uint64_t nbytes, const pbsgpu_segment *blobs,
                             uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
                             pbsgpu_blob_stats *stats);
+
+/* ---- classify and frame in one device-side call --------------------------------------------------------------------
+ * The middle of the incremental writer's loop — known-chunk check, then upload framing of what is new (SURVEY.md §3A;
+ * the upload of commit_orchestrate.go:137-158 behind the known-chunk check, refs of commit_reuse.go:315-341 being known by
+ * construction) — without the host in between: the flags stay on the device, the encode plan is built there, and the
+ * call comes back once. On success every output is what pbsgpu_known_classify_host(known, recs, n, insert, flags, stats)
+ * followed by the encode over the records flagged 0 produces: blobs in record order, back to back from dst; blob_off[i]
+ * and crcs[i] (may be NULL) untouched for known records; *used = bytes written; the set afterwards as classify leaves it.
+ * Decided on the host before any device work, with dst and the set untouched: PBSGPU_E_INVALID / PBSGPU_E_STATE as for
+ * the two calls, except that EVERY record has to be available (which ones are new is not known on the host), plus
+ * PBSGPU_E_INVALID for a host dst, a chunk of 2 GiB or more, or a set of another engine than the ring's.
+ * Whether the blobs fit is known only on the device: PBSGPU_E_CAPACITY when they need more than dst_cap — *used is then
+ * the size needed, no byte of dst is written and the set is UNCHANGED (insert has not taken effect, or the chunks would
+ * never be uploaded), while known_out and stats are valid: retry with a buffer of *used bytes for the same answer.
+ * dst may be NULL with dst_cap = 0 (a sizing call). One leased stream of the engine and one synchronisation of it (two
+ * when the set has to grow); waits only for that stream, so it is usable between pumps while the services run.
+ * Threads: the ring's rule and the set's rule (one thread per set at a time). n < 2^32. */
+#define PBSGPU_HAS_UPLOAD_NEW 1
+/* classify recs against `known`, then frame the NEW ones as uncompressed blobs straight out of the ring's held pages
+ * (PBSGPU_RING_F_HOLD_PAGES; recs as pbsgpu_ring_poll / _poll_any returned them, see pbsgpu_ring_blob_encode_device).
+ * A chunk in two pages gets one CRC over both parts. */
+int pbsgpu_ring_upload_new_device(pbsgpu_ring *ring, pbsgpu_known *known, uint32_t stream /* or PBSGPU_RING_ANY_STREAM */,
+                                  const pbsgpu_record *recs /* host, as polled */, uint64_t n, int insert,
+                                  void *dst, uint64_t dst_cap,
+                                  uint8_t *known_out /* n, may be NULL */, uint64_t *blob_off /* n */,
+                                  uint32_t *crcs /* n, may be NULL */, uint64_t *used, pbsgpu_dedup_stats *stats);
+/* the same for chunks in one contiguous device buffer (the batch path): chunk i = src[chunks[i].offset .. +length),
+ * framed as pbsgpu_blob_encode_device frames it; every chunks[i] must lie inside src */
+int pbsgpu_known_upload_new_device(pbsgpu_known *known, const void *src, uint64_t src_bytes,
+                                   const pbsgpu_record *recs /* host: the digests */, const pbsgpu_segment *chunks /* n */,
+                                   uint64_t n, int insert, void *dst, uint64_t dst_cap, uint8_t *known_out,
+                                   uint64_t *blob_off, uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats);
 
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or

@@ -85,6 +85,16 @@ struct KnownChunkRef {
     uint64_t Size = 0;
 };
 
+// What KnownChunks::UploadNew / transfer::PageRing::UploadNew return: the classify result and the blobs of the new chunks
+struct Uploaded {
+    uint64_t bytes = 0;              // blob bytes written to dst — or, with a dst that is too small (an error: nothing
+                                     // written, the set unchanged, known / stats valid), the bytes needed
+    std::vector<uint8_t> known;      // per record: 1 = the server has the chunk
+    std::vector<uint64_t> offsets;   // per new record: its blob's offset in dst
+    std::vector<uint32_t> crcs;      // per new record
+    pbsgpu_dedup_stats stats{};
+};
+
 // The known-chunk set of an incremental session (pbsgpu_known_*, device resident): the digests of the previous
 // snapshot's indexes (PreviousBackup, commit_orchestrate.go:127-158) plus every chunk already sent or injected
 // (InjectChunks refs, commit_reuse.go:315-341). Classify flags, per record, the chunks the server already has; the rest
@@ -138,11 +148,31 @@ class KnownChunks {
         r.value.assign(flags.begin(), flags.end());
         return r;
     }
+    // Classify and the upload framing of the new chunks in one device-side call (commit_orchestrate.go:137-158 behind the
+    // known-chunk check; commit_reuse.go:315-341 refs are known): chunk i = chunks[i] of device buffer src carries the
+    // digest of recs[i]; the blobs of the new ones go back to back into device buffer dst.
+    Result<Uploaded> UploadNew(const void *src, uint64_t srcBytes, const std::vector<pbsgpu_record> &recs,
+                               const std::vector<pbsgpu_segment> &chunks, bool insert, void *dst, uint64_t dstCap) {
+        Result<Uploaded> r;
+        if (chunks.size() != recs.size()) {
+            r.err = errorf("known chunks upload new", PBSGPU_E_INVALID);
+            return r;
+        }
+        r.value.known.assign(recs.size(), 0);
+        r.value.offsets.assign(recs.size(), 0);
+        r.value.crcs.assign(recs.size(), 0);
+        const int st = pbsgpu_known_upload_new_device(k_, src, srcBytes, recs.data(), chunks.data(), recs.size(), insert ? 1 : 0,
+                                                      dst, dstCap, r.value.known.data(), r.value.offsets.data(),
+                                                      r.value.crcs.data(), &r.value.bytes, &r.value.stats);
+        if (st != PBSGPU_OK) r.err = errorf("known chunks upload new", st);
+        return r;
+    }
     uint64_t Len() const {
         uint64_t n = 0;
         pbsgpu_known_count(k_, &n);
         return n;
     }
+    pbsgpu_known *Handle() const { return k_; }
 
   private:
     explicit KnownChunks(pbsgpu_known *k) : k_(k) {}
@@ -624,6 +654,20 @@ class PageRing {
         const int st = pbsgpu_ring_blob_encode_device(r_, stream, recs.data(), recs.size(), skip.empty() ? nullptr : skip.data(),
                                                       dst, dstCap, r.value.offsets.data(), r.value.crcs.data(), &r.value.bytes);
         if (st != PBSGPU_OK) r.err = errorf("ring blob encode", st);
+        return r;
+    }
+    // Classify + EncodeBlobs(skip = known) in one device-side call: the delivered entries recs are classified against
+    // `known` and the new ones framed out of the ring's pages; the flags never leave the device in between.
+    Result<datastore::Uploaded> UploadNew(datastore::KnownChunks &known, uint32_t stream, const std::vector<pbsgpu_record> &recs,
+                                          bool insert, void *dst, uint64_t dstCap) {
+        Result<datastore::Uploaded> r;
+        r.value.known.assign(recs.size(), 0);
+        r.value.offsets.assign(recs.size(), 0);
+        r.value.crcs.assign(recs.size(), 0);
+        const int st = pbsgpu_ring_upload_new_device(r_, known.Handle(), stream, recs.data(), recs.size(), insert ? 1 : 0, dst,
+                                                     dstCap, r.value.known.data(), r.value.offsets.data(),
+                                                     r.value.crcs.data(), &r.value.bytes, &r.value.stats);
+        if (st != PBSGPU_OK) r.err = errorf("ring upload new", st);
         return r;
     }
     // the raw stream bytes [offset, offset + length) into device buffer dst

@@ -241,6 +241,10 @@ SYMBOLS = {
     "pbsgpu_blob_encode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _U64P, _P, _P]),
     "pbsgpu_blob_verify_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
     "pbsgpu_blob_verify_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
+    "pbsgpu_ring_upload_new_device": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P, _U64P,
+                                                C.POINTER(DedupStats)]),
+    "pbsgpu_known_upload_new_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P,
+                                                 _U64P, C.POINTER(DedupStats)]),
     "pbsgpu_comm_unique_id": (C.c_int, [_P]),
     "pbsgpu_comm_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "pbsgpu_comm_destroy": (None, [_P]),

@@ -40,6 +40,7 @@ constexpr uint32_t kGap = kRow - 16;
 constexpr uint32_t kPieceLog = 16;
 constexpr uint64_t kPiece = 1ull << kPieceLog;
 constexpr uint32_t kFoldLanes = 64;
+static_assert(kPieceLog == kBlobPieceLog, "ring.cpp bounds the piece count with this");
 
 __host__ __device__ constexpr uint32_t mul(uint32_t a, uint32_t b) {
     uint32_t p = 0;
@@ -336,6 +337,8 @@ struct PartPlan {
     uint8_t *dst;
     uint32_t npieces, nparts, nblob;
     uint32_t magic_lo, magic_hi;
+    const uint32_t *counts;  // nullptr (the host-built plan: the three counts above), or npieces / nparts / nblob in device
+                             // memory, from the plan kernels below: the launch grids then only know upper bounds
 };
 typedef const CRC_GLOBAL PartDesc *gpart_ptr;
 typedef const CRC_GLOBAL BlobDesc *gblob_ptr;
@@ -360,7 +363,8 @@ __global__ __launch_bounds__(256) void k_pagecrc_pieces(PartPlan pl) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t kl = kDev.klane[lane];
     const uint32_t nw = gridDim.x * 4;
-    for (uint32_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.npieces; p += nw) {
+    const uint32_t npieces = pl.counts ? __builtin_amdgcn_readfirstlane(((gword_ptr)pl.counts)[0]) : pl.npieces;
+    for (uint32_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < npieces; p += nw) {
         const uint32_t i = ((gword_ptr)pl.ppart)[p];
         const gpart_ptr pd = (gpart_ptr)pl.parts + i;
         const uint32_t len = pd->len, pinv = pd->inv;
@@ -422,7 +426,8 @@ __device__ __forceinline__ uint32_t fold_part(gword_ptr raw, uint32_t m, uint32_
 __global__ __launch_bounds__(256) void k_pagecrc_fold(PartPlan pl) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t nw = gridDim.x * 4;
-    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < pl.nblob; i += nw) {
+    const uint32_t nblob = pl.counts ? __builtin_amdgcn_readfirstlane(((gword_ptr)pl.counts)[2]) : pl.nblob;
+    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < nblob; i += nw) {
         const gblob_ptr bd = (gblob_ptr)pl.blobs + i;
         const uint32_t np = bd->nparts, len = bd->len;
         const gpart_ptr pd = (gpart_ptr)pl.parts + bd->part0;
@@ -455,6 +460,233 @@ __global__ __launch_bounds__(256) void k_page_copy(PartPlan pl) {
         }
         const uint32_t t = 16 * units + threadIdx.x;
         if (blockIdx.x == 0 && t < len) ((gbyte_out)o)[t] = ((gbyte_ptr)d)[t];
+    }
+}
+
+
+// ---- the plan built on the device: classify and frame in one call (pbsgpu_*_upload_new_device) --------
+// Which records are new is known only on the device (the flags of k_known_mark), so what blob_encode_parts builds on the
+// host is built here: per record its blob bytes, parts and pieces; exclusive prefix sums of the three (and of the blob
+// count) give every descriptor its place. Three kernels over blocks of 256 records: the blocks' sums, one workgroup that
+// scans those sums and decides whether the blobs fit, and the fill that repeats the per-record shape, scans inside its
+// block and writes the descriptors. A fourth gives every piece its part.
+struct UpCount {
+    uint64_t bytes;  // 12 + size per new record
+    uint32_t parts, pieces, blobs;
+    uint32_t pad;
+};
+struct UpHead {  // the first 64 bytes of the block that goes back to the host
+    uint64_t stats[4];  // k_known_mark's
+    uint64_t total;     // bytes the blobs need
+    uint32_t npieces, nparts, nblob;  // what the CRC pair sees (PartPlan::counts): all 0 when total > dst_cap
+    uint32_t over;      // total > dst_cap
+    uint64_t pad;
+};
+struct UpPlan {
+    const uint8_t *recs;           // n records (stride 48)
+    const uint8_t *known;          // n: k_known_mark's flags
+    const pbsgpu_segment *chunks;  // the contiguous form: chunk i is one part at chunks[i].offset (nullptr: the ring's pages)
+    const PageTab *tabs;           // per stream slot: its logical pages [k0, k0 + n) are ptab[off ..)
+    const uint64_t *ptab;          // offset of a page's body from PartPlan::base
+    uint64_t page_bytes;
+    uint64_t dst_cap;
+    uint32_t stream;               // or PBSGPU_RING_ANY_STREAM: a record's stream is the low 28 bits of its segment
+    uint32_t n;
+    UpCount *bsum;                 // per block of 256 records: its sum, then (k_upnew_scan) the sum of the blocks before it
+    UpHead *head;
+    uint64_t *boff;                // n: blob offset of every new record
+    uint8_t *skip;                 // n: the insert's flags (known, or all 1 when the blobs do not fit)
+    PartDesc *parts;
+    BlobDesc *blobs;
+    uint32_t *ppart;
+};
+typedef const CRC_GLOBAL UpCount *gcount_ptr;
+typedef CRC_GLOBAL UpCount *gcount_out;
+typedef const CRC_GLOBAL UpHead *ghead_ptr;
+
+// a new record's bytes: part a at src0 and, when it straddles two pages, part b at src1
+struct UpShape {
+    uint64_t src0, src1;
+    uint32_t a, b;
+};
+__device__ __forceinline__ bool up_shape(const UpPlan &pl, uint32_t i, UpShape &sh) {
+    sh = UpShape{0, 0, 0, 0};
+    if (i >= pl.n || ((gbyte_ptr)pl.known)[i]) return false;
+    if (pl.chunks) {
+        sh.src0 = ((gquad_ptr)pl.chunks)[2 * (uint64_t)i];
+        sh.a = (uint32_t)((gquad_ptr)pl.chunks)[2 * (uint64_t)i + 1];
+        return true;
+    }
+    const uint8_t *rc = pl.recs + 48ull * i;
+    const uint32_t size = ((gword_ptr)rc)[11];
+    if (size == 0) return true;
+    const uint32_t sid = pl.stream == PBSGPU_RING_ANY_STREAM ? ((gword_ptr)rc)[10] & 0x0fffffffu : pl.stream;
+    const uint64_t start = ((gquad_ptr)rc)[0] - size;
+    const uint64_t k = start / pl.page_bytes, in = start - k * pl.page_bytes;
+    const gquad_ptr tab = (gquad_ptr)pl.tabs + 2 * (uint64_t)sid;  // PageTab: k0 | off, n
+    const gquad_ptr pg = (gquad_ptr)pl.ptab + (uint32_t)tab[1] + (k - tab[0]);
+    sh.a = (uint32_t)(pl.page_bytes - in < size ? pl.page_bytes - in : size);
+    sh.b = size - sh.a;
+    sh.src0 = pg[0] + in;
+    if (sh.b) sh.src1 = pg[1];
+    return true;
+}
+__device__ __forceinline__ uint32_t up_pieces(uint32_t len) { return (len + (uint32_t)kPiece - 1) >> kPieceLog; }
+__device__ __forceinline__ UpCount up_count(bool is_new, const UpShape &sh) {
+    UpCount c{0, 0, 0, 0, 0};
+    if (is_new) {
+        c.bytes = (uint64_t)sh.a + sh.b + PBSGPU_BLOB_HEADER_SIZE;
+        c.parts = (sh.a ? 1u : 0u) + (sh.b ? 1u : 0u);
+        c.pieces = up_pieces(sh.a) + up_pieces(sh.b);
+        c.blobs = 1;
+    }
+    return c;
+}
+__device__ __forceinline__ UpCount up_add(UpCount x, const UpCount &y) {
+    x.bytes += y.bytes;
+    x.parts += y.parts;
+    x.pieces += y.pieces;
+    x.blobs += y.blobs;
+    return x;
+}
+// inclusive scan over the workgroup's 256 threads (ws: four entries of LDS); *total = the workgroup's sum
+__device__ __forceinline__ UpCount up_block_scan(UpCount v, UpCount (&ws)[4], UpCount *total) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        UpCount u;
+        u.bytes = __shfl_up((unsigned long long)v.bytes, d, 64);
+        u.parts = __shfl_up(v.parts, d, 64);
+        u.pieces = __shfl_up(v.pieces, d, 64);
+        u.blobs = __shfl_up(v.blobs, d, 64);
+        if (lane >= (uint32_t)d) v = up_add(v, u);
+    }
+    if (lane == 63) ws[w] = v;
+    __syncthreads();
+    UpCount pre{0, 0, 0, 0, 0}, tot{0, 0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const UpCount t = ws[j];
+        if (j < w) pre = up_add(pre, t);
+        tot = up_add(tot, t);
+    }
+    __syncthreads();  // (ws may be written again)
+    *total = tot;
+    return up_add(v, pre);
+}
+__device__ __forceinline__ void up_store(gcount_out o, const UpCount &c) {
+    o->bytes = c.bytes;
+    o->parts = c.parts;
+    o->pieces = c.pieces;
+    o->blobs = c.blobs;
+}
+
+__global__ __launch_bounds__(256) void k_upnew_count(UpPlan pl) {
+    __shared__ UpCount ws[4];
+    UpShape sh;
+    const bool is_new = up_shape(pl, blockIdx.x * 256 + threadIdx.x, sh);
+    UpCount tot;
+    (void)up_block_scan(up_count(is_new, sh), ws, &tot);
+    if (threadIdx.x == 0) up_store((gcount_out)pl.bsum + blockIdx.x, tot);
+}
+
+// one workgroup: the blocks' sums become exclusive prefixes; the totals and the verdict go to the head
+__global__ __launch_bounds__(256) void k_upnew_scan(UpPlan pl) {
+    __shared__ UpCount ws[4];
+    const uint32_t nb = (pl.n + 255) / 256;
+    UpCount carry{0, 0, 0, 0, 0};
+    for (uint32_t b0 = 0; b0 < nb; b0 += 256) {
+        const uint32_t b = b0 + threadIdx.x;
+        UpCount v{0, 0, 0, 0, 0};
+        if (b < nb) {
+            const gcount_ptr q = (gcount_ptr)pl.bsum + b;
+            v.bytes = q->bytes;
+            v.parts = q->parts;
+            v.pieces = q->pieces;
+            v.blobs = q->blobs;
+        }
+        UpCount tot;
+        const UpCount inc = up_block_scan(v, ws, &tot);
+        if (b < nb) {
+            UpCount ex = up_add(carry, inc);
+            ex.bytes -= v.bytes;
+            ex.parts -= v.parts;
+            ex.pieces -= v.pieces;
+            ex.blobs -= v.blobs;
+            up_store((gcount_out)pl.bsum + b, ex);
+        }
+        carry = up_add(carry, tot);
+    }
+    if (threadIdx.x == 0) {
+        CRC_GLOBAL UpHead *h = (CRC_GLOBAL UpHead *)pl.head;
+        const bool over = carry.bytes > pl.dst_cap;
+        h->total = carry.bytes;
+        h->npieces = over ? 0u : carry.pieces;
+        h->nparts = over ? 0u : carry.parts;
+        h->nblob = over ? 0u : carry.blobs;
+        h->over = over ? 1u : 0u;
+        h->pad = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_upnew_fill(UpPlan pl) {
+    __shared__ UpCount ws[4];
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    UpShape sh;
+    const bool is_new = up_shape(pl, i, sh);
+    const UpCount c = up_count(is_new, sh);
+    UpCount tot;
+    UpCount ex = up_block_scan(c, ws, &tot);
+    if (i >= pl.n) return;
+    ((gbyte_out)pl.skip)[i] = ((ghead_ptr)pl.head)->over ? (uint8_t)1 : (uint8_t)(is_new ? 0 : 1);
+    if (!is_new) return;
+    const gcount_ptr bp = (gcount_ptr)pl.bsum + blockIdx.x;
+    const uint64_t hdr = bp->bytes + ex.bytes - c.bytes;
+    const uint32_t part0 = bp->parts + ex.parts - c.parts;
+    const uint32_t piece0 = bp->pieces + ex.pieces - c.pieces;
+    const uint32_t len = sh.a + sh.b;
+    uint32_t join = kOne;  // x^(8 b)
+    for (int j = 0; j < 32; ++j)
+        if ((sh.b >> j) & 1u) join = mul(join, kDev.x8[j]);
+    CRC_GLOBAL BlobDesc *bd = (CRC_GLOBAL BlobDesc *)pl.blobs + (bp->blobs + ex.blobs - c.blobs);
+    bd->hdr = hdr;
+    bd->part0 = part0;
+    bd->nparts = c.parts;
+    bd->join = join;
+    bd->len = len;
+    ((CRC_GLOBAL uint64_t *)pl.boff)[i] = hdr;
+    CRC_GLOBAL PartDesc *pd = (CRC_GLOBAL PartDesc *)pl.parts + part0;
+    if (sh.a) {
+        pd->src = sh.src0;
+        pd->dst = hdr + PBSGPU_BLOB_HEADER_SIZE;
+        pd->len = sh.a;
+        pd->inv = len >= 4 ? (sh.a < 4 ? sh.a : 4u) : 0u;
+        pd->pbase = piece0;
+        pd->pad = 0;
+    }
+    if (sh.b) {  // (a first part of 1-3 bytes leaves the rest of the chunk's first four to this one)
+        pd[1].src = sh.src1;
+        pd[1].dst = hdr + PBSGPU_BLOB_HEADER_SIZE + sh.a;
+        pd[1].len = sh.b;
+        pd[1].inv = (len >= 4 && sh.a < 4) ? (4 - sh.a < sh.b ? 4 - sh.a : sh.b) : 0u;
+        pd[1].pbase = piece0 + up_pieces(sh.a);
+        pd[1].pad = 0;
+    }
+}
+
+// the part of each piece: one thread per piece, a binary search for the last part that begins at or before it
+__global__ __launch_bounds__(256) void k_upnew_ppart(UpPlan pl) {
+    const ghead_ptr h = (ghead_ptr)pl.head;
+    const uint32_t npieces = h->npieces, nparts = h->nparts;
+    const gpart_ptr parts = (gpart_ptr)pl.parts;
+    for (uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x; p < npieces; p += (uint64_t)gridDim.x * 256) {
+        uint32_t lo = 0, hi = nparts;  // parts[lo].pbase <= p < parts[hi].pbase
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (parts[mid].pbase <= p) lo = mid;
+            else hi = mid;
+        }
+        ((gword_out)pl.ppart)[p] = lo;
     }
 }
 
@@ -788,6 +1020,143 @@ int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32
     return PBSGPU_OK;
 }
 
+// Layout on the one lease (known_common and enqueue_parts would both want tile_cnt and dense; here every array has a
+// buffer of its own for as long as something reads it):
+//   recs                 the records as staged, read by lookup / mark / the plan / the insert
+//   sugg                 the PageTabs and the page array (ring form), or the chunk ranges (contiguous form)
+//   dense | tile_slots   sort keys | indices, each with its double buffer: dead behind k_known_mark
+//   tile_cnt             before[n] | skip[n] (the insert's flags, written by k_upnew_fill)
+//   scan_tmp             the sort's temporary storage
+//   par                  the plan's block sums
+//   segs | seg_off       PartDesc | BlobDesc
+//   tile_off | seg_cnt   ppart | praw
+//   order                what goes back in one transfer: UpHead (stats, total, counts, verdict) | blob_off[n] u64 |
+//                        crcs u32 (compacted: one per new record) | known[n]
+// Order on the stream: mark -> (growth only: the number of new digests is read back and the table rebuilt) -> plan with
+// the verdict -> insert with the plan's flags -> CRC pair on the plan's counts -> publish. The verdict comes before the
+// insert and before the first byte of dst: when the blobs do not fit, the insert sees all-ones flags and the pair sees
+// zero counts, so the set and dst are as they were, while flags, stats and the size needed are already final.
+int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint8_t *dst,
+               uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
+               pbsgpu_dedup_stats *stats) {
+    pbsgpu_engine *e = known_engine(k);
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const hipStream_t st = s->stream;
+    KnownPass p;
+    CHK(known_sort_bytes(n, st, &p.tmp_bytes));
+    const uint32_t nb = (uint32_t)((n + 255) / 256);
+    const size_t out_bytes = sizeof(UpHead) + (size_t)n * 13;
+    const size_t src_bytes = src.chunks ? (size_t)n * sizeof(pbsgpu_segment) : src.tab_words * sizeof(uint64_t);
+    CHK(s->recs.ensure((size_t)n * sizeof(pbsgpu_record) + 64));
+    CHK(s->sugg.ensure(src_bytes + 64));
+    CHK(s->dense.ensure((size_t)n * 8 + 64));
+    CHK(s->tile_slots.ensure((size_t)n * 8 + 64));
+    CHK(s->tile_cnt.ensure((size_t)n * 2 + 64));
+    CHK(s->scan_tmp.ensure(p.tmp_bytes));
+    CHK(s->par.ensure((size_t)nb * sizeof(UpCount) + 64));
+    CHK(s->segs.ensure((size_t)std::min<uint64_t>(2 * n, src.pieces_max) * sizeof(PartDesc) + 64));
+    CHK(s->seg_off.ensure((size_t)n * sizeof(BlobDesc) + 64));
+    CHK(s->tile_off.ensure((size_t)src.pieces_max * sizeof(uint32_t) + 64));
+    CHK(s->seg_cnt.ensure((size_t)src.pieces_max * sizeof(uint32_t) + 64));
+    CHK(s->order.ensure(out_bytes + 64));
+    CHK(s->h_recs.ensure(out_bytes + 64));
+    CHK(s->h_scalars.ensure(64));
+    // the small table first: the records' copy then waits for nothing but that
+    if (src_bytes)
+        CHK(staged_h2d(*s, s->sugg.p, src.chunks ? (const void *)src.chunks : (const void *)src.tabs, src_bytes, st));
+    CHK(staged_h2d(*s, s->recs.p, recs, n * sizeof(pbsgpu_record), st));
+    uint8_t *out = s->order.as<uint8_t>();
+    p.recs = s->recs.as<uint8_t>();
+    p.stride = sizeof(pbsgpu_record);
+    p.n = n;
+    p.keys = s->dense.as<uint32_t>();
+    p.idx = s->tile_slots.as<uint32_t>();
+    p.before = s->tile_cnt.as<uint8_t>();
+    p.known = out + sizeof(UpHead) + (size_t)n * 12;
+    p.stats = reinterpret_cast<uint64_t *>(out);
+    p.tmp = s->scan_tmp.p;
+    CHK(known_enqueue_mark(k, p, st));
+    if (insert && known_may_grow(k, n)) {  // as known_common: the one case with a second synchronisation
+        HIPCHK(hipMemcpyAsync(s->h_scalars.p, p.stats, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        CHK(known_reserve(k, s->h_scalars.as<uint64_t>()[1], st));
+    }
+    UpPlan up{};
+    up.recs = p.recs;
+    up.known = p.known;
+    if (src.chunks) {
+        up.chunks = s->sugg.as<pbsgpu_segment>();
+    } else {
+        up.tabs = s->sugg.as<PageTab>();
+        up.ptab = s->sugg.as<uint64_t>() + 2 * (size_t)src.nslots;
+    }
+    up.page_bytes = src.page_bytes;
+    up.dst_cap = dst_cap;
+    up.stream = src.stream;
+    up.n = (uint32_t)n;
+    up.bsum = s->par.as<UpCount>();
+    up.head = reinterpret_cast<UpHead *>(out);
+    up.boff = reinterpret_cast<uint64_t *>(out + sizeof(UpHead));
+    up.skip = p.before + n;
+    up.parts = s->segs.as<PartDesc>();
+    up.blobs = s->seg_off.as<BlobDesc>();
+    up.ppart = s->tile_off.as<uint32_t>();
+    hipLaunchKernelGGL(pbsk::crc::k_upnew_count, dim3(nb), dim3(256), 0, st, up);
+    hipLaunchKernelGGL(pbsk::crc::k_upnew_scan, dim3(1), dim3(256), 0, st, up);
+    hipLaunchKernelGGL(pbsk::crc::k_upnew_fill, dim3(nb), dim3(256), 0, st, up);
+    HIPCHK(hipGetLastError());
+    if (src.pieces_max) {
+        const uint64_t wg = std::min<uint64_t>((src.pieces_max + 255) / 256, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pbsk::crc::k_upnew_ppart, dim3((unsigned)wg), dim3(256), 0, st, up);
+        HIPCHK(hipGetLastError());
+    }
+    if (insert) CHK(known_enqueue_insert(k, p, up.skip, st));
+    PartPlan pl{};
+    pl.base = src.base;
+    pl.dst = dst;
+    pl.parts = up.parts;
+    pl.blobs = up.blobs;
+    pl.ppart = up.ppart;
+    pl.praw = s->seg_cnt.as<uint32_t>();
+    pl.crcs = reinterpret_cast<uint32_t *>(out + sizeof(UpHead) + (size_t)n * 8);
+    pl.counts = &up.head->npieces;
+    pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
+    pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
+    if (src.pieces_max) {  // the capped grids of enqueue_parts, from the upper bounds the host knows
+        const uint64_t wg = std::min<uint64_t>((src.pieces_max + 3) / 4, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pbsk::crc::k_pagecrc_pieces, dim3((unsigned)wg), dim3(256), 0, st, pl);
+        HIPCHK(hipGetLastError());
+    }
+    const uint64_t wg = std::min<uint64_t>((n + 3) / 4, (uint64_t)e->num_cus * 16);
+    hipLaunchKernelGGL(pbsk::crc::k_pagecrc_fold, dim3((unsigned)wg), dim3(256), 0, st, pl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(pbsk::launch_publish(s->h_recs.p, out, out_bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const uint8_t *h = s->h_recs.as<uint8_t>();
+    UpHead head;
+    std::memcpy(&head, h, sizeof(head));
+    const uint8_t *h_known = h + sizeof(UpHead) + (size_t)n * 12;
+    if (known_out) std::memcpy(known_out, h_known, (size_t)n);
+    if (stats) {
+        stats->nrecords = head.stats[0];
+        stats->nunique = head.stats[1];
+        stats->total_bytes = head.stats[2];
+        stats->unique_bytes = head.stats[3];
+    }
+    *used = head.total;
+    if (head.over) return PBSGPU_E_CAPACITY;
+    const uint8_t *h_boff = h + sizeof(UpHead), *h_crcs = h_boff + (size_t)n * 8;
+    for (uint64_t i = 0, j = 0; i < n; ++i) {
+        if (h_known[i]) continue;
+        std::memcpy(&blob_off[i], h_boff + i * 8, 8);
+        if (crcs) std::memcpy(&crcs[i], h_crcs + j * 4, 4);
+        ++j;
+    }
+    if (insert) known_inserted(k, head.stats[1]);
+    return PBSGPU_OK;
+}
+
 }  // namespace pbse
 
 extern "C" {
@@ -854,6 +1223,31 @@ int pbsgpu_blob_verify_host(pbsgpu_engine *e, const void *hptr, uint64_t nbytes,
                             uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
                             pbsgpu_blob_stats *stats) {
     return blob_verify(e, hptr, true, nbytes, blobs, nblob, digests, sizes, status, stats);
+}
+
+int pbsgpu_known_upload_new_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,
+                                   const pbsgpu_segment *chunks, uint64_t n, int insert, void *dst, uint64_t dst_cap,
+                                   uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
+                                   pbsgpu_dedup_stats *stats) {
+    if (!k || !used || !stats || (!src && src_bytes) || (n && (!recs || !chunks || !blob_off)) || n >= (1ull << 32))
+        return PBSGPU_E_INVALID;
+    if (!dst && dst_cap) return PBSGPU_E_INVALID;
+    UploadSrc us;
+    for (uint64_t i = 0; i < n; ++i) {  // every chunk, not only the new ones: which ones are new is not known here
+        const pbsgpu_segment &c = chunks[i];
+        if (c.length > src_bytes || c.offset > src_bytes - c.length || c.length >= (1ull << 31)) return PBSGPU_E_INVALID;
+        us.pieces_max += (c.length + pbsk::crc::kPiece - 1) >> pbsk::crc::kPieceLog;
+    }
+    if (us.pieces_max >= (1ull << 32)) return PBSGPU_E_INVALID;
+    *used = 0;
+    std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return PBSGPU_OK;
+    CHK(set_device(known_engine(k)));
+    if ((dst && !is_device_pointer(dst)) || (src_bytes && !is_device_pointer(src))) return PBSGPU_E_INVALID;
+    us.base = static_cast<const uint8_t *>(src);
+    us.chunks = chunks;
+    return upload_new(k, us, recs, n, insert != 0, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, crcs, used,
+                      stats);
 }
 
 }  // extern "C"

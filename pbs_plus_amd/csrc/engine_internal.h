@@ -197,6 +197,7 @@ struct Slot {
 
 struct pbsgpu_stream;
 struct pbsgpu_ring;
+struct pbsgpu_known;
 struct pbsgpu_engine {
     int device = 0;
     int num_cus = 256;
@@ -299,5 +300,32 @@ void stream_pool_release(pbsgpu_engine *e);
 
 // the engine's page ring (stream.cpp): destroyed at engine teardown / trim
 void engine_ring_release(pbsgpu_engine *e);
+
+// known.hip: one classify pass of a known-chunk set in pieces, enqueued on a stream the caller owns (the lease of
+// known_common, or the fused upload of blob.hip, which builds its encode plan between the marking and the insert).
+// The arrays are the caller's: it decides where they live and for how long.
+struct KnownPass {
+    const uint8_t *recs = nullptr;  // device: n records or .didx entries (`stride` 48 or 40), the digest at offset 8
+    uint32_t stride = 0;
+    uint64_t n = 0;
+    uint32_t *keys = nullptr;       // 2 n: sort keys and their double buffer
+    uint32_t *idx = nullptr;        // 2 n: record indices and their double buffer
+    uint8_t *before = nullptr;      // n: the digest was in the set before the call
+    uint8_t *known = nullptr;       // n: the result
+    uint64_t *stats = nullptr;      // 4: records, new, total bytes, new bytes
+    void *tmp = nullptr;            // the sort's temporary storage (known_sort_bytes)
+    size_t tmp_bytes = 0;
+};
+int known_sort_bytes(uint64_t n, hipStream_t st, size_t *bytes);
+// lookup (k = NULL: nothing is known before the call) / sort / mark: p.known and p.stats are final behind it
+int known_enqueue_mark(const pbsgpu_known *k, const KnownPass &p, hipStream_t st);
+// true when n more digests could pass the table's load limit: the caller reads p.stats[1] back and calls known_reserve
+bool known_may_grow(const pbsgpu_known *k, uint64_t n);
+// room for nnew more digests (synchronises `st` when it grows); PBSGPU_E_CAPACITY at the limit of the set's size
+int known_reserve(pbsgpu_known *k, uint64_t nnew, hipStream_t st);
+// the digests of the records with skip[i] == 0 into the table (they are new: pairwise distinct and absent)
+int known_enqueue_insert(pbsgpu_known *k, const KnownPass &p, const uint8_t *skip, hipStream_t st);
+void known_inserted(pbsgpu_known *k, uint64_t nnew);  // the insert has completed: the set's count
+pbsgpu_engine *known_engine(const pbsgpu_known *k);
 
 }  // namespace pbse

@@ -24,6 +24,10 @@
 //
 // The batch dedup (pbsgpu_dedup_host / _device) is the same marking with no table: k_known_keys in place of the lookup,
 // so every before[i] = 0 and known[i] = dup[i] — an earlier record of the batch carries the same digest.
+//
+// The pass also comes in pieces (known_enqueue_mark / known_reserve / known_enqueue_insert, engine_internal.h) that run on a
+// stream and arrays the caller owns: the fused upload of blob.hip builds its encode plan from known[] between the marking
+// and the insert, and gives the insert flags of its own when the blobs do not fit.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "engine_internal.h"
@@ -247,6 +251,60 @@ int grow(pbsgpu_known *k, uint64_t want, hipStream_t st) {
     return PBSGPU_OK;
 }
 
+}  // namespace
+
+namespace pbse {
+
+int known_sort_bytes(uint64_t n, hipStream_t st, size_t *bytes) {
+    size_t tmp_bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                     (uint32_t *)nullptr, (size_t)n, 0, 32, st));
+    *bytes = tmp_bytes + 256;
+    return PBSGPU_OK;
+}
+
+int known_enqueue_mark(const pbsgpu_known *k, const KnownPass &p, hipStream_t st) {
+    const uint64_t n = p.n;
+    uint32_t *keys_alt = p.keys + n, *idx_alt = p.idx + n;
+    const unsigned nb = blocks_for(n);
+    size_t tmp_bytes = p.tmp_bytes;
+    HIPCHK(hipMemsetAsync(p.stats, 0, 32, st));
+    if (k)
+        hipLaunchKernelGGL(pbsk::k_known_lookup, dim3(nb), dim3(256), 0, st, p.recs, p.stride, n, k->tags.as<uint64_t>(),
+                           k->digs.as<uint64_t>(), k->slots - 1, p.keys, p.idx, p.before);
+    else
+        hipLaunchKernelGGL(pbsk::k_known_keys, dim3(nb), dim3(256), 0, st, p.recs, p.stride, n, p.keys, p.idx, p.before);
+    HIPCHK(hipGetLastError());
+    HIPCHK(rocprim::radix_sort_pairs(p.tmp, tmp_bytes, p.keys, keys_alt, p.idx, idx_alt, (size_t)n, 0, 32, st));
+    hipLaunchKernelGGL(pbsk::k_known_mark, dim3(nb), dim3(256), 0, st, p.recs, p.stride, n, keys_alt, idx_alt, p.before,
+                       p.known, p.stats);
+    HIPCHK(hipGetLastError());
+    return PBSGPU_OK;
+}
+
+bool known_may_grow(const pbsgpu_known *k, uint64_t n) { return k->count + n > k->slots / 2; }
+
+int known_reserve(pbsgpu_known *k, uint64_t nnew, hipStream_t st) {
+    if (k->count + nnew >= kMaxCount) return PBSGPU_E_CAPACITY;
+    if (k->count + nnew > k->slots / 2) CHK(grow(k, k->count + nnew, st));
+    return PBSGPU_OK;
+}
+
+int known_enqueue_insert(pbsgpu_known *k, const KnownPass &p, const uint8_t *skip, hipStream_t st) {
+    hipLaunchKernelGGL(pbsk::k_known_insert, dim3(blocks_for(p.n)), dim3(256), 0, st, p.recs, p.stride, p.n, skip,
+                       k->tags.as<uint64_t>(), k->digs.as<uint64_t>(), k->slots - 1);
+    HIPCHK(hipGetLastError());
+    return PBSGPU_OK;
+}
+
+void known_inserted(pbsgpu_known *k, uint64_t nnew) { k->count += nnew; }
+
+pbsgpu_engine *known_engine(const pbsgpu_known *k) { return k->eng; }
+
+}  // namespace pbse
+
+namespace {
+
 // Records (stride 48) or .didx entries (stride 40), host or device; `known` (host, may be NULL) and `stats` (may be NULL
 // for the add paths) as pbsgpu_known_classify_*. k = NULL: no table, and insert is false — the batch dedup.
 int known_common(pbsgpu_engine *e, pbsgpu_known *k, const uint8_t *src, uint32_t stride, bool on_device, uint64_t n,
@@ -257,60 +315,44 @@ int known_common(pbsgpu_engine *e, pbsgpu_known *k, const uint8_t *src, uint32_t
     AuxLease lease(e);
     Slot *s = lease.s;
     const hipStream_t st = s->stream;
-    size_t tmp_bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                     (uint32_t *)nullptr, (size_t)n, 0, 32, st));
-    tmp_bytes += 256;
+    KnownPass p;
+    CHK(known_sort_bytes(n, st, &p.tmp_bytes));
     // layout inside the lease's buffers: recs | keys, keys_alt | idx, idx_alt | before, known | stats | sort tmp
     if (!on_device) CHK(s->recs.ensure((size_t)n * stride + 64));
     CHK(s->dense.ensure((size_t)n * 8 + 64));
     CHK(s->tile_slots.ensure((size_t)n * 8 + 64));
     CHK(s->tile_cnt.ensure((size_t)n * 2 + 64));
     CHK(s->scalars.ensure(SC_COUNT * 4 + 64));
-    CHK(s->scan_tmp.ensure(tmp_bytes));
+    CHK(s->scan_tmp.ensure(p.tmp_bytes));
     CHK(s->h_scalars.ensure(64));
-    const uint8_t *base = src;
+    p.recs = src;
     if (!on_device) {
         CHK(staged_h2d(*s, s->recs.p, src, n * stride, st));
-        base = s->recs.as<uint8_t>();
+        p.recs = s->recs.as<uint8_t>();
     }
-    uint32_t *keys = s->dense.as<uint32_t>();
-    uint32_t *keys_alt = keys + n;
-    uint32_t *idx = s->tile_slots.as<uint32_t>();
-    uint32_t *idx_alt = idx + n;
-    uint8_t *d_before = s->tile_cnt.as<uint8_t>();
-    uint8_t *d_known = d_before + n;
-    uint64_t *d_stats = reinterpret_cast<uint64_t *>(s->scalars.as<uint8_t>() + 32);
+    p.stride = stride;
+    p.n = n;
+    p.keys = s->dense.as<uint32_t>();
+    p.idx = s->tile_slots.as<uint32_t>();
+    p.before = s->tile_cnt.as<uint8_t>();
+    p.known = p.before + n;
+    p.stats = reinterpret_cast<uint64_t *>(s->scalars.as<uint8_t>() + 32);
+    p.tmp = s->scan_tmp.p;
     const uint64_t *hs = s->h_scalars.as<uint64_t>();
-    const unsigned nb = blocks_for(n);
-    HIPCHK(hipMemsetAsync(d_stats, 0, 32, st));
-    if (k)
-        hipLaunchKernelGGL(pbsk::k_known_lookup, dim3(nb), dim3(256), 0, st, base, stride, n, k->tags.as<uint64_t>(),
-                           k->digs.as<uint64_t>(), k->slots - 1, keys, idx, d_before);
-    else
-        hipLaunchKernelGGL(pbsk::k_known_keys, dim3(nb), dim3(256), 0, st, base, stride, n, keys, idx, d_before);
-    HIPCHK(hipGetLastError());
-    HIPCHK(rocprim::radix_sort_pairs(s->scan_tmp.p, tmp_bytes, keys, keys_alt, idx, idx_alt, (size_t)n, 0, 32, st));
-    hipLaunchKernelGGL(pbsk::k_known_mark, dim3(nb), dim3(256), 0, st, base, stride, n, keys_alt, idx_alt, d_before,
-                       d_known, d_stats);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_scalars.p, d_stats, 32, hipMemcpyDeviceToHost, st));
+    CHK(known_enqueue_mark(k, p, st));
+    HIPCHK(hipMemcpyAsync(s->h_scalars.p, p.stats, 32, hipMemcpyDeviceToHost, st));
     if (insert) {
         // the table can only pass its load limit when the whole batch might be new: only then is the number of new
         // digests read back before the insert (one more synchronisation of the lease's stream)
-        if (k->count + n > k->slots / 2) {
+        if (known_may_grow(k, n)) {
             HIPCHK(hipStreamSynchronize(st));
-            const uint64_t nnew = hs[1];
-            if (k->count + nnew >= kMaxCount) return PBSGPU_E_CAPACITY;
-            if (k->count + nnew > k->slots / 2) CHK(grow(k, k->count + nnew, st));
+            CHK(known_reserve(k, hs[1], st));
         }
-        hipLaunchKernelGGL(pbsk::k_known_insert, dim3(nb), dim3(256), 0, st, base, stride, n, d_known,
-                           k->tags.as<uint64_t>(), k->digs.as<uint64_t>(), k->slots - 1);
-        HIPCHK(hipGetLastError());
+        CHK(known_enqueue_insert(k, p, p.known, st));
     }
-    if (known) HIPCHK(hipMemcpyAsync(known, d_known, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (known) HIPCHK(hipMemcpyAsync(known, p.known, (size_t)n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (insert) k->count += hs[1];
+    if (insert) known_inserted(k, hs[1]);
     if (stats) {
         stats->nrecords = hs[0];
         stats->nunique = hs[1];

@@ -1222,6 +1222,71 @@ int pbsgpu_ring_blob_encode_device(pbsgpu_ring *r, uint32_t stream, const pbsgpu
     return PBSGPU_OK;
 }
 
+// The fused form: which records are new is decided on the device, so EVERY record must be available, and
+// the host's part is per stream and per page: the span of stream bytes the batch touches, then one page-table entry per
+// logical page of that span. A page inside [first available offset, last polled end) is always there — pages go only
+// below the release watermark, and nothing beyond a polled record is uncommitted — so the two range checks per record
+// refuse what the per-record page lookup of pbsgpu_ring_blob_encode_device refuses; the lookup per page stays as the proof.
+int pbsgpu_ring_upload_new_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
+                                  int insert, void *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off,
+                                  uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats) {
+    if (!r || !k || !used || !stats || (n && (!recs || !blob_off)) || n >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (!dst && dst_cap) return PBSGPU_E_INVALID;
+    if (!r->hold) return PBSGPU_E_STATE;
+    if (known_engine(k) != r->eng) return PBSGPU_E_INVALID;
+    struct Span {
+        uint64_t lo = ~0ull, hi = 0;  // stream bytes [lo, hi) hold every chunk of the batch
+    };
+    std::vector<Span> span(r->slots.size());
+    UploadSrc us;
+    uint64_t first = 0, polled = 0;
+    uint32_t cur = PBSGPU_RING_ANY_STREAM;
+    for (uint64_t i = 0; i < n; ++i) {
+        const pbsgpu_record &rc = recs[i];
+        const uint32_t sid = stream == PBSGPU_RING_ANY_STREAM ? (rc.segment & 0x0fffffffu) : stream;
+        if (sid != cur) {
+            if (sid >= r->slots.size() || !r->slots[sid].open) return PBSGPU_E_INVALID;
+            cur = sid;
+            first = r->held.first_offset(sid);
+            polled = r->slots[sid].polled_end;
+        }
+        if (rc.size > rc.end || rc.size > r->page_bytes) return PBSGPU_E_INVALID;
+        const uint64_t start = rc.end - rc.size;
+        if (rc.end > polled || start < first) return PBSGPU_E_STATE;
+        if (rc.size == 0) continue;
+        span[sid].lo = std::min(span[sid].lo, start);
+        span[sid].hi = std::max(span[sid].hi, rc.end);
+        us.pieces_max += ((rc.size + (1ull << kBlobPieceLog) - 1) >> kBlobPieceLog) + 1;  // (+1: a chunk in two pages)
+    }
+    if (us.pieces_max >= (1ull << 32)) return PBSGPU_E_INVALID;
+    std::vector<uint64_t> tabs(2 * span.size(), 0);  // PageTabs, then the pages
+    for (uint32_t sid = 0; sid < span.size(); ++sid) {
+        if (span[sid].lo >= span[sid].hi) continue;
+        const uint64_t k0 = span[sid].lo / r->page_bytes, k1 = (span[sid].hi - 1) / r->page_bytes;
+        tabs[2 * sid] = k0;
+        tabs[2 * sid + 1] = (uint64_t)(tabs.size() - 2 * span.size()) | (k1 - k0 + 1) << 32;
+        for (uint64_t pg = k0; pg <= k1; ++pg) {
+            const int64_t phys = r->held.phys_of(sid, pg);
+            if (phys < 0) return PBSGPU_E_STATE;
+            tabs.push_back((uint64_t)phys * r->stride + 128u);
+        }
+    }
+    *used = 0;
+    std::memset(stats, 0, sizeof(*stats));
+    if (n == 0) return PBSGPU_OK;
+    CHK(set_device(r->eng));
+    if (dst && !is_device_pointer(dst)) return PBSGPU_E_INVALID;
+    ring_heartbeat(r);
+    us.base = r->arena.as<uint8_t>();
+    us.tabs = tabs.data();
+    us.tab_words = tabs.size();
+    us.nslots = (uint32_t)span.size();
+    us.stream = stream;
+    us.page_bytes = r->page_bytes;
+    return upload_new(k, us, recs, n, insert != 0, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, crcs, used,
+                      stats);
+}
+
 int pbsgpu_ring_copy_device(pbsgpu_ring *r, uint32_t stream, uint64_t offset, uint64_t length, void *dst) {
     if (!r || (length && !dst)) return PBSGPU_E_INVALID;
     if (!r->hold) return PBSGPU_E_STATE;

@@ -204,4 +204,27 @@ int blob_encode_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart (*src
 // the parts' bytes back to back at dst
 int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32_t nparts, uint8_t *dst);
 
+// blob.hip: classify against a known-chunk set and frame the new chunks with a plan built on the device
+// (pbsgpu_ring_upload_new_device / pbsgpu_known_upload_new_device). The callers have checked everything
+// that can be refused on the host.
+constexpr uint32_t kBlobPieceLog = 16;  // blob.hip cuts every part into pieces of 64 KiB (its kPieceLog)
+struct PageTab {     // one per stream slot of the ring
+    uint64_t k0;     // first logical page of the table
+    uint32_t off;    // its index in the page array that follows the PageTabs
+    uint32_t n;      // pages
+};
+struct UploadSrc {
+    const uint8_t *base = nullptr;           // the ring's arena, or the contiguous source
+    const pbsgpu_segment *chunks = nullptr;  // host, n: the contiguous form (then no tables)
+    const uint64_t *tabs = nullptr;          // host image: nslots PageTabs, then the offset of every listed page's body from base
+    size_t tab_words = 0;
+    uint32_t nslots = 0;
+    uint32_t stream = 0;                     // or PBSGPU_RING_ANY_STREAM
+    uint64_t page_bytes = 0;
+    uint64_t pieces_max = 0;                 // upper bound of the 64 KiB pieces of all n chunks, < 2^32
+};
+int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint8_t *dst,
+               uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
+               pbsgpu_dedup_stats *stats);
+
 }  // namespace pbse

@@ -448,6 +448,38 @@ class KnownChunks:
               "known_classify_device")
         return (known[:n] if want_flags else None), {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
 
+    def upload_new(self, src, recs: np.ndarray, chunks, insert: bool = True, dst: DeviceBuffer | None = None,
+                   nbytes: int | None = None):
+        """classify + Engine.blob_encode of the new chunks in one device-side call (pbsgpu_known_upload_new_device):
+        chunk i = (offset, length) `chunks[i]` of the device buffer `src` carries the digest of `recs[i]`. dst None
+        allocates the worst case, sum(length + 12). Returns (buffer with .used, known flags (n), offsets (n, uint64; 0 for
+        known records), CRCs (n, uint32), stats)."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        n = int(recs.size)
+        segs, nseg = _segs(chunks)
+        assert nseg == n, "one chunk range per record"
+        sp, sn = self._eng._dev(src, nbytes)
+        assert sp is not None, "upload_new() wants device memory"
+        own = dst is None
+        if own:
+            lens = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)[:, 1] if n else np.zeros(0, dtype=np.uint64)
+            dst = self._eng.alloc(max(int(lens.sum()) + 12 * n, 16))
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        used, st = C.c_uint64(), _lib.DedupStats()
+        try:
+            check(self._L.pbsgpu_known_upload_new_device(self._h, sp, sn, recs.ctypes.data if n else None, segs, n, int(insert),
+                                                         dst.ptr, dst.nbytes, flags.ctypes.data, offs.ctypes.data,
+                                                         crcs.ctypes.data, C.byref(used), C.byref(st)),
+                  "known_upload_new_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        dst.used = int(used.value)
+        return dst, flags[:n], offs[:n], crcs[:n], {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
+
     def __len__(self) -> int:
         n = C.c_uint64()
         check(self._L.pbsgpu_known_count(self._h, C.byref(n)), "known_count")
@@ -810,6 +842,34 @@ class PageRing:
             raise
         dst.used = int(used.value)
         return dst, offs[:n], crcs[:n]
+
+    def upload_new(self, known: "KnownChunks", stream, recs: np.ndarray, insert: bool = True, dst: DeviceBuffer | None = None):
+        """classify + blob_encode(skip = known) in one device-side call (pbsgpu_ring_upload_new_device): the polled
+        records `recs` are classified against `known`, and the new ones framed out of the ring's pages with a plan built on
+        the device. `stream` None: every record's stream is its `segment` (poll_any). dst None allocates the worst case,
+        sum(size + 12); a dst that is too small raises PbsGpuError(E_CAPACITY) with the set unchanged. Returns (buffer
+        with .used, known flags (n), offsets (n, uint64; 0 for known records), CRCs (n, uint32), stats)."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        n = int(recs.size)
+        sid = _lib.RING_ANY_STREAM if stream is None else int(stream)
+        own = dst is None
+        if own:
+            dst = self._eng.alloc(max(int(recs["size"].astype(np.uint64).sum()) + 12 * n, 16))
+        flags = np.zeros(max(n, 1), dtype=np.uint8)
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        used, st = C.c_uint64(), _lib.DedupStats()
+        try:
+            check(self._L.pbsgpu_ring_upload_new_device(self._h, known._h, sid, recs.ctypes.data if n else None, n, int(insert),
+                                                        dst.ptr, dst.nbytes, flags.ctypes.data, offs.ctypes.data,
+                                                        crcs.ctypes.data, C.byref(used), C.byref(st)),
+                  "ring_upload_new_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        dst.used = int(used.value)
+        return dst, flags[:n], offs[:n], crcs[:n], {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
 
     def copy(self, stream: int, offset: int, length: int) -> DeviceBuffer:
         """The raw stream bytes [offset, offset + length) out of the ring's pages into a new DeviceBuffer (the range must

@@ -5,13 +5,17 @@
   one call (the ring is quiesced first: the figure is the encode alone);
 * (b) blob_encode_device over the same chunks, copied into one contiguous buffer with pbsgpu_ring_copy_device, in the same
   run; and the ratio (a) / (b);
+* (d) the same ring-sourced encode with the known-chunk check in front of it, half of the digests in the set beforehand and
+  insert = 0 (so that repeated calls see the same set): pbsgpu_ring_upload_new_device, which keeps the flags on the device
+  and builds the plan there, against pbsgpu_known_classify_host + pbsgpu_ring_blob_encode_device(skip = known), on the same
+  polled records, alternating in the same run;
 * (c) the feed rate of a ring with the flag on whose consumer releases after every poll against the same ring with the flag
   off (GiB/s from the first fill to the last record), and the share of the arena that was held on average.
 
-(a) and (b) are the median of a few synchronous calls timed with a host clock, after one warm-up call; (c) alternates the
-two rings and reports the median of its runs.
+(a), (b) and (d) are the median of a few synchronous calls timed with a host clock, after one warm-up call; (c) alternates
+the two rings and reports the median of its runs (--no-feed leaves it out).
 
-    python tools/ring_upload_rate.py [--big-gib 2] [--small-mib 256] [--feed-gib 512] [--reps 5]
+    python tools/ring_upload_rate.py [--big-gib 2] [--small-mib 256] [--feed-gib 512] [--reps 5] [--no-feed]
 """
 import argparse
 import ctypes as C
@@ -51,6 +55,57 @@ def _ingest(ring, seed, kind, nbytes):
     return sid, np.concatenate(recs)
 
 
+def _alternating_ms(fns, reps):
+    """every function once as a warm-up, then `reps` rounds that run them one after the other: [ms per round] per function"""
+    for fn in fns:
+        fn()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for t, fn in zip(ts, fns):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def fused_against_two_calls(a, eng, ring, sid, recs, dst):
+    """(d): the row's "upload_new" entry"""
+    from pbs_plus_amd import KnownChunks, _lib
+
+    L = _lib.lib()
+    n = int(recs.size)
+    known = KnownChunks(eng, capacity=2 * n)
+    known.add(recs[::2])
+    out = [dict(flags=np.zeros(n, dtype=np.uint8), offs=np.zeros(n, dtype=np.uint64), crcs=np.zeros(n, dtype=np.uint32),
+                used=C.c_uint64(), st=_lib.DedupStats()) for _ in range(2)]
+
+    def two_calls():
+        o = out[0]
+        _lib.check(L.pbsgpu_known_classify_host(known._h, recs.ctypes.data, n, 0, o["flags"].ctypes.data, C.byref(o["st"])),
+                   "known_classify_host")
+        _lib.check(L.pbsgpu_ring_blob_encode_device(ring._h, sid, recs.ctypes.data, n, o["flags"].ctypes.data, dst.ptr, dst.nbytes,
+                                                    o["offs"].ctypes.data, o["crcs"].ctypes.data, C.byref(o["used"])),
+                   "ring_blob_encode_device")
+
+    def fused():
+        o = out[1]
+        _lib.check(L.pbsgpu_ring_upload_new_device(ring._h, known._h, sid, recs.ctypes.data, n, 0, dst.ptr, dst.nbytes,
+                                                   o["flags"].ctypes.data, o["offs"].ctypes.data, o["crcs"].ctypes.data,
+                                                   C.byref(o["used"]), C.byref(o["st"])), "ring_upload_new_device")
+
+    t_two, t_fused = _alternating_ms((two_calls, fused), a.reps)
+    for k in ("flags", "offs", "crcs"):
+        assert np.array_equal(out[0][k], out[1][k]), k
+    assert out[0]["used"].value == out[1]["used"].value and len(known) == recs[::2].size
+    new_bytes = int(out[1]["st"].unique_bytes)
+    known.close()
+    med2, medf = statistics.median(t_two), statistics.median(t_fused)
+    return {"new_chunks": int(out[1]["st"].nunique), "new_bytes": new_bytes,
+            "two_calls_ms": [round(x, 3) for x in t_two], "fused_ms": [round(x, 3) for x in t_fused],
+            "two_calls_median_ms": med2, "fused_median_ms": medf,
+            "two_calls_GBps": new_bytes / med2 / 1e6, "fused_GBps": new_bytes / medf / 1e6, "fused_over_two_calls": med2 / medf}
+
+
 def encode_rates(a, name, avg, nbytes, ring_opt):
     from pbs_plus_amd import Engine, PageRing, _lib, buzhash
     from pbs_plus_amd.engine import _segs
@@ -77,6 +132,7 @@ def encode_rates(a, name, avg, nbytes, ring_opt):
 
     t_ring = _median_s(from_ring, a.reps)
     crc_ring = crcs.copy()
+    upload_new = fused_against_two_calls(a, eng, ring, sid, recs, dst)
     flat = ring.copy(sid, 0, nbytes)
     segs, ns = _segs(list(zip(starts.tolist(), recs["size"].tolist())))
 
@@ -88,7 +144,7 @@ def encode_rates(a, name, avg, nbytes, ring_opt):
     assert np.array_equal(crc_ring, crcs)
     row = {"batch": name, "chunks": n, "bytes": data, "chunks_in_two_pages": two_pages, "page_bytes": page,
            "ring_encode_GBps": data / t_ring / 1e9, "contiguous_encode_GBps": data / t_flat / 1e9,
-           "ring_over_contiguous": t_flat / t_ring, "ms": {"ring": t_ring * 1e3, "contiguous": t_flat * 1e3}}
+           "ring_over_contiguous": t_flat / t_ring, "ms": {"ring": t_ring * 1e3, "contiguous": t_flat * 1e3}, "upload_new": upload_new}
     print(json.dumps(row), flush=True)
     flat.free()
     dst.free()
@@ -139,6 +195,7 @@ def main():
     ap.add_argument("--feed-arena-gib", type=float, default=0.0, help="0 = the ring's default arena, as the benchmark's")
     ap.add_argument("--feed-reps", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-feed", action="store_true", help="only the encode legs")
     a = ap.parse_args()
 
     from pbs_plus_amd import Engine, buzhash
@@ -148,6 +205,8 @@ def main():
     small = a.small_mib << 20
     encode_rates(a, "4KiB-avg", 4096, small,
                  dict(arena_bytes=(small // 65536 + 64) * (65536 + 256), page_bytes=65536, max_streams=2, round_pages=256))
+    if a.no_feed:
+        return
     eng = Engine(buzhash.NewConfig(4 << 20), device=0)
     total, arena = int(a.feed_gib * (1 << 30)), int(a.feed_arena_gib * (1 << 30))
     feed_once(eng, False, total // 8, a.feed_streams, arena)  # warm-up
