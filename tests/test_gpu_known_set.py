@@ -1,10 +1,15 @@
 """The device-resident known-chunk set (pbsgpu_known_*, KnownChunks) on the GPU, bit-exact against a sequential Python
 `set` model: the PBS client's known_chunks rule — upload the first occurrence of a digest the server lacks, reference
 every later one."""
+import os
+import sys
 import time
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from known_inputs import records as _recs, set_model as _model  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -13,34 +18,6 @@ def _engine(avg=4096):
     from pbs_plus_amd import Engine, buzhash
 
     return Engine(buzhash.NewConfig(avg), device=0)
-
-
-def _recs(digests, sizes=None, seed=0):
-    from pbs_plus_amd import RECORD_DTYPE
-
-    d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
-    r = np.zeros(d.shape[0], dtype=RECORD_DTYPE)
-    r["digest"] = d
-    r["size"] = sizes if sizes is not None else np.random.default_rng(seed).integers(1, 1 << 20, d.shape[0])
-    r["end"] = np.cumsum(r["size"].astype(np.uint64))
-    return r
-
-
-def _model(initial, recs, insert=True):
-    """The reference rule, sequentially: (known flags, stats, the set afterwards)."""
-    s = set(initial)
-    seen = set()
-    known = np.zeros(recs.size, dtype=np.uint8)
-    for i, d in enumerate(recs["digest"]):
-        b = d.tobytes()
-        if b in s or b in seen:
-            known[i] = 1
-        else:
-            seen.add(b)
-    sizes = recs["size"].astype(np.uint64)
-    stats = {"nrecords": int(recs.size), "nunique": int((known == 0).sum()), "total_bytes": int(sizes.sum()),
-             "unique_bytes": int(sizes[known == 0].sum())}
-    return known, stats, (s | seen) if insert else s
 
 
 def _digest_set(recs):
