@@ -212,3 +212,13 @@ func (e *Engine) VerifyBlobs([]byte, []uint64, []uint64, [][32]byte, []uint32) (
 func (e *Engine) VerifyBlobsDevice(unsafe.Pointer, uint64, []uint64, []uint64, [][32]byte, []uint32) ([]uint8, BlobStats, error) {
 	return nil, BlobStats{}, ErrNotBuilt
 }
+
+// DecodeStats counts DecodeBlobs' statuses per index entry and the bytes it touched.
+type DecodeStats struct {
+	Count                                      [6]uint64
+	BlobBytes, CRCBytes, SHA256Bytes, OutBytes uint64
+}
+
+func (e *Engine) DecodeBlobs(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, unsafe.Pointer, uint64) ([]uint8, DecodeStats, error) {
+	return nil, DecodeStats{}, ErrNotBuilt
+}

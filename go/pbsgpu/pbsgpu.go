@@ -1354,3 +1354,61 @@ func (e *Engine) VerifyBlobsDevice(dptr unsafe.Pointer, nbytes uint64, offsets, 
 	defer runtime.KeepAlive(e)
 	return e.verifyBlobs(true, dptr, nbytes, offsets, lengths, digests, sizes)
 }
+
+// DecodeStats counts DecodeBlobs' statuses per index entry (indexed by Blob*) and the bytes it touched: BlobBytes,
+// CRCBytes and SHA256Bytes once per distinct referenced blob, OutBytes what was written to dst.
+type DecodeStats struct {
+	Count                                      [6]uint64
+	BlobBytes, CRCBytes, SHA256Bytes, OutBytes uint64
+}
+
+// DecodeBlobs restores the stream bytes [rangeStart, rangeEnd) into device memory dst from a contiguous slice idx of a
+// dynamic index and the blobs (offsets, lengths) of a device buffer: what datastore.NewChunkStore +
+// transfer.NewChunkedReader(idx, source) deliver (internal/server/verification/job.go:931-966,
+// internal/pxar/format.go:101-129) and the ranged reads of internal/pxar/client.go:236. blobOf[i] is the blob that carries
+// entry i (nil: blob i). The status per entry is VerifyBlobsDevice's for that blob with the entry's size and digest
+// (checkDigest false: without the digest). An entry whose blob is not an uncompressed one of its size leaves its part of
+// dst untouched.
+func (e *Engine) DecodeBlobs(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, idx []ChunkInfo, blobOf []uint32,
+	rangeStart, rangeEnd uint64, checkDigest bool, dst unsafe.Pointer, dstCap uint64) ([]uint8, DecodeStats, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, DecodeStats{}, err
+	}
+	if blobOf != nil && len(blobOf) != len(idx) {
+		return nil, DecodeStats{}, errors.New("pbsgpu: DecodeBlobs needs one blobOf per index entry")
+	}
+	cr := toRecords(idx)
+	var sp *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp = &segs[0]
+	}
+	var rp *C.pbsgpu_record
+	var bo *C.uint32_t
+	status := make([]uint8, len(cr)+1)
+	if len(cr) > 0 {
+		rp = &cr[0]
+		if blobOf != nil {
+			bo = (*C.uint32_t)(unsafe.Pointer(&blobOf[0]))
+		}
+	}
+	chk := C.int(0)
+	if checkDigest {
+		chk = 1
+	}
+	var st C.pbsgpu_decode_stats
+	err = check(C.pbsgpu_blob_decode_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), rp, C.uint64_t(len(cr)), bo,
+		C.uint64_t(rangeStart), C.uint64_t(rangeEnd), chk, dst, C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])),
+		&st), "blob_decode_device")
+	if err != nil {
+		return nil, DecodeStats{}, err
+	}
+	var out DecodeStats
+	for i := range out.Count {
+		out.Count[i] = uint64(st.count[i])
+	}
+	out.BlobBytes, out.CRCBytes, out.SHA256Bytes = uint64(st.blob_bytes), uint64(st.crc_bytes), uint64(st.sha_bytes)
+	out.OutBytes = uint64(st.out_bytes)
+	return status[:len(cr)], out, nil
+}

@@ -637,6 +637,60 @@ int pbsgpu_blob_verify_host(pbsgpu_engine *eng, const void *hptr, uint64_t nbyte
                             uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
                             pbsgpu_blob_stats *stats);
 
+/* ---- restore a stream from its index and data blobs ---------------------------------------------------------------
+ * The read every consumer of a snapshot makes: datastore.NewChunkStore + transfer.NewChunkedReader(idx, source) /
+ * NewSplitReader (internal/server/verification/job.go:931-966, internal/pxar/format.go:101-129,
+ * internal/pxarmount/commit_orchestrate.go:356-368) and the 4 MiB ranged content reads of the restore client
+ * (internal/pxar/client.go:236: DynamicIndexReader.ChunkFromOffset, then a partial read of the first and the last chunk).
+ * The mirror image of pbsgpu_blob_encode_device: one pass reads a blob's data once, folds its CRC and stores the bytes at
+ * their place in the stream, so the payload is never reassembled on the host; pbsgpu_sha256_many_device /
+ * pbsgpu_xxh3_many_device over dst then give the file hashes of the verification flow.
+ *
+ * idx is a contiguous slice of an index (as pbsgpu_didx_decode returns it): entry i is the stream bytes
+ * [idx[i].end - idx[i].size, idx[i].end), idx[i].end - idx[i].size == idx[i - 1].end for i > 0, `segment` is ignored. The
+ * slice spans [S, E) = [idx[0].end - idx[0].size, idx[nidx - 1].end); S <= range_start <= range_end <= E. The blob that
+ * carries entry i is blobs[blob_of[i]] (offset, length inside the device buffer, header included); blob_of NULL is the
+ * identity and needs nblob == nidx. dst[0] is stream byte range_start.
+ *
+ * status[i] is exactly what pbsgpu_blob_verify_device reports for the single blob blobs[blob_of[i]] with
+ * sizes = idx[i].size and digests = idx[i].digest (digests = NULL with check_digest = 0): the same checks in the same
+ * order, the same PBSGPU_BLOB_* codes, PBSGPU_BLOB_CRC_ONLY for the compressed and encrypted kinds. Several entries may
+ * name one blob; each gets the blob's status against its own size and digest.
+ * The bytes of entry i inside the range go to dst + (max(start_i, range_start) - range_start) if and only if the blob has
+ * the uncompressed magic, a whole header, and a data length equal to idx[i].size; they are the blob's data bytes as found,
+ * whatever the CRC or the digest say afterwards (read status). An entry's part of dst is left untouched on BAD_MAGIC,
+ * BAD_SIZE, CRC_ONLY, and on a BAD_CRC that hides a size mismatch. Nothing outside dst[0, range_end - range_start) is
+ * written, an entry writes nothing outside its own clipped part, and entries wholly outside the range are checked and
+ * write nothing. A blob referenced by k entries is read once for its CRC and hashed once (crc_bytes, sha_bytes); the
+ * other k - 1 copies are made by a copy pass. Blobs no entry references are neither checked nor counted.
+ * The SHA-256 runs through the pbsgpu_sha256_many_* kernels and their policy applies unchanged (pbsgpu_sha256_many_pays).
+ *
+ * Decided on the host before any device work, with dst untouched: PBSGPU_E_INVALID for a NULL where a value is needed, a
+ * blob outside the buffer, blob_of[i] >= nblob, a slice that is not contiguous, a range outside [S, E) or reversed, a host
+ * pointer for the buffer or for dst, nidx >= 2^32, dst[0, range_end - range_start) overlapping the blob buffer;
+ * PBSGPU_E_CAPACITY when dst_cap < range_end - range_start. nidx == 0 or an empty range is PBSGPU_OK (with an empty range
+ * the entries are still checked; dst may then be NULL).
+ * Runs on one leased stream of the engine and synchronises it ONCE, at the end: kind, header length and stored CRC of
+ * every blob are read on the device and nothing comes back in between. It waits only for that stream, so it is usable
+ * between the pumps of a running ring. */
+#define PBSGPU_HAS_BLOB_DECODE 1
+typedef struct pbsgpu_decode_stats {
+    uint64_t count[PBSGPU_BLOB_NSTATUS]; /* index entries per status */
+    uint64_t blob_bytes;  /* lengths of the DISTINCT blobs that some entry references */
+    uint64_t crc_bytes;   /* bytes a CRC was computed over: once per distinct referenced blob */
+    uint64_t sha_bytes;   /* bytes hashed: once per distinct referenced uncompressed blob; 0 with check_digest = 0 */
+    uint64_t out_bytes;   /* bytes written to dst */
+} pbsgpu_decode_stats;
+int pbsgpu_blob_decode_device(pbsgpu_engine *eng,
+                              const void *blobs_dptr, uint64_t nbytes,     /* device buffer the blobs were loaded into */
+                              const pbsgpu_segment *blobs, uint32_t nblob, /* blob b = [offset, offset + length) of it */
+                              const pbsgpu_record *idx, uint64_t nidx,     /* host: a contiguous slice of an index */
+                              const uint32_t *blob_of,                     /* nidx, host; NULL = identity */
+                              uint64_t range_start, uint64_t range_end,    /* stream bytes wanted */
+                              int check_digest,
+                              void *dst, uint64_t dst_cap,                 /* device memory */
+                              uint8_t *status /* nidx */, pbsgpu_decode_stats *stats /* may be NULL */);
+
 /* ---- classify and frame in one device-side call --------------------------------------------------------------------
  * The middle of the incremental writer's loop — known-chunk check, then upload framing of what is new (SURVEY.md §3A;
  * the upload of commit_orchestrate.go:137-158 behind the known-chunk check, refs of commit_reuse.go:315-341 being known by

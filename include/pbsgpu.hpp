@@ -256,6 +256,29 @@ inline Result<Verified> Verify(pbsgpu_engine *eng, const void *buf, uint64_t nby
     return r;
 }
 
+struct Decoded {
+    std::vector<uint8_t> status;  // PBSGPU_BLOB_* per index entry
+    pbsgpu_decode_stats stats{};
+};
+
+// the stream bytes [rangeStart, rangeEnd) into device buffer dst from a contiguous slice idx of an index and the blobs of
+// a device buffer: transfer.NewChunkedReader(idx, source) over a datastore.NewChunkStore. blobOf[i] = the blob that
+// carries entry i (empty: blob i). An entry whose blob is not an uncompressed one of its size leaves its part of dst
+// untouched: read status.
+inline Result<Decoded> Decode(pbsgpu_engine *eng, const void *blobsDev, uint64_t nbytes,
+                              const std::vector<pbsgpu_segment> &blobs, const std::vector<pbsgpu_record> &idx,
+                              const std::vector<uint32_t> &blobOf, uint64_t rangeStart, uint64_t rangeEnd, bool checkDigest,
+                              void *dst, uint64_t dstCap) {
+    Result<Decoded> r;
+    r.value.status.resize(idx.size() + 1);
+    const int st = pbsgpu_blob_decode_device(eng, blobsDev, nbytes, blobs.data(), (uint32_t)blobs.size(), idx.data(),
+                                             idx.size(), blobOf.empty() ? nullptr : blobOf.data(), rangeStart, rangeEnd,
+                                             checkDigest ? 1 : 0, dst, dstCap, r.value.status.data(), &r.value.stats);
+    r.value.status.resize(idx.size());
+    if (st != PBSGPU_OK) r.err = errorf("blob decode", st);
+    return r;
+}
+
 }  // namespace blob
 
 // datastore.DynamicIndexReader

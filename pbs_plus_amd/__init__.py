@@ -19,7 +19,7 @@ Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no C
 from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
 from .engine import Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
-from .engine import blob_magic, chunk_ranges, crc32_combine  # noqa: F401
+from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine  # noqa: F401
 
 __all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError",
-           "blob_magic", "chunk_ranges", "crc32_combine"]
+           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine"]

@@ -143,6 +143,11 @@ class BlobStats(C.Structure):
     _fields_ = [("count", C.c_uint64 * 6), ("blob_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("sha_bytes", C.c_uint64)]
 
 
+class DecodeStats(C.Structure):
+    _fields_ = [("count", C.c_uint64 * 6), ("blob_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("sha_bytes", C.c_uint64),
+                ("out_bytes", C.c_uint64)]
+
+
 # pbsgpu_record: 48 bytes, same layout as a DIDX entry + (segment, size)
 RECORD_DTYPE = np.dtype([("end", "<u8"), ("digest", "u1", (32,)), ("segment", "<u4"), ("size", "<u4")])
 assert RECORD_DTYPE.itemsize == 48
@@ -241,6 +246,8 @@ SYMBOLS = {
     "pbsgpu_blob_encode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _U64P, _P, _P]),
     "pbsgpu_blob_verify_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
     "pbsgpu_blob_verify_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
+    "pbsgpu_blob_decode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
+                                            C.c_int, _P, C.c_uint64, _P, C.POINTER(DecodeStats)]),
     "pbsgpu_ring_upload_new_device": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P, _U64P,
                                                 C.POINTER(DedupStats)]),
     "pbsgpu_known_upload_new_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P,

@@ -690,6 +690,256 @@ __global__ __launch_bounds__(256) void k_upnew_ppart(UpPlan pl) {
     }
 }
 
+// ---- the read side: (index, blobs) -> stream bytes (pbsgpu_blob_decode_device) ------------------------
+// The mirror image of the encode pass over the DISTINCT blobs that the index slice references: one read of a blob's data
+// gives its CRC and puts the bytes at their place in the stream. What kind a blob is and where its data begins is known
+// only on the device (the magic), and nothing is read back in the middle, so the host plans the pieces for the 12-byte
+// header and the kernels take the data start from k_dec_heads: an encrypted kind (44 bytes) may leave the first planned
+// piece empty, raw CRC 0, which the fold passes over like the zero padding in front of a short piece.
+//   k_dec_heads   per blob: magic -> kind and header length (0 = unknown magic or a cut header), the stored CRC, and the
+//                 range launch_sha256_segments hashes (empty unless the blob is uncompressed)
+//   k_dec_pieces  k_crc_pieces with the CLIPPED store: the blob's data goes to the part of dst that belongs to its
+//                 primary entry, cut at range_start / range_end at byte granularity while the CRC covers every byte;
+//                 stored only when the blob is uncompressed and its data length is the entry's size
+//   k_dec_fold    k_crc_fold over the data length the magic gives
+//   k_dec_copy    the other entries that reference a blob (dedup fan-out), clipped in the same way, blob -> dst
+//   k_dec_status  per entry, in pbsgpu_blob_verify's order: magic, CRC, kind, size, digest
+struct DecInfo {
+    uint32_t hk;      // header bytes (12 / 44; 0 = BAD_MAGIC) | kind << 8
+    uint32_t stored;  // the header's CRC
+};
+struct DecStore {  // data bytes [xlo, xhi) of blob u go to dst + dofs + [xlo, xhi) when the data is `size` bytes long
+    int64_t dofs;  // the entry's stream start - range_start (may be negative: the bytes in front are clipped)
+    uint64_t xlo, xhi;
+    uint32_t size;
+    uint32_t u;
+};
+struct DecEntry {
+    uint32_t u;  // the entry's blob among the distinct ones
+    uint32_t size;
+};
+struct DecPlan {
+    const uint8_t *src;
+    const pbsgpu_segment *blobs;  // nu distinct referenced blobs (header included)
+    const uint64_t *pbase;        // nu + 1
+    const uint32_t *pseg;         // npieces
+    uint32_t *praw;               // npieces
+    uint32_t *crcs;               // nu
+    DecInfo *info;                // nu
+    pbsgpu_segment *sha;          // nu: what is hashed
+    const DecStore *prim;         // nu: the store fused into the piece pass (xlo == xhi: none)
+    const DecStore *copies;       // ncopy
+    const DecEntry *ents;         // nidx
+    const uint8_t *recs;          // nidx records (stride 48): the digests (nullptr: not checked)
+    const uint8_t *digs;          // nu * 32: SHA-256 of the uncompressed blobs' data
+    uint8_t *status;              // nidx
+    uint8_t *dst;
+    uint64_t npieces;
+    uint32_t nu, ncopy, nidx;
+};
+typedef const CRC_GLOBAL DecStore *gstore_ptr;
+
+// little-endian words of the four magics (kMagic below; a static_assert there ties the two together)
+__device__ constexpr uint32_t kDecMagic[4][2] = {{0x0738AB42u, 0xA17083BEu},
+                                                 {0x4258B931u, 0x7FA3B66Fu},
+                                                 {0xBE85677Bu, 0xF04C2D22u},
+                                                 {0xBF1B59E6u, 0x0BD8BF0Bu}};
+
+__global__ __launch_bounds__(256) void k_dec_heads(DecPlan pl) {
+    const uint32_t u = blockIdx.x * 256 + threadIdx.x;
+    if (u >= pl.nu) return;
+    const uint64_t off = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u], len = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u + 1];
+    uint32_t w[3] = {0, 0, 0};
+#pragma unroll
+    for (uint32_t j = 0; j < PBSGPU_BLOB_HEADER_SIZE; ++j)
+        if (j < len) w[j >> 2] |= (uint32_t)((gbyte_ptr)pl.src)[off + j] << (8 * (j & 3));
+    uint32_t hk = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t hdr = k >= PBSGPU_BLOB_ENCRYPTED ? PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE : PBSGPU_BLOB_HEADER_SIZE;
+        if (len >= hdr && w[0] == kDecMagic[k][0] && w[1] == kDecMagic[k][1]) hk = hdr | (k << 8);
+    }
+    CRC_GLOBAL DecInfo *in = (CRC_GLOBAL DecInfo *)pl.info + u;
+    in->hk = hk;
+    in->stored = w[2];
+    const bool plain = hk == PBSGPU_BLOB_HEADER_SIZE;  // uncompressed, header whole
+    CRC_GLOBAL uint64_t *sh = (CRC_GLOBAL uint64_t *)pl.sha + 2 * (uint64_t)u;
+    sh[0] = plain ? off + PBSGPU_BLOB_HEADER_SIZE : off;
+    sh[1] = plain ? len - PBSGPU_BLOB_HEADER_SIZE : 0;
+}
+
+// a lane's 16 bytes at piece position pos, of which [a, b) may be stored (piece coordinates; so = (o + pos) & 3)
+__device__ __forceinline__ void store_clip(uint8_t *o, uint32_t so, int32_t pos, int32_t a, int32_t b,
+                                           const uint32_t (&w)[4]) {
+    if (pos >= a && pos + 16 <= b) {
+        store16(o + pos, so, w);
+    } else if (pos + 16 > a && pos < b) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)  // (fixed bounds: the words stay in registers)
+            if (pos + j >= a && pos + j < b) ((gbyte_out)o)[pos + j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dec_pieces(DecPlan pl) {
+    __shared__ uint32_t tab[17][256];  // as in k_crc_pieces
+    {
+        const uint32_t b = threadIdx.x;
+        uint32_t c = b;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
+        tab[16][b] = c;
+        uint32_t t = mul(c, kDev.gap);
+        tab[0][b] = t;
+        __syncthreads();
+        for (int m = 1; m < 16; ++m) {
+            t = (t >> 8) ^ tab[16][t & 255];
+            tab[m][b] = t;
+        }
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t kl = kDev.klane[lane];
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    for (uint64_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.npieces; p += nw) {
+        const uint32_t u = ((gword_ptr)pl.pseg)[p];
+        const uint64_t b0 = ((gquad_ptr)pl.pbase)[u];
+        const uint64_t m = ((gquad_ptr)pl.pbase)[u + 1] - b0;
+        const uint32_t hk = ((gword_ptr)pl.info)[2 * (uint64_t)u];
+        const uint32_t hdr = hk & 255u;
+        const uint64_t boff = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u], blen = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u + 1];
+        const uint64_t dlen = hdr ? blen - hdr : 0;       // data bytes
+        const uint64_t back = (m - 1 - (p - b0)) * kPiece;  // data bytes behind the piece
+        if (back >= dlen) {  // no data (BAD_MAGIC), or the piece the 44-byte header leaves empty
+            if (lane == 0) ((gword_out)pl.praw)[p] = 0;
+            continue;
+        }
+        const uint64_t hi = dlen - back;  // piece = data bytes [lo, hi)
+        const uint64_t lo = hi > kPiece ? hi - kPiece : 0;
+        const uint32_t n = (uint32_t)(hi - lo);
+        const uint32_t rows = (n + kRow - 1) / kRow;
+        const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
+        const uint8_t *d = pl.src + boff + hdr + lo;
+        // the store: the piece's bytes [a, b) (piece coordinates) belong to the primary entry's part of dst
+        const gstore_ptr ps = (gstore_ptr)pl.prim + u;
+        const uint64_t xlo = ps->xlo, xhi = ps->xhi;
+        const uint64_t cl = xlo > lo ? xlo : lo, ch = xhi < hi ? xhi : hi;
+        const bool put = hk == PBSGPU_BLOB_HEADER_SIZE && dlen == ps->size && cl < ch;
+        const int32_t a = put ? (int32_t)(cl - lo) : 0, b = put ? (int32_t)(ch - lo) : 0;
+        uint8_t *o = put ? pl.dst + ps->dofs + lo : nullptr;
+        const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
+        const uint32_t so = (uint32_t)((uintptr_t)o - z) & 3u;
+        // bytes [0, inv) of the piece are the data's first four: they enter inverted (the init value)
+        const uint32_t inv = (dlen >= 4 && lo < 4) ? (uint32_t)((hi < 4 ? hi : 4) - lo) : 0u;
+        int32_t pos = (int32_t)(16 * lane) - (int32_t)z;
+        Row x = row_edge(d, nullptr, pos, sd, 0, inv);
+        uint32_t c = step(tab, 0u, x.w);
+        if (o && pos < (int32_t)inv) {  // the store takes the bytes as found
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (pos + j >= 0 && pos + j < (int32_t)inv) x.w[j >> 2] ^= 0xffu << (8 * (j & 3));
+        }
+        if (o) store_clip(o, so, pos, a, b, x.w);
+        uint32_t r = 1;
+        if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
+            pos += (int32_t)kRow;
+            x = row_edge(d, nullptr, pos, sd, 0, inv);
+            c = step(tab, c, x.w);
+            if (o && pos < (int32_t)inv) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (pos + j >= 0 && pos + j < (int32_t)inv) x.w[j >> 2] ^= 0xffu << (8 * (j & 3));
+            }
+            if (o) store_clip(o, so, pos, a, b, x.w);
+            r = 2;
+        }
+        for (; r + 4 <= rows; r += 4) {
+            uint32_t w[4][4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (o) store_clip(o, so, (int32_t)((r + k) * kRow + 16 * lane - z), a, b, w[k]);
+                c = step(tab, c, w[k]);
+            }
+        }
+        for (; r < rows; ++r) {
+            uint32_t w[4];
+            load16(d + r * kRow + 16 * lane - z, sd, w);
+            if (o) store_clip(o, so, (int32_t)(r * kRow + 16 * lane - z), a, b, w);
+            c = step(tab, c, w);
+        }
+        const uint32_t v = wave_xor(mul(c, kl));
+        if (lane == 0) ((gword_out)pl.praw)[p] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dec_fold(DecPlan pl) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    for (uint32_t u = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); u < pl.nu; u += nw) {
+        const uint64_t b0 = ((gquad_ptr)pl.pbase)[u];
+        const uint32_t hdr = ((gword_ptr)pl.info)[2 * (uint64_t)u] & 255u;
+        const uint64_t blen = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u + 1];
+        const uint64_t len = hdr ? blen - hdr : 0;
+        // (an empty first piece has raw CRC 0 and is every merge's left half: it adds nothing)
+        const uint32_t m = (uint32_t)(((gquad_ptr)pl.pbase)[u + 1] - b0);
+        const uint32_t acc = m ? fold_part((gword_ptr)pl.praw + b0, m, lane) : 0u;
+        const uint32_t crc = (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+        if (lane == 0) ((gword_out)pl.crcs)[u] = crc;
+    }
+}
+
+// blockIdx.y strides over the copies, x over a copy's 16-byte units (the shape of k_page_copy)
+__global__ __launch_bounds__(256) void k_dec_copy(DecPlan pl) {
+    for (uint32_t i = blockIdx.y; i < pl.ncopy; i += gridDim.y) {
+        const gstore_ptr cs = (gstore_ptr)pl.copies + i;
+        const uint32_t u = cs->u;
+        const uint64_t boff = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u], blen = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u + 1];
+        if (((gword_ptr)pl.info)[2 * (uint64_t)u] != PBSGPU_BLOB_HEADER_SIZE || blen - PBSGPU_BLOB_HEADER_SIZE != cs->size)
+            continue;
+        const uint64_t xlo = cs->xlo;
+        const uint32_t len = (uint32_t)(cs->xhi - xlo), units = len >> 4;
+        const uint8_t *d = pl.src + boff + PBSGPU_BLOB_HEADER_SIZE + xlo;
+        uint8_t *o = pl.dst + cs->dofs + xlo;
+        const uint32_t sd = (uint32_t)(uintptr_t)d & 3u, so = (uint32_t)(uintptr_t)o & 3u;
+        for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < units; k += gridDim.x * 256) {
+            uint32_t w[4];
+            load16(d + 16ull * k, sd, w);
+            store16(o + 16ull * k, so, w);
+        }
+        const uint32_t t = 16 * units + threadIdx.x;
+        if (blockIdx.x == 0 && t < len) ((gbyte_out)o)[t] = ((gbyte_ptr)d)[t];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dec_status(DecPlan pl) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= pl.nidx) return;
+    const uint32_t u = ((gword_ptr)pl.ents)[2 * (uint64_t)i], size = ((gword_ptr)pl.ents)[2 * (uint64_t)i + 1];
+    const uint32_t hk = ((gword_ptr)pl.info)[2 * (uint64_t)u], stored = ((gword_ptr)pl.info)[2 * (uint64_t)u + 1];
+    const uint32_t hdr = hk & 255u;
+    uint8_t r;
+    if (hdr == 0) {
+        r = PBSGPU_BLOB_BAD_MAGIC;
+    } else if (((gword_ptr)pl.crcs)[u] != stored) {
+        r = PBSGPU_BLOB_BAD_CRC;
+    } else if (hk != PBSGPU_BLOB_HEADER_SIZE) {
+        r = PBSGPU_BLOB_CRC_ONLY;
+    } else if (((gquad_ptr)pl.blobs)[2 * (uint64_t)u + 1] - hdr != size) {
+        r = PBSGPU_BLOB_BAD_SIZE;
+    } else {
+        r = PBSGPU_BLOB_OK;
+        if (pl.recs) {
+            const gword_ptr want = (gword_ptr)(pl.recs + 48ull * i + 8), got = (gword_ptr)(pl.digs + 32ull * u);
+            uint32_t diff = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) diff |= want[j] ^ got[j];
+            if (diff) r = PBSGPU_BLOB_BAD_DIGEST;
+        }
+    }
+    ((gbyte_out)pl.status)[i] = r;
+}
+
 }  // namespace crc
 }  // namespace pbsk
 
@@ -897,6 +1147,184 @@ int blob_verify(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, c
     }
     for (uint32_t i = 0; i < n; ++i) st.count[status[i]]++;
     if (stats) *stats = st;
+    return PBSGPU_OK;
+}
+
+constexpr bool magic_words_match() {
+    for (int k = 0; k < 4; ++k)
+        for (int h = 0; h < 2; ++h) {
+            uint32_t w = 0;
+            for (int j = 0; j < 4; ++j) w |= (uint32_t)kMagic[k][4 * h + j] << (8 * j);
+            if (w != kDecMagic[k][h]) return false;
+        }
+    return true;
+}
+static_assert(magic_words_match(), "kDecMagic is kMagic in little-endian words");
+
+// pbsgpu_blob_decode_device. Everything the host can know is decided here before any device work; what depends on the
+// blobs' bytes (kind, data length, CRC, digest) is decided on the device and comes back once, at the end.
+// Layout on the lease:
+//   segs             the distinct referenced blobs (stage_ranges)
+//   sugg             one upload: pbase | prim | copies | ents | pseg
+//   sugg_idx         the index records (check_digest only: the status kernel reads their digests)
+//   dense | seg_cnt  praw | crcs
+//   tile_off | recs  the SHA-256 ranges | the digests
+//   order            what goes back in one transfer: info[nu] | status[nidx]
+int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
+                const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re,
+                int check_digest, void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats *stats) {
+    if (!e || nidx >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (nidx == 0) return PBSGPU_OK;
+    if (!idx || !status || !blobs || nblob == 0 || (!bptr && nbytes)) return PBSGPU_E_INVALID;
+    if (!blob_of && nblob != nidx) return PBSGPU_E_INVALID;
+    if (!ranges_ok(blobs, nblob, nbytes)) return PBSGPU_E_INVALID;
+    for (uint64_t i = 0; i < nidx; ++i) {
+        if (blob_of && blob_of[i] >= nblob) return PBSGPU_E_INVALID;
+        if (idx[i].size > idx[i].end || (i && idx[i].end - idx[i].size != idx[i - 1].end)) return PBSGPU_E_INVALID;
+    }
+    const uint64_t S = idx[0].end - idx[0].size, E = idx[nidx - 1].end;
+    if (rs < S || rs > re || re > E) return PBSGPU_E_INVALID;
+    const uint64_t need = re - rs;
+    if (need) {
+        if (!dst) return PBSGPU_E_INVALID;
+        const uintptr_t d0 = (uintptr_t)dst, b0 = (uintptr_t)bptr;
+        if (nbytes && d0 < b0 + nbytes && b0 < d0 + need) return PBSGPU_E_INVALID;  // dst overlaps the blob buffer
+    }
+    CHK(set_device(e));
+    if ((nbytes && !is_device_pointer(bptr)) || (need && !is_device_pointer(dst))) return PBSGPU_E_INVALID;
+    if (dst_cap < need) return PBSGPU_E_CAPACITY;
+    // the distinct referenced blobs, every entry's part of dst, and per blob the entry whose store rides the CRC pass:
+    // the first one that has bytes inside the range
+    std::vector<uint32_t> uof(nblob, 0xffffffffu);
+    std::vector<pbsgpu_segment> ub;
+    std::vector<DecEntry> ents((size_t)nidx);
+    std::vector<DecStore> prim, copies;
+    std::vector<uint64_t> clip((size_t)nidx);  // bytes of entry i inside the range
+    for (uint64_t i = 0; i < nidx; ++i) {
+        const uint32_t b = blob_of ? blob_of[i] : (uint32_t)i;
+        if (uof[b] == 0xffffffffu) {
+            uof[b] = (uint32_t)ub.size();
+            ub.push_back(blobs[b]);
+            prim.push_back(DecStore{0, 0, 0, 0, uof[b]});
+        }
+        const uint32_t u = uof[b];
+        ents[i] = DecEntry{u, idx[i].size};
+        const uint64_t start = idx[i].end - idx[i].size;
+        const uint64_t lo = std::max(start, rs), hi = std::min<uint64_t>(idx[i].end, re);
+        clip[i] = hi > lo ? hi - lo : 0;
+        if (!clip[i]) continue;
+        const DecStore ds{(int64_t)(start - rs), lo - start, hi - start, idx[i].size, u};
+        if (prim[u].xlo == prim[u].xhi) prim[u] = ds;
+        else copies.push_back(ds);
+    }
+    const uint32_t nu = (uint32_t)ub.size();
+    // pieces for the 12-byte header: the data of an encrypted kind is 32 bytes shorter and may leave the first one empty
+    std::vector<uint64_t> pbase((size_t)nu + 1);
+    uint64_t np = 0, total_blocks = 0, longest = 1;
+    for (uint32_t u = 0; u < nu; ++u) {
+        const uint64_t dl = ub[u].length > PBSGPU_BLOB_HEADER_SIZE ? ub[u].length - PBSGPU_BLOB_HEADER_SIZE : 0;
+        pbase[u] = np;
+        np += (dl + kPiece - 1) >> kPieceLog;
+        const uint64_t blocks = (dl + 8) / 64 + 1;
+        total_blocks += blocks;
+        longest = std::max(longest, blocks);
+    }
+    pbase[nu] = np;
+    if (np >= (1ull << 32)) return PBSGPU_E_INVALID;
+    const size_t o_prim = ((size_t)nu + 1) * 8, o_cop = o_prim + (size_t)nu * sizeof(DecStore);
+    const size_t o_ent = o_cop + copies.size() * sizeof(DecStore), o_pseg = o_ent + (size_t)nidx * sizeof(DecEntry);
+    std::vector<uint8_t> tabs(o_pseg + (size_t)np * 4);
+    std::memcpy(tabs.data(), pbase.data(), o_prim);
+    std::memcpy(tabs.data() + o_prim, prim.data(), (size_t)nu * sizeof(DecStore));
+    if (!copies.empty()) std::memcpy(tabs.data() + o_cop, copies.data(), copies.size() * sizeof(DecStore));
+    std::memcpy(tabs.data() + o_ent, ents.data(), (size_t)nidx * sizeof(DecEntry));
+    {
+        uint32_t *pseg = reinterpret_cast<uint32_t *>(tabs.data() + o_pseg);
+        for (uint32_t u = 0; u < nu; ++u)
+            for (uint64_t p = pbase[u]; p < pbase[u + 1]; ++p) pseg[p] = u;
+    }
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const size_t out_bytes = (size_t)nu * sizeof(DecInfo) + (size_t)nidx;
+    CHK(s->sugg.ensure(tabs.size() + 64));
+    CHK(s->dense.ensure((size_t)np * 4 + 64));
+    CHK(s->seg_cnt.ensure((size_t)nu * 4 + 64));
+    CHK(s->tile_off.ensure((size_t)nu * sizeof(pbsgpu_segment) + 64));
+    CHK(s->order.ensure(out_bytes + 64));
+    if (check_digest) {
+        CHK(s->sugg_idx.ensure((size_t)nidx * sizeof(pbsgpu_record) + 64));
+        CHK(s->recs.ensure((size_t)nu * 32 + 64));
+    }
+    const uint8_t *d = nullptr;
+    CHK(stage_ranges(e, s, bptr, false, nbytes, ub.data(), nu, &d));
+    CHK(staged_h2d(*s, s->sugg.p, tabs.data(), tabs.size(), s->stream));
+    if (check_digest) CHK(staged_h2d(*s, s->sugg_idx.p, idx, nidx * sizeof(pbsgpu_record), s->stream));
+    const uint8_t *t = s->sugg.as<uint8_t>();
+    DecPlan pl{};
+    pl.src = d;
+    pl.blobs = s->segs.as<pbsgpu_segment>();
+    pl.pbase = reinterpret_cast<const uint64_t *>(t);
+    pl.prim = reinterpret_cast<const DecStore *>(t + o_prim);
+    pl.copies = reinterpret_cast<const DecStore *>(t + o_cop);
+    pl.ents = reinterpret_cast<const DecEntry *>(t + o_ent);
+    pl.pseg = reinterpret_cast<const uint32_t *>(t + o_pseg);
+    pl.praw = s->dense.as<uint32_t>();
+    pl.crcs = s->seg_cnt.as<uint32_t>();
+    pl.info = s->order.as<DecInfo>();
+    pl.sha = s->tile_off.as<pbsgpu_segment>();
+    pl.recs = check_digest ? s->sugg_idx.as<uint8_t>() : nullptr;
+    pl.digs = check_digest ? s->recs.as<uint8_t>() : nullptr;
+    pl.status = s->order.as<uint8_t>() + (size_t)nu * sizeof(DecInfo);
+    pl.dst = static_cast<uint8_t *>(dst);
+    pl.npieces = np;
+    pl.nu = nu;
+    pl.ncopy = (uint32_t)copies.size();
+    pl.nidx = (uint32_t)nidx;
+    hipLaunchKernelGGL(pbsk::crc::k_dec_heads, dim3((nu + 255) / 256), dim3(256), 0, s->stream, pl);
+    HIPCHK(hipGetLastError());
+    if (np) {  // grids as in enqueue_crc
+        const uint64_t wg = std::min<uint64_t>((np + 3) / 4, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pbsk::crc::k_dec_pieces, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
+    {
+        const uint64_t wg = std::min<uint64_t>(((uint64_t)nu + 3) / 4, (uint64_t)e->num_cus * 16);
+        hipLaunchKernelGGL(pbsk::crc::k_dec_fold, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
+    if (pl.ncopy) {  // grid as for k_page_copy
+        uint64_t lng = 0;
+        for (const DecStore &c : copies) lng = std::max(lng, c.xhi - c.xlo);
+        const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lng / 16 + 255) / 256, (uint64_t)e->num_cus * 8));
+        hipLaunchKernelGGL(pbsk::crc::k_dec_copy, dim3(gx, std::min<uint32_t>(pl.ncopy, 1024)), dim3(256), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
+    if (check_digest)  // the policy of pbsgpu_sha256_many_device, on the sizes the host knows (exact for uncompressed blobs)
+        HIPCHK(pbsk::launch_sha256_segments(d, pl.sha, nu, s->recs.as<uint8_t>(), s->scalars.as<uint32_t>() + SC_QUEUE,
+                                            e->num_cus,
+                                            pbsk::sha256_dense_pays(total_blocks, longest, e->num_cus, e->opt.sha_dense_pct),
+                                            (int)e->opt.sha_form, s->stream));
+    hipLaunchKernelGGL(pbsk::crc::k_dec_status, dim3((unsigned)((nidx + 255) / 256)), dim3(256), 0, s->stream, pl);
+    HIPCHK(hipGetLastError());
+    std::vector<uint8_t> back(out_bytes);
+    CHK(fetch_result(s, back.data(), s->order.p, out_bytes));  // the call's one synchronisation
+    std::memcpy(status, back.data() + (size_t)nu * sizeof(DecInfo), (size_t)nidx);
+    if (stats) {
+        const DecInfo *info = reinterpret_cast<const DecInfo *>(back.data());
+        for (uint32_t u = 0; u < nu; ++u) {
+            const uint32_t hdr = info[u].hk & 255u;
+            stats->blob_bytes += ub[u].length;
+            if (hdr) stats->crc_bytes += ub[u].length - hdr;
+            if (check_digest && info[u].hk == PBSGPU_BLOB_HEADER_SIZE) stats->sha_bytes += ub[u].length - hdr;
+        }
+        for (uint64_t i = 0; i < nidx; ++i) {
+            stats->count[status[i]]++;
+            const uint32_t u = ents[i].u;
+            if (info[u].hk == PBSGPU_BLOB_HEADER_SIZE && ub[u].length - PBSGPU_BLOB_HEADER_SIZE == ents[i].size)
+                stats->out_bytes += clip[i];
+        }
+    }
     return PBSGPU_OK;
 }
 
@@ -1223,6 +1651,14 @@ int pbsgpu_blob_verify_host(pbsgpu_engine *e, const void *hptr, uint64_t nbytes,
                             uint32_t nblob, const uint8_t *digests, const uint32_t *sizes, uint8_t *status,
                             pbsgpu_blob_stats *stats) {
     return blob_verify(e, hptr, true, nbytes, blobs, nblob, digests, sizes, status, stats);
+}
+
+int pbsgpu_blob_decode_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                              uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                              uint64_t range_start, uint64_t range_end, int check_digest, void *dst, uint64_t dst_cap,
+                              uint8_t *status, pbsgpu_decode_stats *stats) {
+    return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, check_digest, dst,
+                       dst_cap, status, stats);
 }
 
 int pbsgpu_known_upload_new_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,

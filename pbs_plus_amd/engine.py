@@ -298,6 +298,45 @@ class Engine:
         stats.update(blob_bytes=int(st.blob_bytes), crc_bytes=int(st.crc_bytes), sha_bytes=int(st.sha_bytes))
         return status[:n], stats
 
+    def blob_decode(self, data, blobs, idx, blob_of=None, start=None, end=None, check_digest=True, dst=None,
+                    nbytes: int | None = None):
+        """The stream bytes [start, end) from a contiguous slice `idx` of an index (records as didx_decode returns them) and
+        the blobs [(offset, length)] of the device buffer `data` (pbsgpu_blob_decode_device): blob_of[i] = the blob that
+        carries entry i (None: blob i, see blob_index()); start / end default to the slice's span; dst None allocates
+        end - start bytes. Returns (dst DeviceBuffer, status per entry as blob_verify() gives it for that blob with the
+        entry's size and digest, stats dict: a count per status name, blob_bytes / crc_bytes / sha_bytes over the distinct
+        referenced blobs, out_bytes). An entry whose blob is not an uncompressed one of its size leaves its part of dst as
+        it was: read the status."""
+        recs = np.ascontiguousarray(idx, dtype=RECORD_DTYPE).reshape(-1)
+        n = int(recs.size)
+        segs, nblob = _segs(blobs)
+        bp, bn = self._dev(data, nbytes)
+        assert bp is not None, "blob_decode() wants device memory"
+        bo = None if blob_of is None else np.ascontiguousarray(blob_of, dtype=np.uint32).reshape(-1)
+        assert bo is None or bo.size == n
+        if start is None:
+            start = int(recs["end"][0]) - int(recs["size"][0]) if n else 0
+        if end is None:
+            end = int(recs["end"][-1]) if n else start
+        own = dst is None
+        if own:
+            dst = self.alloc(max(int(end) - int(start), 16))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        st = _lib.DecodeStats()
+        try:
+            check(self._L.pbsgpu_blob_decode_device(self._h, bp, bn, segs, nblob, recs.ctypes.data if n else None, n,
+                                                    bo.ctypes.data if bo is not None and n else None, int(start), int(end),
+                                                    int(bool(check_digest)), dst.ptr, dst.nbytes, status.ctypes.data,
+                                                    C.byref(st)), "blob_decode_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        stats = {name: int(st.count[k]) for k, name in enumerate(_lib.BLOB_STATUS_NAMES)}
+        stats.update(blob_bytes=int(st.blob_bytes), crc_bytes=int(st.crc_bytes), sha_bytes=int(st.sha_bytes),
+                     out_bytes=int(st.out_bytes))
+        return dst, status[:n], stats
+
     # ---- payload-stream assembly (.ppxar layout: markers + 16-byte headers + file bodies) ----------
     def payload_pack(self, src, files, dst, with_start: bool = True, with_tail: bool = True):
         """Lay the file bodies `files` = [(offset, length)] of device buffer `src` out as the pxar
@@ -373,6 +412,25 @@ def blob_magic(kind: int) -> bytes:
     out = (C.c_uint8 * 8)()
     check(_lib.lib().pbsgpu_blob_magic(int(kind), out), "blob_magic")
     return bytes(out)
+
+
+def blob_index(blob_digests, idx) -> np.ndarray:
+    """blob_of for Engine.blob_decode by digest: blob_digests is an (nblob, 32) uint8 array (blob b carries the chunk
+    with that SHA-256; of equal digests the first is taken), idx the index entries. KeyError on an entry whose digest no
+    blob carries."""
+    dg = np.ascontiguousarray(blob_digests, dtype=np.uint8).reshape(-1, 32)
+    recs = np.ascontiguousarray(idx, dtype=RECORD_DTYPE).reshape(-1)
+    where = {}
+    for b in range(dg.shape[0]):
+        where.setdefault(dg[b].tobytes(), b)
+    out = np.empty(recs.size, dtype=np.uint32)
+    want = np.ascontiguousarray(recs["digest"])
+    for i in range(recs.size):
+        key = want[i].tobytes()
+        if key not in where:
+            raise KeyError("entry %d: no blob carries digest %s" % (i, key.hex()))
+        out[i] = where[key]
+    return out
 
 
 def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:

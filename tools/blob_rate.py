@@ -2,13 +2,16 @@
 
 * crc32_many on device bytes and on host bytes (the host variant moves the bytes through pinned staging first);
 * blob_encode_device (one pass: the CRC and the copy into the blobs);
-* blob_verify_device with sizes and digests (CRC + SHA-256), beside sha256_many_device over the same chunks.
+* blob_verify_device with sizes and digests (CRC + SHA-256), beside sha256_many_device over the same chunks;
+* the read side: blob_decode_device of the whole stream of those blobs, with and without the digest check, beside the
+  composition it replaces, blob_verify_device (sizes + digests) followed by pbsgpu_gather_device of the same chunks
+  (--no-decode leaves the decode leg out: the composition alone, for a build that has no blob_decode).
 
 Two batches of device-resident chunks: fixed 4 MiB chunks (NewConfig(4 << 20)'s average) and chunks of 1-7 KiB, 4 KiB on
 average (NewConfig(4096)). The corpus is written on the device by the engine's fill kernel. Each figure is the median of
 a few synchronous calls timed with a host clock, after one warm-up call.
 
-    python tools/blob_rate.py [--big-gib 2] [--small-mib 256] [--reps 5]
+    python tools/blob_rate.py [--big-gib 2] [--small-mib 256] [--reps 5] [--no-decode]
 """
 import argparse
 import ctypes as C
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--small-mib", type=int, default=256, help="corpus of the 4 KiB-average batch")
     ap.add_argument("--host-gib", type=float, default=1.0, help="bytes of the host-variant CRC batch")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-decode", action="store_true", help="skip blob_decode (a build without it): the composition only")
     a = ap.parse_args()
 
     from pbs_plus_amd import Engine, _lib, buzhash
@@ -86,10 +90,37 @@ def main():
         status, st = eng.blob_verify(dst, blobs, digs, sizes)
         assert st["ok"] == n, st
         t_ver = _median_s(lambda: eng.blob_verify(dst, blobs, digs, sizes), max(1, a.reps // 2))
+        # the read side: the stream is the chunks back to back, entry i in blob i
+        idx = np.zeros(n, dtype=_lib.RECORD_DTYPE)
+        idx["size"] = sizes
+        idx["end"] = np.cumsum(sizes.astype(np.uint64))
+        idx["digest"] = digs
+        back = eng.alloc(data)
+        items = np.stack([blobs[:, 0] + 12, idx["end"] - sizes, sizes.astype(np.uint64)], axis=1)
+
+        def compose():
+            status, _ = eng.blob_verify(dst, blobs, digs, sizes)
+            eng.gather(dst, back, items)
+            return status
+
+        assert not compose().any()
+        t_cmp = _median_s(compose, a.reps)
+        dec = {}
+        if not a.no_decode:
+            for key, chk in (("decode", True), ("decode_nodigest", False)):
+                _, status, dst_st = eng.blob_decode(dst, blobs, idx, check_digest=chk, dst=back)
+                assert dst_st["ok"] == n and dst_st["out_bytes"] == data, dst_st
+                dec[key] = _median_s(lambda: eng.blob_decode(dst, blobs, idx, check_digest=chk, dst=back), a.reps)
+        back.free()
         row = {"batch": name, "chunks": n, "bytes": data,
                "crc_device_GBps": data / t_crc / 1e9, "encode_GBps": data / t_enc / 1e9,
                "verify_device_GBps": data / t_ver / 1e9, "sha256_many_GBps": data / t_sha / 1e9,
-               "ms": {"crc": t_crc * 1e3, "encode": t_enc * 1e3, "verify": t_ver * 1e3, "sha256_many": t_sha * 1e3}}
+               "verify_then_gather_GBps": data / t_cmp / 1e9,
+               "ms": {"crc": t_crc * 1e3, "encode": t_enc * 1e3, "verify": t_ver * 1e3, "sha256_many": t_sha * 1e3,
+                      "verify_then_gather": t_cmp * 1e3}}
+        for key, t in dec.items():
+            row[key + "_GBps"] = data / t / 1e9
+            row["ms"][key] = t * 1e3
         rows.append(row)
         print(json.dumps(row), flush=True)
         dst.free()
