@@ -24,6 +24,10 @@
 //                 the short piece is the segment's first), then Horner over the blocks; final xor; the blob header.
 // The encode pass is the same pair with a destination: the piece kernel stores every loaded row at the blob's data
 // position (arbitrary alignment, one row and lane at a time) and the fold writes the 12-byte header.
+// The ring's two-part chunks (k_pagecrc_*) and the restore (k_dec_*) have plans and kernels of their own, but one body:
+// piece_raw is the one walk over a piece, with three forms of the store (the whole piece if there is a destination, the
+// whole piece, the piece clipped to a byte range); a piece kernel only finds its piece's bytes, destination and inverted
+// head in its plan. The folds share fold_part, finish and store_header in the same way, the copies copy_bytes.
 // Memory instructions: global_* only (address-space-1 pointers); no scratch (tests/test_blob_surface.py).
 #include "ring_internal.h"
 
@@ -167,32 +171,73 @@ __device__ __forceinline__ uint32_t step(const uint32_t (*tab)[256], uint32_t c,
            tab[3][w[3] & 255] ^ tab[2][(w[3] >> 8) & 255] ^ tab[1][(w[3] >> 16) & 255] ^ tab[0][w[3] >> 24];
 }
 
-// a lane's 16 bytes at piece position pos in the rows that need care: padding in front of the piece (pos < 0: zeros, the
-// lane that straddles the start goes byte by byte) and the segment's first four bytes, which enter inverted ([0, inv))
+// a lane's 16 bytes at piece position pos, as found, in the rows that need care: padding in front of the piece reads as
+// zeros (pos < 0), and the lane that straddles the piece's start goes byte by byte
+// (load and inversion are two helpers although piece_raw alone calls them: the store between them takes the bytes as found,
+// and a fused load-store-invert is what each kernel once had to undo by hand)
 struct Row {
     uint32_t w[4];
 };
-__device__ __forceinline__ Row row_edge(const uint8_t *d, uint8_t *o, int32_t pos, uint32_t sd, uint32_t so, uint32_t inv) {
+__device__ __forceinline__ Row row_edge(const uint8_t *d, int32_t pos, uint32_t sd) {
     Row x{{0, 0, 0, 0}};
     if (pos >= 0) {
         load16(d + pos, sd, x.w);
-        if (o) store16(o + pos, so, x.w);
     } else if (pos > -16) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {  // (fixed bounds: the words stay in registers)
-            if (pos + j < 0) continue;
-            const uint8_t v = ((gbyte_ptr)d)[pos + j];
-            x.w[j >> 2] |= (uint32_t)v << (8 * (j & 3));
-            if (o) ((gbyte_out)o)[pos + j] = v;
-        }
-    }
-    if (pos < (int32_t)inv) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (pos + j >= 0 && pos + j < (int32_t)inv) x.w[j >> 2] ^= 0xffu << (8 * (j & 3));
+        for (int j = 0; j < 16; ++j)  // (fixed bounds: the words stay in registers)
+            if (pos + j >= 0) x.w[j >> 2] |= (uint32_t)((gbyte_ptr)d)[pos + j] << (8 * (j & 3));
     }
     return x;
 }
+
+// bytes [0, inv) of the piece are among the first four of what the CRC covers: they enter inverted (the init value)
+__device__ __forceinline__ void invert_head(uint32_t (&w)[4], int32_t pos, uint32_t inv) {
+    if (pos < (int32_t)inv) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (pos + j >= 0 && pos + j < (int32_t)inv) w[j >> 2] ^= 0xffu << (8 * (j & 3));
+    }
+}
+
+// a lane's 16 bytes at piece position pos, of which [a, b) may be stored (piece coordinates; so = (o + pos) & 3)
+__device__ __forceinline__ void store_clip(uint8_t *o, uint32_t so, int32_t pos, int32_t a, int32_t b,
+                                           const uint32_t (&w)[4]) {
+    if (pos >= a && pos + 16 <= b) {
+        store16(o + pos, so, w);
+    } else if (pos + 16 > a && pos < b) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)  // (fixed bounds: the words stay in registers)
+            if (pos + j >= a && pos + j < b) ((gbyte_out)o)[pos + j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+    }
+}
+
+// What the piece walk does with the bytes it has loaded, in three forms. `o` is where piece position 0 goes; edge() takes
+// a lane of the rows that may hold padding (signed position), row() a lane of a whole row (the offset stays unsigned: a
+// signed one costs the encode kernels a wave of occupancy).
+struct PutAll {  // the whole piece
+    uint8_t *o;
+    __device__ __forceinline__ void edge(uint32_t so, int32_t pos, const uint32_t (&w)[4]) const {
+        store_clip(o, so, pos, 0, INT32_MAX, w);
+    }
+    __device__ __forceinline__ void row(uint32_t so, uint32_t pos, const uint32_t (&w)[4]) const { store16(o + pos, so, w); }
+};
+struct PutIf {  // the whole piece when there is a destination
+    uint8_t *o;
+    __device__ __forceinline__ void edge(uint32_t so, int32_t pos, const uint32_t (&w)[4]) const {
+        if (o) PutAll{o}.edge(so, pos, w);
+    }
+    __device__ __forceinline__ void row(uint32_t so, uint32_t pos, const uint32_t (&w)[4]) const {
+        if (o) PutAll{o}.row(so, pos, w);
+    }
+};
+struct PutClip {  // the piece's bytes [a, b) when there is a destination
+    uint8_t *o;
+    int32_t a, b;
+    __device__ __forceinline__ void edge(uint32_t so, int32_t pos, const uint32_t (&w)[4]) const {
+        if (o) store_clip(o, so, pos, a, b, w);
+    }
+    __device__ __forceinline__ void row(uint32_t so, uint32_t pos, const uint32_t (&w)[4]) const { edge(so, (int32_t)pos, w); }
+};
 
 __device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
 #pragma unroll
@@ -200,26 +245,69 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_crc_pieces(Plan pl) {
-    // tab[m] = T_m (m = 0..15), tab[16] = the byte table raw(b)
-    __shared__ uint32_t tab[17][256];
-    {
-        const uint32_t b = threadIdx.x;
-        uint32_t c = b;
+// tab[m] = T_m (m = 0..15), tab[16] = the byte table raw(b); one entry of each per thread of the workgroup
+__device__ __forceinline__ void build_tables(uint32_t (*tab)[256]) {
+    const uint32_t b = threadIdx.x;
+    uint32_t c = b;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
-        tab[16][b] = c;
-        uint32_t t = mul(c, kDev.gap);
-        tab[0][b] = t;
-        __syncthreads();
-        for (int m = 1; m < 16; ++m) {  // one more zero byte: the plain CRC step
-            t = (t >> 8) ^ tab[16][t & 255];
-            tab[m][b] = t;
-        }
-        __syncthreads();
+    for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
+    tab[16][b] = c;
+    uint32_t t = mul(c, kDev.gap);
+    tab[0][b] = t;
+    __syncthreads();
+    for (int m = 1; m < 16; ++m) {  // one more zero byte: the plain CRC step
+        t = (t >> 8) ^ tab[16][t & 255];
+        tab[m][b] = t;
     }
+    __syncthreads();
+}
+
+// One wave's walk over a piece: raw CRC of the n bytes at d, of which the first inv enter inverted, every loaded row
+// handed to put. The same value in every lane.
+template <class Put>
+__device__ __forceinline__ uint32_t piece_raw(const uint32_t (*tab)[256], const uint8_t *d, uint32_t n, uint32_t inv,
+                                              uint32_t lane, const Put &put) {
+    const uint32_t rows = (n + kRow - 1) / kRow;
+    const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
+    const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
+    const uint32_t so = (uint32_t)((uintptr_t)put.o - z) & 3u;
+    uint32_t c = 0;
+    const auto edge = [&](int32_t pos) __attribute__((always_inline)) {
+        const Row x = row_edge(d, pos, sd);
+        Row y = x;
+        invert_head(y.w, pos, inv);
+        c = step(tab, c, y.w);   // (the table reads are in flight while the store, which takes the bytes as found, goes out)
+        put.edge(so, pos, x.w);
+    };
+    edge((int32_t)(16 * lane) - (int32_t)z);
+    uint32_t r = 1;
+    if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
+        edge((int32_t)(kRow + 16 * lane) - (int32_t)z);
+        r = 2;
+    }
+    for (; r + 4 <= rows; r += 4) {
+        uint32_t w[4][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            put.row(so, (r + k) * kRow + 16 * lane - z, w[k]);
+            c = step(tab, c, w[k]);
+        }
+    }
+    for (; r < rows; ++r) {
+        uint32_t w[4];
+        load16(d + r * kRow + 16 * lane - z, sd, w);
+        put.row(so, r * kRow + 16 * lane - z, w);
+        c = step(tab, c, w);
+    }
+    return wave_xor(mul(c, kDev.klane[lane]));
+}
+
+__global__ __launch_bounds__(256) void k_crc_pieces(Plan pl) {
+    __shared__ uint32_t tab[17][256];
+    build_tables(tab);
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t kl = kDev.klane[lane];
     const uint64_t nw = (uint64_t)gridDim.x * 4;
     for (uint64_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.npieces; p += nw) {
         const uint32_t i = ((gword_ptr)pl.pseg)[p];
@@ -228,39 +316,41 @@ __global__ __launch_bounds__(256) void k_crc_pieces(Plan pl) {
         const pbsgpu_segment sg{((gquad_ptr)pl.segs)[2 * i], ((gquad_ptr)pl.segs)[2 * i + 1]};
         const uint64_t hi = sg.length - (m - 1 - (p - b0)) * kPiece;  // piece = segment bytes [lo, hi)
         const uint64_t lo = hi > kPiece ? hi - kPiece : 0;
-        const uint32_t n = (uint32_t)(hi - lo);
-        const uint32_t rows = (n + kRow - 1) / kRow;
-        const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
-        const uint8_t *d = pl.src + sg.offset + lo;
         uint8_t *o = pl.dst ? pl.dst + ((gquad_ptr)pl.doff)[i] + PBSGPU_BLOB_HEADER_SIZE + lo : nullptr;
-        const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
-        const uint32_t so = (uint32_t)((uintptr_t)o - z) & 3u;
-        // bytes [0, inv) of the piece are the segment's first four: they enter inverted (the init value)
         const uint32_t inv = (sg.length >= 4 && lo < 4) ? (uint32_t)((hi < 4 ? hi : 4) - lo) : 0u;
-        uint32_t c = step(tab, 0u, row_edge(d, o, (int32_t)(16 * lane) - (int32_t)z, sd, so, inv).w);
-        uint32_t r = 1;
-        if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
-            c = step(tab, c, row_edge(d, o, (int32_t)(kRow + 16 * lane) - (int32_t)z, sd, so, inv).w);
-            r = 2;
-        }
-        for (; r + 4 <= rows; r += 4) {
-            uint32_t w[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (o) store16(o + (r + k) * kRow + 16 * lane - z, so, w[k]);
-                c = step(tab, c, w[k]);
-            }
-        }
-        for (; r < rows; ++r) {
-            uint32_t w[4];
-            load16(d + r * kRow + 16 * lane - z, sd, w);
-            if (o) store16(o + r * kRow + 16 * lane - z, so, w);
-            c = step(tab, c, w);
-        }
-        const uint32_t v = wave_xor(mul(c, kl));
+        const uint32_t v = piece_raw(tab, pl.src + sg.offset + lo, (uint32_t)(hi - lo), inv, lane, PutIf{o});
         if (lane == 0) ((gword_out)pl.praw)[p] = v;
+    }
+}
+
+// raw CRC of one range from its m >= 1 pieces: right to left in blocks of 64 lanes, a 6-level xor tree, Horner over the
+// blocks (only the first piece is short, so the right half of every merge holds whole pieces)
+__device__ __forceinline__ uint32_t fold_part(gword_ptr raw, uint32_t m, uint32_t lane) {
+    if (m == 1) return raw[0];
+    uint32_t acc = 0;
+    for (uint32_t blk = (m - 1) / kFoldLanes + 1; blk-- > 0;) {  // left to right
+        const uint32_t q = blk * kFoldLanes + lane;              // q = pieces from the range's end
+        uint32_t v = q < m ? raw[m - 1 - q] : 0u;
+#pragma unroll
+        for (int lv = 0; lv < 6; ++lv) {  // the lane with bit lv clear holds the right (later) half
+            const uint32_t u = __shfl_xor(v, 1 << lv, 64);
+            if (!(lane & (1u << lv))) v ^= mul(u, kDev.x8[kPieceLog + lv]);
+        }
+        acc = mul(acc, kDev.x8[kPieceLog + 6]) ^ __shfl(v, 0, 64);
+    }
+    return acc;
+}
+
+// raw -> CRC: the init term that the piece pass leaves to the fold (lengths under 4), and the final xor
+__device__ __forceinline__ uint32_t finish(uint32_t acc, uint64_t len) {
+    return (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+}
+
+// the 12-byte blob header at h, one byte per lane
+__device__ __forceinline__ void store_header(uint8_t *h, uint32_t lane, uint32_t magic_lo, uint32_t magic_hi, uint32_t crc) {
+    if (lane < PBSGPU_BLOB_HEADER_SIZE) {
+        const uint32_t word = lane < 4 ? magic_lo : lane < 8 ? magic_hi : crc;
+        ((gbyte_out)h)[lane] = (uint8_t)(word >> (8 * (lane & 3)));
     }
 }
 
@@ -269,30 +359,11 @@ __global__ __launch_bounds__(256) void k_crc_fold(Plan pl) {
     const uint32_t nw = gridDim.x * 4;
     for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < pl.nseg; i += nw) {
         const uint64_t b0 = ((gquad_ptr)pl.pbase)[i];
-        const uint64_t m = ((gquad_ptr)pl.pbase)[i + 1] - b0;
-        const uint64_t len = ((gquad_ptr)pl.segs)[2 * i + 1];
-        const gword_ptr raw = (gword_ptr)pl.praw + b0;
-        uint32_t acc = 0;
-        if (m == 1) {
-            acc = raw[0];
-        } else if (m > 1) {
-            for (uint64_t blk = (m - 1) / kFoldLanes + 1; blk-- > 0;) {  // left to right: Horner over 64-piece blocks
-                const uint64_t q = blk * kFoldLanes + lane;              // q = pieces from the segment's end
-                uint32_t v = q < m ? raw[m - 1 - q] : 0u;
-#pragma unroll
-                for (int lv = 0; lv < 6; ++lv) {  // the lane with bit lv clear holds the right (later) half
-                    const uint32_t u = __shfl_xor(v, 1 << lv, 64);
-                    if (!(lane & (1u << lv))) v ^= mul(u, kDev.x8[kPieceLog + lv]);
-                }
-                acc = mul(acc, kDev.x8[kPieceLog + 6]) ^ __shfl(v, 0, 64);
-            }
-        }
-        const uint32_t crc = (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+        const uint32_t m = (uint32_t)(((gquad_ptr)pl.pbase)[i + 1] - b0);  // (the host refuses 2^32 pieces)
+        const uint32_t acc = m ? fold_part((gword_ptr)pl.praw + b0, m, lane) : 0u;
+        const uint32_t crc = finish(acc, ((gquad_ptr)pl.segs)[2 * i + 1]);
         if (lane == 0) ((gword_out)pl.crcs)[i] = crc;
-        if (pl.dst && lane < PBSGPU_BLOB_HEADER_SIZE) {
-            const uint32_t word = lane < 4 ? pl.magic_lo : lane < 8 ? pl.magic_hi : crc;
-            ((gbyte_out)pl.dst)[((gquad_ptr)pl.doff)[i] + lane] = (uint8_t)(word >> (8 * (lane & 3)));
-        }
+        if (pl.dst) store_header(pl.dst + ((gquad_ptr)pl.doff)[i], lane, pl.magic_lo, pl.magic_hi, crc);
     }
 }
 
@@ -311,7 +382,7 @@ __global__ __launch_bounds__(256) void k_blob_heads(const uint8_t *src, const pb
 // own for the piece pass (pieces aligned at the part's end, only its first piece short); a part knows how many of its
 // leading bytes are among the chunk's first four (`inv`: a first part of 1-3 bytes leaves the rest to the second part).
 // The fold joins the two parts with one more product: raw(A || B) = raw(A) * x^(8|B|) + raw(B), the constant from the
-// host plan. A pair of its own rather than a second form of k_crc_pieces / k_crc_fold: those stay exactly as measured.
+// host plan. The pair has kernels and a plan of its own; the walk is piece_raw with the unconditional store.
 struct PartDesc {
     uint64_t src;    // offset of the part's first byte from PartPlan::base
     uint64_t dst;    // offset of where its bytes go in PartPlan::dst (behind the blob's header)
@@ -344,24 +415,9 @@ typedef const CRC_GLOBAL PartDesc *gpart_ptr;
 typedef const CRC_GLOBAL BlobDesc *gblob_ptr;
 
 __global__ __launch_bounds__(256) void k_pagecrc_pieces(PartPlan pl) {
-    __shared__ uint32_t tab[17][256];  // as in k_crc_pieces
-    {
-        const uint32_t b = threadIdx.x;
-        uint32_t c = b;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
-        tab[16][b] = c;
-        uint32_t t = mul(c, kDev.gap);
-        tab[0][b] = t;
-        __syncthreads();
-        for (int m = 1; m < 16; ++m) {
-            t = (t >> 8) ^ tab[16][t & 255];
-            tab[m][b] = t;
-        }
-        __syncthreads();
-    }
+    __shared__ uint32_t tab[17][256];
+    build_tables(tab);
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t kl = kDev.klane[lane];
     const uint32_t nw = gridDim.x * 4;
     const uint32_t npieces = pl.counts ? __builtin_amdgcn_readfirstlane(((gword_ptr)pl.counts)[0]) : pl.npieces;
     for (uint32_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < npieces; p += nw) {
@@ -371,56 +427,10 @@ __global__ __launch_bounds__(256) void k_pagecrc_pieces(PartPlan pl) {
         const uint32_t m = (len + (uint32_t)kPiece - 1) >> kPieceLog;
         const uint32_t hi = len - (m - 1 - (p - pd->pbase)) * (uint32_t)kPiece;  // piece = part bytes [lo, hi)
         const uint32_t lo = hi > kPiece ? hi - (uint32_t)kPiece : 0;
-        const uint32_t n = hi - lo;
-        const uint32_t rows = (n + kRow - 1) / kRow;
-        const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
-        const uint8_t *d = pl.base + pd->src + lo;
-        uint8_t *o = pl.dst + pd->dst + lo;
-        const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
-        const uint32_t so = (uint32_t)((uintptr_t)o - z) & 3u;
-        const uint32_t inv = lo < pinv ? (hi < pinv ? hi : pinv) - lo : 0u;  // bytes [0, inv) of the piece enter inverted
-        uint32_t c = step(tab, 0u, row_edge(d, o, (int32_t)(16 * lane) - (int32_t)z, sd, so, inv).w);
-        uint32_t r = 1;
-        if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
-            c = step(tab, c, row_edge(d, o, (int32_t)(kRow + 16 * lane) - (int32_t)z, sd, so, inv).w);
-            r = 2;
-        }
-        for (; r + 4 <= rows; r += 4) {
-            uint32_t w[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                store16(o + (r + k) * kRow + 16 * lane - z, so, w[k]);
-                c = step(tab, c, w[k]);
-            }
-        }
-        for (; r < rows; ++r) {
-            uint32_t w[4];
-            load16(d + r * kRow + 16 * lane - z, sd, w);
-            store16(o + r * kRow + 16 * lane - z, so, w);
-            c = step(tab, c, w);
-        }
-        const uint32_t v = wave_xor(mul(c, kl));
+        const uint32_t inv = lo < pinv ? (hi < pinv ? hi : pinv) - lo : 0u;
+        const uint32_t v = piece_raw(tab, pl.base + pd->src + lo, hi - lo, inv, lane, PutAll{pl.dst + pd->dst + lo});
         if (lane == 0) ((gword_out)pl.praw)[p] = v;
     }
-}
-
-// raw CRC of one part from its m >= 1 pieces (the fold of k_crc_fold: only the first piece is short)
-__device__ __forceinline__ uint32_t fold_part(gword_ptr raw, uint32_t m, uint32_t lane) {
-    if (m == 1) return raw[0];
-    uint32_t acc = 0;
-    for (uint32_t blk = (m - 1) / kFoldLanes + 1; blk-- > 0;) {
-        const uint32_t q = blk * kFoldLanes + lane;  // pieces from the part's end
-        uint32_t v = q < m ? raw[m - 1 - q] : 0u;
-#pragma unroll
-        for (int lv = 0; lv < 6; ++lv) {
-            const uint32_t u = __shfl_xor(v, 1 << lv, 64);
-            if (!(lane & (1u << lv))) v ^= mul(u, kDev.x8[kPieceLog + lv]);
-        }
-        acc = mul(acc, kDev.x8[kPieceLog + 6]) ^ __shfl(v, 0, 64);
-    }
-    return acc;
 }
 
 __global__ __launch_bounds__(256) void k_pagecrc_fold(PartPlan pl) {
@@ -429,37 +439,37 @@ __global__ __launch_bounds__(256) void k_pagecrc_fold(PartPlan pl) {
     const uint32_t nblob = pl.counts ? __builtin_amdgcn_readfirstlane(((gword_ptr)pl.counts)[2]) : pl.nblob;
     for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < nblob; i += nw) {
         const gblob_ptr bd = (gblob_ptr)pl.blobs + i;
-        const uint32_t np = bd->nparts, len = bd->len;
+        const uint32_t np = bd->nparts;
         const gpart_ptr pd = (gpart_ptr)pl.parts + bd->part0;
         uint32_t acc = 0;
         if (np >= 1) acc = fold_part((gword_ptr)pl.praw + pd[0].pbase, (pd[0].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
         if (np == 2)  // the part boundary: a join whose shift is no power of two of kPiece
             acc = mul(acc, bd->join) ^
                   fold_part((gword_ptr)pl.praw + pd[1].pbase, (pd[1].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
-        const uint32_t crc = (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+        const uint32_t crc = finish(acc, bd->len);
         if (lane == 0) ((gword_out)pl.crcs)[i] = crc;
-        if (lane < PBSGPU_BLOB_HEADER_SIZE) {
-            const uint32_t word = lane < 4 ? pl.magic_lo : lane < 8 ? pl.magic_hi : crc;
-            ((gbyte_out)pl.dst)[bd->hdr + lane] = (uint8_t)(word >> (8 * (lane & 3)));
-        }
+        store_header(pl.dst + bd->hdr, lane, pl.magic_lo, pl.magic_hi, crc);
     }
+}
+
+// len bytes from d to o in 16-byte units plus a byte tail, by the workgroups that share blockIdx.y
+__device__ __forceinline__ void copy_bytes(const uint8_t *d, uint8_t *o, uint32_t len) {
+    const uint32_t units = len >> 4;
+    const uint32_t sd = (uint32_t)(uintptr_t)d & 3u, so = (uint32_t)(uintptr_t)o & 3u;
+    for (uint32_t u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+        uint32_t w[4];
+        load16(d + 16ull * u, sd, w);
+        store16(o + 16ull * u, so, w);
+    }
+    const uint32_t t = 16 * units + threadIdx.x;
+    if (blockIdx.x == 0 && t < len) ((gbyte_out)o)[t] = ((gbyte_ptr)d)[t];
 }
 
 // the parts' bytes, unframed (pbsgpu_ring_copy_device): blockIdx.y strides over the parts, x over a part's 16-byte units
 __global__ __launch_bounds__(256) void k_page_copy(PartPlan pl) {
     for (uint32_t i = blockIdx.y; i < pl.nparts; i += gridDim.y) {
         const gpart_ptr pd = (gpart_ptr)pl.parts + i;
-        const uint32_t len = pd->len, units = len >> 4;
-        const uint8_t *d = pl.base + pd->src;
-        uint8_t *o = pl.dst + pd->dst;
-        const uint32_t sd = (uint32_t)(uintptr_t)d & 3u, so = (uint32_t)(uintptr_t)o & 3u;
-        for (uint32_t u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
-            uint32_t w[4];
-            load16(d + 16ull * u, sd, w);
-            store16(o + 16ull * u, so, w);
-        }
-        const uint32_t t = 16 * units + threadIdx.x;
-        if (blockIdx.x == 0 && t < len) ((gbyte_out)o)[t] = ((gbyte_ptr)d)[t];
+        copy_bytes(pl.base + pd->src, pl.dst + pd->dst, pd->len);
     }
 }
 
@@ -698,7 +708,7 @@ __global__ __launch_bounds__(256) void k_upnew_ppart(UpPlan pl) {
 // piece empty, raw CRC 0, which the fold passes over like the zero padding in front of a short piece.
 //   k_dec_heads   per blob: magic -> kind and header length (0 = unknown magic or a cut header), the stored CRC, and the
 //                 range launch_sha256_segments hashes (empty unless the blob is uncompressed)
-//   k_dec_pieces  k_crc_pieces with the CLIPPED store: the blob's data goes to the part of dst that belongs to its
+//   k_dec_pieces  piece_raw with the CLIPPED store: the blob's data goes to the part of dst that belongs to its
 //                 primary entry, cut at range_start / range_end at byte granularity while the CRC covers every byte;
 //                 stored only when the blob is uncompressed and its data length is the entry's size
 //   k_dec_fold    k_crc_fold over the data length the magic gives
@@ -768,37 +778,12 @@ __global__ __launch_bounds__(256) void k_dec_heads(DecPlan pl) {
     sh[1] = plain ? len - PBSGPU_BLOB_HEADER_SIZE : 0;
 }
 
-// a lane's 16 bytes at piece position pos, of which [a, b) may be stored (piece coordinates; so = (o + pos) & 3)
-__device__ __forceinline__ void store_clip(uint8_t *o, uint32_t so, int32_t pos, int32_t a, int32_t b,
-                                           const uint32_t (&w)[4]) {
-    if (pos >= a && pos + 16 <= b) {
-        store16(o + pos, so, w);
-    } else if (pos + 16 > a && pos < b) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j)  // (fixed bounds: the words stay in registers)
-            if (pos + j >= a && pos + j < b) ((gbyte_out)o)[pos + j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_dec_pieces(DecPlan pl) {
-    __shared__ uint32_t tab[17][256];  // as in k_crc_pieces
-    {
-        const uint32_t b = threadIdx.x;
-        uint32_t c = b;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c = (c >> 1) ^ (kPoly & (0u - (c & 1u)));
-        tab[16][b] = c;
-        uint32_t t = mul(c, kDev.gap);
-        tab[0][b] = t;
-        __syncthreads();
-        for (int m = 1; m < 16; ++m) {
-            t = (t >> 8) ^ tab[16][t & 255];
-            tab[m][b] = t;
-        }
-        __syncthreads();
-    }
+// At most 6 waves per SIMD, although its 53 VGPRs would allow 8: with all 8 workgroups of a CU resident at once the 4 MiB
+// restore without digests measured 2 % slower (the rate table)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 6))) void k_dec_pieces(DecPlan pl) {
+    __shared__ uint32_t tab[17][256];
+    build_tables(tab);
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t kl = kDev.klane[lane];
     const uint64_t nw = (uint64_t)gridDim.x * 4;
     for (uint64_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.npieces; p += nw) {
         const uint32_t u = ((gword_ptr)pl.pseg)[p];
@@ -815,60 +800,14 @@ __global__ __launch_bounds__(256) void k_dec_pieces(DecPlan pl) {
         }
         const uint64_t hi = dlen - back;  // piece = data bytes [lo, hi)
         const uint64_t lo = hi > kPiece ? hi - kPiece : 0;
-        const uint32_t n = (uint32_t)(hi - lo);
-        const uint32_t rows = (n + kRow - 1) / kRow;
-        const uint32_t z = rows * kRow - n;  // zero bytes in front of the piece
-        const uint8_t *d = pl.src + boff + hdr + lo;
         // the store: the piece's bytes [a, b) (piece coordinates) belong to the primary entry's part of dst
         const gstore_ptr ps = (gstore_ptr)pl.prim + u;
         const uint64_t xlo = ps->xlo, xhi = ps->xhi;
         const uint64_t cl = xlo > lo ? xlo : lo, ch = xhi < hi ? xhi : hi;
         const bool put = hk == PBSGPU_BLOB_HEADER_SIZE && dlen == ps->size && cl < ch;
-        const int32_t a = put ? (int32_t)(cl - lo) : 0, b = put ? (int32_t)(ch - lo) : 0;
-        uint8_t *o = put ? pl.dst + ps->dofs + lo : nullptr;
-        const uint32_t sd = (uint32_t)((uintptr_t)d - z) & 3u;
-        const uint32_t so = (uint32_t)((uintptr_t)o - z) & 3u;
-        // bytes [0, inv) of the piece are the data's first four: they enter inverted (the init value)
+        const PutClip clip{put ? pl.dst + ps->dofs + lo : nullptr, put ? (int32_t)(cl - lo) : 0, put ? (int32_t)(ch - lo) : 0};
         const uint32_t inv = (dlen >= 4 && lo < 4) ? (uint32_t)((hi < 4 ? hi : 4) - lo) : 0u;
-        int32_t pos = (int32_t)(16 * lane) - (int32_t)z;
-        Row x = row_edge(d, nullptr, pos, sd, 0, inv);
-        uint32_t c = step(tab, 0u, x.w);
-        if (o && pos < (int32_t)inv) {  // the store takes the bytes as found
-#pragma unroll
-            for (int j = 0; j < 16; ++j)
-                if (pos + j >= 0 && pos + j < (int32_t)inv) x.w[j >> 2] ^= 0xffu << (8 * (j & 3));
-        }
-        if (o) store_clip(o, so, pos, a, b, x.w);
-        uint32_t r = 1;
-        if (z > kRow - 4 && rows > 1) {  // the inverted bytes reach into row 1
-            pos += (int32_t)kRow;
-            x = row_edge(d, nullptr, pos, sd, 0, inv);
-            c = step(tab, c, x.w);
-            if (o && pos < (int32_t)inv) {
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (pos + j >= 0 && pos + j < (int32_t)inv) x.w[j >> 2] ^= 0xffu << (8 * (j & 3));
-            }
-            if (o) store_clip(o, so, pos, a, b, x.w);
-            r = 2;
-        }
-        for (; r + 4 <= rows; r += 4) {
-            uint32_t w[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) load16(d + (r + k) * kRow + 16 * lane - z, sd, w[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (o) store_clip(o, so, (int32_t)((r + k) * kRow + 16 * lane - z), a, b, w[k]);
-                c = step(tab, c, w[k]);
-            }
-        }
-        for (; r < rows; ++r) {
-            uint32_t w[4];
-            load16(d + r * kRow + 16 * lane - z, sd, w);
-            if (o) store_clip(o, so, (int32_t)(r * kRow + 16 * lane - z), a, b, w);
-            c = step(tab, c, w);
-        }
-        const uint32_t v = wave_xor(mul(c, kl));
+        const uint32_t v = piece_raw(tab, pl.src + boff + hdr + lo, (uint32_t)(hi - lo), inv, lane, clip);
         if (lane == 0) ((gword_out)pl.praw)[p] = v;
     }
 }
@@ -880,11 +819,10 @@ __global__ __launch_bounds__(256) void k_dec_fold(DecPlan pl) {
         const uint64_t b0 = ((gquad_ptr)pl.pbase)[u];
         const uint32_t hdr = ((gword_ptr)pl.info)[2 * (uint64_t)u] & 255u;
         const uint64_t blen = ((gquad_ptr)pl.blobs)[2 * (uint64_t)u + 1];
-        const uint64_t len = hdr ? blen - hdr : 0;
         // (an empty first piece has raw CRC 0 and is every merge's left half: it adds nothing)
         const uint32_t m = (uint32_t)(((gquad_ptr)pl.pbase)[u + 1] - b0);
         const uint32_t acc = m ? fold_part((gword_ptr)pl.praw + b0, m, lane) : 0u;
-        const uint32_t crc = (len < 4 ? acc ^ mul(0xffffffffu, kDev.small[len]) : acc) ^ 0xffffffffu;
+        const uint32_t crc = finish(acc, hdr ? blen - hdr : 0);
         if (lane == 0) ((gword_out)pl.crcs)[u] = crc;
     }
 }
@@ -898,17 +836,7 @@ __global__ __launch_bounds__(256) void k_dec_copy(DecPlan pl) {
         if (((gword_ptr)pl.info)[2 * (uint64_t)u] != PBSGPU_BLOB_HEADER_SIZE || blen - PBSGPU_BLOB_HEADER_SIZE != cs->size)
             continue;
         const uint64_t xlo = cs->xlo;
-        const uint32_t len = (uint32_t)(cs->xhi - xlo), units = len >> 4;
-        const uint8_t *d = pl.src + boff + PBSGPU_BLOB_HEADER_SIZE + xlo;
-        uint8_t *o = pl.dst + cs->dofs + xlo;
-        const uint32_t sd = (uint32_t)(uintptr_t)d & 3u, so = (uint32_t)(uintptr_t)o & 3u;
-        for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < units; k += gridDim.x * 256) {
-            uint32_t w[4];
-            load16(d + 16ull * k, sd, w);
-            store16(o + 16ull * k, so, w);
-        }
-        const uint32_t t = 16 * units + threadIdx.x;
-        if (blockIdx.x == 0 && t < len) ((gbyte_out)o)[t] = ((gbyte_ptr)d)[t];
+        copy_bytes(pl.src + boff + PBSGPU_BLOB_HEADER_SIZE + xlo, pl.dst + cs->dofs + xlo, (uint32_t)(cs->xhi - xlo));
     }
 }
 
@@ -971,6 +899,35 @@ bool ranges_ok(const pbsgpu_segment *segs, uint32_t nseg, uint64_t nbytes) {
 
 uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
+// the header's magic for the two encode plans: the uncompressed kind
+template <class P>
+void set_magic(P &pl) {
+    pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
+    pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
+}
+
+// owner[p] = the range that piece p belongs to, from pbase (n + 1 entries: the index of each range's first piece)
+void fill_owners(const std::vector<uint64_t> &pbase, uint32_t *owner) {
+    for (uint32_t i = 0; i + 1 < pbase.size(); ++i)
+        for (uint64_t p = pbase[i]; p < pbase[i + 1]; ++p) owner[p] = i;
+}
+
+// A piece kernel over np pieces (an upper bound when the plan's counts are on the device) and its fold over n ranges, on
+// st. Waves stride over the work: 8 workgroups per CU for the pieces (17 KiB of tables each; every workgroup builds its
+// tables once), 16 per CU for the fold.
+template <class P>
+int launch_pair(pbsgpu_engine *e, hipStream_t st, void (*pieces)(P), void (*fold)(P), const P &pl, uint64_t np, uint64_t n) {
+    if (np) {
+        const uint64_t wg = std::min<uint64_t>((np + 3) / 4, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pieces, dim3((unsigned)wg), dim3(256), 0, st, pl);
+        HIPCHK(hipGetLastError());
+    }
+    const uint64_t wg = std::min<uint64_t>((n + 3) / 4, (uint64_t)e->num_cus * 16);
+    hipLaunchKernelGGL(fold, dim3((unsigned)wg), dim3(256), 0, st, pl);
+    HIPCHK(hipGetLastError());
+    return PBSGPU_OK;
+}
+
 // CRC of the nseg ranges already in s->segs over device bytes d; optionally the encode destination. crcs_dev = the
 // device result array (nseg u32). Enqueued on the slot's stream, nothing synchronised.
 int enqueue_crc(pbsgpu_engine *e, Slot *s, const uint8_t *d, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *dst,
@@ -984,8 +941,7 @@ int enqueue_crc(pbsgpu_engine *e, Slot *s, const uint8_t *d, const pbsgpu_segmen
     pbase[nseg] = np;
     if (np >= (1ull << 32)) return PBSGPU_E_INVALID;  // > 256 TiB of pieces in one call
     std::vector<uint32_t> pseg((size_t)np);
-    for (uint32_t i = 0; i < nseg; ++i)
-        for (uint64_t p = pbase[i]; p < pbase[i + 1]; ++p) pseg[p] = i;
+    fill_owners(pbase, pseg.data());
     CHK(s->seg_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
     CHK(s->tile_cnt.ensure(np * sizeof(uint32_t) + 64));
     CHK(s->dense.ensure(np * sizeof(uint32_t) + 64));
@@ -1006,18 +962,9 @@ int enqueue_crc(pbsgpu_engine *e, Slot *s, const uint8_t *d, const pbsgpu_segmen
         CHK(staged_h2d(*s, s->tile_off.p, offsets, (nseg + 1) * sizeof(uint64_t), s->stream));
         pl.dst = dst;
         pl.doff = s->tile_off.as<uint64_t>();
-        pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
-        pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
+        set_magic(pl);
     }
-    if (np) {
-        // 8 workgroups per CU (17 KiB of tables each); every workgroup builds its tables once
-        const uint64_t wg = std::min<uint64_t>((np + 3) / 4, (uint64_t)e->num_cus * 8);
-        hipLaunchKernelGGL(pbsk::crc::k_crc_pieces, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
-        HIPCHK(hipGetLastError());
-    }
-    const uint64_t wg = std::min<uint64_t>((nseg + 3) / 4, (uint64_t)e->num_cus * 16);
-    hipLaunchKernelGGL(pbsk::crc::k_crc_fold, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
-    HIPCHK(hipGetLastError());
+    CHK(launch_pair(e, s->stream, k_crc_pieces, k_crc_fold, pl, np, nseg));
     *crcs_dev = pl.crcs;
     return PBSGPU_OK;
 }
@@ -1239,11 +1186,7 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
     std::memcpy(tabs.data() + o_prim, prim.data(), (size_t)nu * sizeof(DecStore));
     if (!copies.empty()) std::memcpy(tabs.data() + o_cop, copies.data(), copies.size() * sizeof(DecStore));
     std::memcpy(tabs.data() + o_ent, ents.data(), (size_t)nidx * sizeof(DecEntry));
-    {
-        uint32_t *pseg = reinterpret_cast<uint32_t *>(tabs.data() + o_pseg);
-        for (uint32_t u = 0; u < nu; ++u)
-            for (uint64_t p = pbase[u]; p < pbase[u + 1]; ++p) pseg[p] = u;
-    }
+    fill_owners(pbase, reinterpret_cast<uint32_t *>(tabs.data() + o_pseg));
     AuxLease lease(e);
     Slot *s = lease.s;
     const size_t out_bytes = (size_t)nu * sizeof(DecInfo) + (size_t)nidx;
@@ -1283,16 +1226,7 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
     pl.nidx = (uint32_t)nidx;
     hipLaunchKernelGGL(pbsk::crc::k_dec_heads, dim3((nu + 255) / 256), dim3(256), 0, s->stream, pl);
     HIPCHK(hipGetLastError());
-    if (np) {  // grids as in enqueue_crc
-        const uint64_t wg = std::min<uint64_t>((np + 3) / 4, (uint64_t)e->num_cus * 8);
-        hipLaunchKernelGGL(pbsk::crc::k_dec_pieces, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
-        HIPCHK(hipGetLastError());
-    }
-    {
-        const uint64_t wg = std::min<uint64_t>(((uint64_t)nu + 3) / 4, (uint64_t)e->num_cus * 16);
-        hipLaunchKernelGGL(pbsk::crc::k_dec_fold, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
-        HIPCHK(hipGetLastError());
-    }
+    CHK(launch_pair(e, s->stream, k_dec_pieces, k_dec_fold, pl, np, nu));
     if (pl.ncopy) {  // grid as for k_page_copy
         uint64_t lng = 0;
         for (const DecStore &c : copies) lng = std::max(lng, c.xhi - c.xlo);
@@ -1362,17 +1296,8 @@ static int enqueue_parts(pbsgpu_engine *e, Slot *s, PartPlan &pl, const std::vec
     pl.crcs = s->seg_cnt.as<uint32_t>();
     pl.npieces = (uint32_t)ppart.size();
     pl.nblob = (uint32_t)blobs.size();
-    pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
-    pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
-    if (pl.npieces) {  // grids as in enqueue_crc
-        const uint64_t wg = std::min<uint64_t>(((uint64_t)pl.npieces + 3) / 4, (uint64_t)e->num_cus * 8);
-        hipLaunchKernelGGL(pbsk::crc::k_pagecrc_pieces, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
-        HIPCHK(hipGetLastError());
-    }
-    const uint64_t wg = std::min<uint64_t>(((uint64_t)pl.nblob + 3) / 4, (uint64_t)e->num_cus * 16);
-    hipLaunchKernelGGL(pbsk::crc::k_pagecrc_fold, dim3((unsigned)wg), dim3(256), 0, s->stream, pl);
-    HIPCHK(hipGetLastError());
-    return PBSGPU_OK;
+    set_magic(pl);
+    return launch_pair(e, s->stream, k_pagecrc_pieces, k_pagecrc_fold, pl, pl.npieces, pl.nblob);
 }
 
 int blob_encode_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart (*src)[2], uint32_t nblob, uint8_t *dst,
@@ -1549,16 +1474,8 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     pl.praw = s->seg_cnt.as<uint32_t>();
     pl.crcs = reinterpret_cast<uint32_t *>(out + sizeof(UpHead) + (size_t)n * 8);
     pl.counts = &up.head->npieces;
-    pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
-    pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
-    if (src.pieces_max) {  // the capped grids of enqueue_parts, from the upper bounds the host knows
-        const uint64_t wg = std::min<uint64_t>((src.pieces_max + 3) / 4, (uint64_t)e->num_cus * 8);
-        hipLaunchKernelGGL(pbsk::crc::k_pagecrc_pieces, dim3((unsigned)wg), dim3(256), 0, st, pl);
-        HIPCHK(hipGetLastError());
-    }
-    const uint64_t wg = std::min<uint64_t>((n + 3) / 4, (uint64_t)e->num_cus * 16);
-    hipLaunchKernelGGL(pbsk::crc::k_pagecrc_fold, dim3((unsigned)wg), dim3(256), 0, st, pl);
-    HIPCHK(hipGetLastError());
+    set_magic(pl);
+    CHK(launch_pair(e, st, k_pagecrc_pieces, k_pagecrc_fold, pl, src.pieces_max, n));  // the upper bounds the host knows
     HIPCHK(pbsk::launch_publish(s->h_recs.p, out, out_bytes, st));
     HIPCHK(hipStreamSynchronize(st));
     const uint8_t *h = s->h_recs.as<uint8_t>();

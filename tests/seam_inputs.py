@@ -22,6 +22,11 @@ from dense_inputs import _rotl, window_hash
 SHA_P2 = tuple(range(0, 9)) + tuple(range(52, 73))
 # chunker average -> page size the seam tests run it at
 PAGES = {256: 65536, 4096: 65536, 65536: 262144}
+# chunk lengths around the edge rows of blob.hip's piece walk (rows of 1024 bytes, pieces of 64 KiB): under one 16-byte unit,
+# the row and piece edges, and n = 1..3 mod 1024 above a row, where the four inverted bytes reach into row 1
+BLOB_PIECE = 1 << 16
+BLOB_EDGE_LENS = (list(range(1, 21)) + list(range(1023, 1029)) + list(range(2047, 2053)) +
+                  list(range(BLOB_PIECE - 1, BLOB_PIECE + 4)) + list(range(2 * BLOB_PIECE + 1, 2 * BLOB_PIECE + 4)))
 
 
 def effmin(cfg) -> int:

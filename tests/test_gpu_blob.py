@@ -2,10 +2,15 @@
 zlib.crc32, the uncompressed blob against a byte-exact Python model, the encode of a classified corpus's new chunks, the
 verifier's statuses, and all of it beside a running page ring."""
 import hashlib
+import os
+import sys
 import zlib
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from seam_inputs import BLOB_EDGE_LENS as EDGE_LENS  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -44,12 +49,14 @@ def _check_crc(eng, host, dbuf, segs):
 
 
 def test_crc32_lengths_offsets_and_patterns():
-    """Every length 0-130, the row and piece edges, at every residue mod 16 of the offset; overlapping ranges."""
+    """Every length 0-130, the row and piece edges and EDGE_LENS, at every residue mod 16 of the offset; overlapping
+    ranges."""
     eng = _engine()
     rng = np.random.default_rng(1)
     host = rng.integers(0, 256, 3 * PIECE + 4096, dtype=np.uint8)
     d = _dev(eng, host)
     lens = list(range(131)) + [1023, 1024, 1025, 4095, 4096, 4097, PIECE - 1, PIECE, PIECE + 1, 2 * PIECE + 3]
+    lens += [n for n in EDGE_LENS if n not in lens]
     segs = [(off, n) for n in lens for off in range(16) if off + n <= host.size]
     _check_crc(eng, host, d, segs)
     # overlapping ranges and the whole buffer
@@ -114,8 +121,14 @@ def test_encode_is_byte_exact_and_respects_the_capacity():
     src = _dev(eng, host)
     chunks = [(0, 0), (1, 1), (2, 3), (5, 17), (7, 1024), (13, 1025), (0, PIECE + 1), (3, 2 * PIECE - 5), (11, 100), (0, 0)]
     chunks += [(int(rng.integers(0, PIECE)), int(rng.integers(0, 3000))) for _ in range(200)]
+    # the edge rows' store: every length of EDGE_LENS at every source residue mod 16; the running blob offsets give every
+    # one of them every destination residue mod 4
+    edge0 = len(chunks)
+    chunks += [(off, n) for off in range(16) for n in EDGE_LENS]
     dst, offs, crcs = eng.blob_encode(src, chunks, nbytes=host.size)
     assert int(offs[-1]) == sum(12 + n for _, n in chunks) == dst.nbytes
+    assert {(n, (int(offs[i]) + 12) % 4) for i, (_, n) in enumerate(chunks) if i >= edge0} == \
+        {(n, r) for n in EDGE_LENS for r in range(4)}
     _parse(dst.download(), offs, crcs, chunks, host)
     dst.free()
     # guard bytes past dst_cap stay untouched; a capacity one byte short is E_CAPACITY with the needed size

@@ -120,6 +120,8 @@ def _same(got, want):
 
 # ---- 1. lengths and alignments -------------------------------------------------------------------------------------------
 LENGTHS = list(range(131)) + [1023, 1024, 1025, 4095, 4096, 4097, PIECE - 1, PIECE, PIECE + 1, 2 * PIECE + 3]
+# n = 1..3 mod 1024 above a row: the four inverted bytes reach into row 1 of the piece
+LENGTHS += [1026, 1027, 1028, PIECE + 2, PIECE + 3, 2 * PIECE + 1, 2 * PIECE + 2]
 
 
 def _aligned_corpus(make):

@@ -453,3 +453,42 @@ def test_contiguous_form(gpu_lib):
     tw.close()
     buf.free()
     eng.close()
+
+
+def test_contiguous_form_edge_lengths_at_every_source_alignment(gpu_lib):
+    """The piece walk of the two-part kernels on chosen part lengths: chunks of the lengths around its edge rows (under one
+    16-byte unit, the row and piece edges, n = 1..3 mod 1024 above a row) at every source residue mod 16, every record
+    new. Blobs and CRCs against Engine.blob_encode of the same ranges and against zlib."""
+    from pbs_plus_amd import RECORD_DTYPE, KnownChunks
+
+    lens = S.BLOB_EDGE_LENS
+    chunks = np.array([(off, n) for off in range(16) for n in lens], dtype=np.uint64)
+    eng = _engine(4096)
+    host = np.random.default_rng(91).integers(0, 256, 2 * PIECE + 32, dtype=np.uint8)
+    buf = eng.alloc(host.size)
+    buf.upload(host)
+    recs = np.zeros(chunks.shape[0], dtype=RECORD_DTYPE)
+    recs["size"] = chunks[:, 1]
+    recs["end"] = np.cumsum(chunks[:, 1])
+    for i in range(recs.size):  # made-up digests, all distinct: every record is new
+        recs["digest"][i] = np.frombuffer(hashlib.sha256(b"edge %d" % i).digest(), np.uint8)
+    k = KnownChunks(eng)
+    dst, flags, offs, crcs, st = k.upload_new(buf, recs, chunks, insert=True, nbytes=host.size)
+    assert not flags.any() and st["nunique"] == recs.size == len(k)
+    dst2, offs2, crcs2 = eng.blob_encode(buf, chunks, nbytes=host.size)
+    assert dst.used == int(offs2[-1]) == int(chunks[:, 1].sum()) + 12 * recs.size
+    assert np.array_equal(offs, offs2[:-1]) and np.array_equal(crcs, crcs2)
+    # every length meets every destination residue mod 4
+    assert {(int(n), (int(o) + 12) % 4) for o, n in zip(offs, chunks[:, 1])} == {(n, r) for n in lens for r in range(4)}
+    out = dst.download(0, dst.used)
+    assert out.tobytes() == dst2.download(0, dst.used).tobytes()
+    for i, (o, n) in enumerate(chunks):
+        data = host[int(o):int(o + n)].tobytes()
+        crc = zlib.crc32(data)
+        assert int(crcs[i]) == crc, (i, int(o), int(n))
+        assert out[int(offs[i]):int(offs[i]) + 12 + int(n)].tobytes() == MAGIC + crc.to_bytes(4, "little") + data, (i, int(o), int(n))
+    dst.free()
+    dst2.free()
+    k.close()
+    buf.free()
+    eng.close()
