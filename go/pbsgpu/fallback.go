@@ -222,3 +222,40 @@ type DecodeStats struct {
 func (e *Engine) DecodeBlobs(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, unsafe.Pointer, uint64) ([]uint8, DecodeStats, error) {
 	return nil, DecodeStats{}, ErrNotBuilt
 }
+
+// Statuses of DecodeZstd and ZstdFrameInfo.
+const (
+	ZstdOK          = 0
+	ZstdBadFrame    = 1
+	ZstdBadSize     = 2
+	ZstdUnsupported = 3
+)
+
+// ZstdFrame is what the header of one zstd frame declares.
+type ZstdFrame struct {
+	Status         int
+	ContentSize    uint64
+	HasContentSize bool
+	WindowSize     uint64
+	HeaderBytes    uint32
+	HasChecksum    bool
+}
+
+func ZstdFrameInfo([]byte) (ZstdFrame, error) { return ZstdFrame{}, ErrNotBuilt }
+func (e *Engine) DecodeZstd(unsafe.Pointer, uint64, []uint64, []uint64, []uint64, []uint64, unsafe.Pointer, uint64) ([]uint8, []uint64, error) {
+	return nil, nil, ErrNotBuilt
+}
+
+// BlobBadData is DecodeBlobs2's status for a compressed blob whose zstd frame is malformed or unsupported.
+const BlobBadData = 6
+
+// DecodeStats2 is DecodeStats with a count for BlobBadData and the zstd decoder's byte counts.
+type DecodeStats2 struct {
+	Count                                      [8]uint64
+	BlobBytes, CRCBytes, SHA256Bytes, OutBytes uint64
+	ZstdInBytes, ZstdOutBytes                  uint64
+}
+
+func (e *Engine) DecodeBlobs2(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, bool, unsafe.Pointer, uint64) ([]uint8, DecodeStats2, error) {
+	return nil, DecodeStats2{}, ErrNotBuilt
+}

@@ -1412,3 +1412,134 @@ func (e *Engine) DecodeBlobs(dptr unsafe.Pointer, nbytes uint64, offsets, length
 	out.OutBytes = uint64(st.out_bytes)
 	return status[:len(cr)], out, nil
 }
+
+// Statuses of DecodeZstd and ZstdFrameInfo (PBSGPU_ZSTD_*).
+const (
+	ZstdOK          = 0
+	ZstdBadFrame    = 1 // malformed or truncated
+	ZstdBadSize     = 2 // needs more room than given, or the declared content size is not what was decoded
+	ZstdUnsupported = 3 // dictionary, skippable frame, more than one frame, trailing bytes
+)
+
+// ZstdFrame is what the header of one zstd frame declares. ContentSize is valid when HasContentSize is set.
+type ZstdFrame struct {
+	Status         int
+	ContentSize    uint64
+	HasContentSize bool
+	WindowSize     uint64
+	HeaderBytes    uint32
+	HasChecksum    bool
+}
+
+// ZstdFrameInfo reads the header of the zstd frame in `frame` (host only): what a caller without an index sizes the
+// destination of DecodeZstd with.
+func ZstdFrameInfo(frame []byte) (ZstdFrame, error) {
+	var size, window C.uint64_t
+	var hb C.uint32_t
+	var ck C.int
+	var p *C.uint8_t
+	if len(frame) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&frame[0]))
+	}
+	st := C.pbsgpu_zstd_frame_info(p, C.uint64_t(len(frame)), &size, &window, &hb, &ck)
+	if st < 0 {
+		return ZstdFrame{}, check(st, "zstd_frame_info")
+	}
+	return ZstdFrame{Status: int(st), ContentSize: uint64(size), HasContentSize: uint64(size) != ^uint64(0), WindowSize: uint64(window),
+		HeaderBytes: uint32(hb), HasChecksum: ck != 0}, nil
+}
+
+// DecodeZstd decodes the zstd frames (offsets, lengths) of a device buffer in one launch: frame i goes to dst +
+// outOffsets[i], which has outRooms[i] bytes of room. These are the chunks the stock client stores compressed
+// (internal/server/backup/command.go) and that datastore.NewChunkStore reads back (internal/server/verification/job.go:931-966,
+// internal/pxar/format.go:101-129). Returns the status (Zstd*) and the bytes produced per frame; a frame whose status is
+// not ZstdOK leaves unspecified bytes in its own room and nothing anywhere else.
+func (e *Engine) DecodeZstd(dptr unsafe.Pointer, nbytes uint64, offsets, lengths, outOffsets, outRooms []uint64, dst unsafe.Pointer,
+	dstCap uint64) ([]uint8, []uint64, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, nil, err
+	}
+	outs, err := toSegments(outOffsets, outRooms)
+	if err != nil {
+		return nil, nil, err
+	}
+	if len(outs) != len(segs) {
+		return nil, nil, errors.New("pbsgpu: DecodeZstd needs one destination per frame")
+	}
+	status := make([]uint8, len(segs)+1)
+	decoded := make([]uint64, len(segs)+1)
+	var sp, op *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp, op = &segs[0], &outs[0]
+	}
+	err = check(C.pbsgpu_zstd_decode_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), op, dst, C.uint64_t(dstCap),
+		(*C.uint8_t)(unsafe.Pointer(&status[0])), (*C.uint64_t)(unsafe.Pointer(&decoded[0]))), "zstd_decode_device")
+	if err != nil {
+		return nil, nil, err
+	}
+	return status[:len(segs)], decoded[:len(segs)], nil
+}
+
+// BlobBadData is DecodeBlobs2's status for a compressed blob whose zstd frame is malformed or unsupported.
+const BlobBadData = 6
+
+// DecodeStats2 is DecodeStats with a count for BlobBadData and the bytes that went into and came out of the zstd decoder.
+type DecodeStats2 struct {
+	Count                                      [8]uint64
+	BlobBytes, CRCBytes, SHA256Bytes, OutBytes uint64
+	ZstdInBytes, ZstdOutBytes                  uint64
+}
+
+// DecodeBlobs2 is DecodeBlobs with the zstd-compressed blobs decoded on the device (zstd true): the restore loop of a
+// datastore the stock client wrote (internal/server/backup/command.go; the readers of internal/server/verification/job.go:931-966
+// and internal/pxar/format.go:101-129). A compressed blob with a good CRC is decoded to its entries' places and checked for
+// the entry's size and, with checkDigest, the SHA-256 of the decoded bytes; BlobCRCOnly then means encrypted only. With zstd
+// false every output is DecodeBlobs'.
+func (e *Engine) DecodeBlobs2(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, idx []ChunkInfo, blobOf []uint32,
+	rangeStart, rangeEnd uint64, checkDigest, zstd bool, dst unsafe.Pointer, dstCap uint64) ([]uint8, DecodeStats2, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, DecodeStats2{}, err
+	}
+	if blobOf != nil && len(blobOf) != len(idx) {
+		return nil, DecodeStats2{}, errors.New("pbsgpu: DecodeBlobs2 needs one blobOf per index entry")
+	}
+	cr := toRecords(idx)
+	var sp *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp = &segs[0]
+	}
+	var rp *C.pbsgpu_record
+	var bo *C.uint32_t
+	status := make([]uint8, len(cr)+1)
+	if len(cr) > 0 {
+		rp = &cr[0]
+		if blobOf != nil {
+			bo = (*C.uint32_t)(unsafe.Pointer(&blobOf[0]))
+		}
+	}
+	flags := C.uint32_t(0)
+	if checkDigest {
+		flags |= C.PBSGPU_DECODE_F_DIGEST
+	}
+	if zstd {
+		flags |= C.PBSGPU_DECODE_F_ZSTD
+	}
+	var st C.pbsgpu_decode_stats2
+	err = check(C.pbsgpu_blob_decode2_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), rp, C.uint64_t(len(cr)), bo,
+		C.uint64_t(rangeStart), C.uint64_t(rangeEnd), flags, dst, C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])),
+		&st), "blob_decode2_device")
+	if err != nil {
+		return nil, DecodeStats2{}, err
+	}
+	var out DecodeStats2
+	for i := range out.Count {
+		out.Count[i] = uint64(st.count[i])
+	}
+	out.BlobBytes, out.CRCBytes, out.SHA256Bytes = uint64(st.blob_bytes), uint64(st.crc_bytes), uint64(st.sha_bytes)
+	out.OutBytes, out.ZstdInBytes, out.ZstdOutBytes = uint64(st.out_bytes), uint64(st.zstd_in_bytes), uint64(st.zstd_out_bytes)
+	return status[:len(cr)], out, nil
+}

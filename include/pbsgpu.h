@@ -691,6 +691,84 @@ int pbsgpu_blob_decode_device(pbsgpu_engine *eng,
                               void *dst, uint64_t dst_cap,                 /* device memory */
                               uint8_t *status /* nidx */, pbsgpu_decode_stats *stats /* may be NULL */);
 
+/* ---- zstd frames on the device -------------------------------------------------------------------------------------
+ * The chunks the stock client writes are zstd frames: the reference's main backup path shells out to
+ * proxmox-backup-client (internal/server/backup/command.go), which compresses by default, so the blobs that
+ * datastore.NewChunkStore + transfer.NewChunkedReader read back (internal/server/verification/job.go:931-966,
+ * internal/pxar/format.go:101-129, internal/pxarmount/commit_orchestrate.go:356-368) and the ranged reads of the restore
+ * client (internal/pxar/client.go:236) find behind the "zstd compressed" magic one zstd frame each (RFC 8878).
+ * The decoder (pbs_plus_amd/csrc/zstd_decode.h, one source for the kernel and for the CPU build that is fuzzed) takes
+ * everything a conforming encoder may put into one frame. Decisions:
+ *   - the content checksum (XXH64) is parsed and accounted for, NOT verified: the blob's CRC-32 covers the compressed
+ *     bytes and the index digest covers the content;
+ *   - a nonzero dictionary id, a skippable frame, a second frame or trailing bytes behind the frame are UNSUPPORTED;
+ *   - an offset is valid if and only if it does not reach before the frame's first output byte (the output so far is the
+ *     window); a declared window size is read, not enforced and not allocated;
+ *   - the decoder knows the room it may write: a declared content size above it is refused before anything is written,
+ *     and no byte is stored outside it;
+ *   - reading past either end of a backward bit stream, an FSE distribution that does not sum and an incomplete Huffman
+ *     weight set are BAD_FRAME. */
+#define PBSGPU_HAS_ZSTD_DECODE 1
+#define PBSGPU_ZSTD_OK 0
+#define PBSGPU_ZSTD_BAD_FRAME 1   /* malformed or truncated */
+#define PBSGPU_ZSTD_BAD_SIZE 2    /* needs more room than given, or the declared content size is not what was decoded */
+#define PBSGPU_ZSTD_UNSUPPORTED 3 /* dictionary, skippable frame, more than one frame, trailing bytes */
+/* What the header of the frame at frame[0, nbytes) declares; returns a PBSGPU_ZSTD_* status (PBSGPU_E_INVALID for a NULL
+ * frame): what a caller without an index sizes a destination with. *content_size = UINT64_MAX when the frame does not
+ * declare one; *window_size = the content size for a single-segment frame. Every out pointer may be NULL. Host only. */
+int pbsgpu_zstd_frame_info(const uint8_t *frame, uint64_t nbytes, uint64_t *content_size /* UINT64_MAX: not declared */,
+                           uint64_t *window_size, uint32_t *header_bytes, int *has_checksum);
+/* Decode many frames in one launch: frame i = src[frames[i].offset .. +length) goes to dst[out[i].offset .. ), which has
+ * out[i].length bytes of room. status[i] = PBSGPU_ZSTD_*, decoded[i] (may be NULL) = the bytes produced (0 unless OK). A
+ * frame writes nothing outside out[i]; on a status other than OK the contents of out[i] are unspecified; everything else
+ * is untouched. Decided on the host before any device work, with dst untouched: PBSGPU_E_INVALID for a NULL where a value
+ * is needed, a frame outside src, an out[i] outside dst_cap, out ranges that overlap one another or the source, a host
+ * pointer for src or dst, a frame or a room of 4 GiB or more. nframe == 0 is PBSGPU_OK.
+ * One wave per frame; one leased stream of the engine and ONE synchronisation of it, at the end; it waits only for that
+ * stream, so it is usable between the pumps of a running ring (a call that has to grow the slot's literal scratch, 128 KiB per
+ * workgroup, frees the old one first, which waits for the device: DESIGN.md §15). */
+int pbsgpu_zstd_decode_device(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const pbsgpu_segment *frames,
+                              uint32_t nframe, const pbsgpu_segment *out /* nframe: offset and room inside dst */,
+                              void *dst, uint64_t dst_cap, uint8_t *status /* nframe */,
+                              uint64_t *decoded /* nframe, may be NULL */);
+
+/* Restore with the compressed blobs decoded: pbsgpu_blob_decode_device's arguments with `int check_digest` replaced by
+ * flags, and statistics with two more fields. The same call sites (internal/server/verification/job.go:931-966,
+ * internal/pxar/format.go:101-129, internal/pxarmount/commit_orchestrate.go:356-368, internal/pxar/client.go:236), now for
+ * the chunks internal/server/backup/command.go's client stored compressed.
+ * Without PBSGPU_DECODE_F_ZSTD every output equals the old call's with check_digest = (flags & F_DIGEST), byte for byte and
+ * status for status. With it, a blob of the zstd-compressed kind whose CRC is good is decoded on the device; the checks of
+ * such a blob, in order: magic, header, CRC, frame, size, digest.
+ *   - the CRC is bad: PBSGPU_BLOB_BAD_CRC, the blob is not decoded and its part of dst stays untouched;
+ *   - the frame is PBSGPU_ZSTD_BAD_FRAME or _UNSUPPORTED: PBSGPU_BLOB_BAD_DATA;
+ *   - the frame needs more room than the largest entry that names the blob, or does not produce exactly idx[i].size
+ *     bytes: PBSGPU_BLOB_BAD_SIZE;
+ *   - with F_DIGEST, the SHA-256 of the DECODED bytes differs from idx[i].digest: PBSGPU_BLOB_BAD_DIGEST.
+ * Both encrypted kinds stay PBSGPU_BLOB_CRC_ONLY. Decoded bytes go to the entry's place in the stream: a blob whose first
+ * entry inside the range lies wholly inside it (and is the largest entry naming the blob) is decoded straight into dst;
+ * any other (an entry clipped by the range's ends, entries outside the range, entries of differing sizes) is decoded into
+ * engine scratch and its entries' clipped parts are copied. A blob named by k entries is decoded once; a copy pass makes
+ * the rest. On BAD_DATA and on a compressed BAD_SIZE the entry's own clipped part of dst is unspecified; nothing outside
+ * it is written. Everything the old section promises for uncompressed blobs holds unchanged. All of it is decided on
+ * the device — which blobs are compressed, the CRC verdict that gates the decode, the statuses — with ONE synchronisation
+ * at the end. Argument errors as for the old call, plus PBSGPU_E_INVALID with F_ZSTD for a blob or an entry of 4 GiB or more. */
+#define PBSGPU_DECODE_F_DIGEST 1u
+#define PBSGPU_DECODE_F_ZSTD 2u
+#define PBSGPU_BLOB_BAD_DATA 6 /* pbsgpu_blob_decode2_device only: a compressed blob whose frame is malformed or unsupported */
+typedef struct pbsgpu_decode_stats2 {
+    uint64_t count[8];       /* index entries per status (PBSGPU_BLOB_*, BAD_DATA included) */
+    uint64_t blob_bytes;     /* as pbsgpu_decode_stats */
+    uint64_t crc_bytes;
+    uint64_t sha_bytes;      /* with F_ZSTD also the decoded bytes hashed, once per distinct blob */
+    uint64_t out_bytes;
+    uint64_t zstd_in_bytes;  /* frame bytes handed to the decoder: once per distinct compressed blob with a good CRC */
+    uint64_t zstd_out_bytes; /* bytes those frames decoded to (status OK) */
+} pbsgpu_decode_stats2;
+int pbsgpu_blob_decode2_device(pbsgpu_engine *eng, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                               uint64_t range_start, uint64_t range_end, uint32_t flags, void *dst, uint64_t dst_cap,
+                               uint8_t *status /* nidx */, pbsgpu_decode_stats2 *stats /* may be NULL */);
+
 /* ---- classify and frame in one device-side call --------------------------------------------------------------------
  * The middle of the incremental writer's loop — known-chunk check, then upload framing of what is new (SURVEY.md §3A;
  * the upload of commit_orchestrate.go:137-158 behind the known-chunk check, refs of commit_reuse.go:315-341 being known by

@@ -279,6 +279,53 @@ inline Result<Decoded> Decode(pbsgpu_engine *eng, const void *blobsDev, uint64_t
     return r;
 }
 
+struct Decoded2 {
+    std::vector<uint8_t> status;  // PBSGPU_BLOB_* per index entry, PBSGPU_BLOB_BAD_DATA included
+    pbsgpu_decode_stats2 stats{};
+};
+
+// Decode with the zstd-compressed blobs decoded on the device (zstd = true: PBSGPU_DECODE_F_ZSTD): the restore loop of a
+// datastore the stock client wrote (internal/server/backup/command.go). BlobCRCOnly then means encrypted only.
+inline Result<Decoded2> Decode2(pbsgpu_engine *eng, const void *blobsDev, uint64_t nbytes,
+                                const std::vector<pbsgpu_segment> &blobs, const std::vector<pbsgpu_record> &idx,
+                                const std::vector<uint32_t> &blobOf, uint64_t rangeStart, uint64_t rangeEnd, bool checkDigest,
+                                bool zstd, void *dst, uint64_t dstCap) {
+    Result<Decoded2> r;
+    r.value.status.resize(idx.size() + 1);
+    const uint32_t flags = (checkDigest ? PBSGPU_DECODE_F_DIGEST : 0u) | (zstd ? PBSGPU_DECODE_F_ZSTD : 0u);
+    const int st = pbsgpu_blob_decode2_device(eng, blobsDev, nbytes, blobs.data(), (uint32_t)blobs.size(), idx.data(),
+                                              idx.size(), blobOf.empty() ? nullptr : blobOf.data(), rangeStart, rangeEnd,
+                                              flags, dst, dstCap, r.value.status.data(), &r.value.stats);
+    r.value.status.resize(idx.size());
+    if (st != PBSGPU_OK) r.err = errorf("blob decode2", st);
+    return r;
+}
+
+struct ZstdDecoded {
+    std::vector<uint8_t> status;    // PBSGPU_ZSTD_* per frame
+    std::vector<uint64_t> decoded;  // bytes produced per frame (0 unless OK)
+};
+
+// many zstd frames of a device buffer into device buffer dst in one launch: frame i to dst + out[i].offset, which has
+// out[i].length bytes of room (the chunks internal/server/backup/command.go's client stores compressed). A frame whose
+// status is not PBSGPU_ZSTD_OK leaves unspecified bytes in its own room and nothing anywhere else.
+inline Result<ZstdDecoded> DecodeZstd(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const std::vector<pbsgpu_segment> &frames,
+                                      const std::vector<pbsgpu_segment> &out, void *dst, uint64_t dstCap) {
+    Result<ZstdDecoded> r;
+    if (out.size() != frames.size()) {
+        r.err = errorf("zstd decode", PBSGPU_E_INVALID);
+        return r;
+    }
+    r.value.status.resize(frames.size() + 1);
+    r.value.decoded.resize(frames.size() + 1);
+    const int st = pbsgpu_zstd_decode_device(eng, src, nbytes, frames.data(), (uint32_t)frames.size(), out.data(), dst, dstCap,
+                                             r.value.status.data(), r.value.decoded.data());
+    r.value.status.resize(frames.size());
+    r.value.decoded.resize(frames.size());
+    if (st != PBSGPU_OK) r.err = errorf("zstd decode", st);
+    return r;
+}
+
 }  // namespace blob
 
 // datastore.DynamicIndexReader

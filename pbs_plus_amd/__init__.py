@@ -13,13 +13,14 @@ pbs-plus reference uses for its pxar stream path:
 * ``KnownChunks`` — the device-resident known-chunk set of an incremental session (which chunks to upload)
 * ``Engine.crc32_many`` / ``blob_encode`` / ``blob_verify`` — data-blob framing of the uploads and the chunk check
   (``chunk_ranges`` turns records into the byte ranges of their chunks)
+* ``Engine.zstd_decode`` / ``zstd_frame_info`` — the zstd frames behind the compressed blobs, decoded on the device
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
 from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
 from .engine import Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
-from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine  # noqa: F401
+from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine, zstd_frame_info  # noqa: F401
 
 __all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError",
-           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine"]
+           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine", "zstd_frame_info"]

@@ -139,6 +139,20 @@ BLOB_OK, BLOB_BAD_MAGIC, BLOB_BAD_CRC, BLOB_BAD_SIZE, BLOB_BAD_DIGEST, BLOB_CRC_
 BLOB_STATUS_NAMES = ("ok", "bad_magic", "bad_crc", "bad_size", "bad_digest", "crc_only")
 
 
+BLOB_BAD_DATA = 6  # blob_decode2 only
+BLOB_STATUS_NAMES2 = BLOB_STATUS_NAMES + ("bad_data",)
+DECODE_F_DIGEST, DECODE_F_ZSTD = 1, 2
+
+
+class DecodeStats2(C.Structure):
+    _fields_ = [("count", C.c_uint64 * 8), ("blob_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("sha_bytes", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("zstd_in_bytes", C.c_uint64), ("zstd_out_bytes", C.c_uint64)]
+
+
+ZSTD_OK, ZSTD_BAD_FRAME, ZSTD_BAD_SIZE, ZSTD_UNSUPPORTED = range(4)
+ZSTD_STATUS_NAMES = ("ok", "bad_frame", "bad_size", "unsupported")
+
+
 class BlobStats(C.Structure):
     _fields_ = [("count", C.c_uint64 * 6), ("blob_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("sha_bytes", C.c_uint64)]
 
@@ -248,6 +262,10 @@ SYMBOLS = {
     "pbsgpu_blob_verify_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, _P, C.POINTER(BlobStats)]),
     "pbsgpu_blob_decode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
                                             C.c_int, _P, C.c_uint64, _P, C.POINTER(DecodeStats)]),
+    "pbsgpu_blob_decode2_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
+                                             C.c_uint32, _P, C.c_uint64, _P, C.POINTER(DecodeStats2)]),
+    "pbsgpu_zstd_frame_info": (C.c_int, [_P, C.c_uint64, _U64P, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "pbsgpu_zstd_decode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
     "pbsgpu_ring_upload_new_device": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P, _U64P,
                                                 C.POINTER(DedupStats)]),
     "pbsgpu_known_upload_new_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P,

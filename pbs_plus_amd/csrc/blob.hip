@@ -1119,13 +1119,18 @@ static_assert(magic_words_match(), "kDecMagic is kMagic in little-endian words")
 //   order            what goes back in one transfer: info[nu] | status[nidx]
 int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
                 const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re,
-                int check_digest, void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats *stats) {
+                uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats2 *stats) {
+    const int check_digest = (flags & PBSGPU_DECODE_F_DIGEST) != 0;
+    const bool zstd = (flags & PBSGPU_DECODE_F_ZSTD) != 0;
     if (!e || nidx >= (1ull << 32)) return PBSGPU_E_INVALID;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (nidx == 0) return PBSGPU_OK;
     if (!idx || !status || !blobs || nblob == 0 || (!bptr && nbytes)) return PBSGPU_E_INVALID;
     if (!blob_of && nblob != nidx) return PBSGPU_E_INVALID;
     if (!ranges_ok(blobs, nblob, nbytes)) return PBSGPU_E_INVALID;
+    if (zstd)  // the frame decoder counts in 32 bits (a chunk is 16 MiB at the most)
+        for (uint32_t b = 0; b < nblob; ++b)
+            if (blobs[b].length >> 32) return PBSGPU_E_INVALID;
     for (uint64_t i = 0; i < nidx; ++i) {
         if (blob_of && blob_of[i] >= nblob) return PBSGPU_E_INVALID;
         if (idx[i].size > idx[i].end || (i && idx[i].end - idx[i].size != idx[i - 1].end)) return PBSGPU_E_INVALID;
@@ -1189,7 +1194,9 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
     fill_owners(pbase, reinterpret_cast<uint32_t *>(tabs.data() + o_pseg));
     AuxLease lease(e);
     Slot *s = lease.s;
-    const size_t out_bytes = (size_t)nu * sizeof(DecInfo) + (size_t)nidx;
+    // back in one transfer: info[nu] | status[nidx] | (zstd: padding to 8, then the frames' results[nu])
+    const size_t o_zres = ((size_t)nu * sizeof(DecInfo) + (size_t)nidx + 7) & ~(size_t)7;
+    const size_t out_bytes = zstd ? o_zres + (size_t)nu * 8 : (size_t)nu * sizeof(DecInfo) + (size_t)nidx;
     CHK(s->sugg.ensure(tabs.size() + 64));
     CHK(s->dense.ensure((size_t)np * 4 + 64));
     CHK(s->seg_cnt.ensure((size_t)nu * 4 + 64));
@@ -1241,6 +1248,82 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
                                             (int)e->opt.sha_form, s->stream));
     hipLaunchKernelGGL(pbsk::crc::k_dec_status, dim3((unsigned)((nidx + 255) / 256)), dim3(256), 0, s->stream, pl);
     HIPCHK(hipGetLastError());
+    if (zstd) {
+        // The zstd leg (zstd.hip), behind the statuses above on the same stream. Which blobs are compressed is known only on
+        // the device, so EVERY distinct blob gets a room planned: straight in dst when its first entry inside the range lies
+        // wholly inside it and no entry naming the blob is larger, else in scratch with the largest entry's size.
+        namespace pz = pbsk::zstd;
+        std::vector<uint32_t> zmax(nu, 0);
+        for (uint64_t i = 0; i < nidx; ++i) zmax[ents[i].u] = std::max(zmax[ents[i].u], ents[i].size);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(nu, (uint64_t)e->num_cus * 4);
+        const uintptr_t d0 = (uintptr_t)dst;
+        std::vector<pz::RestoreJob> jobs(nu);
+        std::vector<pz::RestoreCopy> zc;
+        uint64_t sc = (uint64_t)grid * pz::kLitBytes, zblocks = 0, zlongest = 1;  // scratch behind the literal buffers
+        std::vector<uint64_t> scratch_at(nu, ~0ull);
+        for (uint32_t u = 0; u < nu; ++u) {
+            const DecStore &ps = prim[u];
+            const bool direct = ps.xlo < ps.xhi && ps.xlo == 0 && ps.xhi == ps.size && ps.size == zmax[u];
+            if (!direct) {
+                scratch_at[u] = sc;
+                sc += ((uint64_t)zmax[u] + 15) & ~15ull;
+            }
+            jobs[u].room = zmax[u];
+            const uint64_t blocks = ((uint64_t)zmax[u] + 8) / 64 + 1;
+            zblocks += blocks;
+            zlongest = std::max(zlongest, blocks);
+        }
+        CHK(s->data.ensure((size_t)sc + 64));
+        const uintptr_t sbase = (uintptr_t)s->data.p;
+        uint32_t lng = 0;
+        auto add_copy = [&](const DecStore &c) {
+            zc.push_back(pz::RestoreCopy{jobs[c.u].place + c.xlo, (uint64_t)c.dofs + c.xlo, (uint32_t)(c.xhi - c.xlo), c.size, c.u, 0});
+            lng = std::max(lng, (uint32_t)(c.xhi - c.xlo));
+        };
+        for (uint32_t u = 0; u < nu; ++u) {
+            jobs[u].place = scratch_at[u] == ~0ull ? (uint64_t)prim[u].dofs : (uint64_t)(sbase + scratch_at[u] - d0);
+            if (scratch_at[u] != ~0ull && prim[u].xlo < prim[u].xhi) add_copy(prim[u]);
+        }
+        for (const DecStore &c : copies) add_copy(c);
+        const size_t o_zc = (size_t)nu * sizeof(pz::RestoreJob);
+        std::vector<uint8_t> ztab(o_zc + zc.size() * sizeof(pz::RestoreCopy));
+        std::memcpy(ztab.data(), jobs.data(), o_zc);
+        if (!zc.empty()) std::memcpy(ztab.data() + o_zc, zc.data(), zc.size() * sizeof(pz::RestoreCopy));
+        // tile_slots: sha ranges[nu] | digests[32 nu] | the hash queue's counter (64 bytes) | the frame descriptors[nu]
+        const size_t o_zdig = (size_t)nu * sizeof(pbsgpu_segment), o_zq = o_zdig + (size_t)nu * 32, o_zdesc = o_zq + 64;
+        CHK(s->seg_off.ensure(ztab.size() + 64));
+        CHK(s->tile_slots.ensure(o_zdesc + (size_t)nu * pz::kDescBytes + 64));
+        CHK(staged_h2d(*s, s->seg_off.p, ztab.data(), ztab.size(), s->stream));
+        pz::RestorePlan zp{};
+        zp.src = d;
+        zp.blobs = pl.blobs;
+        zp.info = reinterpret_cast<const uint32_t *>(pl.info);
+        zp.crcs = pl.crcs;
+        zp.jobs = s->seg_off.as<pz::RestoreJob>();
+        zp.copies = reinterpret_cast<const pz::RestoreCopy *>(s->seg_off.as<uint8_t>() + o_zc);
+        zp.ents = reinterpret_cast<const uint32_t *>(pl.ents);
+        zp.recs = pl.recs;
+        zp.digs = s->tile_slots.as<uint8_t>() + o_zdig;
+        zp.res = reinterpret_cast<uint64_t *>(s->order.as<uint8_t>() + o_zres);
+        zp.sha = s->tile_slots.as<pbsgpu_segment>();
+        zp.status = pl.status;
+        zp.dst = static_cast<uint8_t *>(dst);
+        zp.lit = s->data.as<uint8_t>();
+        zp.nu = nu;
+        zp.ncopy = (uint32_t)zc.size();
+        zp.nidx = (uint32_t)nidx;
+        zp.stride = grid;
+        HIPCHK(pz::launch_restore_frames(zp, s->tile_slots.as<uint8_t>() + o_zdesc, s->stream));
+        if (zp.ncopy) HIPCHK(pz::launch_restore_copy(zp, lng, e->num_cus, s->stream));
+        if (check_digest) {
+            uint32_t *zq = reinterpret_cast<uint32_t *>(s->tile_slots.as<uint8_t>() + o_zq);
+            HIPCHK(hipMemsetAsync(zq, 0, 64, s->stream));
+            HIPCHK(pbsk::launch_sha256_segments(zp.dst, zp.sha, nu, s->tile_slots.as<uint8_t>() + o_zdig, zq, e->num_cus,
+                                                pbsk::sha256_dense_pays(zblocks, zlongest, e->num_cus, e->opt.sha_dense_pct),
+                                                (int)e->opt.sha_form, s->stream));
+        }
+        HIPCHK(pz::launch_restore_status(zp, s->stream));
+    }
     std::vector<uint8_t> back(out_bytes);
     CHK(fetch_result(s, back.data(), s->order.p, out_bytes));  // the call's one synchronisation
     std::memcpy(status, back.data() + (size_t)nu * sizeof(DecInfo), (size_t)nidx);
@@ -1257,6 +1340,18 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
             const uint32_t u = ents[i].u;
             if (info[u].hk == PBSGPU_BLOB_HEADER_SIZE && ub[u].length - PBSGPU_BLOB_HEADER_SIZE == ents[i].size)
                 stats->out_bytes += clip[i];
+        }
+        if (zstd) {
+            const uint64_t *zres = reinterpret_cast<const uint64_t *>(back.data() + o_zres);
+            for (uint32_t u = 0; u < nu; ++u) {
+                if ((uint32_t)(zres[u] >> 32) == pbsk::zstd::kNotDecoded) continue;
+                stats->zstd_in_bytes += ub[u].length - PBSGPU_BLOB_HEADER_SIZE;
+                if ((zres[u] >> 32) != PBSGPU_ZSTD_OK) continue;
+                stats->zstd_out_bytes += (uint32_t)zres[u];
+                if (check_digest) stats->sha_bytes += (uint32_t)zres[u];
+            }
+            for (uint64_t i = 0; i < nidx; ++i)
+                if (zres[ents[i].u] == (uint64_t)ents[i].size) stats->out_bytes += clip[i];  // status OK, the entry's size
         }
     }
     return PBSGPU_OK;
@@ -1574,8 +1669,26 @@ int pbsgpu_blob_decode_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_t
                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
                               uint64_t range_start, uint64_t range_end, int check_digest, void *dst, uint64_t dst_cap,
                               uint8_t *status, pbsgpu_decode_stats *stats) {
-    return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, check_digest, dst,
-                       dst_cap, status, stats);
+    pbsgpu_decode_stats2 st2{};
+    const int r = blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end,
+                              check_digest ? PBSGPU_DECODE_F_DIGEST : 0u, dst, dst_cap, status, &st2);
+    if (stats && e && nidx < (1ull << 32)) {  // (past those two checks the statistics are cleared first, as they always were)
+        for (int k = 0; k < PBSGPU_BLOB_NSTATUS; ++k) stats->count[k] = st2.count[k];
+        stats->blob_bytes = st2.blob_bytes;
+        stats->crc_bytes = st2.crc_bytes;
+        stats->sha_bytes = st2.sha_bytes;
+        stats->out_bytes = st2.out_bytes;
+    }
+    return r;
+}
+
+int pbsgpu_blob_decode2_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                               uint64_t range_start, uint64_t range_end, uint32_t flags, void *dst, uint64_t dst_cap,
+                               uint8_t *status, pbsgpu_decode_stats2 *stats) {
+    if (flags & ~(PBSGPU_DECODE_F_DIGEST | PBSGPU_DECODE_F_ZSTD)) return PBSGPU_E_INVALID;
+    return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, flags, dst, dst_cap,
+                       status, stats);
 }
 
 int pbsgpu_known_upload_new_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,

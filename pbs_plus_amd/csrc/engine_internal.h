@@ -295,6 +295,44 @@ int candidates_sync(pbsgpu_engine *e, Slot &s, const uint8_t *dptr, uint64_t nby
 // write; PBSGPU_COPY_THREADS, default 4 incl. the caller, 1 = off). Small writes stay on the caller's thread.
 void parallel_memcpy(void *dst, const void *src, size_t n);
 
+}  // namespace pbse
+// zstd.hip: the zstd leg of pbsgpu_blob_decode2_device. blob.hip plans it on the host and enqueues these three behind its
+// own restore kernels, on the same stream. Every place is an offset from `dst` (64-bit, wrapping: scratch lies elsewhere).
+namespace pbsk {
+namespace zstd {
+struct RestoreJob {   // one distinct blob: the room its frame is decoded into if it turns out compressed with a good CRC
+    uint64_t place;
+    uint32_t room, pad;
+};
+struct RestoreCopy {  // `len` bytes from `from` to `to` when blob u decoded to exactly `size` bytes
+    uint64_t from, to;
+    uint32_t len, size, u, pad;
+};
+struct RestorePlan {
+    const uint8_t *src;
+    const pbsgpu_segment *blobs;  // nu
+    const uint32_t *info, *crcs;  // blob.hip's DecInfo (two words each) and the computed CRCs
+    const RestoreJob *jobs;       // nu
+    const RestoreCopy *copies;    // ncopy
+    const uint32_t *ents;         // nidx: blob, size
+    const uint8_t *recs;          // nidx records (nullptr: digests not checked)
+    const uint8_t *digs;          // nu * 32: SHA-256 of the decoded bytes
+    uint64_t *res;                // nu: zstd status << 32 | bytes decoded; kNotDecoded << 32 for every other blob
+    pbsgpu_segment *sha;          // nu: what launch_sha256_segments hashes, relative to dst
+    uint8_t *status;              // nidx: blob.hip's statuses, rewritten for the decoded blobs
+    uint8_t *dst, *lit;
+    uint32_t nu, ncopy, nidx, stride;
+};
+constexpr uint32_t kNotDecoded = 0xffu;
+constexpr size_t kLitBytes = 128u << 10;  // literal scratch per workgroup of launch_restore_frames
+constexpr size_t kDescBytes = 32;         // per distinct blob, device scratch handed to launch_restore_frames
+hipError_t launch_restore_frames(const RestorePlan &pl, void *desc /* nu * kDescBytes */, hipStream_t st);  // pl.stride workgroups
+hipError_t launch_restore_copy(const RestorePlan &pl, uint32_t longest, int num_cus, hipStream_t st);
+hipError_t launch_restore_status(const RestorePlan &pl, hipStream_t st);
+}  // namespace zstd
+}  // namespace pbsk
+namespace pbse {
+
 // stream contexts parked in pbsgpu_engine::stream_pool (stream.cpp): really free them (engine teardown, trim)
 void stream_pool_release(pbsgpu_engine *e);
 

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "../../include/pbsgpu.h"
+#include "zstd_decode.h"
 
 namespace {
 
@@ -122,6 +123,18 @@ int pbsgpu_didx_decode(const uint8_t *in, uint64_t nbytes, pbsgpu_record *out, u
         prev = end;
     }
     return PBSGPU_OK;
+}
+
+int pbsgpu_zstd_frame_info(const uint8_t *frame, uint64_t nbytes, uint64_t *content_size, uint64_t *window_size,
+                           uint32_t *header_bytes, int *has_checksum) {
+    if (!frame && nbytes) return PBSGPU_E_INVALID;
+    pbsz::FrameHeader h;
+    const int st = pbsz::parse_frame_header(frame, nbytes, h);
+    if (content_size) *content_size = h.content_size;
+    if (window_size) *window_size = h.window_size;
+    if (header_bytes) *header_bytes = h.header_bytes;
+    if (has_checksum) *has_checksum = (int)h.has_checksum;
+    return st;
 }
 
 int pbsgpu_payload_format_default(pbsgpu_payload_format *out) {

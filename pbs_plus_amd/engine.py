@@ -337,6 +337,90 @@ class Engine:
                      out_bytes=int(st.out_bytes))
         return dst, status[:n], stats
 
+    def blob_decode2(self, data, blobs, idx, blob_of=None, start=None, end=None, check_digest=True, dst=None,
+                     nbytes: int | None = None, zstd=True):
+        """blob_decode() with the zstd-compressed blobs decoded on the device (pbsgpu_blob_decode2_device): with zstd=True a
+        compressed blob whose CRC is good is decoded to its entries' places, checked for the entry's size and, with
+        check_digest, for the SHA-256 of the DECODED bytes; status 6 (bad_data) is a malformed or unsupported frame, and 5
+        (crc_only) then means encrypted only. zstd=False gives blob_decode()'s outputs exactly. The stats dict has a count
+        per status name ("bad_data" included) and zstd_in_bytes / zstd_out_bytes beside blob_decode()'s byte counts."""
+        recs = np.ascontiguousarray(idx, dtype=RECORD_DTYPE).reshape(-1)
+        n = int(recs.size)
+        segs, nblob = _segs(blobs)
+        bp, bn = self._dev(data, nbytes)
+        assert bp is not None, "blob_decode2() wants device memory"
+        bo = None if blob_of is None else np.ascontiguousarray(blob_of, dtype=np.uint32).reshape(-1)
+        assert bo is None or bo.size == n
+        if start is None:
+            start = int(recs["end"][0]) - int(recs["size"][0]) if n else 0
+        if end is None:
+            end = int(recs["end"][-1]) if n else start
+        own = dst is None
+        if own:
+            dst = self.alloc(max(int(end) - int(start), 16))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        st = _lib.DecodeStats2()
+        flags = (_lib.DECODE_F_DIGEST if check_digest else 0) | (_lib.DECODE_F_ZSTD if zstd else 0)
+        try:
+            check(self._L.pbsgpu_blob_decode2_device(self._h, bp, bn, segs, nblob, recs.ctypes.data if n else None, n,
+                                                     bo.ctypes.data if bo is not None and n else None, int(start), int(end),
+                                                     flags, dst.ptr, dst.nbytes, status.ctypes.data, C.byref(st)),
+                  "blob_decode2_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        stats = {name: int(st.count[k]) for k, name in enumerate(_lib.BLOB_STATUS_NAMES2)}
+        stats.update(blob_bytes=int(st.blob_bytes), crc_bytes=int(st.crc_bytes), sha_bytes=int(st.sha_bytes),
+                     out_bytes=int(st.out_bytes), zstd_in_bytes=int(st.zstd_in_bytes), zstd_out_bytes=int(st.zstd_out_bytes))
+        return dst, status[:n], stats
+
+    def zstd_decode(self, data, frames, out=None, dst=None, nbytes: int | None = None):
+        """Decode the zstd frames [(offset, length)] of the device buffer `data` in one launch (pbsgpu_zstd_decode_device):
+        frame i goes to dst at out[i] = (offset, room). out None lays the frames out back to back by the content size
+        their headers declare (read back from the device; a frame that declares none is a ValueError); dst None allocates
+        what `out` needs. Returns (dst, status per frame: 0 ok, 1 bad frame, 2 bad size, 3 unsupported, bytes decoded per
+        frame, out as an (n, 2) array). On a status other than 0 the frame's own room holds unspecified bytes."""
+        dp, dn = self._dev(data, nbytes)
+        assert dp is not None, "zstd_decode() wants device memory"
+        fr = np.ascontiguousarray(frames, dtype=np.uint64).reshape(-1, 2)
+        n = int(fr.shape[0])
+        if out is None:
+            rooms = np.zeros(n, dtype=np.uint64)
+            if n:  # the first 18 bytes of every frame (the longest header), gathered on the device and read back in one copy
+                take = np.minimum(fr[:, 1], 18)
+                items = np.stack([fr[:, 0], np.arange(n, dtype=np.uint64) * 18, take], axis=1)
+                heads = self.alloc(18 * n)
+                try:
+                    check(self._L.pbsgpu_gather_device(self._h, dp, dn, heads.ptr, heads.nbytes, items.ctypes.data, n),
+                          "gather_device")
+                    host = heads.download()
+                finally:
+                    heads.free()
+            for i in range(n):
+                info = zstd_frame_info(host[18 * i:18 * i + int(take[i])])
+                if info["status"] == 0 and info["content_size"] is None:
+                    raise ValueError(f"frame {i} declares no content size: pass out=")
+                rooms[i] = info["content_size"] if info["status"] == 0 else 0
+            ends = np.cumsum(rooms)
+            out = np.stack([ends - rooms, rooms], axis=1)
+        oa = np.ascontiguousarray(out, dtype=np.uint64).reshape(-1, 2)
+        assert oa.shape[0] == n, "one (offset, room) per frame"
+        own = dst is None
+        if own:
+            dst = self.alloc(max(int((oa[:, 0] + oa[:, 1]).max()) if n else 0, 16))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        decoded = np.zeros(max(n, 1), dtype=np.uint64)
+        try:
+            check(self._L.pbsgpu_zstd_decode_device(self._h, dp, dn, fr.ctypes.data if n else None, n, oa.ctypes.data if n else None,
+                                                    dst.ptr, dst.nbytes, status.ctypes.data, decoded.ctypes.data),
+                  "zstd_decode_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return dst, status[:n], decoded[:n], oa
+
     # ---- payload-stream assembly (.ppxar layout: markers + 16-byte headers + file bodies) ----------
     def payload_pack(self, src, files, dst, with_start: bool = True, with_tail: bool = True):
         """Lay the file bodies `files` = [(offset, length)] of device buffer `src` out as the pxar
@@ -412,6 +496,19 @@ def blob_magic(kind: int) -> bytes:
     out = (C.c_uint8 * 8)()
     check(_lib.lib().pbsgpu_blob_magic(int(kind), out), "blob_magic")
     return bytes(out)
+
+
+def zstd_frame_info(frame) -> dict:
+    """What the header of one zstd frame declares (pbsgpu_zstd_frame_info, host only): status (0 ok, 1 bad frame,
+    3 unsupported), content_size (None when the frame declares none), window_size, header_bytes, has_checksum."""
+    a = _host_view(frame)
+    size, window, hb, ck = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_int()
+    st = _lib.lib().pbsgpu_zstd_frame_info(a.ctypes.data if a.size else None, a.size, C.byref(size), C.byref(window), C.byref(hb),
+                                           C.byref(ck))
+    if st < 0:
+        raise _lib.PbsGpuError(st, "zstd_frame_info")
+    return {"status": st, "content_size": None if size.value == (1 << 64) - 1 else size.value, "window_size": window.value,
+            "header_bytes": hb.value, "has_checksum": bool(ck.value)}
 
 
 def blob_index(blob_digests, idx) -> np.ndarray:

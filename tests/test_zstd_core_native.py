@@ -1,0 +1,193 @@
+"""The zstd format core (pbs_plus_amd/csrc/zstd_decode.h) as a CPU program under AddressSanitizer + UBSan: a stand-alone
+program with its own main (tests/native/test_zstd_core.cpp), nothing loaded into Python, nothing preloaded. It decodes
+every fixture of tests/golden/zstd_v1*.npz bit-exact, reports which format branches the fixtures reach, and takes every
+fixture frame through truncations, 2 000 seeded single-byte mutations and a room one byte too small: a malformed frame
+must never read or write out of bounds on a shared GPU, and this build of the same header is where that is checked.
+Where libzstd loads, every mutated frame it decodes must decode to the same bytes here."""
+import hashlib
+import json
+import os
+import struct
+import subprocess
+import sys
+import zlib
+
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import zstd_inputs  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NPROC = 4
+
+# one bit per format branch, in the order of the enum in zstd_decode.h
+BRANCHES = ("single_segment window_descriptor fcs_1 fcs_2 fcs_4 fcs_8 fcs_absent checksum no_checksum "
+            "block_raw block_rle block_compressed many_blocks empty_last_block "
+            "lit_raw_1 lit_raw_2 lit_raw_3 lit_rle_1 lit_rle_2 lit_rle_3 "
+            "huf_1stream huf_4stream_3 huf_4stream_4 huf_4stream_5 huf_treeless weights_direct weights_fse "
+            "nseq_0 nseq_1 nseq_2 nseq_3 ll_predef ll_rle ll_fse ll_repeat of_predef of_rle of_fse of_repeat "
+            "ml_predef ml_rle ml_fse ml_repeat rep_1 rep_2 rep_3 rep_shifted rep_1_minus_1 "
+            "match_overlap match_offset_1 match_across_blocks").split()
+# branches that neither libzstd 1.4.8 nor a hand-assembled frame reaches: at most two, each explained in DESIGN.md §15
+UNREACHED = ()
+
+
+@pytest.fixture(scope="module")
+def run(tmp_path_factory):
+    """builds and runs the program once: (golden module, cases, stdout, result lines)"""
+    tmp = tmp_path_factory.mktemp("zstd_core")
+    g = zstd_inputs.golden()
+    cases = zstd_inputs.cases()
+    assert len(cases) >= 30
+    path = str(tmp / "cases.bin")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", len(cases)))
+        for c in cases:
+            data = c["content"]
+            name = c["name"].encode()
+            f.write(struct.pack("<I", len(name)) + name + struct.pack("<BQ", c["status"], len(c["frame"])) + c["frame"])
+            f.write(struct.pack("<Q", len(data)) + data)
+    exe, res = str(tmp / "test_zstd_core"), str(tmp / "results.txt")
+    flags = ["-std=c++17", "-g", "-O2", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+             "-Wall", "-Wextra"]
+    subprocess.run(["g++", *flags, os.path.join(ROOT, "tests", "native", "test_zstd_core.cpp"), "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1")
+    procs = [subprocess.Popen([exe, path, "%s.%d" % (res, k), str(NPROC), str(k)], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                              text=True, env=env) for k in range(NPROC)]  # the cases k, k + NPROC, ... each: this is CPU work
+    outs, lines = [], []
+    for k, p in enumerate(procs):
+        so, se = p.communicate(timeout=900)
+        outs.append((p.returncode, so, se))
+        if os.path.exists("%s.%d" % (res, k)):
+            lines += [ln.split() for ln in open("%s.%d" % (res, k))]
+    return g, cases, outs, lines
+
+
+def test_every_fixture_decodes_bit_exact_and_no_mutation_escapes(run):
+    g, cases, outs, lines = run
+    for code, so, se in outs:
+        assert code == 0 and "zstd-core-ok" in so, so[-4000:] + se[-4000:]
+        assert "runtime error" not in se and "AddressSanitizer" not in se
+    per_case = {}
+    for ci, kind, *_ in lines:
+        per_case.setdefault(int(ci), {}).setdefault(kind, 0)
+        per_case[int(ci)][kind] += 1
+    for ci, c in enumerate(cases):
+        n = len(c["frame"])
+        assert per_case[ci]["fixture"] == 1
+        assert per_case[ci]["cut"] == min(65, n) + 97 and per_case[ci]["mut"] == 2000, c["name"]
+        assert per_case[ci].get("small", 0) == (1 if c["status"] == 0 and c["length"] else 0)
+    # the fixtures are what the generator says they are
+    for c in cases:
+        assert hashlib.sha256(c["content"]).digest() == c["sha256"], c["name"]
+    # the mutated and the truncated frames of tests/test_gpu_zstd.py went through this run, with the outcome recorded for them
+    names = [c["name"] for c in cases]
+    for name, at, xor, status, decoded, crc in zstd_inputs.MUTATIONS:
+        ci = names.index(name)
+        js = [j for j in range(2000) if zstd_inputs.mutation(ci, j, len(cases[ci]["frame"])) == (at, xor)]
+        assert js, (name, at, xor)
+        row = [ln for ln in lines if ln[:3] == [str(ci), "mut", str(js[0])]]
+        assert row and [int(v) for v in row[0][3:6]] == [status, decoded, crc], (name, at, xor, row)
+    for name, length, status in zstd_inputs.CUTS:
+        row = [ln for ln in lines if ln[:3] == [str(names.index(name)), "cut", str(length)]]
+        assert row and int(row[0][3]) == status, (name, length, row)
+
+
+def test_the_fixtures_reach_every_format_branch(run):
+    g, cases, outs, lines = run
+    cov = 0
+    for code, so, se in outs:
+        word = [w for w in so.split() if w.startswith("0x")]
+        assert word and "of %d bits" % len(BRANCHES) in so, so[-2000:]
+        cov |= int(word[0], 16)
+    missing = [b for i, b in enumerate(BRANCHES) if not cov >> i & 1]
+    print("coverage", hex(cov), "missing", missing)
+    assert len(UNREACHED) <= 2
+    assert sorted(missing) == sorted(UNREACHED)
+
+
+RECORDED = os.path.join(ROOT, "tests", "golden", "zstd_v1_refused_here.json")
+
+
+def _against_libzstd(run):
+    """every truncated or mutated frame of the run through ZSTD_decompress: (compared, accepted there, frames accepted
+    there that are not OK with the same bytes here as a sorted list of [case, kind, parameter, status here], frames that
+    are OK here and an error there for the checksum alone, all frames that are OK here and an error there); None when
+    libzstd does not load"""
+    g, cases, outs, lines = run
+    z = g.load_libzstd()
+    if z is None:
+        return None
+    compared = accepted = checksum_only = ok_here_only = 0
+    differ = []
+    for ci, kind, param, status, decoded, crc in lines:
+        ci, param, status, decoded, crc = int(ci), int(param), int(status), int(decoded), int(crc)
+        c = cases[ci]
+        frame = c["frame"]
+        n = len(frame)
+        at = -1
+        if kind == "cut":
+            if param == 0:
+                continue  # no bytes at all: zero frames and no error for libzstd, no frame and BAD_FRAME here
+            frame = frame[:param]
+        elif kind == "mut":
+            at, xor = zstd_inputs.mutation(ci, param, n)
+            frame = zstd_inputs.mutated(frame, at, xor)
+        else:
+            continue
+        room = c["length"] if c["status"] == 0 else 64 << 10
+        got, err = g.decompress(z, frame, room)
+        compared += 1
+        if got is None:
+            if status == 0:
+                ok_here_only += 1
+                if c["info"][4] and at >= n - 4:
+                    checksum_only += 1
+            continue
+        if c["name"] in ("bad-skippable-frame", "bad-two-frames"):
+            continue  # libzstd skips the one and concatenates the other: UNSUPPORTED here, by decision
+        accepted += 1
+        if status != 0 or decoded != len(got) or crc != zlib.crc32(got):
+            differ.append([c["name"], kind, param, status])
+    return compared, accepted, sorted(differ), checksum_only, ok_here_only
+
+
+def test_what_libzstd_decodes_decodes_the_same_here(run):
+    """Every truncated or mutated frame that libzstd decodes without error is OK here with the same bytes. The converse is
+    not asked: libzstd verifies the content checksum and this decoder, by decision, does not, so a mutation inside the
+    four checksum bytes is OK here and an error there.
+
+    One kind of frame libzstd 1.4.8 decodes and this decoder refuses, by the decision in include/pbsgpu.h that reading
+    past either end of a backward bit stream is BAD_FRAME: a stream read past its START. That release tolerates it in two
+    places. Its sequence decoder checks only that the stream is used up when the last sequence is done and reads whatever
+    its 64-bit container holds beyond the start; its double-symbol Huffman decoder lets the last symbol of a stream run
+    past the start and pads with zero bits. RFC 8878 calls both streams corrupted, and later releases refuse the first.
+    Which frames these are is not asked of the decoder under test: tests/golden/zstd_v1_refused_here.json lists them by
+    case and mutation, every one BAD_FRAME here, recorded once (`python tests/test_zstd_core_native.py` rewrites it) and
+    reviewed as a list. The run must refuse exactly those and differ from libzstd nowhere else."""
+    res = _against_libzstd(run)
+    if res is None:
+        print("libzstd does not load on this machine: nothing to compare against")
+        return
+    compared, accepted, differ, checksum_only, ok_here_only = res
+    print("compared", compared, "accepted by libzstd", accepted, "of them refused here", len(differ),
+          "ok here and an error there", ok_here_only, "of them for the checksum alone", checksum_only)
+    recorded = json.load(open(RECORDED))
+    assert all(row[3] == zstd_inputs.BAD_FRAME for row in recorded)
+    assert differ == recorded, ([r for r in differ if r not in recorded][:10], [r for r in recorded if r not in differ][:10])
+    assert compared > 60_000 and accepted > 0
+
+
+if __name__ == "__main__":  # records the list: run where libzstd loads, then review the diff of the file
+    import tempfile
+    from pathlib import Path
+
+    class _Factory:
+        def mktemp(self, name):
+            return Path(tempfile.mkdtemp(prefix=name))
+
+    res = _against_libzstd(run.__wrapped__(_Factory()))
+    print("compared %d, accepted by libzstd %d, refused here %d, ok here only %d (checksum alone %d)" %
+          (res[0], res[1], len(res[2]), res[4], res[3]))
+    with open(RECORDED, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r) for r in res[2]) + "\n]\n")
