@@ -246,6 +246,32 @@ func (e *Engine) DecodeZstd(unsafe.Pointer, uint64, []uint64, []uint64, []uint64
 	return nil, nil, ErrNotBuilt
 }
 
+// ZstdEncodeBound is the length no frame of EncodeZstd for n bytes of content exceeds.
+func ZstdEncodeBound(n uint64) uint64 { return 0 }
+
+func (e *Engine) EncodeZstd(unsafe.Pointer, uint64, []uint64, []uint64, []uint64, []uint64, unsafe.Pointer, uint64) ([]uint8, []uint64, error) {
+	return nil, nil, ErrNotBuilt
+}
+
+// EncodeStats counts what EncodeBlobs2 wrote, per kind (index 0 uncompressed, 1 compressed).
+type EncodeStats struct {
+	Blobs, BlobBytes, ChunkBytes [2]uint64
+	FrameBytes, CRCBytes         uint64
+}
+
+// Encoded2 is what EncodeBlobs2 returns.
+type Encoded2 struct {
+	Offsets []uint64
+	Lens    []uint32
+	Kinds   []uint8
+	CRCs    []uint32
+	Stats   EncodeStats
+}
+
+func (e *Engine) EncodeBlobs2(unsafe.Pointer, uint64, []uint64, []uint64, bool, unsafe.Pointer, uint64) (Encoded2, error) {
+	return Encoded2{}, ErrNotBuilt
+}
+
 // BlobBadData is DecodeBlobs2's status for a compressed blob whose zstd frame is malformed or unsupported.
 const BlobBadData = 6
 

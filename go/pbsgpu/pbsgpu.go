@@ -1482,6 +1482,96 @@ func (e *Engine) DecodeZstd(dptr unsafe.Pointer, nbytes uint64, offsets, lengths
 	return status[:len(segs)], decoded[:len(segs)], nil
 }
 
+// ZstdEncodeBound is the length no frame of EncodeZstd for n bytes of content exceeds (host only).
+func ZstdEncodeBound(n uint64) uint64 { return uint64(C.pbsgpu_zstd_encode_bound(C.uint64_t(n))) }
+
+// EncodeZstd compresses the chunks (offsets, lengths) of a device buffer to one zstd frame each in one call: chunk i goes
+// to dst + outOffsets[i], which has outRooms[i] bytes of room (ZstdEncodeBound(length) always suffices). These are the
+// writers of the reference that compress: the tape converter's local store (internal/tapeio/converter.go:399) and its PBS
+// store and session with Compress set (converter.go:410-435, cmd/bkf2pxar/main.go:33). Returns the status (ZstdOK or
+// ZstdBadSize) and the frame's length per chunk; a chunk whose status is ZstdBadSize leaves unspecified bytes in its own
+// room and nothing anywhere else.
+func (e *Engine) EncodeZstd(dptr unsafe.Pointer, nbytes uint64, offsets, lengths, outOffsets, outRooms []uint64, dst unsafe.Pointer,
+	dstCap uint64) ([]uint8, []uint64, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, nil, err
+	}
+	outs, err := toSegments(outOffsets, outRooms)
+	if err != nil {
+		return nil, nil, err
+	}
+	if len(outs) != len(segs) {
+		return nil, nil, errors.New("pbsgpu: EncodeZstd needs one destination per chunk")
+	}
+	status := make([]uint8, len(segs)+1)
+	frameLen := make([]uint64, len(segs)+1)
+	var sp, op *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp, op = &segs[0], &outs[0]
+	}
+	err = check(C.pbsgpu_zstd_encode_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), op, dst, C.uint64_t(dstCap),
+		(*C.uint8_t)(unsafe.Pointer(&status[0])), (*C.uint64_t)(unsafe.Pointer(&frameLen[0]))), "zstd_encode_device")
+	if err != nil {
+		return nil, nil, err
+	}
+	return status[:len(segs)], frameLen[:len(segs)], nil
+}
+
+// EncodeStats counts what EncodeBlobs2 wrote, per kind (index 0 uncompressed, 1 compressed).
+type EncodeStats struct {
+	Blobs, BlobBytes, ChunkBytes [2]uint64
+	FrameBytes, CRCBytes         uint64
+}
+
+// Encoded2 is what EncodeBlobs2 returns: blob i lies at Offsets[i], in the slot the uncompressed layout gives it, and is
+// Lens[i] long; Kinds[i] is 0 (uncompressed) or 1 (zstd compressed).
+type Encoded2 struct {
+	Offsets []uint64
+	Lens    []uint32
+	Kinds   []uint8
+	CRCs    []uint32
+	Stats   EncodeStats
+}
+
+// EncodeBlobs2 is EncodeBlobsDevice with the blob's kind decided on the device (zstd true): a chunk whose zstd frame is strictly
+// shorter than the chunk becomes a compressed blob, every other one the uncompressed blob EncodeBlobsDevice writes
+// (internal/tapeio/converter.go:399, :410-435). The server takes one chunk per request: send dst + Offsets[i], Lens[i].
+// With zstd false every output is EncodeBlobsDevice's.
+func (e *Engine) EncodeBlobs2(src unsafe.Pointer, srcBytes uint64, offsets, lengths []uint64, zstd bool, dst unsafe.Pointer,
+	dstCap uint64) (Encoded2, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return Encoded2{}, err
+	}
+	n := len(segs)
+	out := Encoded2{Offsets: make([]uint64, n+1), Lens: make([]uint32, n+1), Kinds: make([]uint8, n+1), CRCs: make([]uint32, n+1)}
+	var sp *C.pbsgpu_segment
+	if n > 0 {
+		sp = &segs[0]
+	}
+	flags := C.uint32_t(0)
+	if zstd {
+		flags |= C.PBSGPU_ENCODE_F_ZSTD
+	}
+	var st C.pbsgpu_encode_stats
+	err = check(C.pbsgpu_blob_encode2_device(e.h, src, C.uint64_t(srcBytes), sp, C.uint32_t(n), flags, dst, C.uint64_t(dstCap),
+		(*C.uint64_t)(unsafe.Pointer(&out.Offsets[0])), (*C.uint32_t)(unsafe.Pointer(&out.Lens[0])),
+		(*C.uint8_t)(unsafe.Pointer(&out.Kinds[0])), (*C.uint32_t)(unsafe.Pointer(&out.CRCs[0])), &st), "blob_encode2_device")
+	if err != nil {
+		return Encoded2{}, err
+	}
+	out.Lens, out.Kinds, out.CRCs = out.Lens[:n], out.Kinds[:n], out.CRCs[:n]
+	for k := 0; k < 2; k++ {
+		out.Stats.Blobs[k], out.Stats.BlobBytes[k] = uint64(st.blobs[k]), uint64(st.blob_bytes[k])
+		out.Stats.ChunkBytes[k] = uint64(st.chunk_bytes[k])
+	}
+	out.Stats.FrameBytes, out.Stats.CRCBytes = uint64(st.frame_bytes), uint64(st.crc_bytes)
+	return out, nil
+}
+
 // BlobBadData is DecodeBlobs2's status for a compressed blob whose zstd frame is malformed or unsupported.
 const BlobBadData = 6
 

@@ -769,6 +769,57 @@ int pbsgpu_blob_decode2_device(pbsgpu_engine *eng, const void *blobs_dptr, uint6
                                uint64_t range_start, uint64_t range_end, uint32_t flags, void *dst, uint64_t dst_cap,
                                uint8_t *status /* nidx */, pbsgpu_decode_stats2 *stats /* may be NULL */);
 
+/* ---- zstd frames written on the device ------------------------------------------------------------------------------
+ * The writers of the reference that compress: the tape converter's local store compresses every chunk
+ * (backupproxy.NewLocalStore(storeDir, c.chunkCfg, true), internal/tapeio/converter.go:399), and its PBS store and
+ * session take Compress from the command line (converter.go:410-435; the flag is cmd/bkf2pxar/main.go:33, "useful for
+ * remote PBS"). The commit path does not (commit_orchestrate.go:137-149, compress=false: pbsgpu_blob_encode_device).
+ * The encoder (pbs_plus_amd/csrc/zstd_encode.h, one source for the kernels and for the CPU build that runs under
+ * sanitizers) writes one frame per chunk: single segment, content size declared, no dictionary, no checksum; blocks of
+ * 128 KiB that are independent of one another (no match reaches before its own block, so repeats more than 128 KiB
+ * apart are not found); per block RLE, raw or compressed, whichever applies first; greedy matching with a minimum match
+ * of 4; predefined sequence tables and no repeat offsets; Huffman literals with directly described weights.
+ * DESIGN.md §16 has the decisions and what they cost in ratio. */
+#define PBSGPU_HAS_ZSTD_ENCODE 1
+/* No frame of n bytes of content is longer: the frame header, three bytes per block, the content. Host only. */
+uint64_t pbsgpu_zstd_encode_bound(uint64_t n);
+/* Encode many chunks in one call: chunk i = src[chunks[i].offset .. +length) becomes one frame at dst + out[i].offset, which
+ * has out[i].length bytes of room. status[i] = PBSGPU_ZSTD_OK, or PBSGPU_ZSTD_BAD_SIZE when the frame needs more room
+ * (a room of pbsgpu_zstd_encode_bound(length) always suffices); frame_len[i] (may be NULL) = the frame's length, 0 unless
+ * OK. A frame writes nothing outside out[i]; on BAD_SIZE the contents of out[i] are unspecified. Argument checks as for
+ * pbsgpu_zstd_decode_device, before any device work: PBSGPU_E_INVALID for a NULL where a value is needed, a chunk outside
+ * src, an out[i] outside dst_cap, out ranges that overlap one another or the source, a host pointer for src or dst, a
+ * chunk or a room of 4 GiB or more. n == 0 is PBSGPU_OK. One wave per 128 KiB block, then one workgroup per chunk that
+ * puts the frame together; one leased stream and ONE synchronisation of it, at the end. */
+int pbsgpu_zstd_encode_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *chunks,
+                              uint32_t n, const pbsgpu_segment *out /* n: offset and room inside dst */, void *dst,
+                              uint64_t dst_cap, uint8_t *status /* n */, uint64_t *frame_len /* n, may be NULL */);
+/* pbsgpu_blob_encode_device with the blob's kind decided on the device. Without PBSGPU_ENCODE_F_ZSTD it is that call output
+ * for output (dst, offsets, crcs), with lens[i] = 12 + length and kinds[i] = PBSGPU_BLOB_UNCOMPRESSED. With it, blob i lies
+ * in the same slot [offsets[i], offsets[i] + 12 + length) that the uncompressed layout gives it, and the verdict is the one
+ * of the PBS client's DataBlob encoder (data_blob.rs, recalled, not checked against a fixture: EXTERNAL): the chunk is
+ * compressed, and if the frame is strictly shorter than the chunk the blob is [compressed magic | CRC-32 LE of the frame |
+ * frame]; otherwise it is the uncompressed blob, byte for byte what the plain call writes. lens[i] = the blob's length
+ * either way, kinds[i] = PBSGPU_BLOB_COMPRESSED or _UNCOMPRESSED. Slots are not compacted: the server takes one chunk per
+ * request, so the caller sends dst + offsets[i], lens[i]; the bytes of a slot behind lens[i] are unspecified. Frame
+ * lengths, CRCs and headers are all made on the device, from lengths only the device knows, with ONE synchronisation at
+ * the end. offsets (nseg + 1), lens, kinds, crcs (nseg each) and stats are host arrays and may be NULL. Errors as for the
+ * plain call (PBSGPU_E_CAPACITY when dst_cap is below offsets[nseg], nothing written; offsets is filled in before), plus
+ * PBSGPU_E_INVALID for an unknown flag, for a chunk of 4 GiB - 12 or more (lens is 32 bits wide) and, with F_ZSTD, for a dst
+ * that overlaps src (the frames are read again for their CRC). */
+#define PBSGPU_ENCODE_F_ZSTD 1u
+typedef struct pbsgpu_encode_stats {
+    uint64_t blobs[2];       /* blobs per kind: PBSGPU_BLOB_UNCOMPRESSED, PBSGPU_BLOB_COMPRESSED */
+    uint64_t blob_bytes[2];  /* sum of lens per kind */
+    uint64_t chunk_bytes[2]; /* sum of the chunk lengths per kind */
+    uint64_t frame_bytes;    /* frame bytes of the compressed blobs */
+    uint64_t crc_bytes;      /* bytes the CRC was computed over: the payload of every blob */
+} pbsgpu_encode_stats;
+int pbsgpu_blob_encode2_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *segs,
+                               uint32_t nseg, uint32_t flags, void *dst, uint64_t dst_cap,
+                               uint64_t *offsets /* nseg + 1 */, uint32_t *lens /* nseg */, uint8_t *kinds /* nseg */,
+                               uint32_t *crcs /* nseg */, pbsgpu_encode_stats *stats);
+
 /* ---- classify and frame in one device-side call --------------------------------------------------------------------
  * The middle of the incremental writer's loop — known-chunk check, then upload framing of what is new (SURVEY.md §3A;
  * the upload of commit_orchestrate.go:137-158 behind the known-chunk check, refs of commit_reuse.go:315-341 being known by

@@ -326,6 +326,59 @@ inline Result<ZstdDecoded> DecodeZstd(pbsgpu_engine *eng, const void *src, uint6
     return r;
 }
 
+struct ZstdEncoded {
+    std::vector<uint8_t> status;     // PBSGPU_ZSTD_OK or PBSGPU_ZSTD_BAD_SIZE per chunk
+    std::vector<uint64_t> frameLen;  // the frame's length (0 unless OK)
+};
+
+// many chunks of a device buffer to one zstd frame each in one call: chunk i to dst + out[i].offset, which has
+// out[i].length bytes of room (pbsgpu_zstd_encode_bound(length) always suffices): the writers of the reference that
+// compress (internal/tapeio/converter.go:399, :410-435). A chunk whose status is PBSGPU_ZSTD_BAD_SIZE leaves unspecified
+// bytes in its own room and nothing anywhere else.
+inline Result<ZstdEncoded> EncodeZstd(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const std::vector<pbsgpu_segment> &chunks,
+                                      const std::vector<pbsgpu_segment> &out, void *dst, uint64_t dstCap) {
+    Result<ZstdEncoded> r;
+    if (out.size() != chunks.size()) {
+        r.err = errorf("zstd encode", PBSGPU_E_INVALID);
+        return r;
+    }
+    r.value.status.resize(chunks.size() + 1);
+    r.value.frameLen.resize(chunks.size() + 1);
+    const int st = pbsgpu_zstd_encode_device(eng, src, nbytes, chunks.data(), (uint32_t)chunks.size(), out.data(), dst, dstCap,
+                                             r.value.status.data(), r.value.frameLen.data());
+    r.value.status.resize(chunks.size());
+    r.value.frameLen.resize(chunks.size());
+    if (st != PBSGPU_OK) r.err = errorf("zstd encode", st);
+    return r;
+}
+
+struct Encoded2 {
+    std::vector<uint64_t> offsets;  // segs.size() + 1: blob i lies at offsets[i], in the slot the uncompressed layout gives it
+    std::vector<uint32_t> lens;     // the blob's length: what is sent
+    std::vector<uint8_t> kinds;     // PBSGPU_BLOB_UNCOMPRESSED or PBSGPU_BLOB_COMPRESSED
+    std::vector<uint32_t> crcs;
+    pbsgpu_encode_stats stats{};
+};
+
+// EncodeDevice with the blob's kind decided on the device (zstd = true: PBSGPU_ENCODE_F_ZSTD): a chunk whose frame is strictly
+// shorter than the chunk becomes a compressed blob, every other one the uncompressed blob EncodeDevice writes.
+inline Result<Encoded2> Encode2(pbsgpu_engine *eng, const void *src, uint64_t srcBytes, const std::vector<pbsgpu_segment> &segs,
+                                bool zstd, void *dst, uint64_t dstCap) {
+    Result<Encoded2> r;
+    r.value.offsets.resize(segs.size() + 1);
+    r.value.lens.resize(segs.size() + 1);
+    r.value.kinds.resize(segs.size() + 1);
+    r.value.crcs.resize(segs.size() + 1);
+    const int st = pbsgpu_blob_encode2_device(eng, src, srcBytes, segs.data(), (uint32_t)segs.size(), zstd ? PBSGPU_ENCODE_F_ZSTD : 0u,
+                                              dst, dstCap, r.value.offsets.data(), r.value.lens.data(), r.value.kinds.data(),
+                                              r.value.crcs.data(), &r.value.stats);
+    r.value.lens.resize(segs.size());
+    r.value.kinds.resize(segs.size());
+    r.value.crcs.resize(segs.size());
+    if (st != PBSGPU_OK) r.err = errorf("blob encode2", st);
+    return r;
+}
+
 }  // namespace blob
 
 // datastore.DynamicIndexReader

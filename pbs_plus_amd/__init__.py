@@ -14,13 +14,15 @@ pbs-plus reference uses for its pxar stream path:
 * ``Engine.crc32_many`` / ``blob_encode`` / ``blob_verify`` — data-blob framing of the uploads and the chunk check
   (``chunk_ranges`` turns records into the byte ranges of their chunks)
 * ``Engine.zstd_decode`` / ``zstd_frame_info`` — the zstd frames behind the compressed blobs, decoded on the device
+* ``Engine.zstd_encode`` / ``blob_encode2`` / ``zstd_encode_bound`` — chunks compressed to zstd frames on the device and
+  framed as blobs whose kind the device decides
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
 from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
 from .engine import Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
-from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine, zstd_frame_info  # noqa: F401
+from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine, zstd_encode_bound, zstd_frame_info  # noqa: F401
 
 __all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError",
-           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine", "zstd_frame_info"]
+           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine", "zstd_encode_bound", "zstd_frame_info"]

@@ -151,6 +151,12 @@ class DecodeStats2(C.Structure):
 
 ZSTD_OK, ZSTD_BAD_FRAME, ZSTD_BAD_SIZE, ZSTD_UNSUPPORTED = range(4)
 ZSTD_STATUS_NAMES = ("ok", "bad_frame", "bad_size", "unsupported")
+ENCODE_F_ZSTD = 1
+
+
+class EncodeStats(C.Structure):
+    _fields_ = [("blobs", C.c_uint64 * 2), ("blob_bytes", C.c_uint64 * 2), ("chunk_bytes", C.c_uint64 * 2),
+                ("frame_bytes", C.c_uint64), ("crc_bytes", C.c_uint64)]
 
 
 class BlobStats(C.Structure):
@@ -266,6 +272,9 @@ SYMBOLS = {
                                              C.c_uint32, _P, C.c_uint64, _P, C.POINTER(DecodeStats2)]),
     "pbsgpu_zstd_frame_info": (C.c_int, [_P, C.c_uint64, _U64P, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "pbsgpu_zstd_decode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
+    "pbsgpu_zstd_encode_bound": (C.c_uint64, [C.c_uint64]),
+    "pbsgpu_zstd_encode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
+    "pbsgpu_blob_encode2_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     "pbsgpu_ring_upload_new_device": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P, _U64P,
                                                 C.POINTER(DedupStats)]),
     "pbsgpu_known_upload_new_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P,

@@ -367,6 +367,64 @@ __global__ __launch_bounds__(256) void k_crc_fold(Plan pl) {
     }
 }
 
+// ---- blobs whose kind the device decides (pbsgpu_blob_encode2_device with PBSGPU_ENCODE_F_ZSTD) -------------
+// zstd_encode.hip has left, per chunk, its verdict and the frame's length (res), and has written the frames that won at
+// their blobs' data positions. The CRC then covers the frame where it lies (no store), or the chunk, which the walk
+// copies as the plain encode does. The pieces are planned on the host for each slot's capacity, the chunk's length; the
+// range actually covered is known only here, and the planned pieces past its end do nothing. Same walk, same fold.
+struct Enc2Plan {
+    Plan p;
+    const uint64_t *res;  // nseg: frame length | kind << 56
+    uint32_t *lens;       // nseg: the blob's length
+    uint8_t *kinds;       // nseg
+    uint32_t zmagic_lo, zmagic_hi;  // the compressed kind's magic
+};
+
+__global__ __launch_bounds__(256) void k_enc2_pieces(Enc2Plan pl) {
+    __shared__ uint32_t tab[17][256];
+    build_tables(tab);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    for (uint64_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.p.npieces; p += nw) {
+        const uint32_t i = ((gword_ptr)pl.p.pseg)[p];
+        const uint64_t b0 = ((gquad_ptr)pl.p.pbase)[i];
+        const pbsgpu_segment sg{((gquad_ptr)pl.p.segs)[2 * i], ((gquad_ptr)pl.p.segs)[2 * i + 1]};
+        const uint64_t res = ((gquad_ptr)pl.res)[i];
+        const bool comp = (res >> 56) == PBSGPU_BLOB_COMPRESSED;
+        const uint64_t len = comp ? res & ((1ull << 56) - 1) : sg.length;  // comp: shorter than the chunk
+        const uint64_t m = (len + kPiece - 1) >> kPieceLog;
+        if (p - b0 >= m) continue;  // (wave-uniform)
+        const uint64_t hi = len - (m - 1 - (p - b0)) * kPiece;
+        const uint64_t lo = hi > kPiece ? hi - kPiece : 0;
+        uint8_t *data = pl.p.dst + ((gquad_ptr)pl.p.doff)[i] + PBSGPU_BLOB_HEADER_SIZE;
+        const uint8_t *from = comp ? data : pl.p.src + sg.offset;
+        const uint32_t inv = (len >= 4 && lo < 4) ? (uint32_t)((hi < 4 ? hi : 4) - lo) : 0u;
+        const uint32_t v = piece_raw(tab, from + lo, (uint32_t)(hi - lo), inv, lane, PutIf{comp ? nullptr : data + lo});
+        if (lane == 0) ((gword_out)pl.p.praw)[p] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_enc2_fold(Enc2Plan pl) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < pl.p.nseg; i += nw) {
+        const uint64_t b0 = ((gquad_ptr)pl.p.pbase)[i];
+        const uint64_t res = ((gquad_ptr)pl.res)[i];
+        const bool comp = (res >> 56) == PBSGPU_BLOB_COMPRESSED;
+        const uint64_t len = comp ? res & ((1ull << 56) - 1) : ((gquad_ptr)pl.p.segs)[2 * i + 1];
+        const uint32_t m = (uint32_t)((len + kPiece - 1) >> kPieceLog);
+        const uint32_t acc = m ? fold_part((gword_ptr)pl.p.praw + b0, m, lane) : 0u;
+        const uint32_t crc = finish(acc, len);
+        if (lane == 0) {
+            ((gword_out)pl.p.crcs)[i] = crc;
+            ((gword_out)pl.lens)[i] = (uint32_t)(len + PBSGPU_BLOB_HEADER_SIZE);
+            ((gbyte_out)pl.kinds)[i] = comp ? PBSGPU_BLOB_COMPRESSED : PBSGPU_BLOB_UNCOMPRESSED;
+        }
+        store_header(pl.p.dst + ((gquad_ptr)pl.p.doff)[i], lane, comp ? pl.zmagic_lo : pl.p.magic_lo,
+                     comp ? pl.zmagic_hi : pl.p.magic_hi, crc);
+    }
+}
+
 // the first min(len, 12) bytes of every blob (verify_device: the host parses the headers)
 __global__ __launch_bounds__(256) void k_blob_heads(const uint8_t *src, const pbsgpu_segment *blobs, uint32_t n,
                                                     uint8_t *heads) {
@@ -995,6 +1053,64 @@ int encoded_size(const pbsgpu_segment *segs, uint32_t nseg, uint64_t *nbytes, ui
     }
     if (offsets) offsets[nseg] = total;
     *nbytes = total;
+    return PBSGPU_OK;
+}
+
+// pbsgpu_blob_encode2_device with PBSGPU_ENCODE_F_ZSTD: the frames (zstd_encode.hip), then the CRC pair over what each
+// slot ended up holding, all on the slot's stream; one read-back of crcs, lens and kinds at the end.
+int blob_encode_zstd(pbsgpu_engine *e, const uint8_t *src, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *dst,
+                     const uint64_t *offs, uint64_t src_bytes, uint32_t *lens, uint8_t *kinds, uint32_t *crcs) {
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const uint8_t *d = nullptr;
+    CHK(stage_ranges(e, s, src, false, src_bytes, segs, nseg, &d));
+    std::vector<pbsk::zenc::Job> jobs(nseg);
+    for (uint32_t i = 0; i < nseg; ++i)
+        jobs[i] = pbsk::zenc::Job{segs[i].offset, offs[i] + PBSGPU_BLOB_HEADER_SIZE, segs[i].length, (uint32_t)segs[i].length, 0};
+    uint64_t *res = nullptr;
+    CHK(pbsk::zenc::enqueue(e, s, d, dst, jobs, true, &res));
+    std::vector<uint64_t> pbase((size_t)nseg + 1);
+    uint64_t np = 0;
+    for (uint32_t i = 0; i < nseg; ++i) {  // for each slot's capacity
+        pbase[i] = np;
+        np += (segs[i].length + kPiece - 1) >> kPieceLog;
+    }
+    pbase[nseg] = np;
+    if (np >= (1ull << 32)) return PBSGPU_E_INVALID;
+    std::vector<uint32_t> pseg((size_t)np);
+    fill_owners(pbase, pseg.data());
+    const size_t out_bytes = (size_t)nseg * 9;  // crcs, lens, kinds: one block, read back once
+    CHK(s->seg_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
+    CHK(s->tile_cnt.ensure(np * sizeof(uint32_t) + 64));
+    CHK(s->dense.ensure(np * sizeof(uint32_t) + 64));
+    CHK(s->tile_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
+    CHK(s->tile_slots.ensure(out_bytes + 64));
+    CHK(staged_h2d(*s, s->seg_off.p, pbase.data(), (nseg + 1) * sizeof(uint64_t), s->stream));
+    if (np) CHK(staged_h2d(*s, s->tile_cnt.p, pseg.data(), np * sizeof(uint32_t), s->stream));
+    CHK(staged_h2d(*s, s->tile_off.p, offs, (nseg + 1) * sizeof(uint64_t), s->stream));
+    Enc2Plan pl{};
+    pl.p.src = d;
+    pl.p.segs = s->segs.as<pbsgpu_segment>();
+    pl.p.pbase = s->seg_off.as<uint64_t>();
+    pl.p.pseg = s->tile_cnt.as<uint32_t>();
+    pl.p.praw = s->dense.as<uint32_t>();
+    pl.p.crcs = s->tile_slots.as<uint32_t>();
+    pl.p.npieces = np;
+    pl.p.nseg = nseg;
+    pl.p.dst = dst;
+    pl.p.doff = s->tile_off.as<uint64_t>();
+    set_magic(pl.p);
+    pl.res = res;
+    pl.lens = s->tile_slots.as<uint32_t>() + nseg;
+    pl.kinds = s->tile_slots.as<uint8_t>() + (size_t)nseg * 8;
+    pl.zmagic_lo = le32(kMagic[PBSGPU_BLOB_COMPRESSED]);
+    pl.zmagic_hi = le32(kMagic[PBSGPU_BLOB_COMPRESSED] + 4);
+    CHK(launch_pair(e, s->stream, k_enc2_pieces, k_enc2_fold, pl, np, nseg));
+    std::vector<uint8_t> back(out_bytes);
+    CHK(fetch_result(s, back.data(), s->tile_slots.p, out_bytes));  // the call's one synchronisation
+    std::memcpy(crcs, back.data(), (size_t)nseg * 4);
+    std::memcpy(lens, back.data() + (size_t)nseg * 4, (size_t)nseg * 4);
+    std::memcpy(kinds, back.data() + (size_t)nseg * 8, nseg);
     return PBSGPU_OK;
 }
 
@@ -1650,6 +1766,50 @@ int pbsgpu_blob_encode_device(pbsgpu_engine *e, const void *src, uint64_t src_by
     CHK(enqueue_crc(e, s, d, segs, nseg, static_cast<uint8_t *>(dst), offs.data(), &dcrcs));
     if (crcs) return fetch_result(s, crcs, dcrcs, (size_t)nseg * 4);
     HIPCHK(hipStreamSynchronize(s->stream));
+    return PBSGPU_OK;
+}
+
+int pbsgpu_blob_encode2_device(pbsgpu_engine *e, const void *src, uint64_t src_bytes, const pbsgpu_segment *segs,
+                               uint32_t nseg, uint32_t flags, void *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *lens,
+                               uint8_t *kinds, uint32_t *crcs, pbsgpu_encode_stats *stats) {
+    if (flags & ~PBSGPU_ENCODE_F_ZSTD) return PBSGPU_E_INVALID;
+    if (!e || (!src && src_bytes) || (nseg && !segs)) return PBSGPU_E_INVALID;
+    if (!ranges_ok(segs, nseg, src_bytes)) return PBSGPU_E_INVALID;
+    for (uint32_t i = 0; i < nseg; ++i)
+        if ((segs[i].length + PBSGPU_BLOB_HEADER_SIZE) >> 32) return PBSGPU_E_INVALID;  // lens is 32 bits wide
+    std::vector<uint64_t> offs((size_t)nseg + 1);
+    uint64_t total = 0;
+    CHK(encoded_size(segs, nseg, &total, offs.data()));
+    if (offsets) std::memcpy(offsets, offs.data(), offs.size() * sizeof(uint64_t));  // (also what a caller sizes dst with)
+    if (total > dst_cap) return PBSGPU_E_CAPACITY;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    std::vector<uint32_t> vlens(nseg), vcrcs(nseg);
+    std::vector<uint8_t> vkinds(nseg, (uint8_t)PBSGPU_BLOB_UNCOMPRESSED);
+    if (!(flags & PBSGPU_ENCODE_F_ZSTD)) {
+        uint64_t out_len = 0;
+        CHK(pbsgpu_blob_encode_device(e, src, src_bytes, segs, nseg, dst, dst_cap, &out_len, nullptr, nseg ? vcrcs.data() : nullptr));
+        for (uint32_t i = 0; i < nseg; ++i) vlens[i] = (uint32_t)(segs[i].length + PBSGPU_BLOB_HEADER_SIZE);
+    } else if (nseg) {
+        if (!dst || !is_device_pointer(dst) || (src_bytes && !is_device_pointer(src))) return PBSGPU_E_INVALID;
+        const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src;
+        if (src_bytes && d0 < s0 + src_bytes && s0 < d0 + total) return PBSGPU_E_INVALID;  // the frames are read back
+        CHK(set_device(e));
+        CHK(blob_encode_zstd(e, static_cast<const uint8_t *>(src), segs, nseg, static_cast<uint8_t *>(dst), offs.data(), src_bytes,
+                             vlens.data(), vkinds.data(), vcrcs.data()));
+    }
+    for (uint32_t i = 0; i < nseg; ++i) {
+        if (stats) {
+            const int k = vkinds[i];
+            stats->blobs[k]++;
+            stats->blob_bytes[k] += vlens[i];
+            stats->chunk_bytes[k] += segs[i].length;
+            if (k == PBSGPU_BLOB_COMPRESSED) stats->frame_bytes += vlens[i] - PBSGPU_BLOB_HEADER_SIZE;
+            stats->crc_bytes += vlens[i] - PBSGPU_BLOB_HEADER_SIZE;
+        }
+    }
+    if (lens && nseg) std::memcpy(lens, vlens.data(), (size_t)nseg * 4);
+    if (kinds && nseg) std::memcpy(kinds, vkinds.data(), nseg);
+    if (crcs && nseg) std::memcpy(crcs, vcrcs.data(), (size_t)nseg * 4);
     return PBSGPU_OK;
 }
 

@@ -331,6 +331,22 @@ hipError_t launch_restore_copy(const RestorePlan &pl, uint32_t longest, int num_
 hipError_t launch_restore_status(const RestorePlan &pl, hipStream_t st);
 }  // namespace zstd
 }  // namespace pbsk
+// zstd_encode.hip: the frames of many chunks, enqueued on a slot's stream (pbsgpu_zstd_encode_device, and the zstd leg of
+// pbsgpu_blob_encode2_device, which blob.hip follows with its CRC and header kernels on the same stream).
+namespace pbsk {
+namespace zenc {
+struct Job {  // one chunk: its bytes at src + src_off, its frame's room at dst + dst_off
+    uint64_t src_off, dst_off, room;
+    uint32_t len, first;  // first: filled in by enqueue
+};
+// res_dev[i] = frame length | status << 56. blob = false: PBSGPU_ZSTD_OK or _BAD_SIZE (nothing written, length 0).
+// blob = true: room is the chunk's length; PBSGPU_BLOB_COMPRESSED when the frame is strictly shorter than the chunk and
+// was written, PBSGPU_BLOB_UNCOMPRESSED (nothing written) otherwise. Uses the slot's recs, sugg_idx, order, data, par and
+// scan_tmp buffers.
+int enqueue(pbsgpu_engine *e, pbse::Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob,
+            uint64_t **res_dev);
+}  // namespace zenc
+}  // namespace pbsk
 namespace pbse {
 
 // stream contexts parked in pbsgpu_engine::stream_pool (stream.cpp): really free them (engine teardown, trim)

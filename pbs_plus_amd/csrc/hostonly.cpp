@@ -5,6 +5,7 @@
 
 #include "../../include/pbsgpu.h"
 #include "zstd_decode.h"
+#include "zstd_encode.h"
 
 namespace {
 
@@ -136,6 +137,8 @@ int pbsgpu_zstd_frame_info(const uint8_t *frame, uint64_t nbytes, uint64_t *cont
     if (has_checksum) *has_checksum = (int)h.has_checksum;
     return st;
 }
+
+uint64_t pbsgpu_zstd_encode_bound(uint64_t n) { return pbsz::enc::encode_bound(n); }
 
 int pbsgpu_payload_format_default(pbsgpu_payload_format *out) {
     if (!out) return PBSGPU_E_INVALID;

@@ -1,0 +1,745 @@
+// Zstandard frame encoding (RFC 8878) for the write side: ONE implementation, compiled twice, in the manner of
+// zstd_decode.h, whose tables, constants and FSE table build it uses. Under hipcc every function is __host__ __device__ and
+// zstd_encode.hip runs encode_block with one wave per 128 KiB block; without hipcc it is plain inline C++, and that build
+// is what tests/native/test_zstd_encode.cpp runs under AddressSanitizer. No HIP and no libc.
+//
+// The policy P is the decoder's (lane, lanes, sync, uni) plus the two read-modify-writes that lanes aim at one word:
+//   P::amax(p, v)  *p = max(*p, v), atomically among the lanes
+//   P::aadd(p, v)  *p += v, atomically among the lanes
+// Every phase is `for (l = P::lane(); l < 64; l += P::lanes())` between P::sync()s, so one host lane does exactly what 64
+// device lanes do and both builds write the same bytes (tests/golden/zstd_enc_v1.json).
+//
+// Decisions (include/pbsgpu.h):
+//   * Frame: magic, single segment, no dictionary id, no checksum; the content size in 1, 2 or 4 bytes. Blocks carry
+//     kBlockMax = 128 KiB of content each; 0 bytes of content is a header and one empty raw last block.
+//   * Blocks are independent: a match never reaches before its block's first byte. Repeats further apart are not found.
+//   * A block of one byte value is an RLE block; a block whose compressed form is not smaller than its content is raw.
+//   * Match finder: greedy, minimum match 4. hash[h] = 1 + the highest block-relative position inserted with hash h.
+//     Positions are worked in batches of 64: every position looks the table up as it stood before the batch, verifies and
+//     extends its candidate up to the block's end; then the batch inserts itself (amax); lane 0 takes the matches in
+//     position order, the first one at or after the cursor, and the cursor moves to that match's end.
+//     A batch starts at the cursor or behind the batch before it, whichever is later: every position of a batch is
+//     inserted, whether a taken match covers it or not, and the positions a taken match carries the cursor over beyond its
+//     batch are neither looked up nor inserted.
+//   * Sequences: Predefined_Mode for all three symbol types, only offset + 3 values (no repeat codes, so no history). At
+//     most kSeqCap per block; behind the cap the block's remaining bytes are literals. kSeqCap < 0x7F00: the 3-byte count
+//     form never occurs. Lane 0 encodes them in reverse into the backward bit stream.
+//   * Literals: histogram by all lanes, the length-limited (kHufMaxBits = 11) code by lane 0, one stream up to 1 023
+//     literals and four streams on lanes 0-3 above. Huffman only if the tree description plus the streams is strictly
+//     smaller than the literals; one byte value is RLE literals; no literals or no gain is raw literals.
+//     The weights are described directly (highest byte value <= 128) or FSE-compressed, whichever is smaller and fits the
+//     header byte; where neither does, the literals stay raw ("Huffman refused").
+//   * The encoder knows its room and writes nothing outside it; a room below what the frame needs is BAD_SIZE.
+//   * Buffers a block needs, all implied by kBlockMax: lit kBlockMax bytes, seqs kSeqCap * 8 bytes, blk kBlockMax bytes (a
+//     compressed form that would pass the block's content length is abandoned where it would).
+#pragma once
+
+#include "zstd_decode.h"
+
+#ifdef PBSGPU_ZSTD_COVERAGE  // CPU test build only: one bit per branch (names: tests/test_zstd_encode_native.py)
+namespace pbsz {
+namespace enc {
+inline uint64_t g_cov = 0;
+}
+}
+#define PBSZ_ECOV(bit) (::pbsz::enc::g_cov |= 1ull << (bit))
+#else
+#define PBSZ_ECOV(bit) ((void)0)
+#endif
+
+namespace pbsz {
+namespace enc {
+
+enum : int {  // coverage bits
+    E_FCS_1, E_FCS_2, E_FCS_4, E_BLOCK_RAW, E_BLOCK_RLE, E_BLOCK_COMPRESSED, E_EMPTY_LAST_BLOCK,
+    E_LIT_RAW, E_LIT_RLE, E_HUF_1STREAM, E_HUF_4STREAM, E_WEIGHTS_DIRECT, E_WEIGHTS_FSE,
+    E_NSEQ_0, E_NSEQ_1, E_NSEQ_2, E_MATCH_OVERLAP, E_MATCH_OFFSET_1, E_LL_EXTRA, E_ML_EXTRA, E_SEQ_CAP, E_HUF_REFUSED,
+    E_NBITS
+};
+
+constexpr uint32_t kHashLog = 12;
+constexpr uint32_t kMinMatch = 4;
+constexpr uint32_t kLanes = 64;           // a batch of positions
+constexpr uint32_t kSeqCap = 24576;       // sequences per block; 8 bytes each in the caller's scratch
+constexpr uint32_t kHufMaxBits = 11;
+constexpr uint32_t kNone = 0xffffffffu;
+enum : uint32_t { B_RAW = 0, B_RLE = 1, B_COMPRESSED = 2 };
+
+struct HostLanes : pbsz::HostLanes {
+    static PBSZ_HD void amax(uint32_t *p, uint32_t v) {
+        if (*p < v) *p = v;
+    }
+    static PBSZ_HD void aadd(uint32_t *p, uint32_t v) { *p += v; }
+};
+
+struct EncTab {  // FSE encoding of one predefined distribution, derived from the decoding table fse_build makes
+    uint8_t state[64];  // state[cum[s] + k]: the k-th state (ascending) that decodes to s
+    uint8_t cum[53], p[53];
+    uint32_t log;
+};
+
+// Per block in flight; LDS in the kernel. The decoder's State is needed only while FSE tables are built (the predefined
+// ones before the first block, the weights' own after a block's match finding): it shares its bytes with the hash table.
+struct State {
+    union {
+        uint32_t hash[1u << kHashLog];
+        pbsz::State dec;
+    } u;
+    uint32_t hist[256];   // literal counts
+    uint32_t key[256];    // the counts in ascending order, then the code lengths (in place)
+    uint16_t code[256];
+    uint8_t len[256];     // 0: the byte value does not occur
+    uint8_t sorted[256];  // byte values by ascending (count, value)
+    EncTab ll, of, ml, wt;  // wt: the weights' own distribution, per block
+    uint8_t wdesc[128];     // the FSE-compressed weight description, header byte first
+    uint32_t mlen[kLanes], moff[kLanes], mh[kLanes], lidx[kLanes];  // the batch
+    uint32_t ncodes[40], start[kHufMaxBits + 2];
+    uint32_t sbits[4];
+    uint32_t flag, cursor, nlit, nseq, ll_run, next_b0;
+    uint32_t nsym, maxsym, maxcnt, maxbits, desc, wfse, size, over;
+};
+
+PBSZ_HD uint32_t header_bytes(uint64_t n) { return 5u + (n <= 255 ? 1u : n <= 65791 ? 2u : 4u); }
+PBSZ_HD uint64_t block_count(uint64_t n) { return n ? (n + kBlockMax - 1) / kBlockMax : 1; }
+// no frame of n bytes of content is longer: the header, three bytes per block, the content
+PBSZ_HD uint64_t encode_bound(uint64_t n) { return header_bytes(n) + 3 * block_count(n) + n; }
+
+// the frame header of n < 4 GiB bytes of content into h[0, header_bytes(n))
+PBSZ_HD void frame_header(uint64_t n, uint8_t *h) {
+    const uint32_t hb = header_bytes(n), fcs = hb - 5;
+    h[0] = 0x28;
+    h[1] = 0xb5;
+    h[2] = 0x2f;
+    h[3] = 0xfd;
+    h[4] = (uint8_t)((fcs == 1 ? 0u : fcs == 2 ? 1u : 2u) << 6 | 1u << 5);
+    const uint64_t v = fcs == 2 ? n - 256 : n;
+    for (uint32_t i = 0; i < fcs; ++i) h[5 + i] = (uint8_t)(v >> (8 * i));
+    PBSZ_ECOV(fcs == 1 ? E_FCS_1 : fcs == 2 ? E_FCS_2 : E_FCS_4);
+}
+
+// a block's three header bytes; bytes = the block's content length for raw and RLE, the compressed size otherwise
+PBSZ_HD void block_header(uint8_t *h, uint32_t last, uint32_t type, uint32_t bytes) {
+    const uint32_t v = last | type << 1 | bytes << 3;
+    h[0] = (uint8_t)v;
+    h[1] = (uint8_t)(v >> 8);
+    h[2] = (uint8_t)(v >> 16);
+}
+// the bytes behind the header: the content, one byte, the compressed form
+PBSZ_HD uint32_t payload_bytes(uint32_t type, uint32_t bn, uint32_t csize) { return type == B_RAW ? bn : type == B_RLE ? 1u : csize; }
+
+PBSZ_HD uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+PBSZ_HD uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashLog); }
+
+// A backward bit stream being written: values go in from bit 0 of p[0] upwards, the reader takes them from the top. No byte
+// at or behind p[cap] is stored; `over` says that one would have been.
+struct BitWriter {
+    uint8_t *p;
+    uint32_t pos, cap, nb;
+    uint64_t acc;
+    bool over;
+
+    PBSZ_HD void init(uint8_t *dst, uint32_t room) {
+        p = dst;
+        pos = 0;
+        cap = room;
+        nb = 0;
+        acc = 0;
+        over = false;
+    }
+    PBSZ_HD void put_byte() {
+        if (pos < cap) p[pos] = (uint8_t)acc;
+        else over = true;
+        ++pos;
+        acc >>= 8;
+    }
+    PBSZ_HD void add(uint32_t v, uint32_t k) {  // v < 1 << k, k <= 32
+        acc |= (uint64_t)v << nb;
+        nb += k;
+        while (nb >= 8) {
+            put_byte();
+            nb -= 8;
+        }
+    }
+    PBSZ_HD uint32_t flush() {  // a forward stream's last partial byte; returns the length
+        if (nb) {
+            put_byte();
+            nb = 0;
+        }
+        return pos;
+    }
+    PBSZ_HD uint32_t finish() {  // the end mark; returns the stream's length
+        add(1, 1);
+        if (nb) {
+            put_byte();
+            nb = 0;
+        }
+        return pos;
+    }
+};
+
+// t.state from t.cum, t.p, t.log and the decoding table: a state's rank among those of its symbol is what its baseline says
+PBSZ_HD void rank_states(EncTab &t, const FseEntry *tab) {
+    const uint32_t size = 1u << t.log;
+    PBSZ_ROLLED
+    for (uint32_t u = 0; u < size; ++u) {
+        const uint32_t s = tab[u].sym;
+        t.state[t.cum[s] + ((tab[u].next + size) >> tab[u].nbits) - t.p[s]] = (uint8_t)u;
+    }
+}
+
+// The three predefined encoding tables (lane 0, once before the first block; the hash table's bytes serve as the decoder
+// state that fse_build works in).
+PBSZ_HD void build_tab(State &st, uint32_t which) {
+    EncTab &t = which == 0 ? st.ll : which == 1 ? st.of : st.ml;
+    uint32_t q = 0;
+    (void)seq_table(st.u.dec, which, 0, nullptr, 0, &q);  // the predefined distribution: cannot fail
+    const FseEntry *tab = which == 0 ? st.u.dec.ll : which == 1 ? st.u.dec.of : st.u.dec.ml;
+    const uint32_t n = which == 0 ? 36u : which == 1 ? 29u : 53u;
+    t.log = which == 1 ? 5u : 6u;
+    uint32_t cum = 0;
+    PBSZ_ROLLED
+    for (uint32_t s = 0; s < n; ++s) {
+        const int32_t v = which == 0 ? kLLDefault[s] : which == 1 ? kOFDefault[s] : kMLDefault[s];
+        const uint32_t p = v < 0 ? 1u : (uint32_t)v;
+        t.p[s] = (uint8_t)p;
+        t.cum[s] = (uint8_t)cum;
+        cum += p;
+    }
+    rank_states(t, tab);
+}
+
+template <class P>
+PBSZ_HD void init_tables(State &st) {
+    if (P::lane() == 0) {
+        build_tab(st, 0);
+        build_tab(st, 1);
+        build_tab(st, 2);
+    }
+    P::sync();
+}
+
+// symbol s goes in front of what state X stands for: the bits the decoder reads to get from s's state to X
+PBSZ_HD void fse_put(const EncTab &t, uint32_t &X, uint32_t s, BitWriter &bw) {
+    const uint32_t x = X + (1u << t.log), p = t.p[s];
+    uint32_t nb = t.log - highbit(p);
+    if ((x >> nb) < p) --nb;
+    bw.add(x & ((1u << nb) - 1), nb);
+    X = t.state[t.cum[s] + (x >> nb) - p];
+}
+
+PBSZ_HD uint32_t ll_code(uint32_t ll) {
+    if (ll < 16) return ll;
+    if (ll >= 64) return highbit(ll) + 19;
+    uint32_t c = 16;
+    PBSZ_ROLLED
+    while (kLLBase[c + 1] <= ll) ++c;  // ends at 24 at the latest: kLLBase[25] = 64
+    return c;
+}
+
+PBSZ_HD uint32_t ml_code(uint32_t ml) {  // ml >= 3
+    const uint32_t b = ml - 3;
+    if (b < 32) return b;
+    if (b >= 128) return highbit(b) + 36;
+    uint32_t c = 32;
+    PBSZ_ROLLED
+    while (kMLBase[c + 1] <= ml) ++c;  // ends at 42 at the latest: kMLBase[43] = 131
+    return c;
+}
+
+// Code lengths of minimum redundancy, in place (Moffat and Katajainen): A[0, n) are the counts in ascending order on entry
+// and the code lengths, longest first, on return. n >= 2.
+PBSZ_HD void min_redundancy(uint32_t *A, int32_t n) {
+    A[0] += A[1];
+    int32_t root = 0, leaf = 2, next;
+    for (next = 1; next < n - 1; ++next) {
+        if (leaf >= n || A[root] < A[leaf]) {
+            A[next] = A[root];
+            A[root++] = (uint32_t)next;
+        } else {
+            A[next] = A[leaf++];
+        }
+        if (leaf >= n || (root < next && A[root] < A[leaf])) {
+            A[next] += A[root];
+            A[root++] = (uint32_t)next;
+        } else {
+            A[next] += A[leaf++];
+        }
+    }
+    A[n - 2] = 0;
+    for (next = n - 3; next >= 0; --next) A[next] = A[A[next]] + 1;
+    int32_t avbl = 1, used = 0, dpth = 0;
+    root = n - 2;
+    next = n - 1;
+    while (avbl > 0) {
+        while (root >= 0 && (int32_t)A[root] == dpth) {
+            ++used;
+            --root;
+        }
+        while (avbl > used) {
+            A[next--] = (uint32_t)dpth;
+            --avbl;
+        }
+        avbl = 2 * used;
+        ++dpth;
+        used = 0;
+    }
+}
+
+// Lane 0: from st.sorted / st.key (nsym >= 2 byte values by ascending count) the code lengths of at most kHufMaxBits and
+// the codes as the decoder's table has them (weight 1 first, byte values ascending within a weight); st.maxbits.
+PBSZ_HD void huf_build(State &st, uint32_t nsym) {
+    min_redundancy(st.key, (int32_t)nsym);
+    PBSZ_ROLLED
+    for (uint32_t i = 0; i < 40; ++i) st.ncodes[i] = 0;
+    for (uint32_t i = 0; i < nsym; ++i) st.ncodes[st.key[i] < 39 ? st.key[i] : 39]++;
+    // the length limit: every longer code becomes kHufMaxBits long, then the Kraft sum is brought back to one
+    for (uint32_t i = kHufMaxBits + 1; i < 40; ++i) st.ncodes[kHufMaxBits] += st.ncodes[i];
+    uint32_t total = 0;
+    for (uint32_t i = kHufMaxBits; i > 0; --i) total += st.ncodes[i] << (kHufMaxBits - i);
+    while (total != (1u << kHufMaxBits)) {
+        st.ncodes[kHufMaxBits]--;
+        for (uint32_t i = kHufMaxBits - 1; i > 0; --i)
+            if (st.ncodes[i]) {
+                st.ncodes[i]--;
+                st.ncodes[i + 1] += 2;
+                break;
+            }
+        --total;
+    }
+    uint32_t j = nsym, maxbits = 0;
+    for (uint32_t i = 1; i <= kHufMaxBits; ++i) {
+        if (st.ncodes[i]) maxbits = i;
+        for (uint32_t l = st.ncodes[i]; l > 0; --l) st.len[st.sorted[--j]] = (uint8_t)i;
+    }
+    st.maxbits = maxbits;
+    uint32_t at = 0;  // first table index of each weight w = maxbits + 1 - length
+    for (uint32_t w = 1; w <= maxbits; ++w) {
+        st.start[w] = at;
+        at += st.ncodes[maxbits + 1 - w] << (w - 1);
+    }
+    PBSZ_ROLLED
+    for (uint32_t s = 0; s < 256; ++s) {
+        const uint32_t l = st.len[s];
+        if (!l) continue;
+        const uint32_t w = maxbits + 1 - l;
+        st.code[s] = (uint16_t)(st.start[w] >> (w - 1));
+        st.start[w] += 1u << (w - 1);
+    }
+}
+
+// Lane 0, after huf_build: the FSE-compressed description of the weights of byte values 0 .. maxsym - 1 into st.wdesc,
+// header byte first. Returns its length, or 0 where there is none: fewer than two weights, one weight value only (its
+// states would take no bits and the decoder could not find the end), or more than 127 bytes. The distribution is brought
+// to 64 (accuracy log 6, the most a weight description may have) by rounding down, at least 1 for a value that occurs,
+// and the difference goes to the most frequent value. Works in the decoder state that shares the hash table's bytes.
+PBSZ_HD uint32_t weights_fse(State &st, uint32_t maxsym) {
+    pbsz::State &d = st.u.dec;
+    const uint32_t maxbits = st.maxbits, nw = maxsym, log = 6;
+    if (nw < 2) return 0;
+    PBSZ_ROLLED
+    for (uint32_t w = 0; w < kHufLogMax + 2; ++w) d.rank[w] = 0;
+    PBSZ_ROLLED
+    for (uint32_t i = 0; i < nw; ++i) {
+        const uint32_t l = st.len[i], w = l ? maxbits + 1 - l : 0u;
+        d.weights[i] = (uint8_t)w;
+        d.rank[w]++;
+    }
+    uint32_t nsym = 0, distinct = 0, sum = 0, big = 0;
+    PBSZ_ROLLED
+    for (uint32_t w = 0; w <= maxbits; ++w) {
+        const uint32_t c = d.rank[w];
+        uint32_t p = 0;
+        if (c) {
+            nsym = w + 1;
+            ++distinct;
+            p = (c << log) / nw;
+            if (!p) p = 1;
+        }
+        d.norm[w] = (int16_t)p;
+        sum += p;
+        if (p > (uint32_t)d.norm[big]) big = w;
+    }
+    if (distinct < 2) return 0;
+    while (sum > (1u << log)) {  // (rounding up to 1 overshot: at most eleven steps, and a value above 1 exists)
+        PBSZ_ROLLED
+        for (uint32_t w = 0; w < nsym; ++w)
+            if (d.norm[w] > d.norm[big]) big = w;
+        d.norm[big]--;
+        --sum;
+    }
+    d.norm[big] = (int16_t)(d.norm[big] + (int32_t)((1u << log) - sum));
+    BitWriter bw;
+    bw.init(st.wdesc + 1, 127);
+    bw.add(log - 5, 4);
+    uint32_t remaining = 1u << log, s = 0;
+    while (remaining > 0 && s < nsym) {  // fse_read_norm, the other way round
+        const uint32_t R = remaining + 1, bits = highbit(R) + 1, lower = (1u << (bits - 1)) - 1, thr = (1u << bits) - 1 - R;
+        const uint32_t p = (uint32_t)d.norm[s++], val = p + 1;
+        if (val < thr) bw.add(val, bits - 1);
+        else bw.add(val > lower ? val + thr : val, bits);
+        remaining -= p;
+        if (p == 0) {
+            uint32_t z = 0;
+            while (s < nsym && d.norm[s] == 0) {
+                ++z;
+                ++s;
+            }
+            while (z >= 3) {
+                bw.add(3, 2);
+                z -= 3;
+            }
+            bw.add(z, 2);
+        }
+    }
+    const uint32_t ncount = bw.flush();
+    if (bw.over || fse_build(d, d.wt, log, nsym) != OK) return 0;
+    EncTab &t = st.wt;
+    t.log = log;
+    uint32_t cum = 0;
+    PBSZ_ROLLED
+    for (uint32_t w = 0; w < nsym; ++w) {
+        t.p[w] = (uint8_t)d.norm[w];
+        t.cum[w] = (uint8_t)cum;
+        cum += (uint32_t)d.norm[w];
+    }
+    rank_states(t, d.wt);
+    // two states in turn, the decoder's first one on the even weights; the last two weights are where the decoder ends:
+    // their states take bits (the first state of a value takes the most, at least one), so its next read runs out
+    bw.init(st.wdesc + 1 + ncount, 127 - ncount);
+    const uint32_t e0 = t.state[t.cum[d.weights[nw - 1]]], e1 = t.state[t.cum[d.weights[nw - 2]]];
+    uint32_t xa = ((nw - 1) & 1) ? e1 : e0, xb = ((nw - 1) & 1) ? e0 : e1;
+    PBSZ_ROLLED
+    for (uint32_t i = nw - 2; i > 0; --i) {
+        if ((i - 1) & 1) fse_put(t, xb, d.weights[i - 1], bw);
+        else fse_put(t, xa, d.weights[i - 1], bw);
+    }
+    bw.add(xb, log);
+    bw.add(xa, log);
+    const uint32_t len = bw.finish();
+    if (bw.over) return 0;
+    st.wdesc[0] = (uint8_t)(ncount + len);  // < 128
+    return 1 + ncount + len;
+}
+
+// The literals section of lit[0, nlit) into blk[0, cap): its length, or kNone where it would not end before blk[cap].
+template <class P>
+PBSZ_HD uint32_t encode_literals(State &st, const uint8_t *lit, uint32_t nlit, uint8_t *blk, uint32_t cap) {
+    uint32_t type = 0;  // raw
+    if (nlit) {
+        for (uint32_t i = (uint32_t)P::lane(); i < nlit; i += (uint32_t)P::lanes()) P::aadd(&st.hist[lit[i]], 1u);
+        P::sync();
+        if (P::lane() == 0) {
+            uint32_t nsym = 0, maxsym = 0, maxcnt = 0;
+            PBSZ_ROLLED
+            for (uint32_t s = 0; s < 256; ++s) {
+                const uint32_t c = st.hist[s];
+                if (c) {
+                    ++nsym;
+                    maxsym = s;
+                    if (c > maxcnt) maxcnt = c;
+                }
+            }
+            st.nsym = nsym;
+            st.maxsym = maxsym;
+            st.maxcnt = maxcnt;
+            st.sbits[0] = st.sbits[1] = st.sbits[2] = st.sbits[3] = 0;
+        }
+        P::sync();
+        const uint32_t nsym = P::uni(st.nsym), maxsym = P::uni(st.maxsym);
+        if (nsym == 1) {
+            type = 1;
+        } else {
+            // byte values by ascending (count, value): each finds its own rank
+            for (uint32_t s = (uint32_t)P::lane(); s < 256; s += (uint32_t)P::lanes()) {
+                const uint32_t c = st.hist[s];
+                st.len[s] = 0;
+                if (!c) continue;
+                uint32_t rank = 0;
+                PBSZ_ROLLED
+                for (uint32_t t = 0; t < 256; ++t) {
+                    const uint32_t d = st.hist[t];
+                    rank += (d && (d < c || (d == c && t < s))) ? 1u : 0u;
+                }
+                st.sorted[rank] = (uint8_t)s;
+                st.key[rank] = c;
+            }
+            P::sync();
+            if (P::lane() == 0) {
+                huf_build(st, nsym);
+                const uint32_t direct = maxsym <= 128 ? 1 + (maxsym + 1) / 2 : 0u;  // the byte 127 + maxsym, then four bits each
+                const uint32_t fse = weights_fse(st, maxsym);
+                st.wfse = fse && (!direct || fse < direct) ? 1u : 0u;
+                st.desc = st.wfse ? fse : direct;  // 0: the weights cannot be described
+            }
+            P::sync();
+            const uint32_t nstreams = nlit <= 1023 ? 1u : 4u, seg = (nlit + 3) / 4;
+            for (uint32_t i = (uint32_t)P::lane(); i < nlit; i += (uint32_t)P::lanes()) {
+                const uint32_t k = nstreams == 1 ? 0u : i / seg;
+                P::aadd(&st.sbits[k], st.len[lit[i]]);
+            }
+            P::sync();
+            const uint32_t desc = st.desc;  // (these five stay vector values: only what is branched on is made uniform)
+            const uint32_t s0 = st.sbits[0] / 8 + 1, s1 = st.sbits[1] / 8 + 1, s2 = st.sbits[2] / 8 + 1,
+                           s3 = st.sbits[3] / 8 + 1;  // with the end mark
+            const uint32_t comp = P::uni(desc + (nstreams == 1 ? s0 : 6 + s0 + s1 + s2 + s3));
+            if (comp >= nlit || !P::uni(st.desc)) {
+                PBSZ_ECOV(E_HUF_REFUSED);
+            } else {
+                const uint32_t lh = nlit <= 1023 ? 3u : nlit <= 16383 ? 4u : 5u;
+                if (lh + comp >= cap) return kNone;
+                uint8_t *d = blk + lh + desc;
+                if (P::lane() == 0) {
+                    const uint32_t sf = nlit <= 1023 ? 0u : nlit <= 16383 ? 2u : 3u, bits = sf == 0 ? 10u : sf == 2 ? 14u : 18u;
+                    const uint64_t v = 2u | sf << 2 | (uint64_t)nlit << 4 | (uint64_t)comp << (4 + bits);
+                    for (uint32_t i = 0; i < lh; ++i) blk[i] = (uint8_t)(v >> (8 * i));
+                    if (st.wfse) {
+                        PBSZ_ROLLED
+                        for (uint32_t i = 0; i < desc; ++i) blk[lh + i] = st.wdesc[i];
+                    } else {
+                        blk[lh] = (uint8_t)(127 + maxsym);
+                        const uint32_t maxbits = st.maxbits;
+                        PBSZ_ROLLED
+                        for (uint32_t i = 0; i < maxsym; i += 2) {
+                            const uint32_t la = st.len[i], lb = i + 1 < maxsym ? st.len[i + 1] : 0u;
+                            const uint32_t wa = la ? maxbits + 1 - la : 0u, wb = lb ? maxbits + 1 - lb : 0u;
+                            blk[lh + 1 + i / 2] = (uint8_t)(wa << 4 | wb);
+                        }
+                    }
+                    if (nstreams == 4) {
+                        d[0] = (uint8_t)s0;
+                        d[1] = (uint8_t)(s0 >> 8);
+                        d[2] = (uint8_t)s1;
+                        d[3] = (uint8_t)(s1 >> 8);
+                        d[4] = (uint8_t)s2;
+                        d[5] = (uint8_t)(s2 >> 8);
+                    }
+                    PBSZ_ECOV(st.wfse ? E_WEIGHTS_FSE : E_WEIGHTS_DIRECT);
+                    PBSZ_ECOV(nstreams == 1 ? E_HUF_1STREAM : E_HUF_4STREAM);
+                }
+                for (uint32_t k = (uint32_t)P::lane(); k < nstreams; k += (uint32_t)P::lanes()) {
+                    const uint32_t from = nstreams == 1 ? 0u : k * seg, to = (nstreams == 1 || k == 3) ? nlit : from + seg;
+                    const uint32_t at = nstreams == 1 ? 0u : 6 + (k > 0 ? s0 : 0u) + (k > 1 ? s1 : 0u) + (k > 2 ? s2 : 0u);
+                    const uint32_t len = k == 0 ? s0 : k == 1 ? s1 : k == 2 ? s2 : s3;
+                    BitWriter bw;
+                    bw.init(d + at, len);
+                    PBSZ_ROLLED
+                    for (uint32_t i = to; i > from; --i) {
+                        const uint32_t b = lit[i - 1];
+                        bw.add(st.code[b], st.len[b]);
+                    }
+                    (void)bw.finish();
+                }
+                P::sync();
+                return lh + comp;
+            }
+        }
+    }
+    // raw or RLE literals
+    const uint32_t lh = nlit <= 31 ? 1u : nlit <= 4095 ? 2u : 3u;
+    const uint32_t body = type == 1 ? 1u : nlit;
+    if (lh + body >= cap) return kNone;
+    if (P::lane() == 0) {
+        const uint32_t v = lh == 1 ? (type | nlit << 3) : (type | (lh == 2 ? 1u : 3u) << 2 | nlit << 4);
+        for (uint32_t i = 0; i < lh; ++i) blk[i] = (uint8_t)(v >> (8 * i));
+        if (type == 1) blk[lh] = lit[0];
+        PBSZ_ECOV(type == 1 ? E_LIT_RLE : E_LIT_RAW);
+    }
+    if (type == 0) copy_bytes<P>(blk + lh, lit, nlit);
+    P::sync();
+    return lh + body;
+}
+
+// Lane 0: the sequences section of seqs[0, nseq) into b[0, cap); its length, or kNone where it would not fit.
+PBSZ_HD uint32_t encode_sequences(const State &st, const uint64_t *seqs, uint32_t nseq, uint8_t *b, uint32_t cap) {
+    uint32_t p = 0;
+    if (cap < 4) return kNone;
+    if (nseq < 128) {
+        b[p++] = (uint8_t)nseq;
+        PBSZ_ECOV(nseq ? E_NSEQ_1 : E_NSEQ_0);
+        if (!nseq) return p;
+    } else {
+        b[p++] = (uint8_t)((nseq >> 8) + 128);
+        b[p++] = (uint8_t)nseq;
+        PBSZ_ECOV(E_NSEQ_2);
+    }
+    b[p++] = 0;  // Predefined_Mode three times
+    BitWriter bw;
+    bw.init(b + p, cap - p);
+    uint32_t x_ll = 0, x_of = 0, x_ml = 0;
+    PBSZ_ROLLED
+    for (uint32_t k = nseq; k-- > 0;) {
+        const uint64_t q = seqs[k];
+        const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu, ov = (uint32_t)(q >> 36) + 3;
+        const uint32_t cl = ll_code(ll), cm = ml_code(ml), co = highbit(ov);
+        if (k == nseq - 1) {  // the decoder ends in these states: any state of the symbol serves
+            x_ll = st.ll.state[st.ll.cum[cl]];
+            x_of = st.of.state[st.of.cum[co]];
+            x_ml = st.ml.state[st.ml.cum[cm]];
+        } else {
+            fse_put(st.of, x_of, co, bw);
+            fse_put(st.ml, x_ml, cm, bw);
+            fse_put(st.ll, x_ll, cl, bw);
+        }
+        if (cl > 15) PBSZ_ECOV(E_LL_EXTRA);
+        if (cm > 31) PBSZ_ECOV(E_ML_EXTRA);
+        bw.add(ll - kLLBase[cl], kLLBits[cl]);
+        bw.add(ml - kMLBase[cm], kMLBits[cm]);
+        bw.add(ov - (1u << co), co);
+        if (bw.over) return kNone;
+    }
+    bw.add(x_ml, st.ml.log);
+    bw.add(x_of, st.of.log);
+    bw.add(x_ll, st.ll.log);
+    const uint32_t len = bw.finish();
+    return bw.over ? kNone : p + len;
+}
+
+// One block src[0, bn), 1 <= bn <= kBlockMax: its type and, for a compressed block, the compressed form in blk[0, size).
+// Returns type | size << 2 (size: payload_bytes), the same in every lane. init_tables has run on st. lit: kBlockMax bytes,
+// seqs: kSeqCap words, blk: bn bytes; nothing else is stored to.
+template <class P>
+PBSZ_HD uint32_t encode_block(State &st, const uint8_t *src, uint32_t bn, uint8_t *blk, uint8_t *lit, uint64_t *seqs) {
+    for (uint32_t i = (uint32_t)P::lane(); i < (1u << kHashLog); i += (uint32_t)P::lanes()) st.u.hash[i] = 0;
+    for (uint32_t i = (uint32_t)P::lane(); i < 256; i += (uint32_t)P::lanes()) st.hist[i] = 0;
+    if (P::lane() == 0) {
+        st.flag = 0;
+        st.cursor = 0;
+        st.nlit = 0;
+        st.nseq = 0;
+        st.ll_run = 0;
+        st.over = 0;
+        st.size = 0;
+    }
+    P::sync();
+    const uint32_t first = P::uni(src[0]);
+    for (uint32_t i = (uint32_t)P::lane(); i < bn; i += (uint32_t)P::lanes())
+        if (src[i] != first) st.flag = 1;
+    P::sync();
+    if (!P::uni(st.flag)) {
+        PBSZ_ECOV(E_BLOCK_RLE);
+        return B_RLE | 1u << 2;
+    }
+    for (uint32_t b0 = 0; b0 < bn;) {
+        // every position of the batch against the table as the batches before left it
+        for (uint32_t l = (uint32_t)P::lane(); l < kLanes; l += (uint32_t)P::lanes()) {
+            const uint32_t pos = b0 + l;
+            uint32_t m = 0, off = 0, h = kNone;
+            if (pos + kMinMatch <= bn) {
+                const uint32_t v = rd32(src + pos);
+                h = hash4(v);
+                const uint32_t c = st.u.hash[h];
+                if (c && rd32(src + c - 1) == v) {
+                    const uint32_t q = c - 1;  // q < pos
+                    off = pos - q;
+                    m = kMinMatch;
+                    bool open = true;
+                    while (open && pos + m + 4 <= bn) {
+                        const uint32_t x = rd32(src + q + m) ^ rd32(src + pos + m);
+                        if (x) {
+                            m += (uint32_t)__builtin_ctz(x) >> 3;
+                            open = false;
+                        } else {
+                            m += 4;
+                        }
+                    }
+                    while (open && pos + m < bn && src[q + m] == src[pos + m]) ++m;
+                }
+            }
+            st.mlen[l] = m;
+            st.moff[l] = off;
+            st.mh[l] = h;
+        }
+        P::sync();
+        for (uint32_t l = (uint32_t)P::lane(); l < kLanes; l += (uint32_t)P::lanes())
+            if (st.mh[l] != kNone) P::amax(&st.u.hash[st.mh[l]], b0 + l + 1);
+        if (P::lane() == 0) {  // the matches in position order: the first at or after the cursor
+            uint32_t cursor = st.cursor, nlit = st.nlit, nseq = st.nseq, run = st.ll_run;
+            PBSZ_ROLLED
+            for (uint32_t l = 0; l < kLanes; ++l) {
+                const uint32_t pos = b0 + l;
+                uint32_t at = kNone;
+                if (pos < bn && pos >= cursor) {
+                    const uint32_t m = st.mlen[l];
+                    if (m >= kMinMatch && nseq < kSeqCap) {
+                        const uint32_t off = st.moff[l];
+                        if (off < m) PBSZ_ECOV(E_MATCH_OVERLAP);
+                        if (off == 1) PBSZ_ECOV(E_MATCH_OFFSET_1);
+                        seqs[nseq++] = (uint64_t)run | (uint64_t)m << 18 | (uint64_t)off << 36;
+                        run = 0;
+                        cursor = pos + m;
+                    } else {
+                        if (m >= kMinMatch) PBSZ_ECOV(E_SEQ_CAP);
+                        at = nlit++;
+                        ++run;
+                    }
+                }
+                st.lidx[l] = at;
+            }
+            st.cursor = cursor;
+            st.nlit = nlit;
+            st.nseq = nseq;
+            st.ll_run = run;
+            st.next_b0 = cursor > b0 + kLanes ? cursor : b0 + kLanes;
+        }
+        P::sync();
+        for (uint32_t l = (uint32_t)P::lane(); l < kLanes; l += (uint32_t)P::lanes())
+            if (st.lidx[l] != kNone) lit[st.lidx[l]] = src[b0 + l];
+        b0 = P::uni(st.next_b0);
+    }
+    P::sync();
+    const uint32_t nlit = P::uni(st.nlit), nseq = P::uni(st.nseq);
+    uint32_t type = B_RAW, size = bn;
+    const uint32_t lsize = encode_literals<P>(st, lit, nlit, blk, bn);
+    if (lsize != kNone) {
+        if (P::lane() == 0) st.size = encode_sequences(st, seqs, nseq, blk + lsize, bn - lsize);
+        P::sync();
+        const uint32_t ssize = P::uni(st.size);
+        if (ssize != kNone && lsize + ssize < bn) {
+            type = B_COMPRESSED;
+            size = lsize + ssize;
+        }
+    }
+    PBSZ_ECOV(type == B_RAW ? E_BLOCK_RAW : E_BLOCK_COMPRESSED);
+    return type | size << 2;
+}
+
+// The frame of src[0, n), n < 4 GiB, into dst[0, room): BAD_SIZE where it needs more, and dst's contents are then
+// unspecified. *flen = the frame's length (with OK). Scratch as for encode_block. Never stores outside dst[0, room) and
+// the scratch.
+template <class P>
+PBSZ_HD int encode_frame(State &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint64_t room, uint8_t *blk, uint8_t *lit,
+                         uint64_t *seqs, uint64_t *flen) {
+    *flen = 0;
+    init_tables<P>(st);
+    const uint32_t hb = header_bytes(n);
+    if (room < (uint64_t)hb + 3) return BAD_SIZE;
+    if (P::lane() == 0) frame_header(n, dst);
+    uint64_t pos = hb;
+    if (n == 0) {
+        if (P::lane() == 0) block_header(dst + pos, 1, B_RAW, 0);
+        PBSZ_ECOV(E_EMPTY_LAST_BLOCK);
+        P::sync();
+        *flen = pos + 3;
+        return OK;
+    }
+    for (uint32_t at = 0; at < n; at += kBlockMax) {
+        const uint32_t bn = n - at < kBlockMax ? n - at : kBlockMax;
+        const uint32_t r = encode_block<P>(st, src + at, bn, blk, lit, seqs);
+        const uint32_t type = r & 3u, size = r >> 2;
+        if (room - pos < (uint64_t)3 + size) return BAD_SIZE;
+        if (P::lane() == 0) block_header(dst + pos, at + bn == n ? 1u : 0u, type, type == B_COMPRESSED ? size : bn);
+        pos += 3;
+        if (type == B_RLE) {
+            if (P::lane() == 0) dst[pos] = src[at];
+        } else {
+            copy_bytes<P>(dst + pos, type == B_RAW ? src + at : blk, size);
+        }
+        pos += size;
+        P::sync();  // blk, lit and seqs go to the next block
+    }
+    *flen = pos;
+    return OK;
+}
+
+}  // namespace enc
+}  // namespace pbsz

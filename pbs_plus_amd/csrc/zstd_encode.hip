@@ -1,0 +1,262 @@
+// Zstandard frames written on the device (pbsgpu_zstd_encode_device, the zstd leg of pbsgpu_blob_encode2_device;
+// include/pbsgpu.h).
+//
+// The format lives in zstd_encode.h, once, for these kernels and for the CPU build that runs under sanitizers. This file
+// adds the cooperation between lanes and the assembly of the blocks into frames:
+//   k_zenc_blocks    one wave (a workgroup of 64) per 128 KiB block, workgroups striding over all blocks of all chunks of a
+//                    round. Blocks are independent (no match reaches before its block), so any wave takes any block. The
+//                    wave's State — the 16 KiB hash table, histogram, Huffman code, the three predefined FSE encoding
+//                    tables, the batch of 64 positions — is the workgroup's LDS (about 20 KiB: seven workgroups fit a CU's
+//                    160 KiB). The block's literals (128 KiB) and sequences (kSeqCap * 8 = 192 KiB) lie in the
+//                    workgroup's part of the slot's scratch; its compressed form goes to the BLOCK's 128 KiB of scratch,
+//                    because the frame it belongs to is put together later. Per block: type and size.
+//   k_zenc_assemble  one workgroup of 256 per chunk: a prefix over its blocks' sizes (wave 0), then the frame header, the
+//                    block headers and the payloads (content for raw blocks, one byte for RLE, the compressed form) to
+//                    their places in the room. It records the frame's length and the status; for the blob call the
+//                    verdict instead: a frame that is not strictly shorter than its chunk is not written.
+//   sync()           a workgroup barrier with its fences, wherever lanes read what other lanes stored.
+// The host plans rounds of whole chunks so that the per-block scratch stays bounded (kRoundBlocks blocks, 256 MiB), and
+// enqueues them back to back on one stream: nothing is read back in between.
+// No scratch memory, no spills, no dynamically indexed private arrays (tests/test_zstd_encode_surface.py).
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "engine_internal.h"
+#include "zstd_encode.h"
+
+using namespace pbse;
+namespace ze = pbsz::enc;
+
+namespace pbsk {
+namespace zenc {
+
+struct Plan {
+    const uint8_t *src;
+    const Job *jobs;         // every chunk of the call
+    const uint32_t *bchunk;  // every block of the call: its chunk
+    uint8_t *blkout;         // the round's blocks, kBlockMax bytes each
+    uint32_t *bres;          // the round's blocks: type | size << 2
+    uint64_t *boff;          // the round's blocks: where the block header goes in its frame
+    uint8_t *lit;            // stride * kBlockMax
+    uint64_t *seqs;          // stride * kSeqCap
+    uint8_t *dst;
+    uint64_t *res;           // every chunk: frame length | status << 56
+    uint32_t b0, b1, c0, c1; // the round
+    uint32_t stride, blob;
+};
+
+struct WaveLanes {
+    static __device__ __forceinline__ int lane() {
+        int x = (int)threadIdx.x;
+        asm volatile("" : "+v"(x));  // taken anew at every use
+        return x;
+    }
+    static __device__ __forceinline__ int lanes() { return 64; }
+    static __device__ __forceinline__ void sync() { __syncthreads(); }
+    static __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+    static __device__ __forceinline__ void amax(uint32_t *p, uint32_t v) { atomicMax(p, v); }
+    static __device__ __forceinline__ void aadd(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
+};
+
+__global__ __launch_bounds__(64) void k_zenc_blocks(Plan pl) {
+    __shared__ ze::State st;
+    ze::init_tables<WaveLanes>(st);
+    uint8_t *lit = pl.lit + (uint64_t)blockIdx.x * pbsz::kBlockMax;
+    uint64_t *seqs = pl.seqs + (uint64_t)blockIdx.x * ze::kSeqCap;
+    for (uint32_t b = pl.b0 + blockIdx.x; b < pl.b1; b += pl.stride) {
+        const Job j = pl.jobs[pl.bchunk[b]];  // (uniform addresses: scalar loads)
+        const uint32_t at = (b - j.first) * pbsz::kBlockMax;
+        const uint32_t bn = j.len - at < pbsz::kBlockMax ? j.len - at : pbsz::kBlockMax;
+        uint8_t *blk = pl.blkout + (uint64_t)(b - pl.b0) * pbsz::kBlockMax;
+        const uint32_t r = ze::encode_block<WaveLanes>(st, pl.src + j.src_off + at, bn, blk, lit, seqs);
+        if (threadIdx.x == 0) pl.bres[b - pl.b0] = r;
+        __syncthreads();  // State, the literals and the sequences go to the next block
+    }
+}
+
+__global__ __launch_bounds__(256) void k_zenc_assemble(Plan pl) {
+    __shared__ uint64_t s_total;
+    const uint32_t t = threadIdx.x;
+    for (uint32_t c = pl.c0 + blockIdx.x; c < pl.c1; c += gridDim.x) {
+        const Job j = pl.jobs[c];
+        const uint32_t nb = (uint32_t)(((uint64_t)j.len + pbsz::kBlockMax - 1) / pbsz::kBlockMax);  // 0: the empty frame
+        const uint32_t hb = ze::header_bytes(j.len);
+        const uint32_t fb = j.first - pl.b0;
+        if (t < 64) {  // where each block goes: 3 + payload bytes each, behind the frame header
+            uint64_t carry = hb;
+            for (uint32_t g = 0; g < nb; g += 64) {
+                const uint32_t k = g + t;
+                const uint32_t sz = k < nb ? 3u + (pl.bres[fb + k] >> 2) : 0u;
+                uint32_t incl = sz;  // (64 blocks: below 2^32)
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t u = __shfl_up(incl, d, 64);
+                    if ((int)t >= d) incl += u;
+                }
+                if (k < nb) pl.boff[fb + k] = carry + incl - sz;
+                carry += __shfl(incl, 63, 64);
+            }
+            if (t == 0) s_total = nb ? carry : (uint64_t)hb + 3;
+        }
+        __syncthreads();
+        const uint64_t flen = s_total;
+        const bool write = pl.blob ? flen < j.len : flen <= j.room;
+        const uint32_t status = pl.blob ? (write ? PBSGPU_BLOB_COMPRESSED : PBSGPU_BLOB_UNCOMPRESSED)
+                                        : (write ? PBSGPU_ZSTD_OK : PBSGPU_ZSTD_BAD_SIZE);
+        if (write) {
+            uint8_t *d = pl.dst + j.dst_off;
+            if (t == 0) {
+                ze::frame_header(j.len, d);
+                if (nb == 0) ze::block_header(d + hb, 1, ze::B_RAW, 0);
+            }
+            for (uint32_t k = 0; k < nb; ++k) {
+                const uint32_t r = pl.bres[fb + k], type = r & 3u, size = r >> 2;
+                const uint32_t at = k * pbsz::kBlockMax;
+                const uint32_t bn = j.len - at < pbsz::kBlockMax ? j.len - at : pbsz::kBlockMax;
+                uint8_t *o = d + pl.boff[fb + k];
+                const uint8_t *content = pl.src + j.src_off + at;
+                if (t == 0) {
+                    ze::block_header(o, k + 1 == nb ? 1u : 0u, type, type == ze::B_COMPRESSED ? size : bn);
+                    if (type == ze::B_RLE) o[3] = content[0];
+                }
+                if (type != ze::B_RLE) {
+                    const uint8_t *from = type == ze::B_RAW ? content : pl.blkout + (uint64_t)(fb + k) * pbsz::kBlockMax;
+#pragma unroll 8
+                    for (uint32_t i = t; i < size; i += 256) o[3 + i] = from[i];
+                }
+            }
+        }
+        if (t == 0) pl.res[c] = (write || pl.blob ? flen : 0ull) | (uint64_t)status << 56;
+        __syncthreads();  // s_total goes to the next chunk
+    }
+}
+
+constexpr uint32_t kRoundBlocks = 2048;  // 256 MiB of per-block scratch
+
+// The frames of jobs[0, n) (Job::first is filled in here), enqueued on the slot's stream, nothing synchronised.
+// *res_dev = per chunk, frame length | status << 56 (blob: the kind, and nothing written unless compressed).
+int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob, uint64_t **res_dev) {
+    const uint32_t n = (uint32_t)jobs.size();
+    uint64_t nblocks = 0;
+    for (Job &j : jobs) {
+        if (nblocks >= (1ull << 32)) return PBSGPU_E_INVALID;
+        j.first = (uint32_t)nblocks;
+        nblocks += ((uint64_t)j.len + pbsz::kBlockMax - 1) / pbsz::kBlockMax;
+    }
+    if (nblocks >= (1ull << 32)) return PBSGPU_E_INVALID;  // 512 TiB in one call
+    std::vector<uint32_t> bchunk((size_t)nblocks);
+    for (uint32_t c = 0; c < n; ++c) {
+        const uint64_t end = c + 1 < n ? jobs[c + 1].first : nblocks;
+        for (uint64_t b = jobs[c].first; b < end; ++b) bchunk[b] = c;
+    }
+    // rounds of whole chunks, kRoundBlocks blocks at the most unless one chunk alone has more
+    std::vector<uint32_t> cuts{0};
+    uint64_t most = 0;
+    for (uint32_t c = 0, from = 0; c < n; ++c) {
+        const uint64_t end = c + 1 < n ? jobs[c + 1].first : nblocks;
+        if (end - jobs[from].first > kRoundBlocks && c > from) {
+            cuts.push_back(c);
+            from = c;
+        }
+        most = std::max(most, end - jobs[from].first);
+    }
+    cuts.push_back(n);
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, (uint64_t)e->num_cus * 4));
+    const size_t lit_bytes = (size_t)grid * pbsz::kBlockMax;
+    CHK(s->recs.ensure((size_t)n * sizeof(Job) + 64));
+    CHK(s->sugg_idx.ensure((size_t)nblocks * 4 + 64));
+    CHK(s->order.ensure((size_t)n * 8 + 64));
+    CHK(s->data.ensure((size_t)most * pbsz::kBlockMax + 64));
+    CHK(s->par.ensure(lit_bytes + (size_t)grid * ze::kSeqCap * 8));
+    CHK(s->scan_tmp.ensure((size_t)most * 16 + 64));
+    CHK(staged_h2d(*s, s->recs.p, jobs.data(), (size_t)n * sizeof(Job), s->stream));
+    if (nblocks) CHK(staged_h2d(*s, s->sugg_idx.p, bchunk.data(), (size_t)nblocks * 4, s->stream));
+    Plan pl{};
+    pl.src = src;
+    pl.jobs = s->recs.as<Job>();
+    pl.bchunk = s->sugg_idx.as<uint32_t>();
+    pl.blkout = s->data.as<uint8_t>();
+    pl.boff = s->scan_tmp.as<uint64_t>();
+    pl.bres = reinterpret_cast<uint32_t *>(s->scan_tmp.as<uint64_t>() + most);
+    pl.lit = s->par.as<uint8_t>();
+    pl.seqs = reinterpret_cast<uint64_t *>(s->par.as<uint8_t>() + lit_bytes);
+    pl.dst = dst;
+    pl.res = s->order.as<uint64_t>();
+    pl.stride = grid;
+    pl.blob = blob ? 1u : 0u;
+    for (size_t r = 0; r + 1 < cuts.size(); ++r) {
+        pl.c0 = cuts[r];
+        pl.c1 = cuts[r + 1];
+        pl.b0 = jobs[pl.c0].first;
+        pl.b1 = pl.c1 < n ? jobs[pl.c1].first : (uint32_t)nblocks;
+        if (pl.c0 == pl.c1) continue;
+        if (pl.b1 > pl.b0) {
+            hipLaunchKernelGGL(k_zenc_blocks, dim3(std::min<uint32_t>(grid, pl.b1 - pl.b0)), dim3(64), 0, s->stream, pl);
+            HIPCHK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_zenc_assemble, dim3(std::min<uint32_t>(pl.c1 - pl.c0, (uint32_t)e->num_cus * 8)), dim3(256), 0,
+                           s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
+    *res_dev = pl.res;
+    return PBSGPU_OK;
+}
+
+}  // namespace zenc
+}  // namespace pbsk
+
+namespace {
+
+int zstd_encode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu_segment *chunks, uint32_t n,
+                const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *frame_len) {
+    if (!e) return PBSGPU_E_INVALID;
+    if (n == 0) return PBSGPU_OK;
+    if (!chunks || !out || !status || (!src && nbytes) || (!dst && dst_cap)) return PBSGPU_E_INVALID;
+    uint64_t lo = ~0ull, hi = 0;  // the part of dst the call may write
+    for (uint32_t i = 0; i < n; ++i) {
+        if (chunks[i].length >> 32) return PBSGPU_E_INVALID;  // a chunk is 16 MiB at the most
+        if (chunks[i].length > nbytes || chunks[i].offset > nbytes - chunks[i].length) return PBSGPU_E_INVALID;
+        if (out[i].length > dst_cap || out[i].offset > dst_cap - out[i].length) return PBSGPU_E_INVALID;
+        if (out[i].length) {
+            lo = std::min(lo, out[i].offset);
+            hi = std::max(hi, out[i].offset + out[i].length);
+        }
+    }
+    std::vector<uint32_t> order;
+    for (uint32_t i = 0; i < n; ++i)
+        if (out[i].length) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return out[a].offset < out[b].offset; });
+    for (size_t k = 1; k < order.size(); ++k)
+        if (out[order[k - 1]].offset + out[order[k - 1]].length > out[order[k]].offset) return PBSGPU_E_INVALID;
+    if (hi > lo && nbytes) {
+        const uintptr_t d0 = (uintptr_t)dst + lo, d1 = (uintptr_t)dst + hi, s0 = (uintptr_t)src;
+        if (d0 < s0 + nbytes && s0 < d1) return PBSGPU_E_INVALID;  // a destination inside the source
+    }
+    CHK(set_device(e));
+    if ((nbytes && !is_device_pointer(src)) || (hi > lo && !is_device_pointer(dst))) return PBSGPU_E_INVALID;
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    std::vector<pbsk::zenc::Job> jobs(n);
+    for (uint32_t i = 0; i < n; ++i) jobs[i] = pbsk::zenc::Job{chunks[i].offset, out[i].offset, out[i].length, (uint32_t)chunks[i].length, 0};
+    uint64_t *res = nullptr;
+    CHK(pbsk::zenc::enqueue(e, s, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), jobs, false, &res));
+    std::vector<uint64_t> back(n);
+    CHK(fetch_result(s, back.data(), res, (size_t)n * 8));  // the call's one synchronisation
+    for (uint32_t i = 0; i < n; ++i) {
+        status[i] = (uint8_t)(back[i] >> 56);
+        if (frame_len) frame_len[i] = back[i] & ((1ull << 56) - 1);
+    }
+    return PBSGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbsgpu_zstd_encode_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *chunks, uint32_t n,
+                              const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *frame_len) {
+    return zstd_encode(eng, src, src_bytes, chunks, n, out, dst, dst_cap, status, frame_len);
+}
+
+}  // extern "C"

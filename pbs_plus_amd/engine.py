@@ -421,6 +421,67 @@ class Engine:
             raise
         return dst, status[:n], decoded[:n], oa
 
+    def zstd_encode(self, data, chunks, out=None, dst=None, nbytes: int | None = None):
+        """Compress the chunks [(offset, length)] of the device buffer `data` to one zstd frame each in one call
+        (pbsgpu_zstd_encode_device): frame i goes to dst at out[i] = (offset, room). out None lays rooms of
+        zstd_encode_bound(length) out back to back; dst None allocates what `out` needs. Returns (dst, status per chunk:
+        0 ok, 2 the room is too small, frame length per chunk (0 unless ok), out as an (n, 2) array)."""
+        dp, dn = self._dev(data, nbytes)
+        assert dp is not None, "zstd_encode() wants device memory"
+        ch = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)
+        n = int(ch.shape[0])
+        if out is None:
+            rooms = np.array([zstd_encode_bound(int(v)) for v in ch[:, 1]], dtype=np.uint64)
+            ends = np.cumsum(rooms)
+            out = np.stack([ends - rooms, rooms], axis=1)
+        oa = np.ascontiguousarray(out, dtype=np.uint64).reshape(-1, 2)
+        assert oa.shape[0] == n, "one (offset, room) per chunk"
+        own = dst is None
+        if own:
+            dst = self.alloc(max(int((oa[:, 0] + oa[:, 1]).max()) if n else 0, 16))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        flen = np.zeros(max(n, 1), dtype=np.uint64)
+        try:
+            check(self._L.pbsgpu_zstd_encode_device(self._h, dp, dn, ch.ctypes.data if n else None, n, oa.ctypes.data if n else None,
+                                                    dst.ptr, dst.nbytes, status.ctypes.data, flen.ctypes.data),
+                  "zstd_encode_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return dst, status[:n], flen[:n], oa
+
+    def blob_encode2(self, src, chunks, dst=None, nbytes: int | None = None, zstd=True):
+        """blob_encode() with the blob's kind decided on the device (pbsgpu_blob_encode2_device): with zstd=True a chunk whose
+        zstd frame is strictly shorter than the chunk becomes a compressed blob, every other one the uncompressed blob
+        blob_encode() writes. Blob i lies at offsets[i] and is lens[i] long; the slots [offsets[i], offsets[i + 1]) are
+        those of the uncompressed layout and are not compacted. zstd=False gives blob_encode()'s outputs exactly.
+        Returns (buffer, offsets (n + 1), lens (n), kinds (n: 0 uncompressed, 1 compressed), CRCs (n), stats dict)."""
+        segs, n = _segs(chunks)
+        sp, sn = self._dev(src, nbytes)
+        assert sp is not None, "blob_encode2() wants device memory"
+        own = dst is None
+        if own:
+            total = C.c_uint64()
+            check(self._L.pbsgpu_blob_encoded_size(segs, n, C.byref(total)), "blob_encoded_size")
+            dst = self.alloc(max(total.value, 16))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        kinds = np.zeros(max(n, 1), dtype=np.uint8)
+        crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        st = _lib.EncodeStats()
+        try:
+            check(self._L.pbsgpu_blob_encode2_device(self._h, sp, sn, segs, n, _lib.ENCODE_F_ZSTD if zstd else 0, dst.ptr,
+                                                     dst.nbytes, offs.ctypes.data, lens.ctypes.data, kinds.ctypes.data,
+                                                     crcs.ctypes.data, C.byref(st)), "blob_encode2_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        stats = dict(blobs=[int(v) for v in st.blobs], blob_bytes=[int(v) for v in st.blob_bytes],
+                     chunk_bytes=[int(v) for v in st.chunk_bytes], frame_bytes=int(st.frame_bytes), crc_bytes=int(st.crc_bytes))
+        return dst, offs, lens[:n], kinds[:n], crcs[:n], stats
+
     # ---- payload-stream assembly (.ppxar layout: markers + 16-byte headers + file bodies) ----------
     def payload_pack(self, src, files, dst, with_start: bool = True, with_tail: bool = True):
         """Lay the file bodies `files` = [(offset, length)] of device buffer `src` out as the pxar
@@ -496,6 +557,11 @@ def blob_magic(kind: int) -> bytes:
     out = (C.c_uint8 * 8)()
     check(_lib.lib().pbsgpu_blob_magic(int(kind), out), "blob_magic")
     return bytes(out)
+
+
+def zstd_encode_bound(n: int) -> int:
+    """No zstd frame Engine.zstd_encode() writes for n bytes of content is longer (pbsgpu_zstd_encode_bound, host only)."""
+    return int(_lib.lib().pbsgpu_zstd_encode_bound(int(n)))
 
 
 def zstd_frame_info(frame) -> dict:
