@@ -49,6 +49,12 @@ type (
 		Used    uint64
 		Stats   DedupStats
 	}
+	Uploaded2 struct {
+		Uploaded
+		Lens    []uint32
+		Kinds   []uint8
+		Encoded EncodeStats
+	}
 	ReuseChunk struct {
 		Size, Padding, EndOffset uint64
 		Digest                   [32]byte
@@ -156,6 +162,9 @@ func (r *Ring) EncodeBlobs(uint32, []ChunkInfo, []bool, unsafe.Pointer, uint64) 
 func (r *Ring) UploadNew(*KnownChunks, uint32, []ChunkInfo, bool, unsafe.Pointer, uint64) (Uploaded, error) {
 	return Uploaded{}, ErrNotBuilt
 }
+func (r *Ring) UploadNew2(*KnownChunks, uint32, []ChunkInfo, bool, bool, unsafe.Pointer, uint64) (Uploaded2, error) {
+	return Uploaded2{}, ErrNotBuilt
+}
 func (r *Ring) Copy(uint32, uint64, uint64, unsafe.Pointer) error                { return ErrNotBuilt }
 func (r *Ring) Quiesce() error                                                   { return ErrNotBuilt }
 func (r *Ring) Park() error                                                      { return ErrNotBuilt }
@@ -174,6 +183,9 @@ func (k *KnownChunks) AddDynamicIndex([]byte) error                           { 
 func (k *KnownChunks) Classify([]ChunkInfo, bool) ([]bool, DedupStats, error) { return nil, DedupStats{}, ErrNotBuilt }
 func (k *KnownChunks) UploadNew(unsafe.Pointer, uint64, []ChunkInfo, []uint64, []uint64, bool, unsafe.Pointer, uint64) (Uploaded, error) {
 	return Uploaded{}, ErrNotBuilt
+}
+func (k *KnownChunks) UploadNew2(unsafe.Pointer, uint64, []ChunkInfo, []uint64, []uint64, bool, bool, unsafe.Pointer, uint64) (Uploaded2, error) {
+	return Uploaded2{}, ErrNotBuilt
 }
 func (k *KnownChunks) Len() int                                               { return 0 }
 func (k *KnownChunks) Close()                                                 {}

@@ -904,6 +904,75 @@ func (r *Ring) UploadNew(known *KnownChunks, stream uint32, recs []ChunkInfo, in
 	return uploadedFrom(flags, offsets, crcs, u, st), err
 }
 
+// Uploaded2 is what UploadNew2 returns: Uploaded, and per new entry the blob's length and kind (0 uncompressed, 1 zstd
+// compressed). Blob i lies at Offsets[i], in the slot the uncompressed layout gives it, and is Lens[i] long; slots are not
+// compacted, so Used, the capacity verdict and a sizing call are those of UploadNew.
+type Uploaded2 struct {
+	Uploaded
+	Lens    []uint32
+	Kinds   []uint8
+	Encoded EncodeStats
+}
+
+// upload2Out holds the C outputs of the two UploadNew2 calls.
+type upload2Out struct {
+	flags   []C.uint8_t
+	offsets []uint64
+	lens    []uint32
+	kinds   []uint8
+	crcs    []uint32
+	used    C.uint64_t
+	st      C.pbsgpu_dedup_stats
+	enc     C.pbsgpu_encode_stats
+}
+
+func newUpload2Out(n int) *upload2Out {
+	return &upload2Out{flags: make([]C.uint8_t, n), offsets: make([]uint64, n), lens: make([]uint32, n), kinds: make([]uint8, n),
+		crcs: make([]uint32, n)}
+}
+
+func (o *upload2Out) result() Uploaded2 {
+	out := Uploaded2{Uploaded: uploadedFrom(o.flags, o.offsets, o.crcs, o.used, o.st), Lens: o.lens, Kinds: o.kinds}
+	for k := 0; k < 2; k++ {
+		out.Encoded.Blobs[k], out.Encoded.BlobBytes[k] = uint64(o.enc.blobs[k]), uint64(o.enc.blob_bytes[k])
+		out.Encoded.ChunkBytes[k] = uint64(o.enc.chunk_bytes[k])
+	}
+	out.Encoded.FrameBytes, out.Encoded.CRCBytes = uint64(o.enc.frame_bytes), uint64(o.enc.crc_bytes)
+	return out
+}
+
+func encodeFlags(zstd bool) C.uint32_t {
+	if zstd {
+		return C.PBSGPU_ENCODE_F_ZSTD
+	}
+	return 0
+}
+
+// UploadNew2 is UploadNew for the writers that compress (internal/tapeio/converter.go:399, :410-435): with zstd true a new
+// chunk whose zstd frame is strictly shorter than the chunk becomes a compressed blob, straight out of the ring's pages;
+// every other one is the uncompressed blob UploadNew writes. The loop of a compressing writer: Poll -> UploadNew2 -> send
+// dst + Offsets[i], Lens[i] for every new entry -> append to the index -> Release(last End). With zstd false every
+// output is UploadNew's.
+func (r *Ring) UploadNew2(known *KnownChunks, stream uint32, recs []ChunkInfo, insert, zstd bool, dst unsafe.Pointer,
+	dstCap uint64) (Uploaded2, error) {
+	defer runtime.KeepAlive(r)
+	defer runtime.KeepAlive(known)
+	if len(recs) == 0 || known == nil {
+		return Uploaded2{}, errors.New("pbsgpu: UploadNew2 needs entries and a known-chunk set")
+	}
+	cr := toRecords(recs)
+	o := newUpload2Out(len(recs))
+	ins := C.int(0)
+	if insert {
+		ins = 1
+	}
+	err := check(C.pbsgpu_ring_upload_new2_device(r.h, known.h, C.uint32_t(stream), &cr[0], C.uint64_t(len(cr)), ins,
+		encodeFlags(zstd), dst, C.uint64_t(dstCap), &o.flags[0], (*C.uint64_t)(unsafe.Pointer(&o.offsets[0])),
+		(*C.uint32_t)(unsafe.Pointer(&o.lens[0])), (*C.uint8_t)(unsafe.Pointer(&o.kinds[0])),
+		(*C.uint32_t)(unsafe.Pointer(&o.crcs[0])), &o.used, &o.st, &o.enc), "ring_upload_new2_device")
+	return o.result(), err
+}
+
 // Copy writes the raw stream bytes [offset, offset + length), which polled entries must cover and no Release may have
 // passed, into device memory dst — for consumers that compress on the host or want the bytes unframed.
 func (r *Ring) Copy(stream uint32, offset, length uint64, dst unsafe.Pointer) error {
@@ -1166,6 +1235,28 @@ func (k *KnownChunks) UploadNew(src unsafe.Pointer, srcBytes uint64, recs []Chun
 		dst, C.uint64_t(dstCap), &flags[0], (*C.uint64_t)(unsafe.Pointer(&boff[0])), (*C.uint32_t)(unsafe.Pointer(&crcs[0])),
 		&u, &st), "known_upload_new_device")
 	return uploadedFrom(flags, boff, crcs, u, st), err
+}
+
+// UploadNew2 is UploadNew with the blob's kind decided on the device (zstd true), as Engine.EncodeBlobs2 decides it: see
+// Ring.UploadNew2. dst must not overlap src: the frames are read again for their CRC.
+func (k *KnownChunks) UploadNew2(src unsafe.Pointer, srcBytes uint64, recs []ChunkInfo, offsets, lengths []uint64, insert, zstd bool,
+	dst unsafe.Pointer, dstCap uint64) (Uploaded2, error) {
+	defer runtime.KeepAlive(k)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 || len(segs) != len(recs) {
+		return Uploaded2{}, errors.New("pbsgpu: UploadNew2 needs entries and one (offset, length) per entry")
+	}
+	cr := toRecords(recs)
+	o := newUpload2Out(len(recs))
+	ins := C.int(0)
+	if insert {
+		ins = 1
+	}
+	err = check(C.pbsgpu_known_upload_new2_device(k.h, src, C.uint64_t(srcBytes), &cr[0], &segs[0], C.uint64_t(len(cr)), ins,
+		encodeFlags(zstd), dst, C.uint64_t(dstCap), &o.flags[0], (*C.uint64_t)(unsafe.Pointer(&o.offsets[0])),
+		(*C.uint32_t)(unsafe.Pointer(&o.lens[0])), (*C.uint8_t)(unsafe.Pointer(&o.kinds[0])),
+		(*C.uint32_t)(unsafe.Pointer(&o.crcs[0])), &o.used, &o.st, &o.enc), "known_upload_new2_device")
+	return o.result(), err
 }
 
 // Len is the number of digests in the set.

@@ -852,6 +852,39 @@ int pbsgpu_known_upload_new_device(pbsgpu_known *known, const void *src, uint64_
                                    uint64_t n, int insert, void *dst, uint64_t dst_cap, uint8_t *known_out,
                                    uint64_t *blob_off, uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats);
 
+/* ---- the fused calls with the blob's kind decided on the device ----------------------------------------------------------
+ * The two calls above for the writers of the reference that compress (the tape converter's local store,
+ * backupproxy.NewLocalStore(storeDir, c.chunkCfg, true), internal/tapeio/converter.go:399, and its PBS store and session
+ * with Compress: c.cfg.Compress, converter.go:410-435): what pbsgpu_blob_encode2_device is to pbsgpu_blob_encode_device.
+ * flags = 0: the call above output for output (dst, blob_off, crcs, *used, known_out, stats, the set afterwards), with
+ * lens[i] = 12 + size and kinds[i] = PBSGPU_BLOB_UNCOMPRESSED for every new record.
+ * flags = PBSGPU_ENCODE_F_ZSTD: blob i of a new record lies in the slot [blob_off[i], blob_off[i] + 12 + size) that the
+ * uncompressed layout gives it, so *used, the capacity verdict and the sizing call (dst = NULL, dst_cap = 0) are exactly
+ * those of the plain call; slots are not compacted and the bytes of a slot behind lens[i] are unspecified. The kind
+ * follows pbsgpu_blob_encode2_device's rule: the chunk is compressed, and only when the frame is strictly shorter than the
+ * chunk the blob is [compressed magic | CRC-32 LE of the frame | frame], the frame byte for byte the one
+ * pbsgpu_zstd_encode_device makes of the chunk's bytes; otherwise it is the uncompressed blob, byte for byte. A ring chunk
+ * in two pages is one chunk to the encoder. blob_off, lens, kinds and crcs (lens, kinds, crcs may be NULL) are untouched
+ * for known records; enc_stats (may be NULL) as in pbsgpu_blob_encode2_device, over the new records.
+ * Everything the section above promises holds: refusals are decided on the host before any device work (the ones above,
+ * plus PBSGPU_E_INVALID for an unknown flag bit and, in the contiguous form with F_ZSTD, for a dst that overlaps src: the
+ * frames are read again for their CRC); on PBSGPU_E_CAPACITY no byte of dst is written, no block is encoded and the set
+ * is unchanged, while known_out, stats and *used are final; one leased stream and one synchronisation (two when the set
+ * grows); usable between pumps while the services run. The encoder's scratch is the engine's (up to 256 MiB of blocks
+ * per round and 448 KiB per workgroup); a call that has to grow it waits for the device once. */
+#define PBSGPU_HAS_UPLOAD_NEW2 1
+int pbsgpu_ring_upload_new2_device(pbsgpu_ring *ring, pbsgpu_known *known, uint32_t stream /* or PBSGPU_RING_ANY_STREAM */,
+                                   const pbsgpu_record *recs /* host, as polled */, uint64_t n, int insert, uint32_t flags,
+                                   void *dst, uint64_t dst_cap, uint8_t *known_out /* n, may be NULL */,
+                                   uint64_t *blob_off /* n */, uint32_t *lens /* n */, uint8_t *kinds /* n */,
+                                   uint32_t *crcs /* n, may be NULL */, uint64_t *used, pbsgpu_dedup_stats *stats,
+                                   pbsgpu_encode_stats *enc_stats /* may be NULL */);
+int pbsgpu_known_upload_new2_device(pbsgpu_known *known, const void *src, uint64_t src_bytes,
+                                    const pbsgpu_record *recs /* host: the digests */, const pbsgpu_segment *chunks /* n */,
+                                    uint64_t n, int insert, uint32_t flags, void *dst, uint64_t dst_cap,
+                                    uint8_t *known_out, uint64_t *blob_off, uint32_t *lens, uint8_t *kinds, uint32_t *crcs,
+                                    uint64_t *used, pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc_stats);
+
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or
  * several engines in one process) ingests its own streams. The one exchange step is the digest-set reduce for cross-file

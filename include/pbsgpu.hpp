@@ -95,6 +95,26 @@ struct Uploaded {
     pbsgpu_dedup_stats stats{};
 };
 
+// What the fused calls with the blob's kind decided on the device return (UploadNew2): Uploaded, and per new record
+// the blob's length and kind; the blob lies at offsets[i] in the slot the uncompressed layout gives it.
+struct Uploaded2 {
+    uint64_t bytes = 0;              // as Uploaded::bytes: the slots' bytes, or the bytes needed
+    std::vector<uint8_t> known;
+    std::vector<uint64_t> offsets;   // per new record: its slot's offset in dst
+    std::vector<uint32_t> lens;      // per new record: the blob's length, what is sent
+    std::vector<uint8_t> kinds;      // per new record: PBSGPU_BLOB_UNCOMPRESSED or PBSGPU_BLOB_COMPRESSED
+    std::vector<uint32_t> crcs;      // per new record
+    pbsgpu_dedup_stats stats{};
+    pbsgpu_encode_stats encoded{};
+    void Resize(size_t n) {
+        known.assign(n, 0);
+        offsets.assign(n, 0);
+        lens.assign(n, 0);
+        kinds.assign(n, 0);
+        crcs.assign(n, 0);
+    }
+};
+
 // The known-chunk set of an incremental session (pbsgpu_known_*, device resident): the digests of the previous
 // snapshot's indexes (PreviousBackup, commit_orchestrate.go:127-158) plus every chunk already sent or injected
 // (InjectChunks refs, commit_reuse.go:315-341). Classify flags, per record, the chunks the server already has; the rest
@@ -165,6 +185,24 @@ class KnownChunks {
                                                       dst, dstCap, r.value.known.data(), r.value.offsets.data(),
                                                       r.value.crcs.data(), &r.value.bytes, &r.value.stats);
         if (st != PBSGPU_OK) r.err = errorf("known chunks upload new", st);
+        return r;
+    }
+    // UploadNew for the writers that compress (converter.go:399, 410-435): with zstd a new chunk whose frame is strictly
+    // shorter than the chunk becomes a compressed blob in its slot; without, UploadNew's outputs with lens and kinds.
+    Result<Uploaded2> UploadNew2(const void *src, uint64_t srcBytes, const std::vector<pbsgpu_record> &recs,
+                                 const std::vector<pbsgpu_segment> &chunks, bool insert, bool zstd, void *dst, uint64_t dstCap) {
+        Result<Uploaded2> r;
+        if (chunks.size() != recs.size()) {
+            r.err = errorf("known chunks upload new2", PBSGPU_E_INVALID);
+            return r;
+        }
+        Uploaded2 &v = r.value;
+        v.Resize(recs.size());
+        const int st = pbsgpu_known_upload_new2_device(k_, src, srcBytes, recs.data(), chunks.data(), recs.size(), insert ? 1 : 0,
+                                                       zstd ? PBSGPU_ENCODE_F_ZSTD : 0u, dst, dstCap, v.known.data(),
+                                                       v.offsets.data(), v.lens.data(), v.kinds.data(), v.crcs.data(), &v.bytes,
+                                                       &v.stats, &v.encoded);
+        if (st != PBSGPU_OK) r.err = errorf("known chunks upload new2", st);
         return r;
     }
     uint64_t Len() const {
@@ -791,6 +829,19 @@ class PageRing {
                                                      dstCap, r.value.known.data(), r.value.offsets.data(),
                                                      r.value.crcs.data(), &r.value.bytes, &r.value.stats);
         if (st != PBSGPU_OK) r.err = errorf("ring upload new", st);
+        return r;
+    }
+    // UploadNew for the writers that compress: the new chunks become compressed blobs where their frames are strictly
+    // shorter, straight out of the ring's pages (a chunk in two pages is one chunk to the encoder).
+    Result<datastore::Uploaded2> UploadNew2(datastore::KnownChunks &known, uint32_t stream, const std::vector<pbsgpu_record> &recs,
+                                            bool insert, bool zstd, void *dst, uint64_t dstCap) {
+        Result<datastore::Uploaded2> r;
+        datastore::Uploaded2 &v = r.value;
+        v.Resize(recs.size());
+        const int st = pbsgpu_ring_upload_new2_device(r_, known.Handle(), stream, recs.data(), recs.size(), insert ? 1 : 0,
+                                                      zstd ? PBSGPU_ENCODE_F_ZSTD : 0u, dst, dstCap, v.known.data(), v.offsets.data(),
+                                                      v.lens.data(), v.kinds.data(), v.crcs.data(), &v.bytes, &v.stats, &v.encoded);
+        if (st != PBSGPU_OK) r.err = errorf("ring upload new2", st);
         return r;
     }
     // the raw stream bytes [offset, offset + length) into device buffer dst

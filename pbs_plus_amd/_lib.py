@@ -279,6 +279,10 @@ SYMBOLS = {
                                                 C.POINTER(DedupStats)]),
     "pbsgpu_known_upload_new_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P,
                                                  _U64P, C.POINTER(DedupStats)]),
+    "pbsgpu_ring_upload_new2_device": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, C.c_uint32, _P, C.c_uint64, _P, _P, _P,
+                                                 _P, _P, _U64P, C.POINTER(DedupStats), C.POINTER(EncodeStats)]),
+    "pbsgpu_known_upload_new2_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, C.c_uint32, _P, C.c_uint64, _P,
+                                                  _P, _P, _P, _P, _U64P, C.POINTER(DedupStats), C.POINTER(EncodeStats)]),
     "pbsgpu_comm_unique_id": (C.c_int, [_P]),
     "pbsgpu_comm_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "pbsgpu_comm_destroy": (None, [_P]),

@@ -447,7 +447,7 @@ struct PartDesc {
     uint32_t len;    // <= a page: < 2^31
     uint32_t inv;    // leading bytes that enter the CRC inverted (0..4)
     uint32_t pbase;  // index of its first piece
-    uint32_t pad;
+    uint32_t blob;   // the blob it belongs to (only the plan built on the device fills it in, for k_upz_pieces)
 };
 struct BlobDesc {
     uint64_t hdr;     // offset of the blob (its header) in PartPlan::dst
@@ -472,6 +472,19 @@ struct PartPlan {
 typedef const CRC_GLOBAL PartDesc *gpart_ptr;
 typedef const CRC_GLOBAL BlobDesc *gblob_ptr;
 
+// piece q of a range of len bytes whose first pinv bytes enter the CRC inverted: range bytes [lo, hi), inv of them inverted
+struct PieceRange {
+    uint32_t lo, hi, inv;
+};
+__device__ __forceinline__ PieceRange range_piece(uint32_t len, uint32_t pinv, uint32_t q) {
+    const uint32_t m = (len + (uint32_t)kPiece - 1) >> kPieceLog;
+    PieceRange r;
+    r.hi = len - (m - 1 - q) * (uint32_t)kPiece;
+    r.lo = r.hi > kPiece ? r.hi - (uint32_t)kPiece : 0;
+    r.inv = r.lo < pinv ? (r.hi < pinv ? r.hi : pinv) - r.lo : 0u;
+    return r;
+}
+
 __global__ __launch_bounds__(256) void k_pagecrc_pieces(PartPlan pl) {
     __shared__ uint32_t tab[17][256];
     build_tables(tab);
@@ -481,14 +494,19 @@ __global__ __launch_bounds__(256) void k_pagecrc_pieces(PartPlan pl) {
     for (uint32_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < npieces; p += nw) {
         const uint32_t i = ((gword_ptr)pl.ppart)[p];
         const gpart_ptr pd = (gpart_ptr)pl.parts + i;
-        const uint32_t len = pd->len, pinv = pd->inv;
-        const uint32_t m = (len + (uint32_t)kPiece - 1) >> kPieceLog;
-        const uint32_t hi = len - (m - 1 - (p - pd->pbase)) * (uint32_t)kPiece;  // piece = part bytes [lo, hi)
-        const uint32_t lo = hi > kPiece ? hi - (uint32_t)kPiece : 0;
-        const uint32_t inv = lo < pinv ? (hi < pinv ? hi : pinv) - lo : 0u;
-        const uint32_t v = piece_raw(tab, pl.base + pd->src + lo, hi - lo, inv, lane, PutAll{pl.dst + pd->dst + lo});
+        const PieceRange r = range_piece(pd->len, pd->inv, p - pd->pbase);
+        const uint32_t v = piece_raw(tab, pl.base + pd->src + r.lo, r.hi - r.lo, r.inv, lane, PutAll{pl.dst + pd->dst + r.lo});
         if (lane == 0) ((gword_out)pl.praw)[p] = v;
     }
+}
+
+// raw CRC of a blob's data from the pieces of its parts; the part boundary is a join whose shift is no power of two of kPiece
+__device__ __forceinline__ uint32_t fold_blob(gword_ptr praw, gblob_ptr bd, gpart_ptr pd, uint32_t lane) {
+    const uint32_t np = bd->nparts;
+    uint32_t acc = 0;
+    if (np >= 1) acc = fold_part(praw + pd[0].pbase, (pd[0].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
+    if (np == 2) acc = mul(acc, bd->join) ^ fold_part(praw + pd[1].pbase, (pd[1].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
+    return acc;
 }
 
 __global__ __launch_bounds__(256) void k_pagecrc_fold(PartPlan pl) {
@@ -497,16 +515,72 @@ __global__ __launch_bounds__(256) void k_pagecrc_fold(PartPlan pl) {
     const uint32_t nblob = pl.counts ? __builtin_amdgcn_readfirstlane(((gword_ptr)pl.counts)[2]) : pl.nblob;
     for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < nblob; i += nw) {
         const gblob_ptr bd = (gblob_ptr)pl.blobs + i;
-        const uint32_t np = bd->nparts;
-        const gpart_ptr pd = (gpart_ptr)pl.parts + bd->part0;
-        uint32_t acc = 0;
-        if (np >= 1) acc = fold_part((gword_ptr)pl.praw + pd[0].pbase, (pd[0].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
-        if (np == 2)  // the part boundary: a join whose shift is no power of two of kPiece
-            acc = mul(acc, bd->join) ^
-                  fold_part((gword_ptr)pl.praw + pd[1].pbase, (pd[1].len + (uint32_t)kPiece - 1) >> kPieceLog, lane);
-        const uint32_t crc = finish(acc, bd->len);
+        const uint32_t crc = finish(fold_blob((gword_ptr)pl.praw, bd, (gpart_ptr)pl.parts + bd->part0, lane), bd->len);
         if (lane == 0) ((gword_out)pl.crcs)[i] = crc;
         store_header(pl.dst + bd->hdr, lane, pl.magic_lo, pl.magic_hi, crc);
+    }
+}
+
+// The same pair behind the encoder's verdict (pbsgpu_*_upload_new2_device with PBSGPU_ENCODE_F_ZSTD): what
+// k_enc2_* are to k_crc_*. zstd_encode.hip has left res[blob] = frame length | kind << 56 and the frames that won behind
+// their blobs' headers. A blob's pieces were planned for its slot, part by part; when its frame won they are numbered
+// through as the pieces of ONE range, the frame where it lies (no store; it is shorter than the chunk, so the pieces past
+// its end do nothing); otherwise they are the parts' pieces and the walk copies the chunk, as above.
+struct UpzPlan {
+    PartPlan p;
+    const uint64_t *res;  // per blob
+    uint32_t *lens;       // per blob: the blob's length
+    uint8_t *kinds;       // per blob
+    uint32_t zmagic_lo, zmagic_hi;  // the compressed kind's magic
+};
+
+__global__ __launch_bounds__(256) void k_upz_pieces(UpzPlan pl) {
+    __shared__ uint32_t tab[17][256];
+    build_tables(tab);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    const uint32_t npieces = __builtin_amdgcn_readfirstlane(((gword_ptr)pl.p.counts)[0]);
+    for (uint32_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < npieces; p += nw) {
+        const gpart_ptr pd = (gpart_ptr)pl.p.parts + ((gword_ptr)pl.p.ppart)[p];
+        const uint32_t b = pd->blob;
+        const uint64_t res = ((gquad_ptr)pl.res)[b];
+        const uint8_t *from = pl.p.base + pd->src;
+        uint8_t *o = pl.p.dst + pd->dst;
+        uint32_t len = pd->len, pinv = pd->inv, q = p - pd->pbase;
+        if ((res >> 56) == PBSGPU_BLOB_COMPRESSED) {  // (wave-uniform)
+            const gblob_ptr bd = (gblob_ptr)pl.p.blobs + b;
+            len = (uint32_t)res;  // below the chunk's length
+            pinv = len < 4 ? 0u : 4u;
+            q = p - ((gpart_ptr)pl.p.parts)[bd->part0].pbase;
+            if (q >= (len + (uint32_t)kPiece - 1) >> kPieceLog) continue;
+            from = pl.p.dst + bd->hdr + PBSGPU_BLOB_HEADER_SIZE;
+            o = nullptr;
+        }
+        const PieceRange r = range_piece(len, pinv, q);
+        const uint32_t v = piece_raw(tab, from + r.lo, r.hi - r.lo, r.inv, lane, PutIf{o ? o + r.lo : nullptr});
+        if (lane == 0) ((gword_out)pl.p.praw)[p] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_upz_fold(UpzPlan pl) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    const uint32_t nblob = __builtin_amdgcn_readfirstlane(((gword_ptr)pl.p.counts)[2]);
+    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < nblob; i += nw) {
+        const gblob_ptr bd = (gblob_ptr)pl.p.blobs + i;
+        const gpart_ptr pd = (gpart_ptr)pl.p.parts + bd->part0;
+        const uint64_t res = ((gquad_ptr)pl.res)[i];
+        const bool comp = (res >> 56) == PBSGPU_BLOB_COMPRESSED;
+        const uint32_t len = comp ? (uint32_t)res : bd->len;
+        const uint32_t acc = comp ? fold_part((gword_ptr)pl.p.praw + pd->pbase, (len + (uint32_t)kPiece - 1) >> kPieceLog, lane)
+                                  : fold_blob((gword_ptr)pl.p.praw, bd, pd, lane);
+        const uint32_t crc = finish(acc, len);
+        if (lane == 0) {
+            ((gword_out)pl.p.crcs)[i] = crc;
+            ((gword_out)pl.lens)[i] = len + PBSGPU_BLOB_HEADER_SIZE;
+            ((gbyte_out)pl.kinds)[i] = comp ? PBSGPU_BLOB_COMPRESSED : PBSGPU_BLOB_UNCOMPRESSED;
+        }
+        store_header(pl.p.dst + bd->hdr, lane, comp ? pl.zmagic_lo : pl.p.magic_lo, comp ? pl.zmagic_hi : pl.p.magic_hi, crc);
     }
 }
 
@@ -567,6 +641,7 @@ struct UpPlan {
     PartDesc *parts;
     BlobDesc *blobs;
     uint32_t *ppart;
+    zenc::Job *jobs;               // n, or nullptr: the encoder's jobs, of which the host knows the lengths and the blocks
 };
 typedef const CRC_GLOBAL UpCount *gcount_ptr;
 typedef CRC_GLOBAL UpCount *gcount_out;
@@ -716,13 +791,22 @@ __global__ __launch_bounds__(256) void k_upnew_fill(UpPlan pl) {
     uint32_t join = kOne;  // x^(8 b)
     for (int j = 0; j < 32; ++j)
         if ((sh.b >> j) & 1u) join = mul(join, kDev.x8[j]);
-    CRC_GLOBAL BlobDesc *bd = (CRC_GLOBAL BlobDesc *)pl.blobs + (bp->blobs + ex.blobs - c.blobs);
+    const uint32_t blob = bp->blobs + ex.blobs - c.blobs;
+    CRC_GLOBAL BlobDesc *bd = (CRC_GLOBAL BlobDesc *)pl.blobs + blob;
     bd->hdr = hdr;
     bd->part0 = part0;
     bd->nparts = c.parts;
     bd->join = join;
     bd->len = len;
     ((CRC_GLOBAL uint64_t *)pl.boff)[i] = hdr;
+    if (pl.jobs && !((ghead_ptr)pl.head)->over) {  // where the chunk lies and where its frame would go: the job is live
+        CRC_GLOBAL zenc::Job *jb = (CRC_GLOBAL zenc::Job *)pl.jobs + i;
+        jb->src_off = sh.src0;
+        jb->src1_off = sh.src1;
+        jb->dst_off = hdr + PBSGPU_BLOB_HEADER_SIZE;
+        jb->a = sh.a;
+        jb->out = blob;
+    }
     CRC_GLOBAL PartDesc *pd = (CRC_GLOBAL PartDesc *)pl.parts + part0;
     if (sh.a) {
         pd->src = sh.src0;
@@ -730,7 +814,7 @@ __global__ __launch_bounds__(256) void k_upnew_fill(UpPlan pl) {
         pd->len = sh.a;
         pd->inv = len >= 4 ? (sh.a < 4 ? sh.a : 4u) : 0u;
         pd->pbase = piece0;
-        pd->pad = 0;
+        pd->blob = blob;
     }
     if (sh.b) {  // (a first part of 1-3 bytes leaves the rest of the chunk's first four to this one)
         pd[1].src = sh.src1;
@@ -738,7 +822,7 @@ __global__ __launch_bounds__(256) void k_upnew_fill(UpPlan pl) {
         pd[1].len = sh.b;
         pd[1].inv = (len >= 4 && sh.a < 4) ? (4 - sh.a < sh.b ? 4 - sh.a : sh.b) : 0u;
         pd[1].pbase = piece0 + up_pieces(sh.a);
-        pd[1].pad = 0;
+        pd[1].blob = blob;
     }
 }
 
@@ -1066,7 +1150,7 @@ int blob_encode_zstd(pbsgpu_engine *e, const uint8_t *src, const pbsgpu_segment 
     CHK(stage_ranges(e, s, src, false, src_bytes, segs, nseg, &d));
     std::vector<pbsk::zenc::Job> jobs(nseg);
     for (uint32_t i = 0; i < nseg; ++i)
-        jobs[i] = pbsk::zenc::Job{segs[i].offset, offs[i] + PBSGPU_BLOB_HEADER_SIZE, segs[i].length, (uint32_t)segs[i].length, 0};
+        jobs[i] = pbsk::zenc::Job{segs[i].offset, 0, offs[i] + PBSGPU_BLOB_HEADER_SIZE, segs[i].length, (uint32_t)segs[i].length, 0, 0, 0};
     uint64_t *res = nullptr;
     CHK(pbsk::zenc::enqueue(e, s, d, dst, jobs, true, &res));
     std::vector<uint64_t> pbase((size_t)nseg + 1);
@@ -1584,8 +1668,8 @@ int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32
     return PBSGPU_OK;
 }
 
-// Layout on the one lease (known_common and enqueue_parts would both want tile_cnt and dense; here every array has a
-// buffer of its own for as long as something reads it):
+// Layout on the one lease (known_common, enqueue_parts and zenc::enqueue would all want tile_cnt, dense, recs, order, par
+// or scan_tmp; here every array has a buffer of its own for as long as something reads it):
 //   recs                 the records as staged, read by lookup / mark / the plan / the insert
 //   sugg                 the PageTabs and the page array (ring form), or the chunk ranges (contiguous form)
 //   dense | tile_slots   sort keys | indices, each with its double buffer: dead behind k_known_mark
@@ -1595,22 +1679,39 @@ int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32
 //   segs | seg_off       PartDesc | BlobDesc
 //   tile_off | seg_cnt   ppart | praw
 //   order                what goes back in one transfer: UpHead (stats, total, counts, verdict) | blob_off[n] u64 |
-//                        crcs u32 (compacted: one per new record) | known[n]
+//                        crcs u32 (compacted: one per new record) | known[n] | with F_ZSTD, from the next multiple of 4:
+//                        lens u32 | kinds u8 (both compacted)
+//   with F_ZSTD (zenc::Room; the sizes are zenc::prepare's, each a multiple of 64):
+//   sugg_idx             the encoder's small arrays: bchunk | jobs (staged with the lengths and blocks, no job live;
+//                        k_upnew_fill makes the new records' jobs live) | res (per blob) | the blocks' places and results
+//   data                 the encoder's large arrays: the round's compressed blocks | per workgroup literals, sequences and
+//                        (ring form) the staged block that holds a chunk's seam
 // Order on the stream: mark -> (growth only: the number of new digests is read back and the table rebuilt) -> plan with
-// the verdict -> insert with the plan's flags -> CRC pair on the plan's counts -> publish. The verdict comes before the
-// insert and before the first byte of dst: when the blobs do not fit, the insert sees all-ones flags and the pair sees
-// zero counts, so the set and dst are as they were, while flags, stats and the size needed are already final.
-int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint8_t *dst,
-               uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
-               pbsgpu_dedup_stats *stats) {
+// the verdict -> insert with the plan's flags -> (F_ZSTD: the encoder's rounds over the live jobs) -> CRC pair on the
+// plan's counts -> publish. The verdict comes before the insert and before the first byte of dst: when the blobs do not
+// fit, the insert sees all-ones flags, no job is live and the pair sees zero counts, so the set and dst are as they were,
+// while flags, stats and the size needed are already final.
+int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint32_t flags,
+               uint8_t *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *lens, uint8_t *kinds,
+               uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc) {
     pbsgpu_engine *e = known_engine(k);
+    const bool zstd = (flags & PBSGPU_ENCODE_F_ZSTD) != 0;
+    const auto size_of = [&](uint64_t i) { return src.chunks ? (uint32_t)src.chunks[i].length : recs[i].size; };
+    std::vector<pbsk::zenc::Job> jobs;
+    pbsk::zenc::Prep zp;
+    if (zstd) {  // (before the lease: the one refusal left, 2^32 blocks, needs no device)
+        jobs.resize((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) jobs[i] = pbsk::zenc::Job{0, 0, 0, size_of(i), size_of(i), 0, 0, pbsk::zenc::kNoJob};
+        CHK(pbsk::zenc::prepare(e, jobs, src.chunks == nullptr, zp));
+    }
     AuxLease lease(e);
     Slot *s = lease.s;
     const hipStream_t st = s->stream;
     KnownPass p;
     CHK(known_sort_bytes(n, st, &p.tmp_bytes));
     const uint32_t nb = (uint32_t)((n + 255) / 256);
-    const size_t out_bytes = sizeof(UpHead) + (size_t)n * 13;
+    const size_t lens_at = (sizeof(UpHead) + (size_t)n * 13 + 3) & ~(size_t)3;
+    const size_t out_bytes = zstd ? lens_at + (size_t)n * 5 : sizeof(UpHead) + (size_t)n * 13;
     const size_t src_bytes = src.chunks ? (size_t)n * sizeof(pbsgpu_segment) : src.tab_words * sizeof(uint64_t);
     CHK(s->recs.ensure((size_t)n * sizeof(pbsgpu_record) + 64));
     CHK(s->sugg.ensure(src_bytes + 64));
@@ -1626,10 +1727,23 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     CHK(s->order.ensure(out_bytes + 64));
     CHK(s->h_recs.ensure(out_bytes + 64));
     CHK(s->h_scalars.ensure(64));
+    pbsk::zenc::Room room{};
+    if (zstd) {
+        CHK(s->sugg_idx.ensure(zp.bchunk_bytes + zp.jobs_bytes + zp.res_bytes + zp.bplace_bytes + 64));
+        CHK(s->data.ensure(zp.blkout_bytes + zp.work_bytes + 64));
+        uint8_t *small = s->sugg_idx.as<uint8_t>(), *large = s->data.as<uint8_t>();
+        room.bchunk = reinterpret_cast<uint32_t *>(small);
+        room.jobs = reinterpret_cast<pbsk::zenc::Job *>(small + zp.bchunk_bytes);
+        room.res = reinterpret_cast<uint64_t *>(small + zp.bchunk_bytes + zp.jobs_bytes);
+        room.bplace = reinterpret_cast<uint64_t *>(small + zp.bchunk_bytes + zp.jobs_bytes + zp.res_bytes);
+        room.blkout = large;
+        room.work = large + zp.blkout_bytes;
+    }
     // the small table first: the records' copy then waits for nothing but that
     if (src_bytes)
         CHK(staged_h2d(*s, s->sugg.p, src.chunks ? (const void *)src.chunks : (const void *)src.tabs, src_bytes, st));
     CHK(staged_h2d(*s, s->recs.p, recs, n * sizeof(pbsgpu_record), st));
+    if (zstd) CHK(pbsk::zenc::upload(s, zp, room, jobs));
     uint8_t *out = s->order.as<uint8_t>();
     p.recs = s->recs.as<uint8_t>();
     p.stride = sizeof(pbsgpu_record);
@@ -1666,6 +1780,7 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     up.parts = s->segs.as<PartDesc>();
     up.blobs = s->seg_off.as<BlobDesc>();
     up.ppart = s->tile_off.as<uint32_t>();
+    up.jobs = room.jobs;
     hipLaunchKernelGGL(pbsk::crc::k_upnew_count, dim3(nb), dim3(256), 0, st, up);
     hipLaunchKernelGGL(pbsk::crc::k_upnew_scan, dim3(1), dim3(256), 0, st, up);
     hipLaunchKernelGGL(pbsk::crc::k_upnew_fill, dim3(nb), dim3(256), 0, st, up);
@@ -1676,7 +1791,8 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
         HIPCHK(hipGetLastError());
     }
     if (insert) CHK(known_enqueue_insert(k, p, up.skip, st));
-    PartPlan pl{};
+    UpzPlan zl{};
+    PartPlan &pl = zl.p;
     pl.base = src.base;
     pl.dst = dst;
     pl.parts = up.parts;
@@ -1686,7 +1802,18 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     pl.crcs = reinterpret_cast<uint32_t *>(out + sizeof(UpHead) + (size_t)n * 8);
     pl.counts = &up.head->npieces;
     set_magic(pl);
-    CHK(launch_pair(e, st, k_pagecrc_pieces, k_pagecrc_fold, pl, src.pieces_max, n));  // the upper bounds the host knows
+    // (the grids of both pairs: the upper bounds the host knows)
+    if (zstd) {
+        CHK(pbsk::zenc::launch(e, st, zp, room, src.base, dst, true));
+        zl.res = room.res;
+        zl.lens = reinterpret_cast<uint32_t *>(out + lens_at);
+        zl.kinds = out + lens_at + (size_t)n * 4;
+        zl.zmagic_lo = le32(kMagic[PBSGPU_BLOB_COMPRESSED]);
+        zl.zmagic_hi = le32(kMagic[PBSGPU_BLOB_COMPRESSED] + 4);
+        CHK(launch_pair(e, st, k_upz_pieces, k_upz_fold, zl, src.pieces_max, n));
+    } else {
+        CHK(launch_pair(e, st, k_pagecrc_pieces, k_pagecrc_fold, pl, src.pieces_max, n));
+    }
     HIPCHK(pbsk::launch_publish(s->h_recs.p, out, out_bytes, st));
     HIPCHK(hipStreamSynchronize(st));
     const uint8_t *h = s->h_recs.as<uint8_t>();
@@ -1703,10 +1830,26 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     *used = head.total;
     if (head.over) return PBSGPU_E_CAPACITY;
     const uint8_t *h_boff = h + sizeof(UpHead), *h_crcs = h_boff + (size_t)n * 8;
+    const uint8_t *h_lens = h + lens_at, *h_kinds = h_lens + (size_t)n * 4;
     for (uint64_t i = 0, j = 0; i < n; ++i) {
         if (h_known[i]) continue;
         std::memcpy(&blob_off[i], h_boff + i * 8, 8);
         if (crcs) std::memcpy(&crcs[i], h_crcs + j * 4, 4);
+        uint32_t len = size_of(i) + PBSGPU_BLOB_HEADER_SIZE;
+        uint8_t kind = PBSGPU_BLOB_UNCOMPRESSED;
+        if (zstd) {
+            std::memcpy(&len, h_lens + j * 4, 4);
+            kind = h_kinds[j];
+        }
+        if (lens) lens[i] = len;
+        if (kinds) kinds[i] = kind;
+        if (enc) {  // as pbsgpu_blob_encode2_device counts them
+            enc->blobs[kind]++;
+            enc->blob_bytes[kind] += len;
+            enc->chunk_bytes[kind] += size_of(i);
+            if (kind == PBSGPU_BLOB_COMPRESSED) enc->frame_bytes += len - PBSGPU_BLOB_HEADER_SIZE;
+            enc->crc_bytes += len - PBSGPU_BLOB_HEADER_SIZE;
+        }
         ++j;
     }
     if (insert) known_inserted(k, head.stats[1]);
@@ -1851,10 +1994,11 @@ int pbsgpu_blob_decode2_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_
                        status, stats);
 }
 
-int pbsgpu_known_upload_new_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,
-                                   const pbsgpu_segment *chunks, uint64_t n, int insert, void *dst, uint64_t dst_cap,
-                                   uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
-                                   pbsgpu_dedup_stats *stats) {
+int pbsgpu_known_upload_new2_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,
+                                    const pbsgpu_segment *chunks, uint64_t n, int insert, uint32_t flags, void *dst,
+                                    uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *lens, uint8_t *kinds,
+                                    uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc_stats) {
+    if (flags & ~PBSGPU_ENCODE_F_ZSTD) return PBSGPU_E_INVALID;
     if (!k || !used || !stats || (!src && src_bytes) || (n && (!recs || !chunks || !blob_off)) || n >= (1ull << 32))
         return PBSGPU_E_INVALID;
     if (!dst && dst_cap) return PBSGPU_E_INVALID;
@@ -1865,15 +2009,28 @@ int pbsgpu_known_upload_new_device(pbsgpu_known *k, const void *src, uint64_t sr
         us.pieces_max += (c.length + pbsk::crc::kPiece - 1) >> pbsk::crc::kPieceLog;
     }
     if (us.pieces_max >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if ((flags & PBSGPU_ENCODE_F_ZSTD) && src_bytes && dst_cap) {  // the frames are read again for their CRC
+        const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src;
+        if (d0 < s0 + src_bytes && s0 < d0 + dst_cap) return PBSGPU_E_INVALID;
+    }
     *used = 0;
     std::memset(stats, 0, sizeof(*stats));
+    if (enc_stats) std::memset(enc_stats, 0, sizeof(*enc_stats));
     if (n == 0) return PBSGPU_OK;
     CHK(set_device(known_engine(k)));
     if ((dst && !is_device_pointer(dst)) || (src_bytes && !is_device_pointer(src))) return PBSGPU_E_INVALID;
     us.base = static_cast<const uint8_t *>(src);
     us.chunks = chunks;
-    return upload_new(k, us, recs, n, insert != 0, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, crcs, used,
-                      stats);
+    return upload_new(k, us, recs, n, insert != 0, flags, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, lens,
+                      kinds, crcs, used, stats, enc_stats);
+}
+
+int pbsgpu_known_upload_new_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,
+                                   const pbsgpu_segment *chunks, uint64_t n, int insert, void *dst, uint64_t dst_cap,
+                                   uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
+                                   pbsgpu_dedup_stats *stats) {
+    return pbsgpu_known_upload_new2_device(k, src, src_bytes, recs, chunks, n, insert, 0, dst, dst_cap, known_out, blob_off,
+                                           nullptr, nullptr, crcs, used, stats, nullptr);
 }
 
 }  // extern "C"

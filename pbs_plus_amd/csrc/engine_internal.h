@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "zstd_plan.h"
 
 namespace pbse {
 
@@ -336,15 +337,40 @@ hipError_t launch_restore_status(const RestorePlan &pl, hipStream_t st);
 namespace pbsk {
 namespace zenc {
 struct Job {  // one chunk: its bytes at src + src_off, its frame's room at dst + dst_off
-    uint64_t src_off, dst_off, room;
-    uint32_t len, first;  // first: filled in by enqueue
+    uint64_t src_off, src1_off;  // the first `a` bytes, and the rest (a ring chunk in two pages; a == len: one part)
+    uint64_t dst_off, room;
+    uint32_t len, first;  // first: its first block in the call's block index space (zstd_plan.h)
+    uint32_t a;
+    uint32_t out;         // its entry of res; kNoJob: not to be encoded, its blocks are left at once
 };
+constexpr uint32_t kNoJob = 0xffffffffu;
 // res_dev[i] = frame length | status << 56. blob = false: PBSGPU_ZSTD_OK or _BAD_SIZE (nothing written, length 0).
 // blob = true: room is the chunk's length; PBSGPU_BLOB_COMPRESSED when the frame is strictly shorter than the chunk and
 // was written, PBSGPU_BLOB_UNCOMPRESSED (nothing written) otherwise. Uses the slot's recs, sugg_idx, order, data, par and
-// scan_tmp buffers.
+// scan_tmp buffers. jobs: src_off, dst_off, room and len from the caller, one part each; the rest is filled in here.
 int enqueue(pbsgpu_engine *e, pbse::Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob,
             uint64_t **res_dev);
+// The same in three steps for a caller that places the arrays itself and has a kernel of its own fill in what only the
+// device knows of a job (blob.hip's fused upload): prepare() plans the blocks from the jobs' `len` and says
+// how much room each array needs; upload() copies the jobs and the block table to the room; launch() enqueues the rounds.
+struct Room {  // device arrays
+    Job *jobs;         // n
+    uint32_t *bchunk;  // every block of the call: its chunk
+    uint64_t *res;     // n
+    uint8_t *blkout;   // the largest round's blocks, 128 KiB each
+    uint64_t *bplace;  // the largest round's blocks: place in the frame (8 bytes each), then type and size (4 each); then a
+                       // block counter per round
+    uint8_t *work;     // per workgroup: literals, sequences and, with sources in two parts, the block that holds the seam
+};
+struct Prep {
+    pbsz::enc::BlockPlan bp;
+    uint32_t grid = 0;  // workgroups of the block kernel
+    bool two_parts = false;
+    size_t jobs_bytes = 0, bchunk_bytes = 0, res_bytes = 0, blkout_bytes = 0, bplace_bytes = 0, work_bytes = 0;  // of Room's arrays
+};
+int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p);  // PBSGPU_E_INVALID: 2^32 blocks or more
+int upload(pbse::Slot *s, const Prep &p, const Room &room, const std::vector<Job> &jobs);
+int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob);
 }  // namespace zenc
 }  // namespace pbsk
 namespace pbse {

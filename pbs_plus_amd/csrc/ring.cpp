@@ -1227,9 +1227,11 @@ int pbsgpu_ring_blob_encode_device(pbsgpu_ring *r, uint32_t stream, const pbsgpu
 // logical page of that span. A page inside [first available offset, last polled end) is always there — pages go only
 // below the release watermark, and nothing beyond a polled record is uncommitted — so the two range checks per record
 // refuse what the per-record page lookup of pbsgpu_ring_blob_encode_device refuses; the lookup per page stays as the proof.
-int pbsgpu_ring_upload_new_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
-                                  int insert, void *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off,
-                                  uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats) {
+int pbsgpu_ring_upload_new2_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
+                                   int insert, uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *known_out,
+                                   uint64_t *blob_off, uint32_t *lens, uint8_t *kinds, uint32_t *crcs, uint64_t *used,
+                                   pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc_stats) {
+    if (flags & ~PBSGPU_ENCODE_F_ZSTD) return PBSGPU_E_INVALID;
     if (!r || !k || !used || !stats || (n && (!recs || !blob_off)) || n >= (1ull << 32)) return PBSGPU_E_INVALID;
     if (!dst && dst_cap) return PBSGPU_E_INVALID;
     if (!r->hold) return PBSGPU_E_STATE;
@@ -1273,6 +1275,7 @@ int pbsgpu_ring_upload_new_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stre
     }
     *used = 0;
     std::memset(stats, 0, sizeof(*stats));
+    if (enc_stats) std::memset(enc_stats, 0, sizeof(*enc_stats));
     if (n == 0) return PBSGPU_OK;
     CHK(set_device(r->eng));
     if (dst && !is_device_pointer(dst)) return PBSGPU_E_INVALID;
@@ -1283,8 +1286,15 @@ int pbsgpu_ring_upload_new_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stre
     us.nslots = (uint32_t)span.size();
     us.stream = stream;
     us.page_bytes = r->page_bytes;
-    return upload_new(k, us, recs, n, insert != 0, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, crcs, used,
-                      stats);
+    return upload_new(k, us, recs, n, insert != 0, flags, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, lens,
+                      kinds, crcs, used, stats, enc_stats);
+}
+
+int pbsgpu_ring_upload_new_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
+                                  int insert, void *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off,
+                                  uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats) {
+    return pbsgpu_ring_upload_new2_device(r, k, stream, recs, n, insert, 0, dst, dst_cap, known_out, blob_off, nullptr, nullptr,
+                                          crcs, used, stats, nullptr);
 }
 
 int pbsgpu_ring_copy_device(pbsgpu_ring *r, uint32_t stream, uint64_t offset, uint64_t length, void *dst) {

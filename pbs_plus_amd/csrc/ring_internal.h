@@ -223,8 +223,9 @@ struct UploadSrc {
     uint64_t page_bytes = 0;
     uint64_t pieces_max = 0;                 // upper bound of the 64 KiB pieces of all n chunks, < 2^32
 };
-int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint8_t *dst,
-               uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *crcs, uint64_t *used,
-               pbsgpu_dedup_stats *stats);
+// flags: PBSGPU_ENCODE_F_ZSTD or 0; lens, kinds, crcs and enc may be NULL (pbsgpu_*_upload_new2_device)
+int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint32_t flags,
+               uint8_t *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *lens, uint8_t *kinds,
+               uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc);
 
 }  // namespace pbse

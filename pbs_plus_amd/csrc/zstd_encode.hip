@@ -3,20 +3,23 @@
 //
 // The format lives in zstd_encode.h, once, for these kernels and for the CPU build that runs under sanitizers. This file
 // adds the cooperation between lanes and the assembly of the blocks into frames:
-//   k_zenc_blocks    one wave (a workgroup of 64) per 128 KiB block, workgroups striding over all blocks of all chunks of a
-//                    round. Blocks are independent (no match reaches before its block), so any wave takes any block. The
-//                    wave's State — the 16 KiB hash table, histogram, Huffman code, the three predefined FSE encoding
-//                    tables, the batch of 64 positions — is the workgroup's LDS (about 20 KiB: seven workgroups fit a CU's
-//                    160 KiB). The block's literals (128 KiB) and sequences (kSeqCap * 8 = 192 KiB) lie in the
-//                    workgroup's part of the slot's scratch; its compressed form goes to the BLOCK's 128 KiB of scratch,
-//                    because the frame it belongs to is put together later. Per block: type and size.
+//   k_zenc_blocks    one wave (a workgroup of 64) per 128 KiB block; the workgroups take the blocks of all chunks of a round
+//                    from a counter, one at a time. Blocks are independent (no match reaches before its block), so any
+//                    wave takes any block, and a block of a chunk that is not to be encoded (Job::out == kNoJob: the fused
+//                    upload's known records) costs the read of its job. The wave's State — the 16 KiB hash
+//                    table, histogram, Huffman code, the three predefined FSE encoding tables, the batch of 64 positions —
+//                    is the workgroup's LDS (about 20 KiB: seven workgroups fit a CU's 160 KiB). The block's literals
+//                    (128 KiB) and sequences (kSeqCap * 8 = 192 KiB) lie in the workgroup's part of the slot's scratch; its
+//                    compressed form goes to the BLOCK's 128 KiB of scratch, because the frame it belongs to is put
+//                    together later. Per block: type and size. A chunk may lie in two parts (a ring chunk in two pages):
+//                    the one block that holds the seam is put together in the workgroup's scratch first.
 //   k_zenc_assemble  one workgroup of 256 per chunk: a prefix over its blocks' sizes (wave 0), then the frame header, the
 //                    block headers and the payloads (content for raw blocks, one byte for RLE, the compressed form) to
 //                    their places in the room. It records the frame's length and the status; for the blob call the
 //                    verdict instead: a frame that is not strictly shorter than its chunk is not written.
 //   sync()           a workgroup barrier with its fences, wherever lanes read what other lanes stored.
-// The host plans rounds of whole chunks so that the per-block scratch stays bounded (kRoundBlocks blocks, 256 MiB), and
-// enqueues them back to back on one stream: nothing is read back in between.
+// The host plans rounds of whole chunks (zstd_plan.h) so that the per-block scratch stays bounded (kRoundBlocks blocks,
+// 256 MiB), and enqueues them back to back on one stream: nothing is read back in between.
 // No scratch memory, no spills, no dynamically indexed private arrays (tests/test_zstd_encode_surface.py).
 #include <algorithm>
 #include <cstring>
@@ -38,13 +41,20 @@ struct Plan {
     uint8_t *blkout;         // the round's blocks, kBlockMax bytes each
     uint32_t *bres;          // the round's blocks: type | size << 2
     uint64_t *boff;          // the round's blocks: where the block header goes in its frame
-    uint8_t *lit;            // stride * kBlockMax
-    uint64_t *seqs;          // stride * kSeqCap
+    uint8_t *lit;            // per workgroup of k_zenc_blocks: kBlockMax
+    uint64_t *seqs;          // per workgroup: kSeqCap
+    uint8_t *stage;          // per workgroup: kBlockMax, when a job may have two parts
     uint8_t *dst;
-    uint64_t *res;           // every chunk: frame length | status << 56
+    uint64_t *res;           // per Job::out: frame length | status << 56
+    uint32_t *next;          // the round's block counter, zero at its start
     uint32_t b0, b1, c0, c1; // the round
-    uint32_t stride, blob;
+    uint32_t blob;
 };
+
+// where byte p of the chunk lies, as an offset from Plan::src
+__device__ __forceinline__ uint64_t chunk_byte(const Job &j, uint32_t p) {
+    return p < j.a ? j.src_off + p : j.src1_off + (p - j.a);
+}
 
 struct WaveLanes {
     static __device__ __forceinline__ int lane() {
@@ -61,17 +71,33 @@ struct WaveLanes {
 
 __global__ __launch_bounds__(64) void k_zenc_blocks(Plan pl) {
     __shared__ ze::State st;
-    ze::init_tables<WaveLanes>(st);
+    bool tables = false;
     uint8_t *lit = pl.lit + (uint64_t)blockIdx.x * pbsz::kBlockMax;
     uint64_t *seqs = pl.seqs + (uint64_t)blockIdx.x * ze::kSeqCap;
-    for (uint32_t b = pl.b0 + blockIdx.x; b < pl.b1; b += pl.stride) {
+    for (;;) {
+        uint32_t b = 0;  // the round's next block: blocks differ in cost, and the device's plan leaves some out altogether
+        if (threadIdx.x == 0) b = atomicAdd(pl.next, 1u);
+        b = pl.b0 + WaveLanes::uni(b);
+        if (b >= pl.b1) break;
         const Job j = pl.jobs[pl.bchunk[b]];  // (uniform addresses: scalar loads)
+        if (j.out == kNoJob) continue;        // a chunk the device's plan does not encode
+        if (!tables) {
+            ze::init_tables<WaveLanes>(st);
+            tables = true;
+        }
         const uint32_t at = (b - j.first) * pbsz::kBlockMax;
         const uint32_t bn = j.len - at < pbsz::kBlockMax ? j.len - at : pbsz::kBlockMax;
         uint8_t *blk = pl.blkout + (uint64_t)(b - pl.b0) * pbsz::kBlockMax;
-        const uint32_t r = ze::encode_block<WaveLanes>(st, pl.src + j.src_off + at, bn, blk, lit, seqs);
+        const uint8_t *content = pl.src + chunk_byte(j, at);
+        if (at < j.a && j.a < at + bn) {  // the one block of a chunk that holds the seam between its parts: put together first
+            uint8_t *sg = pl.stage + (uint64_t)blockIdx.x * pbsz::kBlockMax;
+            for (uint32_t i = threadIdx.x; i < bn; i += 64) sg[i] = pl.src[chunk_byte(j, at + i)];
+            __syncthreads();
+            content = sg;
+        }
+        const uint32_t r = ze::encode_block<WaveLanes>(st, content, bn, blk, lit, seqs);
         if (threadIdx.x == 0) pl.bres[b - pl.b0] = r;
-        __syncthreads();  // State, the literals and the sequences go to the next block
+        __syncthreads();  // State, the literals, the sequences and the staged block go to the next block
     }
 }
 
@@ -80,6 +106,7 @@ __global__ __launch_bounds__(256) void k_zenc_assemble(Plan pl) {
     const uint32_t t = threadIdx.x;
     for (uint32_t c = pl.c0 + blockIdx.x; c < pl.c1; c += gridDim.x) {
         const Job j = pl.jobs[c];
+        if (j.out == kNoJob) continue;
         const uint32_t nb = (uint32_t)(((uint64_t)j.len + pbsz::kBlockMax - 1) / pbsz::kBlockMax);  // 0: the empty frame
         const uint32_t hb = ze::header_bytes(j.len);
         const uint32_t fb = j.first - pl.b0;
@@ -115,91 +142,106 @@ __global__ __launch_bounds__(256) void k_zenc_assemble(Plan pl) {
                 const uint32_t at = k * pbsz::kBlockMax;
                 const uint32_t bn = j.len - at < pbsz::kBlockMax ? j.len - at : pbsz::kBlockMax;
                 uint8_t *o = d + pl.boff[fb + k];
-                const uint8_t *content = pl.src + j.src_off + at;
                 if (t == 0) {
                     ze::block_header(o, k + 1 == nb ? 1u : 0u, type, type == ze::B_COMPRESSED ? size : bn);
-                    if (type == ze::B_RLE) o[3] = content[0];
+                    if (type == ze::B_RLE) o[3] = pl.src[chunk_byte(j, at)];
                 }
-                if (type != ze::B_RLE) {
-                    const uint8_t *from = type == ze::B_RAW ? content : pl.blkout + (uint64_t)(fb + k) * pbsz::kBlockMax;
+                if (type == ze::B_RAW) {
+#pragma unroll 8
+                    for (uint32_t i = t; i < size; i += 256) o[3 + i] = pl.src[chunk_byte(j, at + i)];
+                } else if (type == ze::B_COMPRESSED) {
+                    const uint8_t *from = pl.blkout + (uint64_t)(fb + k) * pbsz::kBlockMax;
 #pragma unroll 8
                     for (uint32_t i = t; i < size; i += 256) o[3 + i] = from[i];
                 }
             }
         }
-        if (t == 0) pl.res[c] = (write || pl.blob ? flen : 0ull) | (uint64_t)status << 56;
+        if (t == 0) pl.res[j.out] = (write || pl.blob ? flen : 0ull) | (uint64_t)status << 56;
         __syncthreads();  // s_total goes to the next chunk
     }
 }
 
 constexpr uint32_t kRoundBlocks = 2048;  // 256 MiB of per-block scratch
 
-// The frames of jobs[0, n) (Job::first is filled in here), enqueued on the slot's stream, nothing synchronised.
-// *res_dev = per chunk, frame length | status << 56 (blob: the kind, and nothing written unless compressed).
-int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob, uint64_t **res_dev) {
+static size_t pad64(size_t n) { return (n + 63) & ~(size_t)63; }
+
+int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p) {
     const uint32_t n = (uint32_t)jobs.size();
-    uint64_t nblocks = 0;
-    for (Job &j : jobs) {
-        if (nblocks >= (1ull << 32)) return PBSGPU_E_INVALID;
-        j.first = (uint32_t)nblocks;
-        nblocks += ((uint64_t)j.len + pbsz::kBlockMax - 1) / pbsz::kBlockMax;
-    }
-    if (nblocks >= (1ull << 32)) return PBSGPU_E_INVALID;  // 512 TiB in one call
-    std::vector<uint32_t> bchunk((size_t)nblocks);
-    for (uint32_t c = 0; c < n; ++c) {
-        const uint64_t end = c + 1 < n ? jobs[c + 1].first : nblocks;
-        for (uint64_t b = jobs[c].first; b < end; ++b) bchunk[b] = c;
-    }
-    // rounds of whole chunks, kRoundBlocks blocks at the most unless one chunk alone has more
-    std::vector<uint32_t> cuts{0};
-    uint64_t most = 0;
-    for (uint32_t c = 0, from = 0; c < n; ++c) {
-        const uint64_t end = c + 1 < n ? jobs[c + 1].first : nblocks;
-        if (end - jobs[from].first > kRoundBlocks && c > from) {
-            cuts.push_back(c);
-            from = c;
-        }
-        most = std::max(most, end - jobs[from].first);
-    }
-    cuts.push_back(n);
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(most, (uint64_t)e->num_cus * 4));
-    const size_t lit_bytes = (size_t)grid * pbsz::kBlockMax;
-    CHK(s->recs.ensure((size_t)n * sizeof(Job) + 64));
-    CHK(s->sugg_idx.ensure((size_t)nblocks * 4 + 64));
-    CHK(s->order.ensure((size_t)n * 8 + 64));
-    CHK(s->data.ensure((size_t)most * pbsz::kBlockMax + 64));
-    CHK(s->par.ensure(lit_bytes + (size_t)grid * ze::kSeqCap * 8));
-    CHK(s->scan_tmp.ensure((size_t)most * 16 + 64));
-    CHK(staged_h2d(*s, s->recs.p, jobs.data(), (size_t)n * sizeof(Job), s->stream));
-    if (nblocks) CHK(staged_h2d(*s, s->sugg_idx.p, bchunk.data(), (size_t)nblocks * 4, s->stream));
+    if (!ze::plan_blocks(n, [&](uint32_t c) { return jobs[c].len; }, pbsz::kBlockMax, kRoundBlocks, p.bp))
+        return PBSGPU_E_INVALID;  // 512 TiB in one call
+    for (uint32_t c = 0; c < n; ++c) jobs[c].first = p.bp.first[c];
+    p.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(p.bp.most, (uint64_t)e->num_cus * 4));
+    p.two_parts = two_parts;
+    p.jobs_bytes = pad64((size_t)n * sizeof(Job));
+    p.bchunk_bytes = pad64((size_t)p.bp.nblocks * 4);
+    p.res_bytes = pad64((size_t)n * 8);
+    p.blkout_bytes = pad64((size_t)p.bp.most * pbsz::kBlockMax);
+    p.bplace_bytes = pad64((size_t)p.bp.most * 12 + (p.bp.cuts.size() - 1) * 4);
+    p.work_bytes = (size_t)p.grid * ((two_parts ? 2 : 1) * (size_t)pbsz::kBlockMax + (size_t)ze::kSeqCap * 8);
+    return PBSGPU_OK;
+}
+
+int upload(Slot *s, const Prep &p, const Room &room, const std::vector<Job> &jobs) {
+    CHK(staged_h2d(*s, room.jobs, jobs.data(), jobs.size() * sizeof(Job), s->stream));
+    if (p.bp.nblocks) CHK(staged_h2d(*s, room.bchunk, p.bp.bchunk.data(), (size_t)p.bp.nblocks * 4, s->stream));
+    return PBSGPU_OK;
+}
+
+// the rounds, back to back on st; nothing synchronised
+int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob) {
     Plan pl{};
     pl.src = src;
-    pl.jobs = s->recs.as<Job>();
-    pl.bchunk = s->sugg_idx.as<uint32_t>();
-    pl.blkout = s->data.as<uint8_t>();
-    pl.boff = s->scan_tmp.as<uint64_t>();
-    pl.bres = reinterpret_cast<uint32_t *>(s->scan_tmp.as<uint64_t>() + most);
-    pl.lit = s->par.as<uint8_t>();
-    pl.seqs = reinterpret_cast<uint64_t *>(s->par.as<uint8_t>() + lit_bytes);
+    pl.jobs = room.jobs;
+    pl.bchunk = room.bchunk;
+    pl.blkout = room.blkout;
+    pl.boff = room.bplace;
+    pl.bres = reinterpret_cast<uint32_t *>(room.bplace + p.bp.most);
+    pl.lit = room.work;
+    pl.seqs = reinterpret_cast<uint64_t *>(room.work + (size_t)p.grid * pbsz::kBlockMax);
+    pl.stage = p.two_parts ? room.work + (size_t)p.grid * (pbsz::kBlockMax + (size_t)ze::kSeqCap * 8) : nullptr;
     pl.dst = dst;
-    pl.res = s->order.as<uint64_t>();
-    pl.stride = grid;
+    pl.res = room.res;
     pl.blob = blob ? 1u : 0u;
-    for (size_t r = 0; r + 1 < cuts.size(); ++r) {
-        pl.c0 = cuts[r];
-        pl.c1 = cuts[r + 1];
-        pl.b0 = jobs[pl.c0].first;
-        pl.b1 = pl.c1 < n ? jobs[pl.c1].first : (uint32_t)nblocks;
+    uint32_t *counters = pl.bres + p.bp.most;  // one per round
+    HIPCHK(hipMemsetAsync(counters, 0, (p.bp.cuts.size() - 1) * 4, st));
+    for (size_t r = 0; r + 1 < p.bp.cuts.size(); ++r) {
+        pl.next = counters + r;
+        pl.c0 = p.bp.cuts[r];
+        pl.c1 = p.bp.cuts[r + 1];
+        pl.b0 = p.bp.block_begin(pl.c0);
+        pl.b1 = p.bp.block_begin(pl.c1);
         if (pl.c0 == pl.c1) continue;
         if (pl.b1 > pl.b0) {
-            hipLaunchKernelGGL(k_zenc_blocks, dim3(std::min<uint32_t>(grid, pl.b1 - pl.b0)), dim3(64), 0, s->stream, pl);
+            hipLaunchKernelGGL(k_zenc_blocks, dim3(std::min<uint32_t>(p.grid, pl.b1 - pl.b0)), dim3(64), 0, st, pl);
             HIPCHK(hipGetLastError());
         }
-        hipLaunchKernelGGL(k_zenc_assemble, dim3(std::min<uint32_t>(pl.c1 - pl.c0, (uint32_t)e->num_cus * 8)), dim3(256), 0,
-                           s->stream, pl);
+        hipLaunchKernelGGL(k_zenc_assemble, dim3(std::min<uint32_t>(pl.c1 - pl.c0, (uint32_t)e->num_cus * 8)), dim3(256), 0, st, pl);
         HIPCHK(hipGetLastError());
     }
-    *res_dev = pl.res;
+    return PBSGPU_OK;
+}
+
+// The frames of jobs[0, n), every one of them, enqueued on the slot's stream, nothing synchronised.
+// *res_dev = per chunk, frame length | status << 56 (blob: the kind, and nothing written unless compressed).
+int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob, uint64_t **res_dev) {
+    for (uint32_t c = 0; c < jobs.size(); ++c) {
+        jobs[c].src1_off = 0;
+        jobs[c].a = jobs[c].len;
+        jobs[c].out = c;
+    }
+    Prep p;
+    CHK(prepare(e, jobs, false, p));
+    CHK(s->recs.ensure(p.jobs_bytes + 64));
+    CHK(s->sugg_idx.ensure(p.bchunk_bytes + 64));
+    CHK(s->order.ensure(p.res_bytes + 64));
+    CHK(s->data.ensure(p.blkout_bytes + 64));
+    CHK(s->par.ensure(p.work_bytes));
+    CHK(s->scan_tmp.ensure(p.bplace_bytes + 64));
+    const Room room{s->recs.as<Job>(),    s->sugg_idx.as<uint32_t>(), s->order.as<uint64_t>(),
+                    s->data.as<uint8_t>(), s->scan_tmp.as<uint64_t>(), s->par.as<uint8_t>()};
+    CHK(upload(s, p, room, jobs));
+    CHK(launch(e, s->stream, p, room, src, dst, blob));
+    *res_dev = room.res;
     return PBSGPU_OK;
 }
 
@@ -238,7 +280,7 @@ int zstd_encode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu
     AuxLease lease(e);
     Slot *s = lease.s;
     std::vector<pbsk::zenc::Job> jobs(n);
-    for (uint32_t i = 0; i < n; ++i) jobs[i] = pbsk::zenc::Job{chunks[i].offset, out[i].offset, out[i].length, (uint32_t)chunks[i].length, 0};
+    for (uint32_t i = 0; i < n; ++i) jobs[i] = pbsk::zenc::Job{chunks[i].offset, 0, out[i].offset, out[i].length, (uint32_t)chunks[i].length, 0, 0, 0};
     uint64_t *res = nullptr;
     CHK(pbsk::zenc::enqueue(e, s, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), jobs, false, &res));
     std::vector<uint64_t> back(n);

@@ -478,9 +478,7 @@ class Engine:
             if own:
                 dst.free()
             raise
-        stats = dict(blobs=[int(v) for v in st.blobs], blob_bytes=[int(v) for v in st.blob_bytes],
-                     chunk_bytes=[int(v) for v in st.chunk_bytes], frame_bytes=int(st.frame_bytes), crc_bytes=int(st.crc_bytes))
-        return dst, offs, lens[:n], kinds[:n], crcs[:n], stats
+        return dst, offs, lens[:n], kinds[:n], crcs[:n], _encode_stats(st)
 
     # ---- payload-stream assembly (.ppxar layout: markers + 16-byte headers + file bodies) ----------
     def payload_pack(self, src, files, dst, with_start: bool = True, with_tail: bool = True):
@@ -557,6 +555,34 @@ def blob_magic(kind: int) -> bytes:
     out = (C.c_uint8 * 8)()
     check(_lib.lib().pbsgpu_blob_magic(int(kind), out), "blob_magic")
     return bytes(out)
+
+
+def _encode_stats(st) -> dict:
+    return dict(blobs=[int(v) for v in st.blobs], blob_bytes=[int(v) for v in st.blob_bytes],
+                chunk_bytes=[int(v) for v in st.chunk_bytes], frame_bytes=int(st.frame_bytes), crc_bytes=int(st.crc_bytes))
+
+
+class _Upload2Out:
+    """the host outputs of the two upload_new2 calls"""
+
+    def __init__(self, n):
+        self.n = n
+        self.flags = np.zeros(max(n, 1), dtype=np.uint8)
+        self.offs = np.zeros(max(n, 1), dtype=np.uint64)
+        self.lens = np.zeros(max(n, 1), dtype=np.uint32)
+        self.kinds = np.zeros(max(n, 1), dtype=np.uint8)
+        self.crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        self.used, self.st, self.enc = C.c_uint64(), _lib.DedupStats(), _lib.EncodeStats()
+
+    def args(self):
+        return (self.flags.ctypes.data, self.offs.ctypes.data, self.lens.ctypes.data, self.kinds.ctypes.data,
+                self.crcs.ctypes.data, C.byref(self.used), C.byref(self.st), C.byref(self.enc))
+
+    def result(self, dst):
+        n = self.n
+        dst.used = int(self.used.value)
+        return (dst, self.flags[:n], self.offs[:n], self.lens[:n], self.kinds[:n], self.crcs[:n],
+                {k: getattr(self.st, k) for k, _ in _lib.DedupStats._fields_}, _encode_stats(self.enc))
 
 
 def zstd_encode_bound(n: int) -> int:
@@ -700,6 +726,34 @@ class KnownChunks:
             raise
         dst.used = int(used.value)
         return dst, flags[:n], offs[:n], crcs[:n], {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
+
+    def upload_new2(self, src, recs: np.ndarray, chunks, insert: bool = True, zstd: bool = False,
+                    dst: DeviceBuffer | None = None, nbytes: int | None = None):
+        """upload_new() with the blob's kind decided on the device (pbsgpu_known_upload_new2_device): with zstd=True a new
+        chunk whose zstd frame is strictly shorter than the chunk becomes a compressed blob, as Engine.blob_encode2() makes
+        it; blob i lies at offsets[i], in the slot of the uncompressed layout, and is lens[i] long. zstd=False gives
+        upload_new()'s outputs exactly. Returns (buffer with .used, known flags, offsets, lens, kinds (0 uncompressed,
+        1 compressed), CRCs (n each; 0 for known records), stats, encode stats as Engine.blob_encode2())."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        n = int(recs.size)
+        segs, nseg = _segs(chunks)
+        assert nseg == n, "one chunk range per record"
+        sp, sn = self._eng._dev(src, nbytes)
+        assert sp is not None, "upload_new2() wants device memory"
+        own = dst is None
+        if own:
+            sizes = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)[:, 1] if n else np.zeros(0, dtype=np.uint64)
+            dst = self._eng.alloc(max(int(sizes.sum()) + 12 * n, 16))
+        o = _Upload2Out(n)
+        try:
+            check(self._L.pbsgpu_known_upload_new2_device(self._h, sp, sn, recs.ctypes.data if n else None, segs, n, int(insert),
+                                                          _lib.ENCODE_F_ZSTD if zstd else 0, dst.ptr, dst.nbytes, *o.args()),
+                  "known_upload_new2_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return o.result(dst)
 
     def __len__(self) -> int:
         n = C.c_uint64()
@@ -1091,6 +1145,30 @@ class PageRing:
             raise
         dst.used = int(used.value)
         return dst, flags[:n], offs[:n], crcs[:n], {k: getattr(st, k) for k, _ in _lib.DedupStats._fields_}
+
+    def upload_new2(self, known: "KnownChunks", stream, recs: np.ndarray, insert: bool = True, zstd: bool = False,
+                    dst: DeviceBuffer | None = None):
+        """upload_new() with the blob's kind decided on the device (pbsgpu_ring_upload_new2_device): with zstd=True a new
+        chunk whose zstd frame is strictly shorter than the chunk becomes a compressed blob, straight out of the ring's
+        pages; blob i lies at offsets[i], in the slot of the uncompressed layout, and is lens[i] long. zstd=False gives
+        upload_new()'s outputs exactly. Returns (buffer with .used, known flags, offsets, lens, kinds (0 uncompressed,
+        1 compressed), CRCs (n each; 0 for known records), stats, encode stats as Engine.blob_encode2())."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        n = int(recs.size)
+        sid = _lib.RING_ANY_STREAM if stream is None else int(stream)
+        own = dst is None
+        if own:
+            dst = self._eng.alloc(max(int(recs["size"].astype(np.uint64).sum()) + 12 * n, 16))
+        o = _Upload2Out(n)
+        try:
+            check(self._L.pbsgpu_ring_upload_new2_device(self._h, known._h, sid, recs.ctypes.data if n else None, n, int(insert),
+                                                         _lib.ENCODE_F_ZSTD if zstd else 0, dst.ptr, dst.nbytes, *o.args()),
+                  "ring_upload_new2_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return o.result(dst)
 
     def copy(self, stream: int, offset: int, length: int) -> DeviceBuffer:
         """The raw stream bytes [offset, offset + length) out of the ring's pages into a new DeviceBuffer (the range must

@@ -9,13 +9,18 @@
   insert = 0 (so that repeated calls see the same set): pbsgpu_ring_upload_new_device, which keeps the flags on the device
   and builds the plan there, against pbsgpu_known_classify_host + pbsgpu_ring_blob_encode_device(skip = known), on the same
   polled records, alternating in the same run;
+* (e) the compressing writer's call (--zstd, only these legs): pbsgpu_ring_upload_new2_device with PBSGPU_ENCODE_F_ZSTD
+  against the route it replaces, pbsgpu_known_classify_host -> pbsgpu_ring_copy_device of every new chunk into one flat
+  buffer -> pbsgpu_blob_encode2_device(F_ZSTD), on the same polled records with half of the digests known, alternating;
+  the same call with flags = 0 against pbsgpu_ring_upload_new_device; and both with EVERY digest known, which is the
+  cost of the encoder's grid when it has nothing to do;
 * (c) the feed rate of a ring with the flag on whose consumer releases after every poll against the same ring with the flag
   off (GiB/s from the first fill to the last record), and the share of the arena that was held on average.
 
 (a), (b) and (d) are the median of a few synchronous calls timed with a host clock, after one warm-up call; (c) alternates
 the two rings and reports the median of its runs (--no-feed leaves it out).
 
-    python tools/ring_upload_rate.py [--big-gib 2] [--small-mib 256] [--feed-gib 512] [--reps 5] [--no-feed]
+    python tools/ring_upload_rate.py [--big-gib 2] [--small-mib 256] [--feed-gib 512] [--reps 5] [--no-feed] [--zstd]
 """
 import argparse
 import ctypes as C
@@ -104,6 +109,107 @@ def fused_against_two_calls(a, eng, ring, sid, recs, dst):
             "two_calls_ms": [round(x, 3) for x in t_two], "fused_ms": [round(x, 3) for x in t_fused],
             "two_calls_median_ms": med2, "fused_median_ms": medf,
             "two_calls_GBps": new_bytes / med2 / 1e6, "fused_GBps": new_bytes / medf / 1e6, "fused_over_two_calls": med2 / medf}
+
+
+def zstd_against_three_calls(a, eng, ring, sid, recs, dst):
+    """(e): the row's "upload_new2" entry"""
+    from pbs_plus_amd import KnownChunks, _lib
+
+    L = _lib.lib()
+    n = int(recs.size)
+    half, every = KnownChunks(eng, capacity=2 * n), KnownChunks(eng, capacity=2 * n)
+    half.add(recs[::2])
+    every.add(recs)
+    starts = (recs["end"] - recs["size"]).astype(np.uint64)
+    flat = eng.alloc(max(int(recs["size"].astype(np.uint64).sum()), 16))
+
+    def outputs():
+        return dict(flags=np.zeros(n, dtype=np.uint8), offs=np.zeros(n, dtype=np.uint64), lens=np.zeros(n, dtype=np.uint32),
+                    kinds=np.zeros(n, dtype=np.uint8), crcs=np.zeros(n, dtype=np.uint32), used=C.c_uint64(), st=_lib.DedupStats(),
+                    enc=_lib.EncodeStats())
+
+    out = {k: outputs() for k in ("three", "fused", "plain_old", "plain_new", "known_old", "known_new")}
+
+    def three_calls():
+        o = out["three"]
+        _lib.check(L.pbsgpu_known_classify_host(half._h, recs.ctypes.data, n, 0, o["flags"].ctypes.data, C.byref(o["st"])),
+                   "known_classify_host")
+        new = np.flatnonzero(o["flags"] == 0)
+        sizes = recs["size"][new].astype(np.uint64)
+        ends = np.cumsum(sizes)
+        for j, i in enumerate(new):
+            _lib.check(L.pbsgpu_ring_copy_device(ring._h, sid, int(starts[i]), int(sizes[j]), flat.ptr + int(ends[j] - sizes[j])),
+                       "ring_copy_device")
+        segs = np.ascontiguousarray(np.stack([ends - sizes, sizes], axis=1))
+        offs = np.zeros(new.size + 1, dtype=np.uint64)
+        lens, kinds, crcs = (np.zeros(new.size, dtype=t) for t in (np.uint32, np.uint8, np.uint32))
+        _lib.check(L.pbsgpu_blob_encode2_device(eng._h, flat.ptr, int(ends[-1]), segs.ctypes.data, new.size, _lib.ENCODE_F_ZSTD,
+                                                dst.ptr, dst.nbytes, offs.ctypes.data, lens.ctypes.data, kinds.ctypes.data,
+                                                crcs.ctypes.data, C.byref(o["enc"])), "blob_encode2_device")
+        o["offs"][new], o["lens"][new], o["kinds"][new], o["crcs"][new] = offs[:-1], lens, kinds, crcs
+        o["used"].value = int(offs[-1])
+
+    def new2(key, known, flags):
+        def run():
+            o = out[key]
+            _lib.check(L.pbsgpu_ring_upload_new2_device(ring._h, known._h, sid, recs.ctypes.data, n, 0, flags, dst.ptr, dst.nbytes,
+                                                        o["flags"].ctypes.data, o["offs"].ctypes.data, o["lens"].ctypes.data,
+                                                        o["kinds"].ctypes.data, o["crcs"].ctypes.data, C.byref(o["used"]),
+                                                        C.byref(o["st"]), C.byref(o["enc"])), "ring_upload_new2_device")
+        return run
+
+    def old(key, known):
+        def run():
+            o = out[key]
+            _lib.check(L.pbsgpu_ring_upload_new_device(ring._h, known._h, sid, recs.ctypes.data, n, 0, dst.ptr, dst.nbytes,
+                                                       o["flags"].ctypes.data, o["offs"].ctypes.data, o["crcs"].ctypes.data,
+                                                       C.byref(o["used"]), C.byref(o["st"])), "ring_upload_new_device")
+        return run
+
+    t_three, t_fused = _alternating_ms((three_calls, new2("fused", half, _lib.ENCODE_F_ZSTD)), a.reps)
+    for k in ("flags", "offs", "lens", "kinds", "crcs"):
+        assert np.array_equal(out["three"][k], out["fused"][k]), k
+    assert out["three"]["used"].value == out["fused"]["used"].value
+    t_old, t_new = _alternating_ms((old("plain_old", half), new2("plain_new", half, 0)), a.reps)
+    for k in ("flags", "offs", "crcs"):
+        assert np.array_equal(out["plain_old"][k], out["plain_new"][k]), k
+    t_kold, t_knew = _alternating_ms((old("known_old", every), new2("known_new", every, _lib.ENCODE_F_ZSTD)), a.reps)
+    assert out["known_new"]["used"].value == 0 and np.all(out["known_new"]["flags"] == 1)
+    new_bytes = int(out["fused"]["st"].unique_bytes)
+    enc = out["fused"]["enc"]
+    half.close()
+    every.close()
+    flat.free()
+
+    def leg(ts):
+        return {"ms": [round(x, 3) for x in ts], "median_ms": statistics.median(ts)}
+
+    m3, mf = statistics.median(t_three), statistics.median(t_fused)
+    return {"new_chunks": int(out["fused"]["st"].nunique), "new_bytes": new_bytes, "compressed_blobs": int(enc.blobs[1]),
+            "three_calls": leg(t_three), "fused_zstd": leg(t_fused), "fused_over_three_calls": m3 / mf,
+            "three_calls_GiBps": new_bytes / m3 * 1e3 / (1 << 30), "fused_zstd_GiBps": new_bytes / mf * 1e3 / (1 << 30),
+            "plain_upload_new": leg(t_old), "plain_upload_new2": leg(t_new),
+            "all_known_upload_new": leg(t_kold), "all_known_upload_new2_zstd": leg(t_knew)}
+
+
+def zstd_rates(a, name, avg, nbytes, ring_opt):
+    """(e) alone, on the records of one stream held by the ring"""
+    from pbs_plus_amd import Engine, PageRing, buzhash
+
+    eng = Engine(buzhash.NewConfig(avg), device=0)
+    ring = PageRing(eng, hold=True, **ring_opt)
+    sid, recs = _ingest(ring, 0xB10B, 0, nbytes)
+    ring.quiesce()
+    n = int(recs.size)
+    dst = eng.alloc(int(recs["size"].astype(np.uint64).sum()) + 12 * n)
+    row = {"batch": name, "chunks": n, "bytes": nbytes, "page_bytes": ring.page_bytes,
+           "upload_new2": zstd_against_three_calls(a, eng, ring, sid, recs, dst)}
+    print(json.dumps(row), flush=True)
+    dst.free()
+    ring.close_stream(sid)
+    ring.close()
+    eng.close()
+    return row
 
 
 def encode_rates(a, name, avg, nbytes, ring_opt):
@@ -196,15 +302,20 @@ def main():
     ap.add_argument("--feed-reps", type=int, default=3)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-feed", action="store_true", help="only the encode legs")
+    ap.add_argument("--zstd", action="store_true", help="only the legs of the compressing call (e)")
     a = ap.parse_args()
 
     from pbs_plus_amd import Engine, buzhash
 
     big = int(a.big_gib * (1 << 30))
-    encode_rates(a, "4MiB-avg", 4 << 20, big, dict(arena_bytes=big + (256 << 20), max_streams=2))
     small = a.small_mib << 20
-    encode_rates(a, "4KiB-avg", 4096, small,
-                 dict(arena_bytes=(small // 65536 + 64) * (65536 + 256), page_bytes=65536, max_streams=2, round_pages=256))
+    shapes = (("4MiB-avg", 4 << 20, big, dict(arena_bytes=big + (256 << 20), max_streams=2)),
+              ("4KiB-avg", 4096, small,
+               dict(arena_bytes=(small // 65536 + 64) * (65536 + 256), page_bytes=65536, max_streams=2, round_pages=256)))
+    for shape in shapes:
+        (zstd_rates if a.zstd else encode_rates)(a, *shape)
+    if a.zstd:
+        return
     if a.no_feed:
         return
     eng = Engine(buzhash.NewConfig(4 << 20), device=0)
