@@ -68,6 +68,7 @@ type (
 		BacklogMiB, LoneDeferMs, IdleTimeoutS, AutoparkMs                                float64
 		LanesCUs                                                                         uint32
 		ShortBytes                                                                       uint64
+		FillCUs                                                                          uint32
 		HoldPages                                                                        bool
 	}
 	EngineOptions struct {

@@ -682,6 +682,8 @@ type RingOptions struct {
 	// (0 = 3/2 of the average chunk size). Off by default: measured neutral on bulk rings (DESIGN.md 5.5).
 	LanesCUs   uint32
 	ShortBytes uint64
+	// FillCUs > 0 (experiments): the synthetic refill runs as that many whole-CU workgroups beside the scan instead of in turn with it.
+	FillCUs uint32
 	// HoldPages (PBSGPU_RING_F_HOLD_PAGES): pages the services are done with stay with their stream until Release, so
 	// that EncodeBlobs / Copy can still read the polled chunks' bytes. The holder must release, or the ring stalls (ErrBusy).
 	HoldPages bool
@@ -698,7 +700,8 @@ func (e *Engine) NewRing(o RingOptions) (*Ring, error) {
 		max_inflight: C.uint32_t(o.MaxInflight), long_bytes: C.uint32_t(o.LongBytes), long_lo_bytes: C.uint32_t(o.LongLoBytes),
 		long_spill: C.uint32_t(o.LongSpill), poll_every: C.uint32_t(o.PollEvery), flags: C.uint32_t(o.Flags),
 		backlog_mib: C.double(o.BacklogMiB), lone_defer_ms: C.double(o.LoneDeferMs), idle_timeout_s: C.double(o.IdleTimeoutS),
-		autopark_ms: C.double(o.AutoparkMs), lanes_cus: C.uint32_t(o.LanesCUs), short_bytes: C.uint64_t(o.ShortBytes)}
+		autopark_ms: C.double(o.AutoparkMs), lanes_cus: C.uint32_t(o.LanesCUs), short_bytes: C.uint64_t(o.ShortBytes),
+		fill_cus: C.uint32_t(o.FillCUs)}
 	if o.HoldPages {
 		co.flags |= C.PBSGPU_RING_F_HOLD_PAGES
 	}

@@ -362,7 +362,12 @@ typedef struct pbsgpu_ring_options {
     double idle_timeout_s;     /* the service stops on its own after this long without work or a call (0 = 20 s) */
     double autopark_ms;        /* > 0: the ring parks its service when nothing has been anywhere in it for this long */
     uint64_t short_bytes;      /* largest chunk the lanes service takes (0 = 3/2 of the average chunk size; first word of `reserved` before) */
-    uint64_t reserved[3];
+    uint32_t fill_cus;         /* experiments: > 0 = while a service runs the synthetic refill is that many whole-CU workgroups on
+                                * its own stream BESIDE the scan, which gets the rest of the cut side (0 = the default: refill and
+                                * scan one after the other, each on the whole cut side). PBSGPU_RING_FILL_CUS overrides. (first
+                                * word of `reserved` before) */
+    uint32_t reserved1;
+    uint64_t reserved[2];
 } pbsgpu_ring_options;
 #define PBSGPU_RING_OFF 0xffffffffu
 #define PBSGPU_RING_F_NO_OVERLAP 1u      /* scan of round n + 1 NOT beside the control kernel of round n (one scan set) */
@@ -370,7 +375,7 @@ typedef struct pbsgpu_ring_options {
 #define PBSGPU_RING_F_NO_CUT_PRIO 4u     /* refill and scan streams at normal priority */
 #define PBSGPU_RING_F_NO_SPLIT_AUTO 8u   /* the pair / express CU split does not follow the data */
 #define PBSGPU_RING_F_DEFER_SERVICE 16u  /* profiling: rounds only fill the queue, quiesce runs the services alone */
-#define PBSGPU_RING_F_FILL_SERIAL 32u    /* experiments: the synthetic refill in stream order behind the previous scan */
+#define PBSGPU_RING_F_FILL_SERIAL 32u    /* the synthetic refill in stream order behind the previous scan also while NO service runs (the default while one does) */
 #define PBSGPU_RING_F_DENSE_SERVICE 64u  /* the pair service with FOUR pairs (eight waves) per CU: more bytes per CU-second, every chain slower */
 #define PBSGPU_RING_F_DENSE_LANES 128u   /* the lanes service (lanes_cus) with EIGHT waves per CU: 84 instead of 77-81 chain-blocks per us and CU, 6 us per block */
 #define PBSGPU_RING_F_TIER_TAG 256u      /* diagnostics: pbsgpu_ring_poll* report the queue a chunk went through in bits 28-29 of `segment` (0 main, 1 long, 2 short) */

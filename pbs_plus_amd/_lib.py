@@ -99,7 +99,8 @@ class RingOptions(C.Structure):
                 ("min_round_pages", C.c_uint32), ("max_inflight", C.c_uint32), ("long_bytes", C.c_uint32),
                 ("long_lo_bytes", C.c_uint32), ("long_spill", C.c_uint32), ("poll_every", C.c_uint32), ("flags", C.c_uint32),
                 ("lanes_cus", C.c_uint32), ("backlog_mib", C.c_double), ("lone_defer_ms", C.c_double),
-                ("idle_timeout_s", C.c_double), ("autopark_ms", C.c_double), ("short_bytes", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+                ("idle_timeout_s", C.c_double), ("autopark_ms", C.c_double), ("short_bytes", C.c_uint64), ("fill_cus", C.c_uint32),
+                ("reserved1", C.c_uint32), ("reserved", C.c_uint64 * 2)]
 
 
 class EngineOptions(C.Structure):

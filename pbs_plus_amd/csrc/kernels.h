@@ -396,6 +396,7 @@ struct RingRound {
     // stream while round n's control kernel still reads round n's candidates; everything behind the scan runs in order on
     // the control stream and has one set.
     unsigned long long *tile_queue;  // the scan's dynamic tile counter
+    unsigned long long *fill_queue;  // the refill's slice counter: one per round in flight (zero at launch, like tile_queue)
     uint32_t *scalars;         // SC_* layout of engine_internal.h
     uint32_t *tile_cnt, *tile_off, *tile_slots, *scan_tmp;
     uint64_t *dense;
@@ -413,7 +414,9 @@ struct RingRound {
     const uint32_t *sugg_idx;
     uint64_t sugg_feed;        // reader-buffer rule (Suggested::feed / absolute)
     uint32_t sugg_abs;
-    uint32_t pad0;
+    uint32_t fill_blocks;      // workgroups of the synthetic refill (k_ring_fill) ...
+    uint32_t fill_shared;      // ... 0: one whole CU each (they ask for LDS that excludes everybody else); 1: as many as fit
+    uint32_t pad1;
     // fused control kernel: records of segment s go to recs[seg_rec_base[s] .. seg_rec_base[s + 1]) — the host's bound on
     // what the stream's open chunk + new pages can produce (mapped pinned, nseg + 1 entries)
     const uint32_t *seg_rec_base;

@@ -295,7 +295,7 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     pbsk::RingSeg *sg = r->in_segs((uint32_t)in);
     uint32_t *recbase = r->in_recbase((uint32_t)in);
     uint32_t *suggidx = r->in_suggidx((uint32_t)in);
-    uint32_t np = 0, ns = 0;
+    uint32_t np = 0, ns = 0, fill_pages = 0;
     uint64_t cells_needed = 0, new_bytes = 0;
     RoundInfo ri;
     std::vector<hipEvent_t> deps;
@@ -310,6 +310,8 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     // A ring that falls behind once grows its rounds, which makes it fall behind further: round 5's "unexplained" 184 + 8
     // cliff and its few-large-rounds regime. So a round takes at most HALF the configured pages while a service runs; the
     // whole-chip cut-ahead of an idle ring (no service yet: 64 GiB in ~20 ms) keeps full rounds.
+    // (Since the refill takes turns with the scan while a service runs — below — the cap no longer dodges their sharing; it stays
+    // because it was not measured again without it: profiles/ring_cut_partition.log.)
     // (one stream alone is cut-bound on the cut side's quarter of the chip once its service has started, with most lanes
     // idle: there the full round is the faster one — one file alone 407 vs 395 ms — and nothing can pile up behind it)
     uint32_t streams_waiting = 0;
@@ -338,6 +340,7 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
             p.slot = si;
             p.seg = ns;
             p.do_fill = q.do_fill ? 1u : 0u;
+            fill_pages += p.do_fill;
             p.fill_seed = q.seed;
             p.fill_off = q.fill_off;
             p.fill_kind = q.kind;
@@ -447,6 +450,7 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     const uint32_t set = r->ps ? r->scan_set : 0u;
     rr.scalars = r->scalars.as<uint32_t>();
     rr.tile_queue = r->tileq.as<unsigned long long>() + set * 8u;
+    rr.fill_queue = r->tileq.as<unsigned long long>() + 16u + (uint32_t)in;
     rr.tile_cnt = set ? r->tile_cnt2.as<uint32_t>() : r->tile_cnt.as<uint32_t>();
     rr.tile_off = r->tile_off.as<uint32_t>();
     rr.tile_slots = set ? r->tile_slots2.as<uint32_t>() : r->tile_slots.as<uint32_t>();
@@ -494,8 +498,38 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
         rr.q = r->source();
     }
     if (r->svc == SvcState::Stopped) r->deferred_bytes += new_bytes;  // cut ahead of the service (or the start waits for a graveyard flush)
-    if (r->svc == SvcState::Stopped) rr.scan_blocks = (uint32_t)std::max(1, e->num_cus);  // nobody else on the chip: full width
-    else if (r->ps && rr.scan_blocks > 8) rr.scan_blocks -= 1;  // (one CU stays free for the control kernel that runs beside the scan)
+    if (fill_pages) r->rounds_since_fill = 0;
+    else if (r->rounds_since_fill < 1000u) r->rounds_since_fill++;
+    // How the synthetic refill and the scan share the cut side.
+    // No service (the whole-chip cut-ahead of an idle ring, a lone file): both at full width, the refill on its own stream.
+    // A service runs: the cut side is shared IN TIME. The refill of round n + 1 goes in stream order behind the scan of round n,
+    // and each has every cut CU but the one left to the control kernel, which runs beside them on its own stream. Measured
+    // (profiles/ring_cut_partition.log): whenever the two run at the same time both get dearer per byte, on shared CUs
+    // (scan 82, refill 28 CU-ms per GiB) and on disjoint ones alike (58 and 22), against 42 and 16 in turn on small rounds: the refill
+    // is bound by what the memory system takes in beside the services' reads, not by its CUs, and the scan waits on the same
+    // memory. A ring that had fallen behind once then stayed behind (the large-round regime of round 6).
+    // fill_cus > 0 (experiments, tests): the partition IN SPACE instead — that many whole-CU refill workgroups on their own
+    // stream beside the scan, which gets the rest; a ring whose recent rounds had nothing to refill gives them to the scan.
+    bool fill_serial = r->fill_serial;
+    if (r->svc == SvcState::Stopped) {
+        rr.scan_blocks = (uint32_t)std::max(1, e->num_cus);
+        rr.fill_blocks = 2u * rr.scan_blocks;  // (two 1024-thread workgroups fill a CU's wave slots)
+        rr.fill_shared = 1;
+    } else {
+        constexpr uint32_t kFillRecent = 8;  // rounds
+        const int cut = std::max(1, e->num_cus - (int)r->svc_cus);
+        const int rest = cut - ((r->ps && cut > 8) ? 1 : 0);  // (one CU stays free for the control kernel)
+        if (r->opt_fill_cus && !fill_serial && rest >= 2) {
+            const int F = r->rounds_since_fill < kFillRecent ? (int)std::min<uint32_t>(r->opt_fill_cus, (uint32_t)rest - 1u) : 0;
+            rr.scan_blocks = (uint32_t)(rest - F);
+            rr.fill_blocks = (uint32_t)std::max(1, F);
+        } else {
+            fill_serial = true;
+            rr.scan_blocks = (uint32_t)std::max(1, rest);
+            rr.fill_blocks = 2u * rr.scan_blocks;
+            rr.fill_shared = 1;
+        }
+    }
     hipStream_t scan_st = r->ps ? r->ps : r->cs;
     for (hipEvent_t ev : deps)  // host-fed pages: the cut waits for their copies (device-side wait; the copies never wait for a kernel)
         if (hipStreamWaitEvent(scan_st, ev, 0) != hipSuccess) return fail(PBSGPU_E_HIP);
@@ -504,9 +538,6 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     if (r->ps && r->ctl_used[set])  // this scan set's previous user must have been resolved before the scan overwrites it
         if (hipStreamWaitEvent(r->ps, r->ev_ctl[set], 0) != hipSuccess) return fail(PBSGPU_E_HIP);
     {
-        // (PBSGPU_RING_F_FILL_SERIAL, experiments: the synthetic refill in stream order behind the previous round's scan instead
-        // of beside it on its own stream)
-        const bool fill_serial = r->fill_serial;
         pbsk::RingStage stg{};
         if (r->stage_inputs) {
             const uint8_t *hb = r->in((uint32_t)in);
@@ -584,6 +615,7 @@ void ring_env_overrides(pbsgpu_ring_options &o) {
         {"PBSGPU_RING_ROUND_PAGES", U32, &o.round_pages, 0},
         {"PBSGPU_RING_MIN_ROUND_PAGES", U32, &o.min_round_pages, 0},
         {"PBSGPU_RING_MAX_INFLIGHT", U32, &o.max_inflight, 0},
+        {"PBSGPU_RING_FILL_CUS", U32, &o.fill_cus, 0},
         {"PBSGPU_RING_LONG_BYTES", U32_ZERO_OFF, &o.long_bytes, 0},
         {"PBSGPU_RING_LONG_LO_BYTES", U32_ZERO_OFF, &o.long_lo_bytes, 0},
         {"PBSGPU_RING_LONG_SPILL", U32, &o.long_spill, 0},
@@ -857,6 +889,7 @@ int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool 
         r->opt_long_lo = o.long_lo_bytes;
         r->opt_long_spill = o.long_spill;
         r->opt_poll_every = o.poll_every;
+        r->opt_fill_cus = o.fill_cus;
         // Candidate slots per scan tile. The batch path starts small and RE-RUNS a batch whose tile overflowed; a ring round
         // cannot be re-run (later rounds continue from it), so the ring provisions for periodic data up front: one
         // candidate per 128 bytes (a repeating block of >= 128 bytes whose every period holds a candidate — BASELINE
@@ -900,7 +933,7 @@ int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool 
         CHK(r->tile_cnt.ensure((size_t)ntiles * 4 + 16));
         CHK(r->tile_off.ensure((size_t)ntiles * 4 + 16));
         CHK(r->tile_slots.ensure((size_t)ntiles * r->cap * 4 + 16));
-        CHK(r->tileq.ensure(128));
+        CHK(r->tileq.ensure(128 + kRingInputs * 8));  // two tile counters (64 bytes apart), then one refill counter per round in flight
         const bool overlap = !(o.flags & PBSGPU_RING_F_NO_OVERLAP);
         if (overlap) {
             CHK(r->tile_cnt2.ensure((size_t)ntiles * 4 + 16));
@@ -955,7 +988,7 @@ int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool 
         HIPCHK(hipMemsetAsync(r->streams.p, 0, (size_t)r->max_streams * sizeof(pbsk::RingStreamState), r->cs));
         HIPCHK(hipMemsetAsync(r->pending.p, 0, (size_t)r->npages * 4 + 64, r->cs));
         HIPCHK(hipMemsetAsync(r->scalars.p, 0, pbsk::kRsCount * 4 + 64, r->cs));
-        HIPCHK(hipMemsetAsync(r->tileq.p, 0, 128, r->cs));
+        HIPCHK(hipMemsetAsync(r->tileq.p, 0, 128 + kRingInputs * 8, r->cs));
         HIPCHK(hipStreamSynchronize(r->cs));
         for (auto &ev : r->ev_fill) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         if (overlap) {

@@ -146,6 +146,8 @@ struct pbsgpu_ring {
     bool hold = false;                    // PBSGPU_RING_F_HOLD_PAGES: handed-back pages wait in `held` for pbsgpu_ring_release
     pbse::HeldPages held;
     uint32_t opt_long_lo = 0, opt_long_spill = 0, opt_poll_every = 0;  // pbsgpu_ring_options (0 = the default rule)
+    uint32_t opt_fill_cus = 0;            // pbsgpu_ring_options::fill_cus (0 = the rule in ring_enqueue_round)
+    uint32_t rounds_since_fill = 1000;    // rounds enqueued since the last one with pages for the synthetic refill
     bool defer_service = false;           // PBSGPU_RING_F_DEFER_SERVICE (profiling): rounds only enqueue; quiesce runs the service ALONE
     double lone_defer_ms = 25.0;          // a lone bulk stream's rounds are cut ahead of the service start for at most this long (0 = off)
     double defer_t0 = 0;                  // when the current deferral began (0 = none)

@@ -2,10 +2,11 @@
 // namespace pbsk). Host side: ring.cpp. What a round does, in order (scan side and control side on their own HIP streams):
 //   k_ring_stage    the round's host-written tables -> device memory, once
 //   k_ring_fill     (bench / tests) the synthetic producer writes the round's new pages
-//   k_ring_prep_pages / k_ring_prep   page tables, the 128-byte pads that make a page boundary invisible to the scan window and
-//                   to a SHA block, and the round's segment table {open chunk start .. new end} per stream
+//   k_ring_prep_pages / ring_prep (the head of k_ring_control)   page tables, the 128-byte pads that make a page boundary
+//                   invisible to the scan window and to a SHA block, and the round's segment table {open chunk start .. new end}
+//                   per stream
 //   k_scan3         candidates of the NEW pages only (tile -> page through the round's page table)
-//   k_ring_control  ONE 1024-thread workgroup: tile prefix scan + compaction (dense ascending candidate list in logical
+//   k_ring_control  ONE 1024-thread workgroup: ring_prep, tile prefix scan + compaction (dense ascending candidate list in logical
 //                   coordinates), the multi-stream resolve (one wave per stream, single pass), records -> host-visible
 //                   record cells + queue descriptors + page reference counts, open-chunk holds, stream state, queue tail
 //                   (release), round status. (Round 3 ran this as TEN launch-bound kernels; that chain is gone since round 6.)
@@ -28,57 +29,86 @@ __device__ __forceinline__ bool ring_short_ticket(const RingRound &r, const Ring
     return true;
 }
 
-// synthetic producer: page bodies of the round that asked for it (grid.y = page entry)
-__global__ __launch_bounds__(256) void k_ring_fill(RingRound r) {
-    // (Through this reference the compiler re-reads the seed from the table behind every store of the generator loop. While the
-    // table lived in mapped pinned HOST memory (rounds 3-4) those reads went over PCIe and queued up: 3.7 us per page in a
-    // 68-page round, 11 us in a full one; copying the entry into registers first was tried in round 4 and was SLOWER — eight
-    // dependent PCIe loads at the start of every short-lived wave. Since round 5 r.pages is the device copy k_ring_stage
-    // makes: 2.7 / 3.6 us per page.)
-    const RingPage &pe = r.pages[blockIdx.y];
-    if (!pe.do_fill) return;
-    uint64_t *dst = reinterpret_cast<uint64_t *>(r.arena + pe.phys_off);
-    const uint64_t nwords = ((uint64_t)pe.valid + 7u) / 8u;  // a page body is a multiple of 128 bytes: room for the last word
-    const uint64_t w0 = pe.fill_off >> 3;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    if (pe.fill_kind == 4u) {  // 16-byte blocks (page bodies and their stream offsets are 128-aligned); a page is < 2^31 bytes
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        const uint32_t nblk = (uint32_t)((nwords + 1u) / 2u), step = gridDim.x * blockDim.x;
-        const uint64_t q0 = w0 >> 1;
-        uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-        for (; i + 3u * step < nblk; i += 4u * step) {  // four independent blocks per trip: stores and ALU overlap
-            const uint4 a = chacha2_block(q0 + i, pe.fill_seed), b = chacha2_block(q0 + i + step, pe.fill_seed);
-            const uint4 c = chacha2_block(q0 + i + 2u * step, pe.fill_seed), d = chacha2_block(q0 + i + 3u * step, pe.fill_seed);
-            d4[i] = a;
-            d4[i + step] = b;
-            d4[i + 2u * step] = c;
-            d4[i + 3u * step] = d;
-        }
-        for (; i < nblk; i += step) d4[i] = chacha2_block(q0 + i, pe.fill_seed);
-        return;
-    }
-    if (pe.fill_kind == 5u) {  // piece table: every 16-byte block comes from generator 4 at (piece seed, piece source offset)
-        uint4 *d4 = reinterpret_cast<uint4 *>(dst);
-        const uint32_t nblk = (uint32_t)((nwords + 1u) / 2u), step = gridDim.x * blockDim.x;
-        const FillPiece *tab = pe.fill_tab;  // mapped pinned HOST memory: every load is a PCIe round trip — the current piece
-        const uint32_t nt = pe.fill_ntab;    // lives in registers and the table is only searched when a block leaves it
-        FillPiece pc{~0ull, 0, 0, 0};
-        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nblk; i += step) {
-            const uint64_t x = pe.fill_off + 16ull * i;
-            if (!(x >= pc.dst_off && x - pc.dst_off < pc.len)) {
-                uint32_t lo = 0, hi = nt;
-                while (hi - lo > 1u) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (tab[mid].dst_off <= x) lo = mid; else hi = mid;
+// synthetic producer: page bodies of the round that asked for it. A FIXED count of 1024-thread workgroups (RingRound::fill_blocks)
+// over an atomic counter, in one of two forms (ring.cpp, ring_enqueue_round, and profiles/ring_cut_partition.log):
+//   fill_shared (the default): a 1 KiB LDS tag like every ring-side kernel, two workgroups per cut CU. Nothing runs beside it but
+//       the control kernel: it goes in stream order between two scans.
+//   whole-CU (pbsgpu_ring_options::fill_cus): each asks for kRingFillLds of LDS it never touches. 96 KiB cannot share a CU's
+//       160 KiB with a scan workgroup (64 KiB static + 40 KiB dynamic), with a second refill workgroup, or with a service
+//       workgroup (the whole LDS) — so the refill of round n + 1 and the scan of round n, on their own streams, never want the same
+//       CU once their two counts add up to no more than the CUs the services leave free. (Until round 6 the refill was
+//       npages x 16 light blocks that the dispatcher trickled onto every CU with room, and a scan workgroup — which needs a CU to
+//       itself — found none.)
+// Work: the round's pages cut into slices of kRingFillSlice bytes, handed out by the counter (RingRound::fill_queue, as
+// tile_queue for the scan; zeroed with it by k_ring_prep_pages of the round, which runs behind this kernel). A workgroup that
+// finds the counter beyond the last slice leaves; it waits for nothing. The next ticket is fetched while the current slice is
+// written (one atomic round trip per slice would otherwise cost as much as the slice). The bytes are a pure function of
+// (seed, kind, stream offset), whoever writes them.
+constexpr unsigned kRingFillLds = 96u << 10;
+constexpr uint32_t kRingFillSlice = 128u << 10;  // two trips of the kind-4 loop (1024 threads x 4 blocks x 16 bytes)
+__global__ __launch_bounds__(1024) void k_ring_fill(RingRound r) {
+    __shared__ unsigned long long ticket[2];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t spp = (r.page_bytes + kRingFillSlice - 1u) / kRingFillSlice;  // slices per page (the last one may be partial)
+    const unsigned long long nitems = (unsigned long long)r.npages * spp;
+    unsigned long long next = 0;
+    if (tid == 0) ticket[0] = atomicAdd(r.fill_queue, 1ull);
+    __syncthreads();
+    for (uint32_t it = 0;; ++it) {
+        const unsigned long long item = ticket[it & 1u];
+        if (item >= nitems) break;
+        if (tid == 0) next = atomicAdd(r.fill_queue, 1ull);
+        // (Through this reference the compiler re-reads the seed from the table behind every store of the generator loop. While the
+        // table lived in mapped pinned HOST memory (rounds 3-4) those reads went over PCIe and queued up; copying the entry into
+        // registers first was tried in round 4 and was SLOWER. Since round 5 r.pages is the device copy k_ring_stage makes.)
+        const RingPage &pe = r.pages[item / spp];
+        const uint32_t sl = (uint32_t)(item % spp);
+        if (pe.do_fill) {
+            uint64_t *dst = reinterpret_cast<uint64_t *>(r.arena + pe.phys_off);
+            const uint64_t nwords = ((uint64_t)pe.valid + 7u) / 8u;  // a page body is a multiple of 128 bytes: room for the last word
+            const uint64_t w0 = pe.fill_off >> 3;
+            // 16-byte blocks (page bodies and their stream offsets are 128-aligned); a page is < 2^31 bytes
+            const uint32_t nblk = (uint32_t)((nwords + 1u) / 2u);
+            const uint32_t b0 = sl * (kRingFillSlice / 16u), b1 = min(nblk, b0 + kRingFillSlice / 16u);
+            if (pe.fill_kind == 4u) {
+                uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+                constexpr uint32_t step = 1024u;
+                const uint64_t q0 = w0 >> 1;
+                uint32_t i = b0 + tid;
+                for (; i + 3u * step < b1; i += 4u * step) {  // four independent blocks per trip: stores and ALU overlap
+                    const uint4 a = chacha2_block(q0 + i, pe.fill_seed), b = chacha2_block(q0 + i + step, pe.fill_seed);
+                    const uint4 c = chacha2_block(q0 + i + 2u * step, pe.fill_seed), d = chacha2_block(q0 + i + 3u * step, pe.fill_seed);
+                    d4[i] = a;
+                    d4[i + step] = b;
+                    d4[i + 2u * step] = c;
+                    d4[i + 3u * step] = d;
                 }
-                pc = tab[lo];
+                for (; i < b1; i += step) d4[i] = chacha2_block(q0 + i, pe.fill_seed);
+            } else if (pe.fill_kind == 5u) {  // piece table: every 16-byte block comes from generator 4 at (piece seed, piece source offset)
+                uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+                const FillPiece *tab = pe.fill_tab;  // mapped pinned HOST memory: every load is a PCIe round trip — the current piece
+                const uint32_t nt = pe.fill_ntab;    // lives in registers and the table is only searched when a block leaves it
+                FillPiece pc{~0ull, 0, 0, 0};
+                for (uint32_t i = b0 + tid; i < b1; i += 1024u) {
+                    const uint64_t x = pe.fill_off + 16ull * i;
+                    if (!(x >= pc.dst_off && x - pc.dst_off < pc.len)) {
+                        uint32_t lo = 0, hi = nt;
+                        while (hi - lo > 1u) {
+                            const uint32_t mid = (lo + hi) >> 1;
+                            if (tab[mid].dst_off <= x) lo = mid; else hi = mid;
+                        }
+                        pc = tab[lo];
+                    }
+                    d4[i] = chacha2_block((pc.src_off + (x - pc.dst_off)) >> 4, pc.seed);
+                }
+            } else {
+                const uint64_t e = min(nwords, 2ull * b1);
+                for (uint64_t i = 2ull * b0 + tid; i < e; i += 1024u) dst[i] = fill_word(w0 + i, pe.fill_seed, pe.fill_kind);
             }
-            d4[i] = chacha2_block((pc.src_off + (x - pc.dst_off)) >> 4, pc.seed);
         }
-        return;
+        if (tid == 0) ticket[(it + 1u) & 1u] = next;  // (the other word is still being read by slower waves of this trip)
+        __syncthreads();
     }
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += stride)
-        dst[i] = fill_word(w0 + i, pe.fill_seed, pe.fill_kind);
 }
 
 // SCAN side (no device state): the head pad of every new page = the last 128 bytes of the stream's previous page, which the
@@ -89,7 +119,10 @@ __global__ __launch_bounds__(256) void k_ring_fill(RingRound r) {
 __global__ __launch_bounds__(64) void k_ring_prep_pages(RingRound r) {
     const uint32_t b = blockIdx.x;
     const int t = threadIdx.x;
-    if (b == 0 && t == 0) *r.tile_queue = 0ull;
+    if (b == 0 && t == 0) {
+        *r.tile_queue = 0ull;
+        *r.fill_queue = 0ull;  // (this round's refill has ended: the scan stream waits for it)
+    }
     if (b >= r.npages || t >= 8) return;
     const RingPage &pe = r.pages[b];
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -98,14 +131,13 @@ __global__ __launch_bounds__(64) void k_ring_prep_pages(RingRound r) {
     reinterpret_cast<uint4 *>(r.arena + pe.phys_off - 128)[t] = v;
 }
 
-// CONTROL side, in order behind the previous round's control kernel.
-// blocks [0, npages): page table entry + TAIL pad of the previous page; blocks [npages, npages + nseg): one stream's segment
-__global__ __launch_bounds__(64) void k_ring_prep(RingRound r) {
-    const uint32_t b = blockIdx.x;
-    const int t = threadIdx.x;
-    if (b == 0 && t < kRsCount) {  // candidate / record counters
+// CONTROL side, in order behind the previous round's control kernel: the head of k_ring_control (its own launch until round 6 —
+// 48 us elapsed for 4.5 us of work on the chain that publishes chunks). Items [0, npages): page table entry + TAIL pad of the
+// previous page, 16 threads each; then one thread per segment.
+__device__ __forceinline__ void ring_prep(const RingRound &r, const uint32_t tid) {
+    if (tid < (uint32_t)kRsCount) {  // candidate / record counters
         uint32_t v = 0;
-        if (t == kRsShortRoom && r.q.short_bytes) {
+        if (tid == (uint32_t)kRsShortRoom && r.q.short_bytes) {
             // how many short chunks this round may send to the lanes service: what keeps its queue at `short_room` entries.
             // ONE value per round (stail only moves in the control kernels of this stream, shead only grows): every record thread
             // of the control kernel compares its ticket with the same number, so the positions handed out have no holes.
@@ -113,9 +145,10 @@ __global__ __launch_bounds__(64) void k_ring_prep(RingRound r) {
             const uint32_t waiting = (uint32_t)sq - (uint32_t)(sq >> 32);
             v = waiting < r.q.short_room ? r.q.short_room - waiting : 0u;
         }
-        r.scalars[t] = v;
+        r.scalars[tid] = v;
     }
-    if (b < r.npages) {
+    const uint32_t t = tid & 15u;
+    for (uint32_t b = tid >> 4; b < r.npages; b += 64u) {
         const RingPage &pe = r.pages[b];
         const RingSeg &sg = r.segs_in[pe.seg];
         RingStreamState *st = r.streams + pe.slot;
@@ -136,20 +169,21 @@ __global__ __launch_bounds__(64) void k_ring_prep(RingRound r) {
             uint4 *tailpad = reinterpret_cast<uint4 *>(const_cast<uint8_t *>(prev) + r.page_bytes);
             tailpad[t] = reinterpret_cast<const uint4 *>(body)[t];
         }
-        if (t == 32) st->pt[k % kRingPT] = pe.phys;  // read above only for k - 1: no conflict inside the block
-        return;
+        // (pt[k - 1] above is read by the same 16 lanes of one wave, before this store; another page of the round writes pt[k']
+        // with k' >= k, which aliases k - 1 only 511 pages on — more than a stream gives one round)
+        if (t == 8) st->pt[k % kRingPT] = pe.phys;
     }
-    const uint32_t s = b - r.npages;
-    if (s >= r.nseg || t != 0) return;
-    const RingSeg &sg = r.segs_in[s];
-    const RingStreamState *st = r.streams + sg.slot;
-    const uint64_t c = sg.reset ? 0ull : st->c;
-    r.segs[s].offset = ((uint64_t)sg.slot << kRingOffBits) | c;
-    r.segs[s].length = sg.new_end - c;
-    r.seg_newc[s] = c;   // a segment without records leaves its stream where it was
-    r.seg_open[s] = (sg.new_end > c && !sg.final) ? 1u : 0u;
-    r.seg_ecand_in[s] = sg.reset ? ~0ull : st->ecand;
-    r.seg_ecand[s] = ~0ull;
+    for (uint32_t s = tid; s < r.nseg; s += 1024u) {
+        const RingSeg &sg = r.segs_in[s];
+        const RingStreamState *st = r.streams + sg.slot;
+        const uint64_t c = sg.reset ? 0ull : st->c;
+        r.segs[s].offset = ((uint64_t)sg.slot << kRingOffBits) | c;
+        r.segs[s].length = sg.new_end - c;
+        r.seg_newc[s] = c;   // a segment without records leaves its stream where it was
+        r.seg_open[s] = (sg.new_end > c && !sg.final) ? 1u : 0u;
+        r.seg_ecand_in[s] = sg.reset ? ~0ull : st->ecand;
+        r.seg_ecand[s] = ~0ull;
+    }
 }
 
 // ---- one record of the round: record cell + queue descriptor + page references ------------------------------------------
@@ -336,6 +370,9 @@ __global__ __launch_bounds__(1024) void k_ring_control(RingRound r, SuggFeed fr)
     const int lane = tid & 63, wave = tid >> 6;
     RingCtl *ctl = r.q.ctl;
     const unsigned long long tk0 = wall_clock64();  // phase times of this round -> RingRoundStatus::phase_ticks (thread 0)
+    ring_prep(r, tid);  // (counted with phase A)
+    __threadfence();
+    __syncthreads();
     // ---- (A) tile prefix scan + compaction: thread t owns a contiguous run of tiles -------------------------------------
     const uint64_t ntiles = (uint64_t)r.npages * r.tpp;
     const uint64_t per = (ntiles + 1023u) / 1024u;
@@ -519,7 +556,10 @@ hipError_t launch_ring_round(const RingRound &r, int num_cus, hipStream_t st, hi
     if (any_fill) {
         // the synthetic producer runs on its own HIP stream: the refill of round n + 1 overlaps the cut of round n (both
         // live on the CUs the SHA service leaves free)
-        hipLaunchKernelGGL(k_ring_fill, dim3(16, r.npages), dim3(256), kRingLdsTag, fill_st ? fill_st : sst, r);
+        hipError_t fe = allow_lds(&k_ring_fill, kRingFillLds);
+        if (fe != hipSuccess) return fe;
+        hipLaunchKernelGGL(k_ring_fill, dim3(std::max(1u, r.fill_blocks)), dim3(1024), r.fill_shared ? kRingLdsTag : kRingFillLds,
+                           fill_st ? fill_st : sst, r);
         if (fill_st && fill_st != sst) {
             hipError_t e = hipEventRecord(fill_ev, fill_st);
             if (e != hipSuccess) return e;
@@ -554,7 +594,6 @@ hipError_t launch_ring_round(const RingRound &r, int num_cus, hipStream_t st, hi
         e = hipStreamWaitEvent(st, scan_ev, 0);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_ring_prep, dim3(r.npages + r.nseg), dim3(64), kRingLdsTag, st, r);
     hipLaunchKernelGGL(k_ring_control, dim3(1), dim3(1024), kRingLdsTag, st, r, SuggFeed{r.sugg_feed, 0, r.sugg_abs, 0});
     return hipGetLastError();
 }
