@@ -78,6 +78,7 @@ type (
 		StreamShaCUs, StreamExpressCUs, StreamRingSlots, StreamCtxPool   uint32
 		StreamRingGiB                                                    float64
 		StreamPageBytes                                                  uint64
+		ZstdSeqTables                                                    uint32
 	}
 	RingStats struct {
 		PageBytes, BytesEnqueued, Chunks uint64

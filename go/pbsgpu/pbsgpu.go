@@ -100,6 +100,7 @@ type EngineOptions struct {
 	StreamCtxPool       uint32  // closed stream contexts kept for re-use (0 = 8; ^uint32(0) = none)
 	StreamRingGiB       float64 // its arena (0 = 48)
 	StreamPageBytes     uint64  // its page size (0 = default)
+	ZstdSeqTables       uint32  // the zstd encoder's sequences: 0 predefined tables, explicit offsets; 1 repeat offsets and per-block tables
 }
 
 func NewEngineOpt(device int, cfg Config, o EngineOptions) (*Engine, error) {
@@ -109,7 +110,8 @@ func NewEngineOpt(device int, cfg Config, o EngineOptions) (*Engine, error) {
 		resolve_par_min: C.uint64_t(o.ResolveParMin), sha_many_files_per_core: C.uint32_t(o.ShaManyFilesPerCore),
 		stream_sha_cus: C.uint32_t(o.StreamShaCUs), stream_express_cus: C.uint32_t(o.StreamExpressCUs),
 		stream_ring_slots: C.uint32_t(o.StreamRingSlots), stream_ctx_pool: C.uint32_t(o.StreamCtxPool),
-		stream_ring_gib: C.double(o.StreamRingGiB), stream_page_bytes: C.uint64_t(o.StreamPageBytes)}
+		stream_ring_gib: C.double(o.StreamRingGiB), stream_page_bytes: C.uint64_t(o.StreamPageBytes),
+		zstd_seq_tables: C.uint32_t(o.ZstdSeqTables)}
 	if err := check(C.pbsgpu_engine_create_opt(C.int(device), &cfg.c, &co, &e.h), "engine_create"); err != nil {
 		return nil, err
 	}

@@ -133,7 +133,11 @@ typedef struct pbsgpu_engine_options {
     uint32_t stream_express_cus;     /* ... of its express service (0 = default 8; 0xffffffff = none); PBSGPU_STREAM_XP_CUS */
     uint32_t stream_ring_slots;      /* ring streams (sections of all payload streams) open at once (0 = 256); PBSGPU_STREAM_RING_SLOTS */
     uint32_t stream_ctx_pool;        /* closed stream contexts kept for re-use (0 = default 8; 0xffffffff = none); PBSGPU_STREAM_CTX_POOL */
-    uint32_t reserved0;
+    uint32_t zstd_seq_tables;        /* how this engine's zstd encoder (pbsgpu_zstd_encode_device, pbsgpu_blob_encode2_device, the two
+                                      * *_upload_new2_device calls) writes a block's sequences: 0 = predefined tables, explicit
+                                      * offsets (default; `reserved0` before); 1 = repeat offsets and per-block FSE / RLE tables
+                                      * where they pay: shorter frames, never longer. Any other value: PBSGPU_E_INVALID.
+                                      * PBSGPU_ZSTD_SEQ_TABLES overrides. */
     double stream_ring_gib;          /* its arena (0 = default 48 GiB); PBSGPU_STREAM_RING_GIB */
     uint64_t stream_page_bytes;      /* its page size (0 = default); PBSGPU_STREAM_PAGE_BYTES */
     uint64_t reserved[4];
@@ -783,9 +787,16 @@ int pbsgpu_blob_decode2_device(pbsgpu_engine *eng, const void *blobs_dptr, uint6
  * sanitizers) writes one frame per chunk: single segment, content size declared, no dictionary, no checksum; blocks of
  * 128 KiB that are independent of one another (no match reaches before its own block, so repeats more than 128 KiB
  * apart are not found); per block RLE, raw or compressed, whichever applies first; greedy matching with a minimum match
- * of 4; predefined sequence tables and no repeat offsets; Huffman literals with directly described weights.
+ * of 4; Huffman literals with directly described or FSE-compressed weights. A block's sequences are written in one of
+ * two ways, by the ENGINE's option pbsgpu_engine_options.zstd_seq_tables, for every call below and for the two
+ * *_upload_new2_device calls alike: 0 (default), predefined sequence tables and no repeat offsets; 1, repeat offsets
+ * against a history that starts unknown in every block (blocks stay independent) and per block and symbol type the
+ * predefined table, RLE_Mode or an FSE table described in the block, whichever is estimated shortest, never Repeat_Mode.
+ * Both find the same matches; frames of mode 1 are never longer and on text about a fifth shorter. Slots, capacities,
+ * verdict rules and synchronisations do not depend on the mode; frame bytes, lens, kinds and crcs may.
  * DESIGN.md §16 has the decisions and what they cost in ratio. */
 #define PBSGPU_HAS_ZSTD_ENCODE 1
+#define PBSGPU_HAS_ZSTD_SEQ_TABLES 1
 /* No frame of n bytes of content is longer: the frame header, three bytes per block, the content. Host only. */
 uint64_t pbsgpu_zstd_encode_bound(uint64_t n);
 /* Encode many chunks in one call: chunk i = src[chunks[i].offset .. +length) becomes one frame at dst + out[i].offset, which

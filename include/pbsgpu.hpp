@@ -520,7 +520,9 @@ class Engine {
         r.value = std::shared_ptr<Engine>(new Engine(h));
         return r;
     }
-    // ... with every per-engine tuning value (pbsgpu_engine_options, ABI v5; zero fields = the defaults)
+    // ... with every per-engine tuning value (pbsgpu_engine_options, ABI v5; zero fields = the defaults). Among them
+    // zstd_seq_tables = 1: blob::EncodeZstd, blob::Encode2 and the fused uploads of this engine write repeat offsets and
+    // per-block sequence tables (shorter frames, never longer).
     static Result<std::shared_ptr<Engine>> New(int device, const buzhash::Config &cfg, const pbsgpu_engine_options &opt) {
         Result<std::shared_ptr<Engine>> r;
         pbsgpu_engine *h = nullptr;

@@ -108,7 +108,7 @@ class EngineOptions(C.Structure):
     _fields_ = [("inflight", C.c_uint32), ("sha_form", C.c_uint32), ("sha_slack_pct", C.c_uint32), ("sha_dense_pct", C.c_uint32),
                 ("resolve_par_min", C.c_uint64), ("sha_many_files_per_core", C.c_uint32), ("stream_sha_cus", C.c_uint32),
                 ("stream_express_cus", C.c_uint32), ("stream_ring_slots", C.c_uint32), ("stream_ctx_pool", C.c_uint32),
-                ("reserved0", C.c_uint32), ("stream_ring_gib", C.c_double), ("stream_page_bytes", C.c_uint64),
+                ("zstd_seq_tables", C.c_uint32), ("stream_ring_gib", C.c_double), ("stream_page_bytes", C.c_uint64),
                 ("reserved", C.c_uint64 * 4)]
 
 

@@ -701,6 +701,7 @@ static void engine_env_overrides(pbsgpu_engine_options &o) {
         {"PBSGPU_STREAM_CTX_POOL", U32_ZERO_OFF, &o.stream_ctx_pool},
         {"PBSGPU_STREAM_RING_GIB", F64, &o.stream_ring_gib},
         {"PBSGPU_STREAM_PAGE_BYTES", U64, &o.stream_page_bytes},
+        {"PBSGPU_ZSTD_SEQ_TABLES", U32, &o.zstd_seq_tables},
     };
     for (const Entry &e : table) {
         const char *v = getenv(e.name);
@@ -731,7 +732,7 @@ int pbsgpu_engine_create_opt(int device, const pbsgpu_config *cfg, const pbsgpu_
     if (opt) o = *opt;
     engine_env_overrides(o);
     uint32_t inflight = o.inflight;
-    if (o.sha_form > 2) return PBSGPU_E_INVALID;
+    if (o.sha_form > 2 || o.zstd_seq_tables > 1) return PBSGPU_E_INVALID;
     // the candidate/resolve split needs: window 64, mask = 2^k - 1, min >= window, max > min
     if (cfg->window != pbsk::kWindow) return PBSGPU_E_INVALID;
     const uint64_t m1 = (uint64_t)cfg->mask + 1;

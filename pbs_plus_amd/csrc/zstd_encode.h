@@ -30,6 +30,19 @@
 //     The weights are described directly (highest byte value <= 128) or FSE-compressed, whichever is smaller and fits the
 //     header byte; where neither does, the literals stay raw ("Huffman refused").
 //   * The encoder knows its room and writes nothing outside it; a room below what the frame needs is BAD_SIZE.
+//   * A second way to write the sequences (TState instead of State; pbsgpu_engine_options::zstd_seq_tables = 1): the same
+//     sequences, with repeat codes and per-block tables. The match finder, the literals and every other rule are the above.
+//     - Repeat codes against a history that starts UNKNOWN in every block, because the decoder's history comes from the
+//       blocks before and a block's encoder does not know them: an explicit offset makes entry 0 known and shifts values
+//       and known flags as the decoder shifts; a repeat code is written only for a known entry that equals the offset,
+//       and its rotation moves the flags too. Lane 0 converts where it takes the matches; bits 53-54 of the word.
+//     - Per symbol type Predefined_Mode, RLE_Mode (one code occurs) or FSE_Compressed_Mode, never Repeat_Mode. The
+//       accuracy log is highbit(nseq - 1) - 2 within [5, 9 / 8 / 9], raised until every occurring code has a state; the
+//       counts are scaled to 1 << log with rounding, at least 1 each, and the difference goes to (or comes off) the most
+//       frequent code; "less than 1" probabilities are not used (such a code gets one state either way). The choice is
+//       by count * (log - log2 p) in 1/256 bit plus the description's bytes, integers on both builds; RLE and compressed
+//       must beat predefined by kSeqMargin bits, which covers what the estimate can be off by, so that a frame of this
+//       mode is never longer than the other mode's.
 //   * Buffers a block needs, all implied by kBlockMax: lit kBlockMax bytes, seqs kSeqCap * 8 bytes, blk kBlockMax bytes (a
 //     compressed form that would pass the block's content length is abandoned where it would).
 #pragma once
@@ -56,6 +69,13 @@ enum : int {  // coverage bits
     E_NSEQ_0, E_NSEQ_1, E_NSEQ_2, E_MATCH_OVERLAP, E_MATCH_OFFSET_1, E_LL_EXTRA, E_ML_EXTRA, E_SEQ_CAP, E_HUF_REFUSED,
     E_NBITS
 };
+enum : int {  // ... of the mode with tables and repeat codes alone: the mode of each type (predefined, RLE, compressed; LL, OF,
+              // ML), the repeat codes behind literals and behind none, a repeat the decoder could have taken whose entry
+              // this block does not know, the longest accuracy log of each type
+    E_LL_PREDEF = E_NBITS, E_LL_RLE, E_LL_FSE, E_OF_PREDEF, E_OF_RLE, E_OF_FSE, E_ML_PREDEF, E_ML_RLE, E_ML_FSE,
+    E_REP_1, E_REP_2, E_REP_3, E_REP0_1, E_REP0_2, E_REP0_3, E_REP_UNKNOWN, E_LL_LOG_MAX, E_OF_LOG_MAX, E_ML_LOG_MAX,
+    E_NBITS_TABLES
+};
 
 constexpr uint32_t kHashLog = 12;
 constexpr uint32_t kMinMatch = 4;
@@ -73,6 +93,7 @@ struct HostLanes : pbsz::HostLanes {
 };
 
 struct EncTab {  // FSE encoding of one predefined distribution, derived from the decoding table fse_build makes
+    typedef uint8_t state_t;
     uint8_t state[64];  // state[cum[s] + k]: the k-th state (ascending) that decodes to s
     uint8_t cum[53], p[53];
     uint32_t log;
@@ -81,6 +102,7 @@ struct EncTab {  // FSE encoding of one predefined distribution, derived from th
 // Per block in flight; LDS in the kernel. The decoder's State is needed only while FSE tables are built (the predefined
 // ones before the first block, the weights' own after a block's match finding): it shares its bytes with the hash table.
 struct State {
+    static constexpr bool kSeqTables = false;
     union {
         uint32_t hash[1u << kHashLog];
         pbsz::State dec;
@@ -98,6 +120,29 @@ struct State {
     uint32_t flag, cursor, nlit, nseq, ll_run, next_b0;
     uint32_t nsym, maxsym, maxcnt, maxbits, desc, wfse, size, over;
 };
+
+// The mode with per-block sequence tables and repeat codes: State and what that mode adds. enc::State itself stays as it
+// is, and with it the kernel of the other mode.
+struct SeqTab {  // FSE encoding of one block's distribution of one symbol type: up to 512 states, probabilities up to 512
+    typedef uint16_t state_t;
+    uint16_t state[512];
+    uint16_t cum[53], p[53];
+    uint32_t log;  // 0: RLE_Mode, one state that takes no bits
+};
+constexpr uint32_t kSeqDescMax = 80;  // an NCount stream: 4 bits, then at most 10 bits and a 2-bit zero run per code: 4 + 53 * 12 bits
+constexpr uint32_t kSeqMargin = 16;   // bits, plus nseq / 64 (see choose_table)
+struct TState : State {
+    static constexpr bool kSeqTables = true;
+    SeqTab tab[3];                  // LL, OF, ML
+    uint32_t shist[3][64];          // the counts of the three code streams
+    uint8_t sdesc[3][kSeqDescMax];  // RLE_Mode: the code; FSE_Compressed_Mode: the NCount stream
+    uint32_t smode[3], sdlen[3];
+    uint32_t rep[3], known;         // the block's own offset history; known: bit i says that rep[i] is what the decoder has
+};
+
+#ifdef PBSGPU_ZSTD_COVERAGE  // CPU test build only: the history the decoder really has, for E_REP_UNKNOWN alone
+inline uint32_t g_dec_rep[3] = {1, 4, 8}, g_dec_rep_block[3] = {1, 4, 8};
+#endif
 
 PBSZ_HD uint32_t header_bytes(uint64_t n) { return 5u + (n <= 255 ? 1u : n <= 65791 ? 2u : 4u); }
 PBSZ_HD uint64_t block_count(uint64_t n) { return n ? (n + kBlockMax - 1) / kBlockMax : 1; }
@@ -178,12 +223,13 @@ struct BitWriter {
 };
 
 // t.state from t.cum, t.p, t.log and the decoding table: a state's rank among those of its symbol is what its baseline says
-PBSZ_HD void rank_states(EncTab &t, const FseEntry *tab) {
+template <class T>
+PBSZ_HD void rank_states(T &t, const FseEntry *tab) {
     const uint32_t size = 1u << t.log;
     PBSZ_ROLLED
     for (uint32_t u = 0; u < size; ++u) {
         const uint32_t s = tab[u].sym;
-        t.state[t.cum[s] + ((tab[u].next + size) >> tab[u].nbits) - t.p[s]] = (uint8_t)u;
+        t.state[t.cum[s] + ((tab[u].next + size) >> tab[u].nbits) - t.p[s]] = (typename T::state_t)u;
     }
 }
 
@@ -219,7 +265,8 @@ PBSZ_HD void init_tables(State &st) {
 }
 
 // symbol s goes in front of what state X stands for: the bits the decoder reads to get from s's state to X
-PBSZ_HD void fse_put(const EncTab &t, uint32_t &X, uint32_t s, BitWriter &bw) {
+template <class T>
+PBSZ_HD void fse_put(const T &t, uint32_t &X, uint32_t s, BitWriter &bw) {
     const uint32_t x = X + (1u << t.log), p = t.p[s];
     uint32_t nb = t.log - highbit(p);
     if ((x >> nb) < p) --nb;
@@ -549,8 +596,175 @@ PBSZ_HD uint32_t encode_literals(State &st, const uint8_t *lit, uint32_t nlit, u
     return lh + body;
 }
 
-// Lane 0: the sequences section of seqs[0, nseq) into b[0, cap); its length, or kNone where it would not fit.
-PBSZ_HD uint32_t encode_sequences(const State &st, const uint64_t *seqs, uint32_t nseq, uint8_t *b, uint32_t cap) {
+// The description of norm[0, nsym), which sums to 1 << log, as a forward bit stream (fse_read_norm, the other way round).
+// weights_fse has the same loop in its own body and keeps it: taken out into this function, the block kernel of the other
+// mode comes out of the compiler an instruction longer behind it, and that kernel is to stay the one it was.
+PBSZ_HD void ncount_write(BitWriter &bw, const int16_t *norm, uint32_t nsym, uint32_t log) {
+    bw.add(log - 5, 4);
+    uint32_t remaining = 1u << log, s = 0;
+    while (remaining > 0 && s < nsym) {
+        const uint32_t R = remaining + 1, bits = highbit(R) + 1, lower = (1u << (bits - 1)) - 1, thr = (1u << bits) - 1 - R;
+        const uint32_t p = (uint32_t)norm[s++], val = p + 1;
+        if (val < thr) bw.add(val, bits - 1);
+        else bw.add(val > lower ? val + thr : val, bits);
+        remaining -= p;
+        if (p == 0) {
+            uint32_t z = 0;
+            while (s < nsym && norm[s] == 0) {
+                ++z;
+                ++s;
+            }
+            while (z >= 3) {
+                bw.add(3, 2);
+                z -= 3;
+            }
+            bw.add(z, 2);
+        }
+    }
+}
+
+// log2(p) in 1/256, rounded down; 1 <= p <= 1 << 15. Eight squarings of the mantissa, one bit each: integers only, so both
+// builds cost a table alike.
+PBSZ_HD uint32_t log2_q8(uint32_t p) {
+    const uint32_t hb = highbit(p);
+    uint32_t x = p << (15 - hb), r = hb;  // x in [2^15, 2^16)
+    PBSZ_ROLLED
+    for (uint32_t i = 0; i < 8; ++i) {
+        x = (x * x) >> 15;
+        r <<= 1;
+        if (x >> 16) {
+            r |= 1;
+            x >>= 1;
+        }
+    }
+    return r;
+}
+
+// Lane 0, after the literals section (the hash table is dead: fse_build works in its bytes): the table of one symbol type
+// for this block from st.shist[which], nseq >= 1 counts in all. Predefined_Mode unless one of the others is estimated to be
+// shorter by more than the margin: kSeqMargin bits for the final state, whose width differs between the tables, and a
+// 1/64 bit per sequence for the estimate itself, which is exact to 1/256 bit per code and assumes the states evenly used.
+PBSZ_HD void choose_table(TState &st, uint32_t which, uint32_t nseq) {
+    pbsz::State &d = st.u.dec;
+    const EncTab &pre = which == 0 ? st.ll : which == 1 ? st.of : st.ml;
+    const uint32_t npre = which == 0 ? 36u : which == 1 ? 29u : 53u, maxlog = which == 1 ? 8u : 9u;
+    const uint32_t *cnt = st.shist[which];
+    SeqTab &t = st.tab[which];
+    uint32_t distinct = 0, nsym = 0, big = 0, cost0 = 0;
+    PBSZ_ROLLED
+    for (uint32_t s = 0; s < npre; ++s) {
+        const uint32_t c = cnt[s];
+        if (!c) continue;
+        ++distinct;
+        nsym = s + 1;
+        if (c > cnt[big]) big = s;
+        cost0 += c * ((pre.log << 8) - log2_q8(pre.p[s]));
+    }
+    const uint32_t margin = (kSeqMargin + nseq / 64) << 8;
+    uint32_t mode = 0, log = 0, dlen = 0;
+    if (distinct == 1) {
+        if ((8u << 8) + margin < cost0) {
+            mode = 1;
+            dlen = 1;
+            st.sdesc[which][0] = (uint8_t)big;
+        }
+    } else {
+        // a state per 4 to 8 sequences, as far as the format lets the table grow; every code that occurs needs one
+        log = nseq > 1 ? highbit(nseq - 1) : 0u;
+        log = log < 7 ? 5u : log - 2 > maxlog ? maxlog : log - 2;
+        while ((1u << log) < distinct) ++log;  // at most 6: 53 codes
+        const uint32_t size = 1u << log;
+        uint32_t sum = 0;
+        PBSZ_ROLLED
+        for (uint32_t s = 0; s < nsym; ++s) {
+            const uint32_t c = cnt[s];
+            uint32_t q = c ? (c * size + nseq / 2) / nseq : 0u;  // c <= kSeqCap, size <= 512: below 2^24
+            if (c && !q) q = 1;
+            d.norm[s] = (int16_t)q;
+            sum += q;
+        }
+        while (sum > size) {  // rounding up overshot, by fewer than there are codes: off the largest, which stays above 1
+            PBSZ_ROLLED
+            for (uint32_t s = 0; s < nsym; ++s)
+                if (d.norm[s] > d.norm[big]) big = s;
+            d.norm[big]--;
+            --sum;
+        }
+        d.norm[big] = (int16_t)(d.norm[big] + (int32_t)(size - sum));
+        uint32_t cost2 = 0;
+        PBSZ_ROLLED
+        for (uint32_t s = 0; s < nsym; ++s)
+            if (cnt[s]) cost2 += cnt[s] * ((log << 8) - log2_q8((uint32_t)d.norm[s]));
+        BitWriter bw;
+        bw.init(st.sdesc[which], kSeqDescMax);
+        ncount_write(bw, d.norm, nsym, log);
+        dlen = bw.flush();
+        if (!bw.over && cost2 + (dlen << 11) + margin < cost0 && fse_build(d, d.ll, log, nsym) == OK) mode = 2;
+    }
+    st.smode[which] = mode;
+    st.sdlen[which] = mode ? dlen : 0u;
+    PBSZ_ECOV((which == 0 ? E_LL_PREDEF : which == 1 ? E_OF_PREDEF : E_ML_PREDEF) + (int)mode);
+    if (mode == 2 && log == maxlog) PBSZ_ECOV(which == 0 ? E_LL_LOG_MAX : which == 1 ? E_OF_LOG_MAX : E_ML_LOG_MAX);
+    if (mode == 0) {  // the predefined table in the wider form
+        t.log = pre.log;
+        PBSZ_ROLLED
+        for (uint32_t u = 0; u < (1u << pre.log); ++u) t.state[u] = pre.state[u];
+        PBSZ_ROLLED
+        for (uint32_t s = 0; s < npre; ++s) {
+            t.cum[s] = pre.cum[s];
+            t.p[s] = pre.p[s];
+        }
+    } else if (mode == 1) {  // one state, no bits
+        t.log = 0;
+        t.state[0] = 0;
+        t.cum[big] = 0;
+        t.p[big] = 1;
+    } else {
+        t.log = log;
+        uint32_t cum = 0;
+        PBSZ_ROLLED
+        for (uint32_t s = 0; s < nsym; ++s) {
+            t.p[s] = (uint16_t)d.norm[s];
+            t.cum[s] = (uint16_t)cum;
+            cum += (uint32_t)d.norm[s];
+        }
+        rank_states(t, d.ll);
+    }
+}
+
+// The block's tables (the mode with tables only): the three code streams counted by all lanes, then lane 0 chooses.
+template <class P>
+PBSZ_HD void seq_tables(TState &st, const uint64_t *seqs, uint32_t nseq) {
+    for (uint32_t i = (uint32_t)P::lane(); i < 3 * 64; i += (uint32_t)P::lanes()) st.shist[i >> 6][i & 63] = 0;
+    P::sync();
+    for (uint32_t i = (uint32_t)P::lane(); i < nseq; i += (uint32_t)P::lanes()) {
+        const uint64_t q = seqs[i];
+        const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu, rc = (uint32_t)(q >> 53) & 3u;
+        const uint32_t ov = rc ? rc : ((uint32_t)(q >> 36) & 0x1ffffu) + 3;
+        P::aadd(&st.shist[0][ll_code(ll)], 1u);
+        P::aadd(&st.shist[1][highbit(ov)], 1u);
+        P::aadd(&st.shist[2][ml_code(ml)], 1u);
+    }
+    P::sync();
+    if (P::lane() == 0 && nseq) {
+        choose_table(st, 0, nseq);
+        choose_table(st, 1, nseq);
+        choose_table(st, 2, nseq);
+    }
+    P::sync();
+}
+
+PBSZ_HD const EncTab &tab_ll(const State &st) { return st.ll; }
+PBSZ_HD const EncTab &tab_of(const State &st) { return st.of; }
+PBSZ_HD const EncTab &tab_ml(const State &st) { return st.ml; }
+PBSZ_HD const SeqTab &tab_ll(const TState &st) { return st.tab[0]; }
+PBSZ_HD const SeqTab &tab_of(const TState &st) { return st.tab[1]; }
+PBSZ_HD const SeqTab &tab_ml(const TState &st) { return st.tab[2]; }
+
+// Lane 0: the sequences section of seqs[0, nseq) into b[0, cap); its length, or kNone where it would not fit. With tables
+// (S = TState, after seq_tables): the modes and descriptions the block chose, and the repeat codes of the words.
+template <class S>
+PBSZ_HD uint32_t encode_sequences(const S &st, const uint64_t *seqs, uint32_t nseq, uint8_t *b, uint32_t cap) {
     uint32_t p = 0;
     if (cap < 4) return kNone;
     if (nseq < 128) {
@@ -562,23 +776,41 @@ PBSZ_HD uint32_t encode_sequences(const State &st, const uint64_t *seqs, uint32_
         b[p++] = (uint8_t)nseq;
         PBSZ_ECOV(E_NSEQ_2);
     }
-    b[p++] = 0;  // Predefined_Mode three times
+    if constexpr (S::kSeqTables) {
+        if (cap - p < 1 + st.sdlen[0] + st.sdlen[1] + st.sdlen[2]) return kNone;
+        b[p++] = (uint8_t)(st.smode[0] << 6 | st.smode[1] << 4 | st.smode[2] << 2);
+        PBSZ_ROLLED
+        for (uint32_t w = 0; w < 3; ++w) {
+            PBSZ_ROLLED
+            for (uint32_t i = 0; i < st.sdlen[w]; ++i) b[p++] = st.sdesc[w][i];
+        }
+    } else {
+        b[p++] = 0;  // Predefined_Mode three times
+    }
+    const auto &t_ll = tab_ll(st);
+    const auto &t_of = tab_of(st);
+    const auto &t_ml = tab_ml(st);
     BitWriter bw;
     bw.init(b + p, cap - p);
     uint32_t x_ll = 0, x_of = 0, x_ml = 0;
     PBSZ_ROLLED
     for (uint32_t k = nseq; k-- > 0;) {
         const uint64_t q = seqs[k];
-        const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu, ov = (uint32_t)(q >> 36) + 3;
+        const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu;
+        uint32_t ov = (uint32_t)(q >> 36) + 3;
+        if constexpr (S::kSeqTables) {
+            const uint32_t rc = (uint32_t)(q >> 53) & 3u;
+            ov = rc ? rc : ((uint32_t)(q >> 36) & 0x1ffffu) + 3;
+        }
         const uint32_t cl = ll_code(ll), cm = ml_code(ml), co = highbit(ov);
         if (k == nseq - 1) {  // the decoder ends in these states: any state of the symbol serves
-            x_ll = st.ll.state[st.ll.cum[cl]];
-            x_of = st.of.state[st.of.cum[co]];
-            x_ml = st.ml.state[st.ml.cum[cm]];
+            x_ll = t_ll.state[t_ll.cum[cl]];
+            x_of = t_of.state[t_of.cum[co]];
+            x_ml = t_ml.state[t_ml.cum[cm]];
         } else {
-            fse_put(st.of, x_of, co, bw);
-            fse_put(st.ml, x_ml, cm, bw);
-            fse_put(st.ll, x_ll, cl, bw);
+            fse_put(t_of, x_of, co, bw);
+            fse_put(t_ml, x_ml, cm, bw);
+            fse_put(t_ll, x_ll, cl, bw);
         }
         if (cl > 15) PBSZ_ECOV(E_LL_EXTRA);
         if (cm > 31) PBSZ_ECOV(E_ML_EXTRA);
@@ -587,18 +819,50 @@ PBSZ_HD uint32_t encode_sequences(const State &st, const uint64_t *seqs, uint32_
         bw.add(ov - (1u << co), co);
         if (bw.over) return kNone;
     }
-    bw.add(x_ml, st.ml.log);
-    bw.add(x_of, st.of.log);
-    bw.add(x_ll, st.ll.log);
+    bw.add(x_ml, t_ml.log);
+    bw.add(x_of, t_of.log);
+    bw.add(x_ll, t_ll.log);
     const uint32_t len = bw.finish();
     return bw.over ? kNone : p + len;
 }
 
+// Lane 0, the mode with repeat codes: the code (1..3, or 0 for the explicit offset + 3) of a match at `off` behind `ll`
+// literals, and the block's history moved as the decoder moves its own (zstd_decode.h, decode_block). An entry is used only
+// where this block has set it: what the blocks before left in the decoder is not known here.
+PBSZ_HD uint32_t rep_code(uint32_t (&r)[3], uint32_t &known, uint32_t ll, uint32_t off) {
+    const uint32_t k0 = known & 1u, k1 = known >> 1 & 1u, k2 = known >> 2 & 1u;
+    const uint32_t r0 = r[0], r1 = r[1], r2 = r[2];
+    uint32_t idx = 0;  // the decoder's: code + (ll == 0)
+    if (ll && k0 && r0 == off) idx = 1;
+    else if (k1 && r1 == off) idx = 2;
+    else if (k2 && r2 == off) idx = 3;
+    else if (!ll && k0 && r0 > 1 && r0 - 1 == off) idx = 4;
+#ifdef PBSGPU_ZSTD_COVERAGE
+    {
+        uint32_t *g = g_dec_rep;
+        const bool avail = (ll && g[0] == off) || g[1] == off || g[2] == off || (!ll && g[0] > 1 && g[0] - 1 == off);
+        if (avail && !idx) PBSZ_ECOV(E_REP_UNKNOWN);
+        if (idx) PBSZ_ECOV((ll ? E_REP_1 : E_REP0_1) + (int)idx - (ll ? 1 : 2));
+        if (idx != 1) {  // (where idx names a known entry the decoder's holds the same value)
+            if (idx != 2) g[2] = g[1];
+            g[1] = g[0];
+            g[0] = off;
+        }
+    }
+#endif
+    if (idx == 1) return 1;
+    r[0] = off;
+    r[1] = r0;
+    r[2] = idx == 2 ? r2 : r1;
+    known = 1u | k0 << 1 | (idx == 2 ? k2 : k1) << 2;
+    return idx ? idx - (ll ? 0u : 1u) : 0u;
+}
+
 // One block src[0, bn), 1 <= bn <= kBlockMax: its type and, for a compressed block, the compressed form in blk[0, size).
 // Returns type | size << 2 (size: payload_bytes), the same in every lane. init_tables has run on st. lit: kBlockMax bytes,
-// seqs: kSeqCap words, blk: bn bytes; nothing else is stored to.
-template <class P>
-PBSZ_HD uint32_t encode_block(State &st, const uint8_t *src, uint32_t bn, uint8_t *blk, uint8_t *lit, uint64_t *seqs) {
+// seqs: kSeqCap words, blk: bn bytes; nothing else is stored to. S = TState: the mode with tables and repeat codes.
+template <class P, class S = State>
+PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *blk, uint8_t *lit, uint64_t *seqs) {
     for (uint32_t i = (uint32_t)P::lane(); i < (1u << kHashLog); i += (uint32_t)P::lanes()) st.u.hash[i] = 0;
     for (uint32_t i = (uint32_t)P::lane(); i < 256; i += (uint32_t)P::lanes()) st.hist[i] = 0;
     if (P::lane() == 0) {
@@ -609,6 +873,13 @@ PBSZ_HD uint32_t encode_block(State &st, const uint8_t *src, uint32_t bn, uint8_
         st.ll_run = 0;
         st.over = 0;
         st.size = 0;
+        if constexpr (S::kSeqTables) {
+            st.known = 0;  // nothing of the decoder's history is known at a block's start
+            st.rep[0] = st.rep[1] = st.rep[2] = 0;
+#ifdef PBSGPU_ZSTD_COVERAGE
+            for (int i = 0; i < 3; ++i) g_dec_rep_block[i] = g_dec_rep[i];
+#endif
+        }
     }
     P::sync();
     const uint32_t first = P::uni(src[0]);
@@ -664,7 +935,9 @@ PBSZ_HD uint32_t encode_block(State &st, const uint8_t *src, uint32_t bn, uint8_
                         const uint32_t off = st.moff[l];
                         if (off < m) PBSZ_ECOV(E_MATCH_OVERLAP);
                         if (off == 1) PBSZ_ECOV(E_MATCH_OFFSET_1);
-                        seqs[nseq++] = (uint64_t)run | (uint64_t)m << 18 | (uint64_t)off << 36;
+                        uint64_t q = (uint64_t)run | (uint64_t)m << 18 | (uint64_t)off << 36;
+                        if constexpr (S::kSeqTables) q |= (uint64_t)rep_code(st.rep, st.known, run, off) << 53;
+                        seqs[nseq++] = q;
                         run = 0;
                         cursor = pos + m;
                     } else {
@@ -691,6 +964,7 @@ PBSZ_HD uint32_t encode_block(State &st, const uint8_t *src, uint32_t bn, uint8_
     uint32_t type = B_RAW, size = bn;
     const uint32_t lsize = encode_literals<P>(st, lit, nlit, blk, bn);
     if (lsize != kNone) {
+        if constexpr (S::kSeqTables) seq_tables<P>(st, seqs, nseq);
         if (P::lane() == 0) st.size = encode_sequences(st, seqs, nseq, blk + lsize, bn - lsize);
         P::sync();
         const uint32_t ssize = P::uni(st.size);
@@ -700,16 +974,24 @@ PBSZ_HD uint32_t encode_block(State &st, const uint8_t *src, uint32_t bn, uint8_
         }
     }
     PBSZ_ECOV(type == B_RAW ? E_BLOCK_RAW : E_BLOCK_COMPRESSED);
+#ifdef PBSGPU_ZSTD_COVERAGE
+    if constexpr (S::kSeqTables)
+        if (type == B_RAW)  // its sequences never reach the decoder
+            for (int i = 0; i < 3; ++i) g_dec_rep[i] = g_dec_rep_block[i];
+#endif
     return type | size << 2;
 }
 
 // The frame of src[0, n), n < 4 GiB, into dst[0, room): BAD_SIZE where it needs more, and dst's contents are then
 // unspecified. *flen = the frame's length (with OK). Scratch as for encode_block. Never stores outside dst[0, room) and
 // the scratch.
-template <class P>
-PBSZ_HD int encode_frame(State &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint64_t room, uint8_t *blk, uint8_t *lit,
+template <class P, class S = State>
+PBSZ_HD int encode_frame(S &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint64_t room, uint8_t *blk, uint8_t *lit,
                          uint64_t *seqs, uint64_t *flen) {
     *flen = 0;
+#ifdef PBSGPU_ZSTD_COVERAGE
+    g_dec_rep[0] = 1, g_dec_rep[1] = 4, g_dec_rep[2] = 8;  // a frame's decoder starts here
+#endif
     init_tables<P>(st);
     const uint32_t hb = header_bytes(n);
     if (room < (uint64_t)hb + 3) return BAD_SIZE;
@@ -724,7 +1006,7 @@ PBSZ_HD int encode_frame(State &st, const uint8_t *src, uint32_t n, uint8_t *dst
     }
     for (uint32_t at = 0; at < n; at += kBlockMax) {
         const uint32_t bn = n - at < kBlockMax ? n - at : kBlockMax;
-        const uint32_t r = encode_block<P>(st, src + at, bn, blk, lit, seqs);
+        const uint32_t r = encode_block<P, S>(st, src + at, bn, blk, lit, seqs);
         const uint32_t type = r & 3u, size = r >> 2;
         if (room - pos < (uint64_t)3 + size) return BAD_SIZE;
         if (P::lane() == 0) block_header(dst + pos, at + bn == n ? 1u : 0u, type, type == B_COMPRESSED ? size : bn);

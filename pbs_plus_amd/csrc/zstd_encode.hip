@@ -13,6 +13,8 @@
 //                    compressed form goes to the BLOCK's 128 KiB of scratch, because the frame it belongs to is put
 //                    together later. Per block: type and size. A chunk may lie in two parts (a ring chunk in two pages):
 //                    the one block that holds the seam is put together in the workgroup's scratch first.
+//                    With pbsgpu_engine_options::zstd_seq_tables the same loop runs as k_zenc_tblocks, in a translation unit
+//                    of its own (zstd_encode_tables.hip), on a State that adds the per-block sequence tables.
 //   k_zenc_assemble  one workgroup of 256 per chunk: a prefix over its blocks' sizes (wave 0), then the frame header, the
 //                    block headers and the payloads (content for raw blocks, one byte for RLE, the compressed form) to
 //                    their places in the room. It records the frame's length and the status; for the blob call the
@@ -25,8 +27,7 @@
 #include <cstring>
 #include <vector>
 
-#include "engine_internal.h"
-#include "zstd_encode.h"
+#include "zstd_encode_blocks.h"
 
 using namespace pbse;
 namespace ze = pbsz::enc;
@@ -34,71 +35,9 @@ namespace ze = pbsz::enc;
 namespace pbsk {
 namespace zenc {
 
-struct Plan {
-    const uint8_t *src;
-    const Job *jobs;         // every chunk of the call
-    const uint32_t *bchunk;  // every block of the call: its chunk
-    uint8_t *blkout;         // the round's blocks, kBlockMax bytes each
-    uint32_t *bres;          // the round's blocks: type | size << 2
-    uint64_t *boff;          // the round's blocks: where the block header goes in its frame
-    uint8_t *lit;            // per workgroup of k_zenc_blocks: kBlockMax
-    uint64_t *seqs;          // per workgroup: kSeqCap
-    uint8_t *stage;          // per workgroup: kBlockMax, when a job may have two parts
-    uint8_t *dst;
-    uint64_t *res;           // per Job::out: frame length | status << 56
-    uint32_t *next;          // the round's block counter, zero at its start
-    uint32_t b0, b1, c0, c1; // the round
-    uint32_t blob;
-};
-
-// where byte p of the chunk lies, as an offset from Plan::src
-__device__ __forceinline__ uint64_t chunk_byte(const Job &j, uint32_t p) {
-    return p < j.a ? j.src_off + p : j.src1_off + (p - j.a);
-}
-
-struct WaveLanes {
-    static __device__ __forceinline__ int lane() {
-        int x = (int)threadIdx.x;
-        asm volatile("" : "+v"(x));  // taken anew at every use
-        return x;
-    }
-    static __device__ __forceinline__ int lanes() { return 64; }
-    static __device__ __forceinline__ void sync() { __syncthreads(); }
-    static __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-    static __device__ __forceinline__ void amax(uint32_t *p, uint32_t v) { atomicMax(p, v); }
-    static __device__ __forceinline__ void aadd(uint32_t *p, uint32_t v) { atomicAdd(p, v); }
-};
-
 __global__ __launch_bounds__(64) void k_zenc_blocks(Plan pl) {
     __shared__ ze::State st;
-    bool tables = false;
-    uint8_t *lit = pl.lit + (uint64_t)blockIdx.x * pbsz::kBlockMax;
-    uint64_t *seqs = pl.seqs + (uint64_t)blockIdx.x * ze::kSeqCap;
-    for (;;) {
-        uint32_t b = 0;  // the round's next block: blocks differ in cost, and the device's plan leaves some out altogether
-        if (threadIdx.x == 0) b = atomicAdd(pl.next, 1u);
-        b = pl.b0 + WaveLanes::uni(b);
-        if (b >= pl.b1) break;
-        const Job j = pl.jobs[pl.bchunk[b]];  // (uniform addresses: scalar loads)
-        if (j.out == kNoJob) continue;        // a chunk the device's plan does not encode
-        if (!tables) {
-            ze::init_tables<WaveLanes>(st);
-            tables = true;
-        }
-        const uint32_t at = (b - j.first) * pbsz::kBlockMax;
-        const uint32_t bn = j.len - at < pbsz::kBlockMax ? j.len - at : pbsz::kBlockMax;
-        uint8_t *blk = pl.blkout + (uint64_t)(b - pl.b0) * pbsz::kBlockMax;
-        const uint8_t *content = pl.src + chunk_byte(j, at);
-        if (at < j.a && j.a < at + bn) {  // the one block of a chunk that holds the seam between its parts: put together first
-            uint8_t *sg = pl.stage + (uint64_t)blockIdx.x * pbsz::kBlockMax;
-            for (uint32_t i = threadIdx.x; i < bn; i += 64) sg[i] = pl.src[chunk_byte(j, at + i)];
-            __syncthreads();
-            content = sg;
-        }
-        const uint32_t r = ze::encode_block<WaveLanes>(st, content, bn, blk, lit, seqs);
-        if (threadIdx.x == 0) pl.bres[b - pl.b0] = r;
-        __syncthreads();  // State, the literals, the sequences and the staged block go to the next block
-    }
+    encode_blocks(pl, st);
 }
 
 __global__ __launch_bounds__(256) void k_zenc_assemble(Plan pl) {
@@ -212,8 +151,13 @@ int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, co
         pl.b1 = p.bp.block_begin(pl.c1);
         if (pl.c0 == pl.c1) continue;
         if (pl.b1 > pl.b0) {
-            hipLaunchKernelGGL(k_zenc_blocks, dim3(std::min<uint32_t>(p.grid, pl.b1 - pl.b0)), dim3(64), 0, st, pl);
-            HIPCHK(hipGetLastError());
+            const uint32_t grid = std::min<uint32_t>(p.grid, pl.b1 - pl.b0);
+            if (e->opt.zstd_seq_tables) {  // the engine's option: per-block tables and repeat codes
+                HIPCHK(launch_blocks_tables(pl, grid, st));
+            } else {
+                hipLaunchKernelGGL(k_zenc_blocks, dim3(grid), dim3(64), 0, st, pl);
+                HIPCHK(hipGetLastError());
+            }
         }
         hipLaunchKernelGGL(k_zenc_assemble, dim3(std::min<uint32_t>(pl.c1 - pl.c0, (uint32_t)e->num_cus * 8)), dim3(256), 0, st, pl);
         HIPCHK(hipGetLastError());

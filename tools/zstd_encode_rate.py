@@ -1,6 +1,8 @@
 """Rate of the blob encode with chunks compressed on the device (pbsgpu_blob_encode2_device with PBSGPU_ENCODE_F_ZSTD), in
 GiB/s of CONTENT, beside what it is measured against:
 
+* with --seq-tables the same call on an engine created with zstd_seq_tables=1 (repeat offsets and per-block sequence
+  tables): its rate and its bytes per content byte beside the default mode's;
 * the plain pbsgpu_blob_encode_device of the same chunks (what the write side did before it could compress);
 * ZSTD_compress level 1 of the same chunks on 16 host threads, where libzstd.so.1 loads (ctypes releases the GIL); where it
   does not load, the leg says so and is left out.
@@ -12,7 +14,7 @@ the run. Each figure is the median of --reps synchronous calls timed with a host
 fastest and the slowest beside it. Not measured: the share of the serial lane (sequence and Huffman code), which needs a
 kernel variant or a trace, not a clock around the call.
 
-    python tools/zstd_encode_rate.py [--chunks 4096] [--reps 5] [--limit 600]
+    python tools/zstd_encode_rate.py [--chunks 4096] [--reps 5] [--limit 600] [--seq-tables]
 """
 import argparse
 import ctypes as C
@@ -67,20 +69,22 @@ def _rates(total, t):
             "GiBps_fastest": round(gib / t[1], 3)}
 
 
-def leg_device(a, zstd):
+def leg_device(a, zstd, tables=False):
     from pbs_plus_amd import Engine, buzhash
 
     host, ranges, kinds = _batch(a.chunks)
     total = int(ranges[:, 1].sum())
-    eng = Engine(buzhash.NewConfig(4 << 20), device=0)
+    eng = Engine(buzhash.NewConfig(4 << 20), device=0, **({"zstd_seq_tables": 1} if tables else {}))
     dev = eng.alloc(host.size)
     dev.upload(host)
     dst = eng.alloc(total + 12 * a.chunks)
-    res = {"leg": "encode2_zstd" if zstd else "blob_encode_device", "chunks": a.chunks, "content_bytes": total}
+    res = {"leg": ("encode2_zstd_seq_tables" if tables else "encode2_zstd") if zstd else "blob_encode_device", "chunks": a.chunks,
+           "content_bytes": total}
     if zstd:
         fn = lambda: eng.blob_encode2(dev, ranges, dst=dst, zstd=True)  # noqa: E731
         _, offs, lens, kd, crcs, stats = fn()
         res["blob_bytes"] = int(lens.sum())
+        res["bytes_per_content_byte"] = round(float(lens.sum()) / total, 4)
         res["compressed_blobs"] = int(kd.sum())
         for k, name in enumerate(KINDS):
             m = kinds == k
@@ -142,12 +146,15 @@ def main():
     ap.add_argument("--chunks", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=600, help="seconds each leg may take")
-    ap.add_argument("--leg", choices=("zstd", "plain", "host"), help="(internal) run one leg in this process")
+    ap.add_argument("--seq-tables", action="store_true", help="also the zstd leg on an engine with zstd_seq_tables=1")
+    ap.add_argument("--leg", choices=("zstd", "tables", "plain", "host"), help="(internal) run one leg in this process")
     a = ap.parse_args()
     if a.leg:
-        {"zstd": lambda: leg_device(a, True), "plain": lambda: leg_device(a, False), "host": lambda: leg_host(a)}[a.leg]()
+        {"zstd": lambda: leg_device(a, True), "tables": lambda: leg_device(a, True, True), "plain": lambda: leg_device(a, False),
+         "host": lambda: leg_host(a)}[a.leg]()
         return
-    for leg in ("plain", "zstd", "host"):  # each in a fresh process under its own limit; the first that fails ends the run
+    legs = ("plain", "zstd", "tables", "host") if a.seq_tables else ("plain", "zstd", "host")
+    for leg in legs:  # each in a fresh process under its own limit; the first that fails ends the run
         cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--chunks", str(a.chunks), "--reps", str(a.reps)]
         try:
             r = subprocess.run(cmd, timeout=a.limit)
