@@ -41,8 +41,6 @@ constexpr uint32_t kOne = 0x80000000u;  // x^0
 constexpr uint32_t kXInv = ((kPoly << 1) & 0xffffffffu) | 1u;  // x^-1 = (P - 1) / x
 constexpr uint32_t kRow = 1024;
 constexpr uint32_t kGap = kRow - 16;
-constexpr uint32_t kPieceLog = 16;
-constexpr uint64_t kPiece = 1ull << kPieceLog;
 constexpr uint32_t kFoldLanes = 64;
 static_assert(kPieceLog == kBlobPieceLog, "ring.cpp bounds the piece count with this");
 
@@ -617,13 +615,7 @@ struct UpCount {
     uint32_t parts, pieces, blobs;
     uint32_t pad;
 };
-struct UpHead {  // the first 64 bytes of the block that goes back to the host
-    uint64_t stats[4];  // k_known_mark's
-    uint64_t total;     // bytes the blobs need
-    uint32_t npieces, nparts, nblob;  // what the CRC pair sees (PartPlan::counts): all 0 when total > dst_cap
-    uint32_t over;      // total > dst_cap
-    uint64_t pad;
-};
+// (UpHead, the first 64 bytes of the block that goes back to the host: blob_plan.h)
 struct UpPlan {
     const uint8_t *recs;           // n records (stride 48)
     const uint8_t *known;          // n: k_known_mark's flags
@@ -856,20 +848,7 @@ __global__ __launch_bounds__(256) void k_upnew_ppart(UpPlan pl) {
 //   k_dec_fold    k_crc_fold over the data length the magic gives
 //   k_dec_copy    the other entries that reference a blob (dedup fan-out), clipped in the same way, blob -> dst
 //   k_dec_status  per entry, in pbsgpu_blob_verify's order: magic, CRC, kind, size, digest
-struct DecInfo {
-    uint32_t hk;      // header bytes (12 / 44; 0 = BAD_MAGIC) | kind << 8
-    uint32_t stored;  // the header's CRC
-};
-struct DecStore {  // data bytes [xlo, xhi) of blob u go to dst + dofs + [xlo, xhi) when the data is `size` bytes long
-    int64_t dofs;  // the entry's stream start - range_start (may be negative: the bytes in front are clipped)
-    uint64_t xlo, xhi;
-    uint32_t size;
-    uint32_t u;
-};
-struct DecEntry {
-    uint32_t u;  // the entry's blob among the distinct ones
-    uint32_t size;
-};
+// (DecInfo, DecStore and DecEntry, which the host plan fills in: blob_plan.h)
 struct DecPlan {
     const uint8_t *src;
     const pbsgpu_segment *blobs;  // nu distinct referenced blobs (header included)
@@ -1016,6 +995,7 @@ __global__ __launch_bounds__(256) void k_dec_status(DecPlan pl) {
 namespace {
 
 using namespace pbsk::crc;
+using namespace pbsp;
 
 // SHA-256("Proxmox Backup ... blob v1.0")[0..8): uncompressed, zstd compressed, encrypted, zstd compressed encrypted
 constexpr uint8_t kMagic[4][8] = {{66, 171, 56, 7, 190, 131, 112, 161},
@@ -1033,12 +1013,6 @@ uint64_t header_size(int kind) {
     return kind >= PBSGPU_BLOB_ENCRYPTED ? PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE : PBSGPU_BLOB_HEADER_SIZE;
 }
 
-bool ranges_ok(const pbsgpu_segment *segs, uint32_t nseg, uint64_t nbytes) {
-    for (uint32_t i = 0; i < nseg; ++i)
-        if (segs[i].length > nbytes || segs[i].offset > nbytes - segs[i].length) return false;
-    return true;
-}
-
 uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 
 // the header's magic for the two encode plans: the uncompressed kind
@@ -1046,12 +1020,6 @@ template <class P>
 void set_magic(P &pl) {
     pl.magic_lo = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED]);
     pl.magic_hi = le32(kMagic[PBSGPU_BLOB_UNCOMPRESSED] + 4);
-}
-
-// owner[p] = the range that piece p belongs to, from pbase (n + 1 entries: the index of each range's first piece)
-void fill_owners(const std::vector<uint64_t> &pbase, uint32_t *owner) {
-    for (uint32_t i = 0; i + 1 < pbase.size(); ++i)
-        for (uint64_t p = pbase[i]; p < pbase[i + 1]; ++p) owner[p] = i;
 }
 
 // A piece kernel over np pieces (an upper bound when the plan's counts are on the device) and its fold over n ranges, on
@@ -1070,43 +1038,34 @@ int launch_pair(pbsgpu_engine *e, hipStream_t st, void (*pieces)(P), void (*fold
     return PBSGPU_OK;
 }
 
+// a plan's piece table onto the slot's scratch: pbase, pseg, and room for praw
+int put_pieces(Slot *s, const PieceTable &t, Plan &pl) {
+    CHK(put_table(s, t.pbase.data(), t.pbase.size(), &pl.pbase));
+    CHK(put_table(s, t.owner.data(), t.owner.size(), &pl.pseg));
+    pl.praw = s->take<uint32_t>((size_t)t.np);
+    pl.npieces = t.np;
+    return s->taken();
+}
+
 // CRC of the nseg ranges already in s->segs over device bytes d; optionally the encode destination. crcs_dev = the
 // device result array (nseg u32). Enqueued on the slot's stream, nothing synchronised.
 int enqueue_crc(pbsgpu_engine *e, Slot *s, const uint8_t *d, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *dst,
                 const uint64_t *offsets, uint32_t **crcs_dev) {
-    std::vector<uint64_t> pbase((size_t)nseg + 1);
-    uint64_t np = 0;
-    for (uint32_t i = 0; i < nseg; ++i) {
-        pbase[i] = np;
-        np += (segs[i].length + kPiece - 1) >> kPieceLog;
-    }
-    pbase[nseg] = np;
-    if (np >= (1ull << 32)) return PBSGPU_E_INVALID;  // > 256 TiB of pieces in one call
-    std::vector<uint32_t> pseg((size_t)np);
-    fill_owners(pbase, pseg.data());
-    CHK(s->seg_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
-    CHK(s->tile_cnt.ensure(np * sizeof(uint32_t) + 64));
-    CHK(s->dense.ensure(np * sizeof(uint32_t) + 64));
-    CHK(s->seg_cnt.ensure((size_t)nseg * sizeof(uint32_t) + 64));
-    CHK(staged_h2d(*s, s->seg_off.p, pbase.data(), (nseg + 1) * sizeof(uint64_t), s->stream));
-    if (np) CHK(staged_h2d(*s, s->tile_cnt.p, pseg.data(), np * sizeof(uint32_t), s->stream));
+    PieceTable t;
+    if (!piece_table(nseg, [&](uint64_t i) { return segs[i].length; }, t)) return PBSGPU_E_INVALID;
     Plan pl{};
     pl.src = d;
     pl.segs = s->segs.as<pbsgpu_segment>();
-    pl.pbase = s->seg_off.as<uint64_t>();
-    pl.pseg = s->tile_cnt.as<uint32_t>();
-    pl.praw = s->dense.as<uint32_t>();
-    pl.crcs = s->seg_cnt.as<uint32_t>();
-    pl.npieces = np;
     pl.nseg = nseg;
+    CHK(put_pieces(s, t, pl));
+    pl.crcs = s->take<uint32_t>(nseg);
+    CHK(s->taken());
     if (dst) {
-        CHK(s->tile_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
-        CHK(staged_h2d(*s, s->tile_off.p, offsets, (nseg + 1) * sizeof(uint64_t), s->stream));
+        CHK(put_table(s, offsets, (size_t)nseg + 1, &pl.doff));
         pl.dst = dst;
-        pl.doff = s->tile_off.as<uint64_t>();
         set_magic(pl);
     }
-    CHK(launch_pair(e, s->stream, k_crc_pieces, k_crc_fold, pl, np, nseg));
+    CHK(launch_pair(e, s->stream, k_crc_pieces, k_crc_fold, pl, t.np, nseg));
     *crcs_dev = pl.crcs;
     return PBSGPU_OK;
 }
@@ -1153,49 +1112,54 @@ int blob_encode_zstd(pbsgpu_engine *e, const uint8_t *src, const pbsgpu_segment 
         jobs[i] = pbsk::zenc::Job{segs[i].offset, 0, offs[i] + PBSGPU_BLOB_HEADER_SIZE, segs[i].length, (uint32_t)segs[i].length, 0, 0, 0};
     uint64_t *res = nullptr;
     CHK(pbsk::zenc::enqueue(e, s, d, dst, jobs, true, &res));
-    std::vector<uint64_t> pbase((size_t)nseg + 1);
-    uint64_t np = 0;
-    for (uint32_t i = 0; i < nseg; ++i) {  // for each slot's capacity
-        pbase[i] = np;
-        np += (segs[i].length + kPiece - 1) >> kPieceLog;
-    }
-    pbase[nseg] = np;
-    if (np >= (1ull << 32)) return PBSGPU_E_INVALID;
-    std::vector<uint32_t> pseg((size_t)np);
-    fill_owners(pbase, pseg.data());
-    const size_t out_bytes = (size_t)nseg * 9;  // crcs, lens, kinds: one block, read back once
-    CHK(s->seg_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
-    CHK(s->tile_cnt.ensure(np * sizeof(uint32_t) + 64));
-    CHK(s->dense.ensure(np * sizeof(uint32_t) + 64));
-    CHK(s->tile_off.ensure((nseg + 1) * sizeof(uint64_t) + 64));
-    CHK(s->tile_slots.ensure(out_bytes + 64));
-    CHK(staged_h2d(*s, s->seg_off.p, pbase.data(), (nseg + 1) * sizeof(uint64_t), s->stream));
-    if (np) CHK(staged_h2d(*s, s->tile_cnt.p, pseg.data(), np * sizeof(uint32_t), s->stream));
-    CHK(staged_h2d(*s, s->tile_off.p, offs, (nseg + 1) * sizeof(uint64_t), s->stream));
+    PieceTable t;  // for each slot's capacity
+    if (!piece_table(nseg, [&](uint64_t i) { return segs[i].length; }, t)) return PBSGPU_E_INVALID;
+    const Enc2Block ob(nseg);  // crcs, lens, kinds: one block, read back once
     Enc2Plan pl{};
     pl.p.src = d;
     pl.p.segs = s->segs.as<pbsgpu_segment>();
-    pl.p.pbase = s->seg_off.as<uint64_t>();
-    pl.p.pseg = s->tile_cnt.as<uint32_t>();
-    pl.p.praw = s->dense.as<uint32_t>();
-    pl.p.crcs = s->tile_slots.as<uint32_t>();
-    pl.p.npieces = np;
     pl.p.nseg = nseg;
+    CHK(put_pieces(s, t, pl.p));
+    CHK(put_table(s, offs, (size_t)nseg + 1, &pl.p.doff));
+    uint8_t *out = s->take<uint8_t>(ob.total);
+    CHK(s->taken());
+    pl.p.crcs = reinterpret_cast<uint32_t *>(out + ob.crcs);
     pl.p.dst = dst;
-    pl.p.doff = s->tile_off.as<uint64_t>();
     set_magic(pl.p);
     pl.res = res;
-    pl.lens = s->tile_slots.as<uint32_t>() + nseg;
-    pl.kinds = s->tile_slots.as<uint8_t>() + (size_t)nseg * 8;
+    pl.lens = reinterpret_cast<uint32_t *>(out + ob.lens);
+    pl.kinds = out + ob.kinds;
     pl.zmagic_lo = le32(kMagic[PBSGPU_BLOB_COMPRESSED]);
     pl.zmagic_hi = le32(kMagic[PBSGPU_BLOB_COMPRESSED] + 4);
-    CHK(launch_pair(e, s->stream, k_enc2_pieces, k_enc2_fold, pl, np, nseg));
-    std::vector<uint8_t> back(out_bytes);
-    CHK(fetch_result(s, back.data(), s->tile_slots.p, out_bytes));  // the call's one synchronisation
-    std::memcpy(crcs, back.data(), (size_t)nseg * 4);
-    std::memcpy(lens, back.data() + (size_t)nseg * 4, (size_t)nseg * 4);
-    std::memcpy(kinds, back.data() + (size_t)nseg * 8, nseg);
+    CHK(launch_pair(e, s->stream, k_enc2_pieces, k_enc2_fold, pl, t.np, nseg));
+    std::vector<uint8_t> back(ob.total);
+    CHK(fetch_result(s, back.data(), out, ob.total));  // the call's one synchronisation
+    std::memcpy(crcs, back.data() + ob.crcs, (size_t)nseg * 4);
+    std::memcpy(lens, back.data() + ob.lens, (size_t)nseg * 4);
+    std::memcpy(kinds, back.data() + ob.kinds, nseg);
     return PBSGPU_OK;
+}
+
+// the first PBSGPU_BLOB_HEADER_SIZE bytes of every blob (zero-padded when it is shorter) to the host
+int read_heads(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t n,
+               std::vector<uint8_t> &heads) {
+    heads.resize((size_t)n * PBSGPU_BLOB_HEADER_SIZE);
+    if (host) {
+        const uint8_t *h = static_cast<const uint8_t *>(ptr);
+        for (uint32_t i = 0; i < n; ++i)
+            for (uint32_t j = 0; j < PBSGPU_BLOB_HEADER_SIZE; ++j)
+                heads[(size_t)i * PBSGPU_BLOB_HEADER_SIZE + j] = j < blobs[i].length ? h[blobs[i].offset + j] : 0;
+        return PBSGPU_OK;
+    }
+    const uint8_t *d = nullptr;
+    CHK(stage_ranges(e, s, ptr, false, nbytes, blobs, n, &d));
+    uint8_t *heads_dev = s->take<uint8_t>(heads.size());
+    CHK(s->taken());
+    const uint64_t threads = heads.size();
+    hipLaunchKernelGGL(pbsk::crc::k_blob_heads, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s->stream, d,
+                       s->segs.as<pbsgpu_segment>(), n, heads_dev);
+    HIPCHK(hipGetLastError());
+    return fetch_result(s, heads.data(), heads_dev, heads.size());  // (synchronises: the staged ranges are free)
 }
 
 int blob_verify(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t n,
@@ -1209,22 +1173,8 @@ int blob_verify(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, c
     AuxLease lease(e);
     Slot *s = lease.s;
     // 1. the headers, on the host
-    std::vector<uint8_t> heads((size_t)n * PBSGPU_BLOB_HEADER_SIZE);
-    if (host) {
-        const uint8_t *h = static_cast<const uint8_t *>(ptr);
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t j = 0; j < PBSGPU_BLOB_HEADER_SIZE; ++j)
-                heads[(size_t)i * PBSGPU_BLOB_HEADER_SIZE + j] = j < blobs[i].length ? h[blobs[i].offset + j] : 0;
-    } else {
-        const uint8_t *d = nullptr;
-        CHK(stage_ranges(e, s, ptr, false, nbytes, blobs, n, &d));
-        CHK(s->tile_slots.ensure(heads.size() + 64));
-        const uint64_t threads = heads.size();
-        hipLaunchKernelGGL(pbsk::crc::k_blob_heads, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s->stream, d,
-                           s->segs.as<pbsgpu_segment>(), n, s->tile_slots.as<uint8_t>());
-        HIPCHK(hipGetLastError());
-        CHK(fetch_result(s, heads.data(), s->tile_slots.p, heads.size()));  // (synchronises: the slot's tables are free)
-    }
+    std::vector<uint8_t> heads;
+    CHK(read_heads(e, s, ptr, host, nbytes, blobs, n, heads));
     // 2. data ranges of the blobs with a known magic and a whole header: uncompressed ones first (the SHA-256 batch is a
     // prefix of the CRC batch)
     std::vector<int> kind(n);
@@ -1253,21 +1203,17 @@ int blob_verify(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, c
         CHK(stage_ranges(e, s, ptr, host, nbytes, data.data(), nd, &d));
         uint32_t *crcs = nullptr;
         CHK(enqueue_crc(e, s, d, data.data(), nd, nullptr, nullptr, &crcs));
+        uint8_t *digs_dev = nullptr;
         if (digests && nunc) {
-            uint64_t total_blocks = 0, longest = 1;
-            for (uint32_t j = 0; j < nunc; ++j) {
-                const uint64_t blocks = (data[j].length + 8) / 64 + 1;
-                total_blocks += blocks;
-                longest = std::max(longest, blocks);
-            }
-            CHK(s->recs.ensure((size_t)nunc * 32 + 64));
-            HIPCHK(pbsk::launch_sha256_segments(d, s->segs.as<pbsgpu_segment>(), nunc, s->recs.as<uint8_t>(),
-                                                s->scalars.as<uint32_t>() + SC_QUEUE, e->num_cus,
-                                                pbsk::sha256_dense_pays(total_blocks, longest, e->num_cus, e->opt.sha_dense_pct),
-                                                (int)e->opt.sha_form, s->stream));
+            ShaWork work;
+            for (uint32_t j = 0; j < nunc; ++j) work.add(data[j].length);
+            digs_dev = s->take<uint8_t>((size_t)nunc * 32);
+            CHK(s->taken());
+            CHK(enqueue_sha256(e, s->stream, d, s->segs.as<pbsgpu_segment>(), nunc, digs_dev,
+                               s->scalars.as<uint32_t>() + SC_QUEUE, work));
         }
         CHK(fetch_result(s, crc.data(), crcs, (size_t)nd * 4));
-        if (digests && nunc) CHK(fetch_result(s, dig.data(), s->recs.p, (size_t)nunc * 32));
+        if (digs_dev) CHK(fetch_result(s, dig.data(), digs_dev, (size_t)nunc * 32));
     }
     // 3. the statuses, in the order of the checks
     pbsgpu_blob_stats st{};
@@ -1308,24 +1254,11 @@ constexpr bool magic_words_match() {
 }
 static_assert(magic_words_match(), "kDecMagic is kMagic in little-endian words");
 
-// pbsgpu_blob_decode_device. Everything the host can know is decided here before any device work; what depends on the
-// blobs' bytes (kind, data length, CRC, digest) is decided on the device and comes back once, at the end.
-// Layout on the lease:
-//   segs             the distinct referenced blobs (stage_ranges)
-//   sugg             one upload: pbase | prim | copies | ents | pseg
-//   sugg_idx         the index records (check_digest only: the status kernel reads their digests)
-//   dense | seg_cnt  praw | crcs
-//   tile_off | recs  the SHA-256 ranges | the digests
-//   order            what goes back in one transfer: info[nu] | status[nidx]
-int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
-                const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re,
-                uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats2 *stats) {
-    const int check_digest = (flags & PBSGPU_DECODE_F_DIGEST) != 0;
-    const bool zstd = (flags & PBSGPU_DECODE_F_ZSTD) != 0;
-    if (!e || nidx >= (1ull << 32)) return PBSGPU_E_INVALID;
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (nidx == 0) return PBSGPU_OK;
-    if (!idx || !status || !blobs || nblob == 0 || (!bptr && nbytes)) return PBSGPU_E_INVALID;
+// pbsgpu_blob_decode*_device past "no engine" and "nothing to do": the argument checks, in their order
+int check_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
+                 const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re, bool zstd,
+                 const void *dst, uint64_t dst_cap) {
+    if (!idx || !blobs || nblob == 0 || (!bptr && nbytes)) return PBSGPU_E_INVALID;
     if (!blob_of && nblob != nidx) return PBSGPU_E_INVALID;
     if (!ranges_ok(blobs, nblob, nbytes)) return PBSGPU_E_INVALID;
     if (zstd)  // the frame decoder counts in 32 bits (a chunk is 16 MiB at the most)
@@ -1338,222 +1271,174 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
     const uint64_t S = idx[0].end - idx[0].size, E = idx[nidx - 1].end;
     if (rs < S || rs > re || re > E) return PBSGPU_E_INVALID;
     const uint64_t need = re - rs;
-    if (need) {
-        if (!dst) return PBSGPU_E_INVALID;
-        const uintptr_t d0 = (uintptr_t)dst, b0 = (uintptr_t)bptr;
-        if (nbytes && d0 < b0 + nbytes && b0 < d0 + need) return PBSGPU_E_INVALID;  // dst overlaps the blob buffer
-    }
+    if (need && (!dst || overlaps(dst, need, bptr, nbytes))) return PBSGPU_E_INVALID;  // dst overlaps the blob buffer
     CHK(set_device(e));
     if ((nbytes && !is_device_pointer(bptr)) || (need && !is_device_pointer(dst))) return PBSGPU_E_INVALID;
-    if (dst_cap < need) return PBSGPU_E_CAPACITY;
-    // the distinct referenced blobs, every entry's part of dst, and per blob the entry whose store rides the CRC pass:
-    // the first one that has bytes inside the range
-    std::vector<uint32_t> uof(nblob, 0xffffffffu);
-    std::vector<pbsgpu_segment> ub;
-    std::vector<DecEntry> ents((size_t)nidx);
-    std::vector<DecStore> prim, copies;
-    std::vector<uint64_t> clip((size_t)nidx);  // bytes of entry i inside the range
-    for (uint64_t i = 0; i < nidx; ++i) {
-        const uint32_t b = blob_of ? blob_of[i] : (uint32_t)i;
-        if (uof[b] == 0xffffffffu) {
-            uof[b] = (uint32_t)ub.size();
-            ub.push_back(blobs[b]);
-            prim.push_back(DecStore{0, 0, 0, 0, uof[b]});
-        }
-        const uint32_t u = uof[b];
-        ents[i] = DecEntry{u, idx[i].size};
-        const uint64_t start = idx[i].end - idx[i].size;
-        const uint64_t lo = std::max(start, rs), hi = std::min<uint64_t>(idx[i].end, re);
-        clip[i] = hi > lo ? hi - lo : 0;
-        if (!clip[i]) continue;
-        const DecStore ds{(int64_t)(start - rs), lo - start, hi - start, idx[i].size, u};
-        if (prim[u].xlo == prim[u].xhi) prim[u] = ds;
-        else copies.push_back(ds);
-    }
-    const uint32_t nu = (uint32_t)ub.size();
-    // pieces for the 12-byte header: the data of an encrypted kind is 32 bytes shorter and may leave the first one empty
-    std::vector<uint64_t> pbase((size_t)nu + 1);
-    uint64_t np = 0, total_blocks = 0, longest = 1;
-    for (uint32_t u = 0; u < nu; ++u) {
-        const uint64_t dl = ub[u].length > PBSGPU_BLOB_HEADER_SIZE ? ub[u].length - PBSGPU_BLOB_HEADER_SIZE : 0;
-        pbase[u] = np;
-        np += (dl + kPiece - 1) >> kPieceLog;
-        const uint64_t blocks = (dl + 8) / 64 + 1;
-        total_blocks += blocks;
-        longest = std::max(longest, blocks);
-    }
-    pbase[nu] = np;
-    if (np >= (1ull << 32)) return PBSGPU_E_INVALID;
-    const size_t o_prim = ((size_t)nu + 1) * 8, o_cop = o_prim + (size_t)nu * sizeof(DecStore);
-    const size_t o_ent = o_cop + copies.size() * sizeof(DecStore), o_pseg = o_ent + (size_t)nidx * sizeof(DecEntry);
-    std::vector<uint8_t> tabs(o_pseg + (size_t)np * 4);
-    std::memcpy(tabs.data(), pbase.data(), o_prim);
-    std::memcpy(tabs.data() + o_prim, prim.data(), (size_t)nu * sizeof(DecStore));
-    if (!copies.empty()) std::memcpy(tabs.data() + o_cop, copies.data(), copies.size() * sizeof(DecStore));
-    std::memcpy(tabs.data() + o_ent, ents.data(), (size_t)nidx * sizeof(DecEntry));
-    fill_owners(pbase, reinterpret_cast<uint32_t *>(tabs.data() + o_pseg));
-    AuxLease lease(e);
-    Slot *s = lease.s;
-    // back in one transfer: info[nu] | status[nidx] | (zstd: padding to 8, then the frames' results[nu])
-    const size_t o_zres = ((size_t)nu * sizeof(DecInfo) + (size_t)nidx + 7) & ~(size_t)7;
-    const size_t out_bytes = zstd ? o_zres + (size_t)nu * 8 : (size_t)nu * sizeof(DecInfo) + (size_t)nidx;
-    CHK(s->sugg.ensure(tabs.size() + 64));
-    CHK(s->dense.ensure((size_t)np * 4 + 64));
-    CHK(s->seg_cnt.ensure((size_t)nu * 4 + 64));
-    CHK(s->tile_off.ensure((size_t)nu * sizeof(pbsgpu_segment) + 64));
-    CHK(s->order.ensure(out_bytes + 64));
-    if (check_digest) {
-        CHK(s->sugg_idx.ensure((size_t)nidx * sizeof(pbsgpu_record) + 64));
-        CHK(s->recs.ensure((size_t)nu * 32 + 64));
-    }
-    const uint8_t *d = nullptr;
-    CHK(stage_ranges(e, s, bptr, false, nbytes, ub.data(), nu, &d));
-    CHK(staged_h2d(*s, s->sugg.p, tabs.data(), tabs.size(), s->stream));
-    if (check_digest) CHK(staged_h2d(*s, s->sugg_idx.p, idx, nidx * sizeof(pbsgpu_record), s->stream));
-    const uint8_t *t = s->sugg.as<uint8_t>();
-    DecPlan pl{};
-    pl.src = d;
+    return dst_cap < need ? PBSGPU_E_CAPACITY : PBSGPU_OK;
+}
+
+// The restore's own kernels on the slot's stream, nothing synchronised: the heads, the CRC pair with the primary stores
+// fused in, the other entries' copies, the digests of the uncompressed blobs and the statuses. `out` is the block that
+// goes back (DecBlock); pl is left filled in for the zstd leg.
+int enqueue_restore(pbsgpu_engine *e, Slot *s, const Restore &r, const void *bptr, uint64_t nbytes, const pbsgpu_record *idx,
+                    bool check_digest, uint8_t *dst, const DecBlock &ob, uint8_t **out, DecPlan &pl) {
+    const uint32_t nu = r.nu();
+    const size_t nidx = r.ents.size(), ncopy = r.copies.size();
+    const DecTables tl(nu, ncopy, nidx, (size_t)r.pieces.np);
+    std::vector<uint8_t> tabs(tl.total);
+    const auto pack = [&](size_t at, const void *from, size_t bytes) {
+        if (bytes) std::memcpy(tabs.data() + at, from, bytes);
+    };
+    pack(tl.pbase, r.pieces.pbase.data(), ((size_t)nu + 1) * 8);
+    pack(tl.prim, r.prim.data(), (size_t)nu * sizeof(DecStore));
+    pack(tl.copies, r.copies.data(), ncopy * sizeof(DecStore));
+    pack(tl.ents, r.ents.data(), nidx * sizeof(DecEntry));
+    pack(tl.pseg, r.pieces.owner.data(), (size_t)r.pieces.np * 4);
+    pl = DecPlan{};
+    CHK(stage_ranges(e, s, bptr, false, nbytes, r.ub.data(), nu, &pl.src));
+    const uint8_t *t = nullptr;
+    CHK(put_table(s, tabs.data(), tabs.size(), &t));
+    pl.praw = s->take<uint32_t>((size_t)r.pieces.np);
+    pl.crcs = s->take<uint32_t>(nu);
+    pl.sha = s->take<pbsgpu_segment>(nu);
+    *out = s->take<uint8_t>(ob.total);
+    uint8_t *digs = check_digest ? s->take<uint8_t>((size_t)nu * 32) : nullptr;
+    CHK(s->taken());
+    if (check_digest) CHK(put_table(s, reinterpret_cast<const uint8_t *>(idx), nidx * sizeof(pbsgpu_record), &pl.recs));
     pl.blobs = s->segs.as<pbsgpu_segment>();
-    pl.pbase = reinterpret_cast<const uint64_t *>(t);
-    pl.prim = reinterpret_cast<const DecStore *>(t + o_prim);
-    pl.copies = reinterpret_cast<const DecStore *>(t + o_cop);
-    pl.ents = reinterpret_cast<const DecEntry *>(t + o_ent);
-    pl.pseg = reinterpret_cast<const uint32_t *>(t + o_pseg);
-    pl.praw = s->dense.as<uint32_t>();
-    pl.crcs = s->seg_cnt.as<uint32_t>();
-    pl.info = s->order.as<DecInfo>();
-    pl.sha = s->tile_off.as<pbsgpu_segment>();
-    pl.recs = check_digest ? s->sugg_idx.as<uint8_t>() : nullptr;
-    pl.digs = check_digest ? s->recs.as<uint8_t>() : nullptr;
-    pl.status = s->order.as<uint8_t>() + (size_t)nu * sizeof(DecInfo);
-    pl.dst = static_cast<uint8_t *>(dst);
-    pl.npieces = np;
+    pl.pbase = reinterpret_cast<const uint64_t *>(t + tl.pbase);
+    pl.prim = reinterpret_cast<const DecStore *>(t + tl.prim);
+    pl.copies = reinterpret_cast<const DecStore *>(t + tl.copies);
+    pl.ents = reinterpret_cast<const DecEntry *>(t + tl.ents);
+    pl.pseg = reinterpret_cast<const uint32_t *>(t + tl.pseg);
+    pl.info = reinterpret_cast<DecInfo *>(*out + ob.info);
+    pl.digs = digs;
+    pl.status = *out + ob.status;
+    pl.dst = dst;
+    pl.npieces = r.pieces.np;
     pl.nu = nu;
-    pl.ncopy = (uint32_t)copies.size();
+    pl.ncopy = (uint32_t)ncopy;
     pl.nidx = (uint32_t)nidx;
     hipLaunchKernelGGL(pbsk::crc::k_dec_heads, dim3((nu + 255) / 256), dim3(256), 0, s->stream, pl);
     HIPCHK(hipGetLastError());
-    CHK(launch_pair(e, s->stream, k_dec_pieces, k_dec_fold, pl, np, nu));
+    CHK(launch_pair(e, s->stream, k_dec_pieces, k_dec_fold, pl, r.pieces.np, nu));
     if (pl.ncopy) {  // grid as for k_page_copy
-        uint64_t lng = 0;
-        for (const DecStore &c : copies) lng = std::max(lng, c.xhi - c.xlo);
-        const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lng / 16 + 255) / 256, (uint64_t)e->num_cus * 8));
+        const uint32_t gx = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((r.longest_copy / 16 + 255) / 256, (uint64_t)e->num_cus * 8));
         hipLaunchKernelGGL(pbsk::crc::k_dec_copy, dim3(gx, std::min<uint32_t>(pl.ncopy, 1024)), dim3(256), 0, s->stream, pl);
         HIPCHK(hipGetLastError());
     }
-    if (check_digest)  // the policy of pbsgpu_sha256_many_device, on the sizes the host knows (exact for uncompressed blobs)
-        HIPCHK(pbsk::launch_sha256_segments(d, pl.sha, nu, s->recs.as<uint8_t>(), s->scalars.as<uint32_t>() + SC_QUEUE,
-                                            e->num_cus,
-                                            pbsk::sha256_dense_pays(total_blocks, longest, e->num_cus, e->opt.sha_dense_pct),
-                                            (int)e->opt.sha_form, s->stream));
+    if (check_digest)  // on the sizes the host knows (exact for uncompressed blobs)
+        CHK(enqueue_sha256(e, s->stream, pl.src, pl.sha, nu, digs, s->scalars.as<uint32_t>() + SC_QUEUE, r.sha));
     hipLaunchKernelGGL(pbsk::crc::k_dec_status, dim3((unsigned)((nidx + 255) / 256)), dim3(256), 0, s->stream, pl);
     HIPCHK(hipGetLastError());
-    if (zstd) {
-        // The zstd leg (zstd.hip), behind the statuses above on the same stream. Which blobs are compressed is known only on
-        // the device, so EVERY distinct blob gets a room planned: straight in dst when its first entry inside the range lies
-        // wholly inside it and no entry naming the blob is larger, else in scratch with the largest entry's size.
-        namespace pz = pbsk::zstd;
-        std::vector<uint32_t> zmax(nu, 0);
-        for (uint64_t i = 0; i < nidx; ++i) zmax[ents[i].u] = std::max(zmax[ents[i].u], ents[i].size);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(nu, (uint64_t)e->num_cus * 4);
-        const uintptr_t d0 = (uintptr_t)dst;
-        std::vector<pz::RestoreJob> jobs(nu);
-        std::vector<pz::RestoreCopy> zc;
-        uint64_t sc = (uint64_t)grid * pz::kLitBytes, zblocks = 0, zlongest = 1;  // scratch behind the literal buffers
-        std::vector<uint64_t> scratch_at(nu, ~0ull);
-        for (uint32_t u = 0; u < nu; ++u) {
-            const DecStore &ps = prim[u];
-            const bool direct = ps.xlo < ps.xhi && ps.xlo == 0 && ps.xhi == ps.size && ps.size == zmax[u];
-            if (!direct) {
-                scratch_at[u] = sc;
-                sc += ((uint64_t)zmax[u] + 15) & ~15ull;
-            }
-            jobs[u].room = zmax[u];
-            const uint64_t blocks = ((uint64_t)zmax[u] + 8) / 64 + 1;
-            zblocks += blocks;
-            zlongest = std::max(zlongest, blocks);
-        }
-        CHK(s->data.ensure((size_t)sc + 64));
-        const uintptr_t sbase = (uintptr_t)s->data.p;
-        uint32_t lng = 0;
-        auto add_copy = [&](const DecStore &c) {
-            zc.push_back(pz::RestoreCopy{jobs[c.u].place + c.xlo, (uint64_t)c.dofs + c.xlo, (uint32_t)(c.xhi - c.xlo), c.size, c.u, 0});
-            lng = std::max(lng, (uint32_t)(c.xhi - c.xlo));
-        };
-        for (uint32_t u = 0; u < nu; ++u) {
-            jobs[u].place = scratch_at[u] == ~0ull ? (uint64_t)prim[u].dofs : (uint64_t)(sbase + scratch_at[u] - d0);
-            if (scratch_at[u] != ~0ull && prim[u].xlo < prim[u].xhi) add_copy(prim[u]);
-        }
-        for (const DecStore &c : copies) add_copy(c);
-        const size_t o_zc = (size_t)nu * sizeof(pz::RestoreJob);
-        std::vector<uint8_t> ztab(o_zc + zc.size() * sizeof(pz::RestoreCopy));
-        std::memcpy(ztab.data(), jobs.data(), o_zc);
-        if (!zc.empty()) std::memcpy(ztab.data() + o_zc, zc.data(), zc.size() * sizeof(pz::RestoreCopy));
-        // tile_slots: sha ranges[nu] | digests[32 nu] | the hash queue's counter (64 bytes) | the frame descriptors[nu]
-        const size_t o_zdig = (size_t)nu * sizeof(pbsgpu_segment), o_zq = o_zdig + (size_t)nu * 32, o_zdesc = o_zq + 64;
-        CHK(s->seg_off.ensure(ztab.size() + 64));
-        CHK(s->tile_slots.ensure(o_zdesc + (size_t)nu * pz::kDescBytes + 64));
-        CHK(staged_h2d(*s, s->seg_off.p, ztab.data(), ztab.size(), s->stream));
-        pz::RestorePlan zp{};
-        zp.src = d;
-        zp.blobs = pl.blobs;
-        zp.info = reinterpret_cast<const uint32_t *>(pl.info);
-        zp.crcs = pl.crcs;
-        zp.jobs = s->seg_off.as<pz::RestoreJob>();
-        zp.copies = reinterpret_cast<const pz::RestoreCopy *>(s->seg_off.as<uint8_t>() + o_zc);
-        zp.ents = reinterpret_cast<const uint32_t *>(pl.ents);
-        zp.recs = pl.recs;
-        zp.digs = s->tile_slots.as<uint8_t>() + o_zdig;
-        zp.res = reinterpret_cast<uint64_t *>(s->order.as<uint8_t>() + o_zres);
-        zp.sha = s->tile_slots.as<pbsgpu_segment>();
-        zp.status = pl.status;
-        zp.dst = static_cast<uint8_t *>(dst);
-        zp.lit = s->data.as<uint8_t>();
-        zp.nu = nu;
-        zp.ncopy = (uint32_t)zc.size();
-        zp.nidx = (uint32_t)nidx;
-        zp.stride = grid;
-        HIPCHK(pz::launch_restore_frames(zp, s->tile_slots.as<uint8_t>() + o_zdesc, s->stream));
-        if (zp.ncopy) HIPCHK(pz::launch_restore_copy(zp, lng, e->num_cus, s->stream));
-        if (check_digest) {
-            uint32_t *zq = reinterpret_cast<uint32_t *>(s->tile_slots.as<uint8_t>() + o_zq);
-            HIPCHK(hipMemsetAsync(zq, 0, 64, s->stream));
-            HIPCHK(pbsk::launch_sha256_segments(zp.dst, zp.sha, nu, s->tile_slots.as<uint8_t>() + o_zdig, zq, e->num_cus,
-                                                pbsk::sha256_dense_pays(zblocks, zlongest, e->num_cus, e->opt.sha_dense_pct),
-                                                (int)e->opt.sha_form, s->stream));
-        }
-        HIPCHK(pz::launch_restore_status(zp, s->stream));
+    return PBSGPU_OK;
+}
+
+// The zstd leg (zstd.hip), behind the statuses above on the same stream: the frames of the compressed blobs with a good
+// CRC into the rooms the plan gave them, the copies out of scratch, the digests of the decoded bytes, and the statuses
+// of the decoded blobs' entries. zres: the frames' results in the block that goes back.
+int enqueue_restore_zstd(pbsgpu_engine *e, Slot *s, Restore &r, const DecPlan &pl, uint64_t *zres) {
+    namespace pz = pbsk::zstd;
+    const uint32_t nu = r.nu();
+    uint8_t *scratch = s->bulk((size_t)r.scratch_bytes);
+    CHK(s->taken());
+    r.place_scratch((uint64_t)((uintptr_t)scratch - (uintptr_t)pl.dst));
+    const ZTables zl(nu, r.zcopies.size());
+    std::vector<uint8_t> ztab(zl.total);
+    std::memcpy(ztab.data() + zl.jobs, r.jobs.data(), (size_t)nu * sizeof(pz::RestoreJob));
+    if (!r.zcopies.empty()) std::memcpy(ztab.data() + zl.copies, r.zcopies.data(), r.zcopies.size() * sizeof(pz::RestoreCopy));
+    const uint8_t *zt = nullptr;
+    CHK(put_table(s, ztab.data(), ztab.size(), &zt));
+    const ZWork zw(nu);
+    uint8_t *w = s->take<uint8_t>(zw.total);
+    CHK(s->taken());
+    pz::RestorePlan zp{};
+    zp.src = pl.src;
+    zp.blobs = pl.blobs;
+    zp.info = reinterpret_cast<const uint32_t *>(pl.info);
+    zp.crcs = pl.crcs;
+    zp.jobs = reinterpret_cast<const pz::RestoreJob *>(zt + zl.jobs);
+    zp.copies = reinterpret_cast<const pz::RestoreCopy *>(zt + zl.copies);
+    zp.ents = reinterpret_cast<const uint32_t *>(pl.ents);
+    zp.recs = pl.recs;
+    zp.digs = w + zw.digs;
+    zp.res = zres;
+    zp.sha = reinterpret_cast<pbsgpu_segment *>(w + zw.sha);
+    zp.status = pl.status;
+    zp.dst = pl.dst;
+    zp.lit = scratch;
+    zp.nu = nu;
+    zp.ncopy = (uint32_t)r.zcopies.size();
+    zp.nidx = pl.nidx;
+    zp.stride = r.lit_groups;
+    HIPCHK(pz::launch_restore_frames(zp, w + zw.desc, s->stream));
+    if (zp.ncopy) HIPCHK(pz::launch_restore_copy(zp, r.longest_zcopy, e->num_cus, s->stream));
+    if (pl.recs) {
+        uint32_t *zq = reinterpret_cast<uint32_t *>(w + zw.queue);
+        HIPCHK(hipMemsetAsync(zq, 0, 64, s->stream));
+        CHK(enqueue_sha256(e, s->stream, zp.dst, zp.sha, nu, w + zw.digs, zq, r.zsha));
     }
-    std::vector<uint8_t> back(out_bytes);
-    CHK(fetch_result(s, back.data(), s->order.p, out_bytes));  // the call's one synchronisation
-    std::memcpy(status, back.data() + (size_t)nu * sizeof(DecInfo), (size_t)nidx);
-    if (stats) {
-        const DecInfo *info = reinterpret_cast<const DecInfo *>(back.data());
-        for (uint32_t u = 0; u < nu; ++u) {
-            const uint32_t hdr = info[u].hk & 255u;
-            stats->blob_bytes += ub[u].length;
-            if (hdr) stats->crc_bytes += ub[u].length - hdr;
-            if (check_digest && info[u].hk == PBSGPU_BLOB_HEADER_SIZE) stats->sha_bytes += ub[u].length - hdr;
-        }
-        for (uint64_t i = 0; i < nidx; ++i) {
-            stats->count[status[i]]++;
-            const uint32_t u = ents[i].u;
-            if (info[u].hk == PBSGPU_BLOB_HEADER_SIZE && ub[u].length - PBSGPU_BLOB_HEADER_SIZE == ents[i].size)
-                stats->out_bytes += clip[i];
-        }
-        if (zstd) {
-            const uint64_t *zres = reinterpret_cast<const uint64_t *>(back.data() + o_zres);
-            for (uint32_t u = 0; u < nu; ++u) {
-                if ((uint32_t)(zres[u] >> 32) == pbsk::zstd::kNotDecoded) continue;
-                stats->zstd_in_bytes += ub[u].length - PBSGPU_BLOB_HEADER_SIZE;
-                if ((zres[u] >> 32) != PBSGPU_ZSTD_OK) continue;
-                stats->zstd_out_bytes += (uint32_t)zres[u];
-                if (check_digest) stats->sha_bytes += (uint32_t)zres[u];
-            }
-            for (uint64_t i = 0; i < nidx; ++i)
-                if (zres[ents[i].u] == (uint64_t)ents[i].size) stats->out_bytes += clip[i];  // status OK, the entry's size
-        }
+    HIPCHK(pz::launch_restore_status(zp, s->stream));
+    return PBSGPU_OK;
+}
+
+// the statistics of a restore from the block that came back
+void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bool check_digest, bool zstd,
+                   const uint8_t *status, pbsgpu_decode_stats2 *stats) {
+    const uint32_t nu = r.nu();
+    const size_t nidx = r.ents.size();
+    const DecInfo *info = reinterpret_cast<const DecInfo *>(back + ob.info);
+    for (uint32_t u = 0; u < nu; ++u) {
+        const uint32_t hdr = info[u].hk & 255u;
+        stats->blob_bytes += r.ub[u].length;
+        if (hdr) stats->crc_bytes += r.ub[u].length - hdr;
+        if (check_digest && info[u].hk == PBSGPU_BLOB_HEADER_SIZE) stats->sha_bytes += r.ub[u].length - hdr;
     }
+    for (size_t i = 0; i < nidx; ++i) {
+        stats->count[status[i]]++;
+        const uint32_t u = r.ents[i].u;
+        if (info[u].hk == PBSGPU_BLOB_HEADER_SIZE && r.ub[u].length - PBSGPU_BLOB_HEADER_SIZE == r.ents[i].size)
+            stats->out_bytes += r.clip[i];
+    }
+    if (!zstd) return;
+    const uint64_t *zres = reinterpret_cast<const uint64_t *>(back + ob.zres);
+    for (uint32_t u = 0; u < nu; ++u) {
+        if ((uint32_t)(zres[u] >> 32) == pbsk::zstd::kNotDecoded) continue;
+        stats->zstd_in_bytes += r.ub[u].length - PBSGPU_BLOB_HEADER_SIZE;
+        if ((zres[u] >> 32) != PBSGPU_ZSTD_OK) continue;
+        stats->zstd_out_bytes += (uint32_t)zres[u];
+        if (check_digest) stats->sha_bytes += (uint32_t)zres[u];
+    }
+    for (size_t i = 0; i < nidx; ++i)
+        if (zres[r.ents[i].u] == (uint64_t)r.ents[i].size) stats->out_bytes += r.clip[i];  // status OK, the entry's size
+}
+
+// pbsgpu_blob_decode*_device: check, plan (blob_plan.h: everything the host can know is decided there, before any device
+// work), enqueue, and the statistics from the one block that comes back. What depends on the blobs' bytes (kind, data
+// length, CRC, digest, the frames) is decided on the device.
+int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
+                const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re,
+                uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats2 *stats) {
+    const bool check_digest = (flags & PBSGPU_DECODE_F_DIGEST) != 0;
+    const bool zstd = (flags & PBSGPU_DECODE_F_ZSTD) != 0;
+    if (!e || nidx >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (nidx == 0) return PBSGPU_OK;
+    if (!status) return PBSGPU_E_INVALID;
+    CHK(check_decode(e, bptr, nbytes, blobs, nblob, idx, nidx, blob_of, rs, re, zstd, dst, dst_cap));
+    Restore r;
+    if (!plan_restore(blobs, nblob, idx, nidx, blob_of, rs, re, zstd, (uint64_t)e->num_cus * 4, r)) return PBSGPU_E_INVALID;
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const DecBlock ob(r.nu(), (size_t)nidx, zstd);
+    uint8_t *out = nullptr;
+    DecPlan pl;
+    CHK(enqueue_restore(e, s, r, bptr, nbytes, idx, check_digest, static_cast<uint8_t *>(dst), ob, &out, pl));
+    if (zstd) CHK(enqueue_restore_zstd(e, s, r, pl, reinterpret_cast<uint64_t *>(out + ob.zres)));
+    std::vector<uint8_t> back(ob.total);
+    CHK(fetch_result(s, back.data(), out, ob.total));  // the call's one synchronisation
+    std::memcpy(status, back.data() + ob.status, (size_t)nidx);
+    if (stats) restore_stats(r, back.data(), ob, check_digest, zstd, status, stats);
     return PBSGPU_OK;
 }
 
@@ -1562,13 +1447,12 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
 namespace pbse {
 
 using namespace pbsk::crc;
+using namespace pbsp;
 
 // the plan's tables onto the aux slot and the launch pair (or the copy kernel) behind them; nothing synchronised
 static int enqueue_parts(pbsgpu_engine *e, Slot *s, PartPlan &pl, const std::vector<PartDesc> &parts,
                          const std::vector<BlobDesc> &blobs, const std::vector<uint32_t> &ppart) {
-    CHK(s->segs.ensure(parts.size() * sizeof(PartDesc) + 64));
-    CHK(staged_h2d(*s, s->segs.p, parts.data(), parts.size() * sizeof(PartDesc), s->stream));
-    pl.parts = s->segs.as<PartDesc>();
+    CHK(put_table(s, parts.data(), parts.size(), &pl.parts));
     pl.nparts = (uint32_t)parts.size();
     if (blobs.empty()) {
         uint32_t longest = 0;
@@ -1579,16 +1463,11 @@ static int enqueue_parts(pbsgpu_engine *e, Slot *s, PartPlan &pl, const std::vec
         HIPCHK(hipGetLastError());
         return PBSGPU_OK;
     }
-    CHK(s->seg_off.ensure(blobs.size() * sizeof(BlobDesc) + 64));
-    CHK(s->tile_cnt.ensure(ppart.size() * sizeof(uint32_t) + 64));
-    CHK(s->dense.ensure(ppart.size() * sizeof(uint32_t) + 64));
-    CHK(s->seg_cnt.ensure(blobs.size() * sizeof(uint32_t) + 64));
-    CHK(staged_h2d(*s, s->seg_off.p, blobs.data(), blobs.size() * sizeof(BlobDesc), s->stream));
-    if (!ppart.empty()) CHK(staged_h2d(*s, s->tile_cnt.p, ppart.data(), ppart.size() * sizeof(uint32_t), s->stream));
-    pl.blobs = s->seg_off.as<BlobDesc>();
-    pl.ppart = s->tile_cnt.as<uint32_t>();
-    pl.praw = s->dense.as<uint32_t>();
-    pl.crcs = s->seg_cnt.as<uint32_t>();
+    CHK(put_table(s, blobs.data(), blobs.size(), &pl.blobs));
+    CHK(put_table(s, ppart.data(), ppart.size(), &pl.ppart));
+    pl.praw = s->take<uint32_t>(ppart.size());
+    pl.crcs = s->take<uint32_t>(blobs.size());
+    CHK(s->taken());
     pl.npieces = (uint32_t)ppart.size();
     pl.nblob = (uint32_t)blobs.size();
     set_magic(pl);
@@ -1668,24 +1547,103 @@ int copy_parts(pbsgpu_engine *e, const uint8_t *base, const SrcPart *src, uint32
     return PBSGPU_OK;
 }
 
-// Layout on the one lease (known_common, enqueue_parts and zenc::enqueue would all want tile_cnt, dense, recs, order, par
-// or scan_tmp; here every array has a buffer of its own for as long as something reads it):
-//   recs                 the records as staged, read by lookup / mark / the plan / the insert
-//   sugg                 the PageTabs and the page array (ring form), or the chunk ranges (contiguous form)
-//   dense | tile_slots   sort keys | indices, each with its double buffer: dead behind k_known_mark
-//   tile_cnt             before[n] | skip[n] (the insert's flags, written by k_upnew_fill)
-//   scan_tmp             the sort's temporary storage
-//   par                  the plan's block sums
-//   segs | seg_off       PartDesc | BlobDesc
-//   tile_off | seg_cnt   ppart | praw
-//   order                what goes back in one transfer: UpHead (stats, total, counts, verdict) | blob_off[n] u64 |
-//                        crcs u32 (compacted: one per new record) | known[n] | with F_ZSTD, from the next multiple of 4:
-//                        lens u32 | kinds u8 (both compacted)
-//   with F_ZSTD (zenc::Room; the sizes are zenc::prepare's, each a multiple of 64):
-//   sugg_idx             the encoder's small arrays: bchunk | jobs (staged with the lengths and blocks, no job live;
-//                        k_upnew_fill makes the new records' jobs live) | res (per blob) | the blocks' places and results
-//   data                 the encoder's large arrays: the round's compressed blocks | per workgroup literals, sequences and
-//                        (ring form) the staged block that holds a chunk's seam
+// what one upload_new call has on the device
+struct UpDev {
+    KnownPass p;
+    UpPlan up{};
+    pbsk::zenc::Room room{};
+    uint32_t *praw = nullptr;
+    uint8_t *out = nullptr;  // the block that goes back (UpBlock)
+};
+
+// The call's arrays from the slot's scratch, and the host's tables onto them: the small source table first (the PageTabs
+// and the page array of the ring form, or the chunk ranges of the contiguous form), so that the records' copy waits for
+// nothing but that; with F_ZSTD the encoder's room, its jobs staged with the lengths and blocks, none of them live
+// (k_upnew_fill makes the new records' jobs live).
+static int stage_upload(Slot *s, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, const UpBlock &ob,
+                        const pbsk::zenc::Prep *zp, const std::vector<pbsk::zenc::Job> &jobs, UpDev &dv) {
+    KnownPass &p = dv.p;
+    UpPlan &up = dv.up;
+    CHK(known_sort_bytes(n, s->stream, &p.tmp_bytes));
+    if (src.chunks) {
+        CHK(put_table(s, src.chunks, (size_t)n, &up.chunks));
+    } else {
+        const uint64_t *tabs = nullptr;
+        CHK(put_table(s, src.tabs, src.tab_words, &tabs));
+        up.tabs = reinterpret_cast<const PageTab *>(tabs);
+        up.ptab = tabs + 2 * (size_t)src.nslots;
+    }
+    CHK(put_table(s, reinterpret_cast<const uint8_t *>(recs), (size_t)n * sizeof(pbsgpu_record), &p.recs));
+    p.keys = s->take<uint32_t>((size_t)n * 2);  // sort keys and indices, each with its double buffer
+    p.idx = s->take<uint32_t>((size_t)n * 2);
+    p.before = s->take<uint8_t>((size_t)n * 2);  // before | skip
+    p.tmp = s->take<uint8_t>(p.tmp_bytes);
+    up.bsum = s->take<UpCount>((size_t)((n + 255) / 256));
+    up.parts = s->take<PartDesc>((size_t)std::min<uint64_t>(2 * n, src.pieces_max));
+    up.blobs = s->take<BlobDesc>((size_t)n);
+    up.ppart = s->take<uint32_t>((size_t)src.pieces_max);
+    dv.praw = s->take<uint32_t>((size_t)src.pieces_max);
+    dv.out = s->take<uint8_t>(ob.total);
+    CHK(s->taken());
+    CHK(s->h_recs.ensure(ob.total + 64));
+    CHK(s->h_scalars.ensure(64));
+    if (zp) CHK(pbsk::zenc::carve(s, *zp, jobs, dv.room));
+    p.stride = sizeof(pbsgpu_record);
+    p.n = n;
+    p.known = dv.out + ob.known;
+    p.stats = reinterpret_cast<uint64_t *>(dv.out + ob.head);
+    up.recs = p.recs;
+    up.known = p.known;
+    up.page_bytes = src.page_bytes;
+    up.stream = src.stream;
+    up.n = (uint32_t)n;
+    up.head = reinterpret_cast<UpHead *>(dv.out + ob.head);
+    up.boff = reinterpret_cast<uint64_t *>(dv.out + ob.boff);
+    up.skip = p.before + n;
+    up.jobs = dv.room.jobs;
+    return PBSGPU_OK;
+}
+
+// the plan kernels: per record its blob, parts and pieces, and the verdict whether the blobs fit
+static int enqueue_upload_plan(pbsgpu_engine *e, hipStream_t st, const UpPlan &up, uint64_t pieces_max) {
+    const uint32_t nb = (up.n + 255) / 256;
+    hipLaunchKernelGGL(pbsk::crc::k_upnew_count, dim3(nb), dim3(256), 0, st, up);
+    hipLaunchKernelGGL(pbsk::crc::k_upnew_scan, dim3(1), dim3(256), 0, st, up);
+    hipLaunchKernelGGL(pbsk::crc::k_upnew_fill, dim3(nb), dim3(256), 0, st, up);
+    HIPCHK(hipGetLastError());
+    if (pieces_max) {
+        const uint64_t wg = std::min<uint64_t>((pieces_max + 255) / 256, (uint64_t)e->num_cus * 8);
+        hipLaunchKernelGGL(pbsk::crc::k_upnew_ppart, dim3((unsigned)wg), dim3(256), 0, st, up);
+        HIPCHK(hipGetLastError());
+    }
+    return PBSGPU_OK;
+}
+
+// with F_ZSTD the encoder's rounds over the live jobs, then the CRC pair on the plan's counts (its grids: the upper bounds
+// the host knows)
+static int enqueue_upload_blobs(pbsgpu_engine *e, hipStream_t st, const UploadSrc &src, uint8_t *dst, const UpBlock &ob,
+                                const pbsk::zenc::Prep *zp, const UpDev &dv) {
+    UpzPlan zl{};
+    PartPlan &pl = zl.p;
+    pl.base = src.base;
+    pl.dst = dst;
+    pl.parts = dv.up.parts;
+    pl.blobs = dv.up.blobs;
+    pl.ppart = dv.up.ppart;
+    pl.praw = dv.praw;
+    pl.crcs = reinterpret_cast<uint32_t *>(dv.out + ob.crcs);
+    pl.counts = &dv.up.head->npieces;
+    set_magic(pl);
+    if (!zp) return launch_pair(e, st, k_pagecrc_pieces, k_pagecrc_fold, pl, src.pieces_max, dv.up.n);
+    CHK(pbsk::zenc::launch(e, st, *zp, dv.room, src.base, dst, true));
+    zl.res = dv.room.res;
+    zl.lens = reinterpret_cast<uint32_t *>(dv.out + ob.lens);
+    zl.kinds = dv.out + ob.kinds;
+    zl.zmagic_lo = le32(kMagic[PBSGPU_BLOB_COMPRESSED]);
+    zl.zmagic_hi = le32(kMagic[PBSGPU_BLOB_COMPRESSED] + 4);
+    return launch_pair(e, st, k_upz_pieces, k_upz_fold, zl, src.pieces_max, dv.up.n);
+}
+
 // Order on the stream: mark -> (growth only: the number of new digests is read back and the table rebuilt) -> plan with
 // the verdict -> insert with the plan's flags -> (F_ZSTD: the encoder's rounds over the live jobs) -> CRC pair on the
 // plan's counts -> publish. The verdict comes before the insert and before the first byte of dst: when the blobs do not
@@ -1707,119 +1665,25 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     AuxLease lease(e);
     Slot *s = lease.s;
     const hipStream_t st = s->stream;
-    KnownPass p;
-    CHK(known_sort_bytes(n, st, &p.tmp_bytes));
-    const uint32_t nb = (uint32_t)((n + 255) / 256);
-    const size_t lens_at = (sizeof(UpHead) + (size_t)n * 13 + 3) & ~(size_t)3;
-    const size_t out_bytes = zstd ? lens_at + (size_t)n * 5 : sizeof(UpHead) + (size_t)n * 13;
-    const size_t src_bytes = src.chunks ? (size_t)n * sizeof(pbsgpu_segment) : src.tab_words * sizeof(uint64_t);
-    CHK(s->recs.ensure((size_t)n * sizeof(pbsgpu_record) + 64));
-    CHK(s->sugg.ensure(src_bytes + 64));
-    CHK(s->dense.ensure((size_t)n * 8 + 64));
-    CHK(s->tile_slots.ensure((size_t)n * 8 + 64));
-    CHK(s->tile_cnt.ensure((size_t)n * 2 + 64));
-    CHK(s->scan_tmp.ensure(p.tmp_bytes));
-    CHK(s->par.ensure((size_t)nb * sizeof(UpCount) + 64));
-    CHK(s->segs.ensure((size_t)std::min<uint64_t>(2 * n, src.pieces_max) * sizeof(PartDesc) + 64));
-    CHK(s->seg_off.ensure((size_t)n * sizeof(BlobDesc) + 64));
-    CHK(s->tile_off.ensure((size_t)src.pieces_max * sizeof(uint32_t) + 64));
-    CHK(s->seg_cnt.ensure((size_t)src.pieces_max * sizeof(uint32_t) + 64));
-    CHK(s->order.ensure(out_bytes + 64));
-    CHK(s->h_recs.ensure(out_bytes + 64));
-    CHK(s->h_scalars.ensure(64));
-    pbsk::zenc::Room room{};
-    if (zstd) {
-        CHK(s->sugg_idx.ensure(zp.bchunk_bytes + zp.jobs_bytes + zp.res_bytes + zp.bplace_bytes + 64));
-        CHK(s->data.ensure(zp.blkout_bytes + zp.work_bytes + 64));
-        uint8_t *small = s->sugg_idx.as<uint8_t>(), *large = s->data.as<uint8_t>();
-        room.bchunk = reinterpret_cast<uint32_t *>(small);
-        room.jobs = reinterpret_cast<pbsk::zenc::Job *>(small + zp.bchunk_bytes);
-        room.res = reinterpret_cast<uint64_t *>(small + zp.bchunk_bytes + zp.jobs_bytes);
-        room.bplace = reinterpret_cast<uint64_t *>(small + zp.bchunk_bytes + zp.jobs_bytes + zp.res_bytes);
-        room.blkout = large;
-        room.work = large + zp.blkout_bytes;
-    }
-    // the small table first: the records' copy then waits for nothing but that
-    if (src_bytes)
-        CHK(staged_h2d(*s, s->sugg.p, src.chunks ? (const void *)src.chunks : (const void *)src.tabs, src_bytes, st));
-    CHK(staged_h2d(*s, s->recs.p, recs, n * sizeof(pbsgpu_record), st));
-    if (zstd) CHK(pbsk::zenc::upload(s, zp, room, jobs));
-    uint8_t *out = s->order.as<uint8_t>();
-    p.recs = s->recs.as<uint8_t>();
-    p.stride = sizeof(pbsgpu_record);
-    p.n = n;
-    p.keys = s->dense.as<uint32_t>();
-    p.idx = s->tile_slots.as<uint32_t>();
-    p.before = s->tile_cnt.as<uint8_t>();
-    p.known = out + sizeof(UpHead) + (size_t)n * 12;
-    p.stats = reinterpret_cast<uint64_t *>(out);
-    p.tmp = s->scan_tmp.p;
-    CHK(known_enqueue_mark(k, p, st));
+    const UpBlock ob((size_t)n, zstd);
+    UpDev dv;
+    CHK(stage_upload(s, src, recs, n, ob, zstd ? &zp : nullptr, jobs, dv));
+    dv.up.dst_cap = dst_cap;
+    CHK(known_enqueue_mark(k, dv.p, st));
     if (insert && known_may_grow(k, n)) {  // as known_common: the one case with a second synchronisation
-        HIPCHK(hipMemcpyAsync(s->h_scalars.p, p.stats, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s->h_scalars.p, dv.p.stats, 32, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         CHK(known_reserve(k, s->h_scalars.as<uint64_t>()[1], st));
     }
-    UpPlan up{};
-    up.recs = p.recs;
-    up.known = p.known;
-    if (src.chunks) {
-        up.chunks = s->sugg.as<pbsgpu_segment>();
-    } else {
-        up.tabs = s->sugg.as<PageTab>();
-        up.ptab = s->sugg.as<uint64_t>() + 2 * (size_t)src.nslots;
-    }
-    up.page_bytes = src.page_bytes;
-    up.dst_cap = dst_cap;
-    up.stream = src.stream;
-    up.n = (uint32_t)n;
-    up.bsum = s->par.as<UpCount>();
-    up.head = reinterpret_cast<UpHead *>(out);
-    up.boff = reinterpret_cast<uint64_t *>(out + sizeof(UpHead));
-    up.skip = p.before + n;
-    up.parts = s->segs.as<PartDesc>();
-    up.blobs = s->seg_off.as<BlobDesc>();
-    up.ppart = s->tile_off.as<uint32_t>();
-    up.jobs = room.jobs;
-    hipLaunchKernelGGL(pbsk::crc::k_upnew_count, dim3(nb), dim3(256), 0, st, up);
-    hipLaunchKernelGGL(pbsk::crc::k_upnew_scan, dim3(1), dim3(256), 0, st, up);
-    hipLaunchKernelGGL(pbsk::crc::k_upnew_fill, dim3(nb), dim3(256), 0, st, up);
-    HIPCHK(hipGetLastError());
-    if (src.pieces_max) {
-        const uint64_t wg = std::min<uint64_t>((src.pieces_max + 255) / 256, (uint64_t)e->num_cus * 8);
-        hipLaunchKernelGGL(pbsk::crc::k_upnew_ppart, dim3((unsigned)wg), dim3(256), 0, st, up);
-        HIPCHK(hipGetLastError());
-    }
-    if (insert) CHK(known_enqueue_insert(k, p, up.skip, st));
-    UpzPlan zl{};
-    PartPlan &pl = zl.p;
-    pl.base = src.base;
-    pl.dst = dst;
-    pl.parts = up.parts;
-    pl.blobs = up.blobs;
-    pl.ppart = up.ppart;
-    pl.praw = s->seg_cnt.as<uint32_t>();
-    pl.crcs = reinterpret_cast<uint32_t *>(out + sizeof(UpHead) + (size_t)n * 8);
-    pl.counts = &up.head->npieces;
-    set_magic(pl);
-    // (the grids of both pairs: the upper bounds the host knows)
-    if (zstd) {
-        CHK(pbsk::zenc::launch(e, st, zp, room, src.base, dst, true));
-        zl.res = room.res;
-        zl.lens = reinterpret_cast<uint32_t *>(out + lens_at);
-        zl.kinds = out + lens_at + (size_t)n * 4;
-        zl.zmagic_lo = le32(kMagic[PBSGPU_BLOB_COMPRESSED]);
-        zl.zmagic_hi = le32(kMagic[PBSGPU_BLOB_COMPRESSED] + 4);
-        CHK(launch_pair(e, st, k_upz_pieces, k_upz_fold, zl, src.pieces_max, n));
-    } else {
-        CHK(launch_pair(e, st, k_pagecrc_pieces, k_pagecrc_fold, pl, src.pieces_max, n));
-    }
-    HIPCHK(pbsk::launch_publish(s->h_recs.p, out, out_bytes, st));
+    CHK(enqueue_upload_plan(e, st, dv.up, src.pieces_max));
+    if (insert) CHK(known_enqueue_insert(k, dv.p, dv.up.skip, st));
+    CHK(enqueue_upload_blobs(e, st, src, dst, ob, zstd ? &zp : nullptr, dv));
+    HIPCHK(pbsk::launch_publish(s->h_recs.p, dv.out, ob.total, st));
     HIPCHK(hipStreamSynchronize(st));
     const uint8_t *h = s->h_recs.as<uint8_t>();
     UpHead head;
-    std::memcpy(&head, h, sizeof(head));
-    const uint8_t *h_known = h + sizeof(UpHead) + (size_t)n * 12;
+    std::memcpy(&head, h + ob.head, sizeof(head));
+    const uint8_t *h_known = h + ob.known;
     if (known_out) std::memcpy(known_out, h_known, (size_t)n);
     if (stats) {
         stats->nrecords = head.stats[0];
@@ -1829,27 +1693,19 @@ int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs,
     }
     *used = head.total;
     if (head.over) return PBSGPU_E_CAPACITY;
-    const uint8_t *h_boff = h + sizeof(UpHead), *h_crcs = h_boff + (size_t)n * 8;
-    const uint8_t *h_lens = h + lens_at, *h_kinds = h_lens + (size_t)n * 4;
-    for (uint64_t i = 0, j = 0; i < n; ++i) {
+    for (uint64_t i = 0, j = 0; i < n; ++i) {  // (crcs, lens and kinds are compacted: one per new record)
         if (h_known[i]) continue;
-        std::memcpy(&blob_off[i], h_boff + i * 8, 8);
-        if (crcs) std::memcpy(&crcs[i], h_crcs + j * 4, 4);
+        std::memcpy(&blob_off[i], h + ob.boff + i * 8, 8);
+        if (crcs) std::memcpy(&crcs[i], h + ob.crcs + j * 4, 4);
         uint32_t len = size_of(i) + PBSGPU_BLOB_HEADER_SIZE;
         uint8_t kind = PBSGPU_BLOB_UNCOMPRESSED;
         if (zstd) {
-            std::memcpy(&len, h_lens + j * 4, 4);
-            kind = h_kinds[j];
+            std::memcpy(&len, h + ob.lens + j * 4, 4);
+            kind = h[ob.kinds + j];
         }
         if (lens) lens[i] = len;
         if (kinds) kinds[i] = kind;
-        if (enc) {  // as pbsgpu_blob_encode2_device counts them
-            enc->blobs[kind]++;
-            enc->blob_bytes[kind] += len;
-            enc->chunk_bytes[kind] += size_of(i);
-            if (kind == PBSGPU_BLOB_COMPRESSED) enc->frame_bytes += len - PBSGPU_BLOB_HEADER_SIZE;
-            enc->crc_bytes += len - PBSGPU_BLOB_HEADER_SIZE;
-        }
+        if (enc) count_blob(*enc, kind, len, size_of(i));  // as pbsgpu_blob_encode2_device counts them
         ++j;
     }
     if (insert) known_inserted(k, head.stats[1]);
@@ -1934,22 +1790,13 @@ int pbsgpu_blob_encode2_device(pbsgpu_engine *e, const void *src, uint64_t src_b
         for (uint32_t i = 0; i < nseg; ++i) vlens[i] = (uint32_t)(segs[i].length + PBSGPU_BLOB_HEADER_SIZE);
     } else if (nseg) {
         if (!dst || !is_device_pointer(dst) || (src_bytes && !is_device_pointer(src))) return PBSGPU_E_INVALID;
-        const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src;
-        if (src_bytes && d0 < s0 + src_bytes && s0 < d0 + total) return PBSGPU_E_INVALID;  // the frames are read back
+        if (overlaps(dst, total, src, src_bytes)) return PBSGPU_E_INVALID;  // the frames are read back
         CHK(set_device(e));
         CHK(blob_encode_zstd(e, static_cast<const uint8_t *>(src), segs, nseg, static_cast<uint8_t *>(dst), offs.data(), src_bytes,
                              vlens.data(), vkinds.data(), vcrcs.data()));
     }
-    for (uint32_t i = 0; i < nseg; ++i) {
-        if (stats) {
-            const int k = vkinds[i];
-            stats->blobs[k]++;
-            stats->blob_bytes[k] += vlens[i];
-            stats->chunk_bytes[k] += segs[i].length;
-            if (k == PBSGPU_BLOB_COMPRESSED) stats->frame_bytes += vlens[i] - PBSGPU_BLOB_HEADER_SIZE;
-            stats->crc_bytes += vlens[i] - PBSGPU_BLOB_HEADER_SIZE;
-        }
-    }
+    if (stats)
+        for (uint32_t i = 0; i < nseg; ++i) count_blob(*stats, vkinds[i], vlens[i], segs[i].length);
     if (lens && nseg) std::memcpy(lens, vlens.data(), (size_t)nseg * 4);
     if (kinds && nseg) std::memcpy(kinds, vkinds.data(), nseg);
     if (crcs && nseg) std::memcpy(crcs, vcrcs.data(), (size_t)nseg * 4);
@@ -2006,13 +1853,11 @@ int pbsgpu_known_upload_new2_device(pbsgpu_known *k, const void *src, uint64_t s
     for (uint64_t i = 0; i < n; ++i) {  // every chunk, not only the new ones: which ones are new is not known here
         const pbsgpu_segment &c = chunks[i];
         if (c.length > src_bytes || c.offset > src_bytes - c.length || c.length >= (1ull << 31)) return PBSGPU_E_INVALID;
-        us.pieces_max += (c.length + pbsk::crc::kPiece - 1) >> pbsk::crc::kPieceLog;
+        us.pieces_max += pbsp::pieces_of(c.length);
     }
     if (us.pieces_max >= (1ull << 32)) return PBSGPU_E_INVALID;
-    if ((flags & PBSGPU_ENCODE_F_ZSTD) && src_bytes && dst_cap) {  // the frames are read again for their CRC
-        const uintptr_t d0 = (uintptr_t)dst, s0 = (uintptr_t)src;
-        if (d0 < s0 + src_bytes && s0 < d0 + dst_cap) return PBSGPU_E_INVALID;
-    }
+    if ((flags & PBSGPU_ENCODE_F_ZSTD) && overlaps(dst, dst_cap, src, src_bytes))  // the frames are read again for their CRC
+        return PBSGPU_E_INVALID;
     *used = 0;
     std::memset(stats, 0, sizeof(*stats));
     if (enc_stats) std::memset(enc_stats, 0, sizeof(*enc_stats));

@@ -184,6 +184,8 @@ void Slot::destroy() {
     for (DevBuf *b : {&data, &tile_cnt, &tile_off, &tile_slots, &dense, &scan_tmp, &scalars, &segs, &seg_cnt, &seg_off,
                       &recs, &order, &sugg, &sugg_idx, &par})
         b->release();
+    tables.release();
+    large.release();
     h_scalars.release();
     h_segs.release();
     h_sugg.release();
@@ -195,6 +197,23 @@ void Slot::destroy() {
         if (e) (void)hipEventDestroy(e);
     if (stream && own_stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
+}
+
+void *Scratch::take(size_t bytes, int *status) {
+    if (next == bufs.size()) bufs.emplace_back();
+    DevBuf &b = bufs[next++];
+    const int r = b.ensure(bytes + 64);
+    if (r != PBSGPU_OK) {
+        *status = r;
+        return nullptr;
+    }
+    return b.p;
+}
+
+void Scratch::release() {
+    for (DevBuf &b : bufs) b.release();
+    bufs.clear();
+    next = 0;
 }
 
 uint32_t default_cap(const pbsgpu_engine *e, uint64_t nbytes) {
@@ -230,6 +249,8 @@ AuxLease::AuxLease(pbsgpu_engine *eng) : e(eng) {
                 e->aux_busy[i] = 1;
                 idx = (int)i;
                 s = e->aux[i].get();
+                s->tables.next = s->large.next = 0;
+                s->scratch_status = PBSGPU_OK;
                 return;
             }
         e->cv.wait(lk);  // helper calls are synchronous and self-contained: a lease always comes back
@@ -1088,6 +1109,14 @@ int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes) {
     return PBSGPU_OK;
 }
 
+int enqueue_sha256(pbsgpu_engine *e, hipStream_t st, const uint8_t *base, const pbsgpu_segment *ranges_dev, uint32_t n,
+                   uint8_t *digs, uint32_t *queue, const pbsp::ShaWork &work) {
+    HIPCHK(pbsk::launch_sha256_segments(base, ranges_dev, n, digs, queue, e->num_cus,
+                                        pbsk::sha256_dense_pays(work.total_blocks, work.longest, e->num_cus, e->opt.sha_dense_pct),
+                                        (int)e->opt.sha_form, st));
+    return PBSGPU_OK;
+}
+
 }  // namespace pbse
 
 extern "C" {
@@ -1096,25 +1125,18 @@ static int sha256_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nb
                        uint32_t nseg, uint8_t *digests) {
     if (!e || (!ptr && nbytes) || (nseg && (!segs || !digests))) return PBSGPU_E_INVALID;
     if (nseg == 0) return PBSGPU_OK;
-    for (uint32_t i = 0; i < nseg; ++i)
-        if (segs[i].length > nbytes || segs[i].offset > nbytes - segs[i].length) return PBSGPU_E_INVALID;
+    if (!pbsp::ranges_ok(segs, nseg, nbytes)) return PBSGPU_E_INVALID;
     CHK(set_device(e));
     AuxLease lease(e);
     Slot *s = lease.s;
     const uint8_t *d = nullptr;
     CHK(stage_ranges(e, s, ptr, host, nbytes, segs, nseg, &d));
-    CHK(s->recs.ensure((size_t)nseg * 32));
-    uint64_t total_blocks = 0, longest = 1;
-    for (uint32_t i = 0; i < nseg; ++i) {
-        const uint64_t blocks = (segs[i].length + 8) / 64 + 1;
-        total_blocks += blocks;
-        longest = std::max(longest, blocks);
-    }
-    HIPCHK(pbsk::launch_sha256_segments(d, s->segs.as<pbsgpu_segment>(), nseg, s->recs.as<uint8_t>(),
-                                        s->scalars.as<uint32_t>() + SC_QUEUE, e->num_cus,
-                                        pbsk::sha256_dense_pays(total_blocks, longest, e->num_cus, e->opt.sha_dense_pct),
-                                        (int)e->opt.sha_form, s->stream));
-    return fetch_result(s, digests, s->recs.p, (size_t)nseg * 32);
+    uint8_t *digs = s->take<uint8_t>((size_t)nseg * 32);
+    CHK(s->taken());
+    pbsp::ShaWork work;
+    for (uint32_t i = 0; i < nseg; ++i) work.add(segs[i].length);
+    CHK(enqueue_sha256(e, s->stream, d, s->segs.as<pbsgpu_segment>(), nseg, digs, s->scalars.as<uint32_t>() + SC_QUEUE, work));
+    return fetch_result(s, digests, digs, (size_t)nseg * 32);
 }
 
 int pbsgpu_sha256_many_device(pbsgpu_engine *e, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,
@@ -1131,8 +1153,7 @@ static int xxh3_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbyt
                      uint32_t nseg, uint64_t *out) {
     if (!e || (!ptr && nbytes) || (nseg && (!segs || !out))) return PBSGPU_E_INVALID;
     if (nseg == 0) return PBSGPU_OK;
-    for (uint32_t i = 0; i < nseg; ++i)
-        if (segs[i].length > nbytes || segs[i].offset > nbytes - segs[i].length) return PBSGPU_E_INVALID;
+    if (!pbsp::ranges_ok(segs, nseg, nbytes)) return PBSGPU_E_INVALID;
     CHK(set_device(e));
     AuxLease lease(e);
     Slot *s = lease.s;
@@ -1148,13 +1169,13 @@ static int xxh3_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbyt
         items[i].out = i;
     }
     const uint64_t total_blocks = pbsk::xxh3_plan_whole(items.data(), nseg);
-    CHK(s->tile_slots.ensure((size_t)nseg * sizeof(pbsk::XxhItem) + 64));
-    CHK(s->dense.ensure((size_t)total_blocks * 64 + 64));
-    CHK(s->recs.ensure((size_t)nseg * 8 + 64));
-    CHK(staged_h2d(*s, s->tile_slots.p, items.data(), (size_t)nseg * sizeof(pbsk::XxhItem), s->stream));
-    HIPCHK(pbsk::launch_xxh3_items(s->tile_slots.as<pbsk::XxhItem>(), nseg, total_blocks, nullptr, s->dense.as<uint64_t>(),
-                                   s->recs.as<uint64_t>(), s->scalars.as<uint32_t>() + SC_QUEUE, e->num_cus, s->stream));
-    return fetch_result(s, out, s->recs.p, (size_t)nseg * 8);
+    const pbsk::XxhItem *items_dev = nullptr;
+    CHK(put_table(s, items.data(), nseg, &items_dev));
+    uint64_t *sums = s->take<uint64_t>((size_t)total_blocks * 8), *hashes = s->take<uint64_t>(nseg);
+    CHK(s->taken());
+    HIPCHK(pbsk::launch_xxh3_items(items_dev, nseg, total_blocks, nullptr, sums, hashes, s->scalars.as<uint32_t>() + SC_QUEUE,
+                                   e->num_cus, s->stream));
+    return fetch_result(s, out, hashes, (size_t)nseg * 8);
 }
 
 int pbsgpu_xxh3_many_device(pbsgpu_engine *e, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,

@@ -23,6 +23,7 @@
 #include <new>
 #include <vector>
 
+#include "blob_plan.h"
 #include "kernels.h"
 #include "zstd_plan.h"
 
@@ -141,6 +142,17 @@ struct PinnedBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// Device scratch of one synchronous helper call (an AuxLease): buffers handed out in call order, each take a DevBuf of its
+// own, so a later take never moves an earlier one that an enqueued kernel still reads. Every buffer has 64 bytes of slack
+// behind what was asked for (the kernels' 16-byte loads may touch them). The cursor goes back to 0 with the next lease; the
+// buffers stay and grow by DevBuf::ensure's policy.
+struct Scratch {
+    std::vector<DevBuf> bufs;
+    size_t next = 0;
+    void *take(size_t bytes, int *status);  // nullptr and *status = PBSGPU_E_NOMEM when the device has no room
+    void release();
+};
+
 // device scalars of one slot (uint32 each)
 enum : int { SC_NCAND = 0, SC_NREC = 1, SC_MAXCNT = 2, SC_QUEUE = 3, SC_WGLIMIT = 4, SC_ZERO = 5 /* stays 0 */,
              SC_TILEQ = 6 /* u64 */, SC_PARFB = 8 /* parallel resolve handed the job back */, SC_PARHOPS = 9, SC_COUNT = 10 };
@@ -157,6 +169,14 @@ struct Slot {
     DevBuf tile_cnt, tile_off, tile_slots, dense, scan_tmp, scalars, segs, seg_cnt, seg_off, recs, order;
     DevBuf sugg, sugg_idx;  // suggested boundaries (optional)
     DevBuf par;             // scratch of the parallel single-stream resolve (doubling tables)
+    // aux slots: what a helper call needs beyond the staged ranges. take() serves tables and result blocks, bulk() the few
+    // large byte buffers (the encoder's block output and work area, the decoders' literal and scratch area), which so
+    // only ever share positions with each other. A failed take is remembered: CHK(taken()) behind a call's takes.
+    Scratch tables, large;
+    int scratch_status = PBSGPU_OK;
+    template <typename T> T *take(size_t count) { return static_cast<T *>(tables.take(count * sizeof(T), &scratch_status)); }
+    uint8_t *bulk(size_t bytes) { return static_cast<uint8_t *>(large.take(bytes, &scratch_status)); }
+    int taken() const { return scratch_status; }
     PinnedBuf h_scalars;    // readback of SC_*
     PinnedBuf h_segs;       // pinned copy of the segment table
     PinnedBuf h_sugg;       // pinned copy of suggested offsets + index
@@ -256,7 +276,8 @@ uint32_t cap_limit(const pbsgpu_engine *e, uint32_t tile_bytes);
 int set_device(const pbsgpu_engine *e);
 bool is_device_pointer(const void *p);
 
-// leases one of the engine's aux slots for the duration of a synchronous helper call (waits for a free one)
+// leases one of the engine's aux slots for the duration of a synchronous helper call (waits for a free one); the slot's
+// scratch starts over
 struct AuxLease {
     pbsgpu_engine *e;
     Slot *s = nullptr;
@@ -280,6 +301,15 @@ struct SuggestedHost {  // caller's suggested boundaries: offsets[index[s] .. in
 int enqueue_candidates(pbsgpu_engine *e, Slot &s, const uint8_t *dptr, uint64_t nbytes, uint32_t cap,
                        uint64_t nseg_hint = 0);
 int staged_h2d(Slot &s, void *dst, const void *src, uint64_t nbytes, hipStream_t st);
+// a host table onto a take of the aux slot's scratch, enqueued on its stream
+template <typename T>
+int put_table(Slot *s, const T *host, size_t count, const T **dev) {
+    T *p = s->take<T>(count);
+    CHK(s->taken());
+    if (count) CHK(staged_h2d(*s, p, host, count * sizeof(T), s->stream));
+    *dev = p;
+    return PBSGPU_OK;
+}
 int stage_segments(pbsgpu_engine *e, Slot &s, const pbsgpu_segment *segs, uint32_t nseg, uint64_t nbytes,
                    const SuggestedHost *sg);
 // front half of the whole-range batches (sha256_many, xxh3_many, crc32_many, the blob calls): the segment table (and, with
@@ -288,6 +318,10 @@ int stage_ranges(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, uint64_t
                  uint32_t nseg, const uint8_t **d);
 // results of a synchronous helper: device -> mapped pinned memory by kernel, stream synchronised, then a host memcpy to dst
 int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes);
+// SHA-256 of n device ranges of `base` into digs (32 bytes each), with the dense-form policy of pbsgpu_sha256_many_device
+// applied to `work`, the sums over the lengths the host knows; queue: a zeroed counter. Enqueued, nothing synchronised.
+int enqueue_sha256(pbsgpu_engine *e, hipStream_t st, const uint8_t *base, const pbsgpu_segment *ranges_dev, uint32_t n,
+                   uint8_t *digs, uint32_t *queue, const pbsp::ShaWork &work);
 // synchronous helper for the upstream-style chunker (the caller owns the slot)
 int candidates_sync(pbsgpu_engine *e, Slot &s, const uint8_t *dptr, uint64_t nbytes, uint64_t *count);
 // Caller bytes -> pinned staging. One thread copies ~12 GB/s, the H2D engine moves 57 GB/s: a single writer (the
@@ -301,14 +335,7 @@ void parallel_memcpy(void *dst, const void *src, size_t n);
 // own restore kernels, on the same stream. Every place is an offset from `dst` (64-bit, wrapping: scratch lies elsewhere).
 namespace pbsk {
 namespace zstd {
-struct RestoreJob {   // one distinct blob: the room its frame is decoded into if it turns out compressed with a good CRC
-    uint64_t place;
-    uint32_t room, pad;
-};
-struct RestoreCopy {  // `len` bytes from `from` to `to` when blob u decoded to exactly `size` bytes
-    uint64_t from, to;
-    uint32_t len, size, u, pad;
-};
+// (RestoreJob, RestoreCopy, kNotDecoded, kLitBytes and kDescBytes: blob_plan.h)
 struct RestorePlan {
     const uint8_t *src;
     const pbsgpu_segment *blobs;  // nu
@@ -324,9 +351,6 @@ struct RestorePlan {
     uint8_t *dst, *lit;
     uint32_t nu, ncopy, nidx, stride;
 };
-constexpr uint32_t kNotDecoded = 0xffu;
-constexpr size_t kLitBytes = 128u << 10;  // literal scratch per workgroup of launch_restore_frames
-constexpr size_t kDescBytes = 32;         // per distinct blob, device scratch handed to launch_restore_frames
 hipError_t launch_restore_frames(const RestorePlan &pl, void *desc /* nu * kDescBytes */, hipStream_t st);  // pl.stride workgroups
 hipError_t launch_restore_copy(const RestorePlan &pl, uint32_t longest, int num_cus, hipStream_t st);
 hipError_t launch_restore_status(const RestorePlan &pl, hipStream_t st);
@@ -346,13 +370,14 @@ struct Job {  // one chunk: its bytes at src + src_off, its frame's room at dst 
 constexpr uint32_t kNoJob = 0xffffffffu;
 // res_dev[i] = frame length | status << 56. blob = false: PBSGPU_ZSTD_OK or _BAD_SIZE (nothing written, length 0).
 // blob = true: room is the chunk's length; PBSGPU_BLOB_COMPRESSED when the frame is strictly shorter than the chunk and
-// was written, PBSGPU_BLOB_UNCOMPRESSED (nothing written) otherwise. Uses the slot's recs, sugg_idx, order, data, par and
-// scan_tmp buffers. jobs: src_off, dst_off, room and len from the caller, one part each; the rest is filled in here.
+// was written, PBSGPU_BLOB_UNCOMPRESSED (nothing written) otherwise. Takes its arrays from the slot's
+// scratch. jobs: src_off, dst_off, room and len from the caller, one part each; the rest is filled in here.
 int enqueue(pbsgpu_engine *e, pbse::Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob,
             uint64_t **res_dev);
-// The same in three steps for a caller that places the arrays itself and has a kernel of its own fill in what only the
-// device knows of a job (blob.hip's fused upload): prepare() plans the blocks from the jobs' `len` and says
-// how much room each array needs; upload() copies the jobs and the block table to the room; launch() enqueues the rounds.
+// The same in three steps for a caller that has a kernel of its own fill in what only the device knows of a job (blob.hip's
+// fused upload): prepare() plans the blocks from the jobs' `len` and says how much room each array needs;
+// carve() takes that room from the slot's scratch and copies the jobs and the block table to it; launch() enqueues the
+// rounds.
 struct Room {  // device arrays
     Job *jobs;         // n
     uint32_t *bchunk;  // every block of the call: its chunk
@@ -369,7 +394,7 @@ struct Prep {
     size_t jobs_bytes = 0, bchunk_bytes = 0, res_bytes = 0, blkout_bytes = 0, bplace_bytes = 0, work_bytes = 0;  // of Room's arrays
 };
 int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p);  // PBSGPU_E_INVALID: 2^32 blocks or more
-int upload(pbse::Slot *s, const Prep &p, const Room &room, const std::vector<Job> &jobs);
+int carve(pbse::Slot *s, const Prep &p, const std::vector<Job> &jobs, Room &room);
 int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob);
 }  // namespace zenc
 }  // namespace pbsk

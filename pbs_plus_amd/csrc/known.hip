@@ -291,27 +291,19 @@ int known_common(pbsgpu_engine *e, pbsgpu_known *k, const uint8_t *src, uint32_t
     const hipStream_t st = s->stream;
     KnownPass p;
     CHK(known_sort_bytes(n, st, &p.tmp_bytes));
-    // layout inside the lease's buffers: recs | keys, keys_alt | idx, idx_alt | before, known | stats | sort tmp
-    if (!on_device) CHK(s->recs.ensure((size_t)n * stride + 64));
-    CHK(s->dense.ensure((size_t)n * 8 + 64));
-    CHK(s->tile_slots.ensure((size_t)n * 8 + 64));
-    CHK(s->tile_cnt.ensure((size_t)n * 2 + 64));
     CHK(s->scalars.ensure(SC_COUNT * 4 + 64));
-    CHK(s->scan_tmp.ensure(p.tmp_bytes));
     CHK(s->h_scalars.ensure(64));
     p.recs = src;
-    if (!on_device) {
-        CHK(staged_h2d(*s, s->recs.p, src, n * stride, st));
-        p.recs = s->recs.as<uint8_t>();
-    }
+    if (!on_device) CHK(put_table(s, src, (size_t)n * stride, &p.recs));
     p.stride = stride;
     p.n = n;
-    p.keys = s->dense.as<uint32_t>();
-    p.idx = s->tile_slots.as<uint32_t>();
-    p.before = s->tile_cnt.as<uint8_t>();
+    p.keys = s->take<uint32_t>((size_t)n * 2);
+    p.idx = s->take<uint32_t>((size_t)n * 2);
+    p.before = s->take<uint8_t>((size_t)n * 2);  // before | known
+    p.tmp = s->take<uint8_t>(p.tmp_bytes);
+    CHK(s->taken());
     p.known = p.before + n;
     p.stats = reinterpret_cast<uint64_t *>(s->scalars.as<uint8_t>() + 32);
-    p.tmp = s->scan_tmp.p;
     const uint64_t *hs = s->h_scalars.as<uint64_t>();
     CHK(known_enqueue_mark(k, p, st));
     HIPCHK(hipMemcpyAsync(s->h_scalars.p, p.stats, 32, hipMemcpyDeviceToHost, st));

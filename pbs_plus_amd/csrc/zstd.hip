@@ -187,10 +187,8 @@ int zstd_decode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return out[a].offset < out[b].offset; });
     for (size_t k = 1; k < order.size(); ++k)
         if (out[order[k - 1]].offset + out[order[k - 1]].length > out[order[k]].offset) return PBSGPU_E_INVALID;
-    if (hi > lo && nbytes) {
-        const uintptr_t d0 = (uintptr_t)dst + lo, d1 = (uintptr_t)dst + hi, s0 = (uintptr_t)src;
-        if (d0 < s0 + nbytes && s0 < d1) return PBSGPU_E_INVALID;  // a destination inside the source
-    }
+    if (hi > lo && pbsp::overlaps(static_cast<const uint8_t *>(dst) + lo, hi - lo, src, nbytes))
+        return PBSGPU_E_INVALID;  // a destination inside the source
     CHK(set_device(e));
     if ((nbytes && !is_device_pointer(src)) || (hi > lo && !is_device_pointer(dst))) return PBSGPU_E_INVALID;
     AuxLease lease(e);
@@ -198,22 +196,19 @@ int zstd_decode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nframe, (uint64_t)e->num_cus * 4);
     std::vector<Desc> desc(nframe);
     for (uint32_t i = 0; i < nframe; ++i) desc[i] = Desc{frames[i].offset, frames[i].length, out[i].offset, out[i].length};
-    CHK(s->seg_off.ensure((size_t)nframe * sizeof(Desc) + 64));
-    CHK(s->order.ensure((size_t)nframe * 8 + 64));
-    CHK(s->data.ensure((size_t)grid * pbsz::kLitMax));
-    CHK(staged_h2d(*s, s->seg_off.p, desc.data(), (size_t)nframe * sizeof(Desc), s->stream));
     Plan pl{};
+    CHK(put_table(s, desc.data(), nframe, &pl.desc));
+    pl.res = s->take<uint64_t>(nframe);
+    pl.lit = s->bulk((size_t)grid * pbsz::kLitMax);
+    CHK(s->taken());
     pl.src = static_cast<const uint8_t *>(src);
-    pl.desc = s->seg_off.as<Desc>();
     pl.dst = static_cast<uint8_t *>(dst);
-    pl.lit = s->data.as<uint8_t>();
-    pl.res = s->order.as<uint64_t>();
     pl.nframe = nframe;
     pl.stride = grid;
     hipLaunchKernelGGL(pbsk::zstd::k_zstd_frames, dim3(grid), dim3(64), 0, s->stream, pl);
     HIPCHK(hipGetLastError());
     std::vector<uint64_t> back(nframe);
-    CHK(fetch_result(s, back.data(), s->order.p, (size_t)nframe * 8));  // the call's one synchronisation
+    CHK(fetch_result(s, back.data(), pl.res, (size_t)nframe * 8));  // the call's one synchronisation
     for (uint32_t i = 0; i < nframe; ++i) {
         status[i] = (uint8_t)(back[i] >> 32);
         if (decoded) decoded[i] = (uint32_t)back[i];

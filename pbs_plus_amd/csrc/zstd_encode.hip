@@ -120,7 +120,14 @@ int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p) {
     return PBSGPU_OK;
 }
 
-int upload(Slot *s, const Prep &p, const Room &room, const std::vector<Job> &jobs) {
+int carve(Slot *s, const Prep &p, const std::vector<Job> &jobs, Room &room) {
+    room.jobs = reinterpret_cast<Job *>(s->take<uint8_t>(p.jobs_bytes));
+    room.bchunk = reinterpret_cast<uint32_t *>(s->take<uint8_t>(p.bchunk_bytes));
+    room.res = reinterpret_cast<uint64_t *>(s->take<uint8_t>(p.res_bytes));
+    room.bplace = reinterpret_cast<uint64_t *>(s->take<uint8_t>(p.bplace_bytes));
+    room.blkout = s->bulk(p.blkout_bytes);
+    room.work = s->bulk(p.work_bytes);
+    CHK(s->taken());
     CHK(staged_h2d(*s, room.jobs, jobs.data(), jobs.size() * sizeof(Job), s->stream));
     if (p.bp.nblocks) CHK(staged_h2d(*s, room.bchunk, p.bp.bchunk.data(), (size_t)p.bp.nblocks * 4, s->stream));
     return PBSGPU_OK;
@@ -175,15 +182,8 @@ int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::ve
     }
     Prep p;
     CHK(prepare(e, jobs, false, p));
-    CHK(s->recs.ensure(p.jobs_bytes + 64));
-    CHK(s->sugg_idx.ensure(p.bchunk_bytes + 64));
-    CHK(s->order.ensure(p.res_bytes + 64));
-    CHK(s->data.ensure(p.blkout_bytes + 64));
-    CHK(s->par.ensure(p.work_bytes));
-    CHK(s->scan_tmp.ensure(p.bplace_bytes + 64));
-    const Room room{s->recs.as<Job>(),    s->sugg_idx.as<uint32_t>(), s->order.as<uint64_t>(),
-                    s->data.as<uint8_t>(), s->scan_tmp.as<uint64_t>(), s->par.as<uint8_t>()};
-    CHK(upload(s, p, room, jobs));
+    Room room;
+    CHK(carve(s, p, jobs, room));
     CHK(launch(e, s->stream, p, room, src, dst, blob));
     *res_dev = room.res;
     return PBSGPU_OK;
@@ -215,10 +215,8 @@ int zstd_encode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu
     std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return out[a].offset < out[b].offset; });
     for (size_t k = 1; k < order.size(); ++k)
         if (out[order[k - 1]].offset + out[order[k - 1]].length > out[order[k]].offset) return PBSGPU_E_INVALID;
-    if (hi > lo && nbytes) {
-        const uintptr_t d0 = (uintptr_t)dst + lo, d1 = (uintptr_t)dst + hi, s0 = (uintptr_t)src;
-        if (d0 < s0 + nbytes && s0 < d1) return PBSGPU_E_INVALID;  // a destination inside the source
-    }
+    if (hi > lo && pbsp::overlaps(static_cast<const uint8_t *>(dst) + lo, hi - lo, src, nbytes))
+        return PBSGPU_E_INVALID;  // a destination inside the source
     CHK(set_device(e));
     if ((nbytes && !is_device_pointer(src)) || (hi > lo && !is_device_pointer(dst))) return PBSGPU_E_INVALID;
     AuxLease lease(e);
