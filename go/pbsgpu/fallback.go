@@ -79,6 +79,7 @@ type (
 		StreamRingGiB                                                    float64
 		StreamPageBytes                                                  uint64
 		ZstdSeqTables                                                    uint32
+		ZstdWindowLog                                                    uint32
 	}
 	RingStats struct {
 		PageBytes, BytesEnqueued, Chunks uint64

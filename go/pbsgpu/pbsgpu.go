@@ -101,6 +101,7 @@ type EngineOptions struct {
 	StreamRingGiB       float64 // its arena (0 = 48)
 	StreamPageBytes     uint64  // its page size (0 = default)
 	ZstdSeqTables       uint32  // the zstd encoder's sequences: 0 predefined tables, explicit offsets; 1 repeat offsets and per-block tables
+	ZstdWindowLog       uint32  // ... and its matches: 0 inside the 128 KiB block; 17, 18, 19 up to 2^log bytes in front of the block, within the chunk
 }
 
 func NewEngineOpt(device int, cfg Config, o EngineOptions) (*Engine, error) {
@@ -111,7 +112,7 @@ func NewEngineOpt(device int, cfg Config, o EngineOptions) (*Engine, error) {
 		stream_sha_cus: C.uint32_t(o.StreamShaCUs), stream_express_cus: C.uint32_t(o.StreamExpressCUs),
 		stream_ring_slots: C.uint32_t(o.StreamRingSlots), stream_ctx_pool: C.uint32_t(o.StreamCtxPool),
 		stream_ring_gib: C.double(o.StreamRingGiB), stream_page_bytes: C.uint64_t(o.StreamPageBytes),
-		zstd_seq_tables: C.uint32_t(o.ZstdSeqTables)}
+		zstd_seq_tables: C.uint32_t(o.ZstdSeqTables), zstd_window_log: C.uint32_t(o.ZstdWindowLog)}
 	if err := check(C.pbsgpu_engine_create_opt(C.int(device), &cfg.c, &co, &e.h), "engine_create"); err != nil {
 		return nil, err
 	}

@@ -140,7 +140,13 @@ typedef struct pbsgpu_engine_options {
                                       * PBSGPU_ZSTD_SEQ_TABLES overrides. */
     double stream_ring_gib;          /* its arena (0 = default 48 GiB); PBSGPU_STREAM_RING_GIB */
     uint64_t stream_page_bytes;      /* its page size (0 = default); PBSGPU_STREAM_PAGE_BYTES */
-    uint64_t reserved[4];
+    uint32_t zstd_window_log;        /* how far this engine's zstd encoder (the same four calls) looks for repeats: 0 = inside the
+                                      * 128 KiB block (default); 17, 18, 19 = a block's matches may start up to 2^log bytes in
+                                      * front of the block's first byte, within the same chunk, with a larger match table
+                                      * (the first word of `reserved[4]` before). Combines freely with zstd_seq_tables. Any
+                                      * other value: PBSGPU_E_INVALID. PBSGPU_ZSTD_WINDOW_LOG overrides. */
+    uint32_t reserved1;
+    uint64_t reserved[3];
 } pbsgpu_engine_options;
 int pbsgpu_engine_create_opt(int device, const pbsgpu_config *cfg, const pbsgpu_engine_options *opt /* NULL = defaults */,
                              pbsgpu_engine **out);
@@ -794,9 +800,21 @@ int pbsgpu_blob_decode2_device(pbsgpu_engine *eng, const void *blobs_dptr, uint6
  * predefined table, RLE_Mode or an FSE table described in the block, whichever is estimated shortest, never Repeat_Mode.
  * Both find the same matches; frames of mode 1 are never longer and on text about a fifth shorter. Slots, capacities,
  * verdict rules and synchronisations do not depend on the mode; frame bytes, lens, kinds and crcs may.
- * DESIGN.md §16 has the decisions and what they cost in ratio. */
+ * DESIGN.md §16 has the decisions and what they cost in ratio.
+ * Where the matches are looked for is the engine's second option, pbsgpu_engine_options.zstd_window_log, for the same
+ * calls and in either way of writing the sequences: 0 (default), inside the block, as above; 17, 18 or 19, a long-range
+ * mode in which a block's matches may start up to 2^log bytes in front of the block's first byte, within the same chunk
+ * and never before the chunk's first byte, found through a table four times as large that lies in the call's scratch
+ * (64 KiB per workgroup more). All of a chunk's content is on the device before its first block is encoded, so blocks
+ * are still encoded independently of one another, and the frame is single-segment, so any decoder takes such offsets.
+ * This mode finds a file, or a part of one, that occurs again further on in the same chunk; on content without far
+ * repeats it may write a slightly LONGER frame than window 0 (a few dozen bytes either way), and it is slower. The blob
+ * rule "compressed only if strictly shorter than the chunk" is unaffected, as are slots, capacities, the bound and the
+ * synchronisations; a ring chunk's frame is that of pbsgpu_zstd_encode_device of the same bytes on the same engine,
+ * also when its pages split it. DESIGN.md §18 has the ratios and what the mode costs. */
 #define PBSGPU_HAS_ZSTD_ENCODE 1
 #define PBSGPU_HAS_ZSTD_SEQ_TABLES 1
+#define PBSGPU_HAS_ZSTD_WINDOW 1
 /* No frame of n bytes of content is longer: the frame header, three bytes per block, the content. Host only. */
 uint64_t pbsgpu_zstd_encode_bound(uint64_t n);
 /* Encode many chunks in one call: chunk i = src[chunks[i].offset .. +length) becomes one frame at dst + out[i].offset, which

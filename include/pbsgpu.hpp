@@ -522,7 +522,9 @@ class Engine {
     }
     // ... with every per-engine tuning value (pbsgpu_engine_options, ABI v5; zero fields = the defaults). Among them
     // zstd_seq_tables = 1: blob::EncodeZstd, blob::Encode2 and the fused uploads of this engine write repeat offsets and
-    // per-block sequence tables (shorter frames, never longer).
+    // per-block sequence tables (shorter frames, never longer); and zstd_window_log = 17, 18 or 19: their blocks' matches may
+    // start up to 2^log bytes in front of the block, within the chunk (far repeats are found; slower, and on content without
+    // far repeats a frame may come out slightly longer).
     static Result<std::shared_ptr<Engine>> New(int device, const buzhash::Config &cfg, const pbsgpu_engine_options &opt) {
         Result<std::shared_ptr<Engine>> r;
         pbsgpu_engine *h = nullptr;

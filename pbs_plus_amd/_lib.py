@@ -109,7 +109,7 @@ class EngineOptions(C.Structure):
                 ("resolve_par_min", C.c_uint64), ("sha_many_files_per_core", C.c_uint32), ("stream_sha_cus", C.c_uint32),
                 ("stream_express_cus", C.c_uint32), ("stream_ring_slots", C.c_uint32), ("stream_ctx_pool", C.c_uint32),
                 ("zstd_seq_tables", C.c_uint32), ("stream_ring_gib", C.c_double), ("stream_page_bytes", C.c_uint64),
-                ("reserved", C.c_uint64 * 4)]
+                ("zstd_window_log", C.c_uint32), ("reserved1", C.c_uint32), ("reserved", C.c_uint64 * 3)]
 
 
 class RingStats(C.Structure):

@@ -723,6 +723,7 @@ static void engine_env_overrides(pbsgpu_engine_options &o) {
         {"PBSGPU_STREAM_RING_GIB", F64, &o.stream_ring_gib},
         {"PBSGPU_STREAM_PAGE_BYTES", U64, &o.stream_page_bytes},
         {"PBSGPU_ZSTD_SEQ_TABLES", U32, &o.zstd_seq_tables},
+        {"PBSGPU_ZSTD_WINDOW_LOG", U32, &o.zstd_window_log},
     };
     for (const Entry &e : table) {
         const char *v = getenv(e.name);
@@ -754,6 +755,7 @@ int pbsgpu_engine_create_opt(int device, const pbsgpu_config *cfg, const pbsgpu_
     engine_env_overrides(o);
     uint32_t inflight = o.inflight;
     if (o.sha_form > 2 || o.zstd_seq_tables > 1) return PBSGPU_E_INVALID;
+    if (o.zstd_window_log && (o.zstd_window_log < 17 || o.zstd_window_log > 19)) return PBSGPU_E_INVALID;
     // the candidate/resolve split needs: window 64, mask = 2^k - 1, min >= window, max > min
     if (cfg->window != pbsk::kWindow) return PBSGPU_E_INVALID;
     const uint64_t m1 = (uint64_t)cfg->mask + 1;

@@ -385,12 +385,14 @@ struct Room {  // device arrays
     uint8_t *blkout;   // the largest round's blocks, 128 KiB each
     uint64_t *bplace;  // the largest round's blocks: place in the frame (8 bytes each), then type and size (4 each); then a
                        // block counter per round
-    uint8_t *work;     // per workgroup: literals, sequences and, with sources in two parts, the block that holds the seam
+    uint8_t *work;     // per workgroup: literals, sequences and, with sources in two parts, the block that holds the seam;
+                       // with the long-range match finder its table instead (64 KiB)
 };
 struct Prep {
     pbsz::enc::BlockPlan bp;
     uint32_t grid = 0;  // workgroups of the block kernel
     bool two_parts = false;
+    uint32_t window_log = 0;  // pbsgpu_engine_options::zstd_window_log: the match finder's table is part of `work`
     size_t jobs_bytes = 0, bchunk_bytes = 0, res_bytes = 0, blkout_bytes = 0, bplace_bytes = 0, work_bytes = 0;  // of Room's arrays
 };
 int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p);  // PBSGPU_E_INVALID: 2^32 blocks or more

@@ -43,6 +43,20 @@
 //       by count * (log - log2 p) in 1/256 bit plus the description's bytes, integers on both builds; RLE and compressed
 //       must beat predefined by kSeqMargin bits, which covers what the estimate can be off by, so that a frame of this
 //       mode is never longer than the other mode's.
+//   * A long-range variant of the match finder (WState / WTState instead of State / TState;
+//     pbsgpu_engine_options::zstd_window_log = 17, 18 or 19), chosen at compile time:
+//     - a block's matches may start in its HISTORY, the hn = min(block's place in the chunk, 1 << window_log) bytes of the
+//       chunk in front of it. All of a chunk's content is there before its first block is encoded, so the blocks stay
+//       independent of each other's ENCODING, and the frame is single-segment: any offset up to the position is valid.
+//     - the table has 1 << kWindowHashLog entries and is the caller's, reached through a pointer; an entry is 1 + the
+//       highest WINDOW-relative position inserted (position 0 is the first history byte). Behind the RLE test every
+//       history position whose four bytes end inside the block's end is inserted; then the batches run as above, from the
+//       block's first byte. A match may start in the history and run into the block; its length is bounded by the
+//       block's end and its offset is the distance in the chunk. A chunk of one block uses this table too.
+//     - the content is read through a source type C (at, rd32, from): a plain pointer, or Src2 for a chunk in two parts.
+//     - offsets reach (1 << 19) + kBlockMax: the word is 18 | 18 | 20 bits with the repeat code in bits 56-57, and offset
+//       codes go up to 19 (the predefined distribution has a state for every code to 28). Repeat offsets as above.
+//     - a frame of this mode may be a little LONGER than the other match finder's on content without far repeats.
 //   * Buffers a block needs, all implied by kBlockMax: lit kBlockMax bytes, seqs kSeqCap * 8 bytes, blk kBlockMax bytes (a
 //     compressed form that would pass the block's content length is abandoned where it would).
 #pragma once
@@ -76,8 +90,15 @@ enum : int {  // ... of the mode with tables and repeat codes alone: the mode of
     E_REP_1, E_REP_2, E_REP_3, E_REP0_1, E_REP0_2, E_REP0_3, E_REP_UNKNOWN, E_LL_LOG_MAX, E_OF_LOG_MAX, E_ML_LOG_MAX,
     E_NBITS_TABLES
 };
+enum : int {  // ... of the long-range match finder alone: a candidate in the history, a match that starts in the history and
+              // runs into the block, a history that the window cuts (what lies before it is not inserted, so a match
+              // there is refused), an offset code of 18 or 19, a history that the chunk's start cuts
+    E_W_CAND_HISTORY = E_NBITS_TABLES, E_W_CROSS, E_W_BEYOND, E_W_OF_18, E_W_CHUNK_START,
+    E_NBITS_WINDOW
+};
 
 constexpr uint32_t kHashLog = 12;
+constexpr uint32_t kWindowHashLog = 14;  // the long-range match finder's table, in the caller's memory
 constexpr uint32_t kMinMatch = 4;
 constexpr uint32_t kLanes = 64;           // a batch of positions
 constexpr uint32_t kSeqCap = 24576;       // sequences per block; 8 bytes each in the caller's scratch
@@ -103,6 +124,7 @@ struct EncTab {  // FSE encoding of one predefined distribution, derived from th
 // ones before the first block, the weights' own after a block's match finding): it shares its bytes with the hash table.
 struct State {
     static constexpr bool kSeqTables = false;
+    static constexpr bool kWindow = false;
     union {
         uint32_t hash[1u << kHashLog];
         pbsz::State dec;
@@ -140,6 +162,24 @@ struct TState : State {
     uint32_t rep[3], known;         // the block's own offset history; known: bit i says that rep[i] is what the decoder has
 };
 
+// The long-range match finder on either way to write the sequences: the same bytes in LDS (u.hash serves only as the
+// decoder's State while tables are built), another type for encode_block to choose by.
+struct WState : State {
+    static constexpr bool kWindow = true;
+};
+struct WTState : TState {
+    static constexpr bool kWindow = true;
+};
+// the sequence word: literal length | match length << 18 | offset << 36 | repeat code << rep_shift
+template <class S> constexpr uint32_t off_mask = S::kWindow ? 0xfffffu : 0x1ffffu;
+template <class S> constexpr uint32_t rep_shift = S::kWindow ? 56u : 53u;
+
+// Content in two parts (a ring chunk in two pages): byte i is p0[i] below a and p1[i - a] from a on. One part: a = its length.
+struct Src2 {
+    const uint8_t *p0, *p1;
+    uint32_t a;
+};
+
 #ifdef PBSGPU_ZSTD_COVERAGE  // CPU test build only: the history the decoder really has, for E_REP_UNKNOWN alone
 inline uint32_t g_dec_rep[3] = {1, 4, 8}, g_dec_rep_block[3] = {1, 4, 8};
 #endif
@@ -173,7 +213,30 @@ PBSZ_HD void block_header(uint8_t *h, uint32_t last, uint32_t type, uint32_t byt
 PBSZ_HD uint32_t payload_bytes(uint32_t type, uint32_t bn, uint32_t csize) { return type == B_RAW ? bn : type == B_RLE ? 1u : csize; }
 
 PBSZ_HD uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-PBSZ_HD uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashLog); }
+PBSZ_HD uint32_t hash4(uint32_t v, uint32_t log = kHashLog) { return (v * 2654435761u) >> (32 - log); }
+// a source C: the byte and the four bytes at i, or at i + k (two steps, so that the pointer form is the expression it
+// always was), and the source k bytes further on
+PBSZ_HD uint8_t at(const uint8_t *s, uint32_t i) { return s[i]; }
+template <class T>
+PBSZ_HD uint8_t at(const uint8_t *s, uint32_t i, T k) { return s[i + k]; }
+PBSZ_HD uint32_t rd32(const uint8_t *s, uint32_t i) { return rd32(s + i); }
+template <class T>
+PBSZ_HD uint32_t rd32(const uint8_t *s, uint32_t i, T k) { return rd32(s + i + k); }
+PBSZ_HD const uint8_t *from(const uint8_t *s, uint32_t k) { return s + k; }
+PBSZ_HD uint8_t at(const Src2 &s, uint32_t i) { return i < s.a ? s.p0[i] : s.p1[i - s.a]; }
+PBSZ_HD uint32_t rd32(const Src2 &s, uint32_t i) {
+    if (i + 4 <= s.a) return rd32(s.p0 + i);
+    if (i >= s.a) return rd32(s.p1 + (i - s.a));
+    return (uint32_t)at(s, i) | (uint32_t)at(s, i + 1) << 8 | (uint32_t)at(s, i + 2) << 16 | (uint32_t)at(s, i + 3) << 24;
+}
+template <class T>
+PBSZ_HD uint8_t at(const Src2 &s, uint32_t i, T k) { return at(s, i + (uint32_t)k); }
+template <class T>
+PBSZ_HD uint32_t rd32(const Src2 &s, uint32_t i, T k) { return rd32(s, i + (uint32_t)k); }
+PBSZ_HD Src2 from(const Src2 &s, uint32_t k) {
+    if (k < s.a) return Src2{s.p0 + k, s.p1, s.a - k};
+    return Src2{s.p1 + (k - s.a), s.p1 + (k - s.a), 0};
+}
 
 // A backward bit stream being written: values go in from bit 0 of p[0] upwards, the reader takes them from the top. No byte
 // at or behind p[cap] is stored; `over` says that one would have been.
@@ -733,14 +796,14 @@ PBSZ_HD void choose_table(TState &st, uint32_t which, uint32_t nseq) {
 }
 
 // The block's tables (the mode with tables only): the three code streams counted by all lanes, then lane 0 chooses.
-template <class P>
-PBSZ_HD void seq_tables(TState &st, const uint64_t *seqs, uint32_t nseq) {
+template <class P, class S>
+PBSZ_HD void seq_tables(S &st, const uint64_t *seqs, uint32_t nseq) {
     for (uint32_t i = (uint32_t)P::lane(); i < 3 * 64; i += (uint32_t)P::lanes()) st.shist[i >> 6][i & 63] = 0;
     P::sync();
     for (uint32_t i = (uint32_t)P::lane(); i < nseq; i += (uint32_t)P::lanes()) {
         const uint64_t q = seqs[i];
-        const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu, rc = (uint32_t)(q >> 53) & 3u;
-        const uint32_t ov = rc ? rc : ((uint32_t)(q >> 36) & 0x1ffffu) + 3;
+        const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu, rc = (uint32_t)(q >> rep_shift<S>) & 3u;
+        const uint32_t ov = rc ? rc : ((uint32_t)(q >> 36) & off_mask<S>) + 3;
         P::aadd(&st.shist[0][ll_code(ll)], 1u);
         P::aadd(&st.shist[1][highbit(ov)], 1u);
         P::aadd(&st.shist[2][ml_code(ml)], 1u);
@@ -799,8 +862,8 @@ PBSZ_HD uint32_t encode_sequences(const S &st, const uint64_t *seqs, uint32_t ns
         const uint32_t ll = (uint32_t)q & 0x3ffffu, ml = (uint32_t)(q >> 18) & 0x3ffffu;
         uint32_t ov = (uint32_t)(q >> 36) + 3;
         if constexpr (S::kSeqTables) {
-            const uint32_t rc = (uint32_t)(q >> 53) & 3u;
-            ov = rc ? rc : ((uint32_t)(q >> 36) & 0x1ffffu) + 3;
+            const uint32_t rc = (uint32_t)(q >> rep_shift<S>) & 3u;
+            ov = rc ? rc : ((uint32_t)(q >> 36) & off_mask<S>) + 3;
         }
         const uint32_t cl = ll_code(ll), cm = ml_code(ml), co = highbit(ov);
         if (k == nseq - 1) {  // the decoder ends in these states: any state of the symbol serves
@@ -814,6 +877,7 @@ PBSZ_HD uint32_t encode_sequences(const S &st, const uint64_t *seqs, uint32_t ns
         }
         if (cl > 15) PBSZ_ECOV(E_LL_EXTRA);
         if (cm > 31) PBSZ_ECOV(E_ML_EXTRA);
+        if (co >= 18) PBSZ_ECOV(E_W_OF_18);
         bw.add(ll - kLLBase[cl], kLLBits[cl]);
         bw.add(ml - kMLBase[cm], kMLBits[cm]);
         bw.add(ov - (1u << co), co);
@@ -861,13 +925,19 @@ PBSZ_HD uint32_t rep_code(uint32_t (&r)[3], uint32_t &known, uint32_t ll, uint32
 // One block src[0, bn), 1 <= bn <= kBlockMax: its type and, for a compressed block, the compressed form in blk[0, size).
 // Returns type | size << 2 (size: payload_bytes), the same in every lane. init_tables has run on st. lit: kBlockMax bytes,
 // seqs: kSeqCap words, blk: bn bytes; nothing else is stored to. S = TState: the mode with tables and repeat codes.
-template <class P, class S = State>
-PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *blk, uint8_t *lit, uint64_t *seqs) {
-    for (uint32_t i = (uint32_t)P::lane(); i < (1u << kHashLog); i += (uint32_t)P::lanes()) st.u.hash[i] = 0;
+// S = WState or WTState, the long-range match finder: src[0, hn) is the block's history and src[hn, hn + bn) the block
+// (positions are window-relative throughout), and wtab[0, 1 << kWindowHashLog) is the table, stored to as well.
+template <class P, class S = State, class C = const uint8_t *>
+PBSZ_HD uint32_t encode_block(S &st, const C src, uint32_t bn, uint8_t *blk, uint8_t *lit, uint64_t *seqs, uint32_t hn = 0,
+                              uint32_t *wtab = nullptr) {
+    constexpr uint32_t hlog = S::kWindow ? kWindowHashLog : kHashLog;
+    uint32_t *const tab = S::kWindow ? wtab : st.u.hash;
+    const uint32_t h0 = S::kWindow ? hn : 0u, end = h0 + bn;  // the block is src[h0, end)
+    for (uint32_t i = (uint32_t)P::lane(); i < (1u << hlog); i += (uint32_t)P::lanes()) tab[i] = 0;
     for (uint32_t i = (uint32_t)P::lane(); i < 256; i += (uint32_t)P::lanes()) st.hist[i] = 0;
     if (P::lane() == 0) {
         st.flag = 0;
-        st.cursor = 0;
+        st.cursor = h0;
         st.nlit = 0;
         st.nseq = 0;
         st.ll_run = 0;
@@ -882,30 +952,35 @@ PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *b
         }
     }
     P::sync();
-    const uint32_t first = P::uni(src[0]);
+    const uint32_t first = P::uni(at(src, h0));
     for (uint32_t i = (uint32_t)P::lane(); i < bn; i += (uint32_t)P::lanes())
-        if (src[i] != first) st.flag = 1;
+        if (at(src, h0 + i) != first) st.flag = 1;
     P::sync();
     if (!P::uni(st.flag)) {
         PBSZ_ECOV(E_BLOCK_RLE);
         return B_RLE | 1u << 2;
     }
-    for (uint32_t b0 = 0; b0 < bn;) {
+    if constexpr (S::kWindow) {  // the history: every position whose four bytes lie in front of the block's end
+        for (uint32_t l = (uint32_t)P::lane(); l < hn; l += (uint32_t)P::lanes())
+            if (l + kMinMatch <= end) P::amax(&tab[hash4(rd32(src, l), hlog)], l + 1);
+        P::sync();
+    }
+    for (uint32_t b0 = h0; b0 < end;) {
         // every position of the batch against the table as the batches before left it
         for (uint32_t l = (uint32_t)P::lane(); l < kLanes; l += (uint32_t)P::lanes()) {
             const uint32_t pos = b0 + l;
             uint32_t m = 0, off = 0, h = kNone;
-            if (pos + kMinMatch <= bn) {
-                const uint32_t v = rd32(src + pos);
-                h = hash4(v);
-                const uint32_t c = st.u.hash[h];
-                if (c && rd32(src + c - 1) == v) {
+            if (pos + kMinMatch <= end) {
+                const uint32_t v = rd32(src, pos);
+                h = hash4(v, hlog);
+                const uint32_t c = tab[h];
+                if (c && rd32(src, c, -1) == v) {
                     const uint32_t q = c - 1;  // q < pos
                     off = pos - q;
                     m = kMinMatch;
                     bool open = true;
-                    while (open && pos + m + 4 <= bn) {
-                        const uint32_t x = rd32(src + q + m) ^ rd32(src + pos + m);
+                    while (open && pos + m + 4 <= end) {
+                        const uint32_t x = rd32(src, q, m) ^ rd32(src, pos, m);
                         if (x) {
                             m += (uint32_t)__builtin_ctz(x) >> 3;
                             open = false;
@@ -913,7 +988,11 @@ PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *b
                             m += 4;
                         }
                     }
-                    while (open && pos + m < bn && src[q + m] == src[pos + m]) ++m;
+                    while (open && pos + m < end && at(src, q, m) == at(src, pos, m)) ++m;
+                    if constexpr (S::kWindow) {
+                        if (q < h0) PBSZ_ECOV(E_W_CAND_HISTORY);
+                        if (q < h0 && q + m > h0) PBSZ_ECOV(E_W_CROSS);
+                    }
                 }
             }
             st.mlen[l] = m;
@@ -922,31 +1001,31 @@ PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *b
         }
         P::sync();
         for (uint32_t l = (uint32_t)P::lane(); l < kLanes; l += (uint32_t)P::lanes())
-            if (st.mh[l] != kNone) P::amax(&st.u.hash[st.mh[l]], b0 + l + 1);
+            if (st.mh[l] != kNone) P::amax(&tab[st.mh[l]], b0 + l + 1);
         if (P::lane() == 0) {  // the matches in position order: the first at or after the cursor
             uint32_t cursor = st.cursor, nlit = st.nlit, nseq = st.nseq, run = st.ll_run;
             PBSZ_ROLLED
             for (uint32_t l = 0; l < kLanes; ++l) {
                 const uint32_t pos = b0 + l;
-                uint32_t at = kNone;
-                if (pos < bn && pos >= cursor) {
+                uint32_t at_lit = kNone;
+                if (pos < end && pos >= cursor) {
                     const uint32_t m = st.mlen[l];
                     if (m >= kMinMatch && nseq < kSeqCap) {
                         const uint32_t off = st.moff[l];
                         if (off < m) PBSZ_ECOV(E_MATCH_OVERLAP);
                         if (off == 1) PBSZ_ECOV(E_MATCH_OFFSET_1);
                         uint64_t q = (uint64_t)run | (uint64_t)m << 18 | (uint64_t)off << 36;
-                        if constexpr (S::kSeqTables) q |= (uint64_t)rep_code(st.rep, st.known, run, off) << 53;
+                        if constexpr (S::kSeqTables) q |= (uint64_t)rep_code(st.rep, st.known, run, off) << rep_shift<S>;
                         seqs[nseq++] = q;
                         run = 0;
                         cursor = pos + m;
                     } else {
                         if (m >= kMinMatch) PBSZ_ECOV(E_SEQ_CAP);
-                        at = nlit++;
+                        at_lit = nlit++;
                         ++run;
                     }
                 }
-                st.lidx[l] = at;
+                st.lidx[l] = at_lit;
             }
             st.cursor = cursor;
             st.nlit = nlit;
@@ -956,7 +1035,7 @@ PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *b
         }
         P::sync();
         for (uint32_t l = (uint32_t)P::lane(); l < kLanes; l += (uint32_t)P::lanes())
-            if (st.lidx[l] != kNone) lit[st.lidx[l]] = src[b0 + l];
+            if (st.lidx[l] != kNone) lit[st.lidx[l]] = at(src, b0 + l);
         b0 = P::uni(st.next_b0);
     }
     P::sync();
@@ -964,7 +1043,7 @@ PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *b
     uint32_t type = B_RAW, size = bn;
     const uint32_t lsize = encode_literals<P>(st, lit, nlit, blk, bn);
     if (lsize != kNone) {
-        if constexpr (S::kSeqTables) seq_tables<P>(st, seqs, nseq);
+        if constexpr (S::kSeqTables) seq_tables<P, S>(st, seqs, nseq);
         if (P::lane() == 0) st.size = encode_sequences(st, seqs, nseq, blk + lsize, bn - lsize);
         P::sync();
         const uint32_t ssize = P::uni(st.size);
@@ -984,10 +1063,11 @@ PBSZ_HD uint32_t encode_block(S &st, const uint8_t *src, uint32_t bn, uint8_t *b
 
 // The frame of src[0, n), n < 4 GiB, into dst[0, room): BAD_SIZE where it needs more, and dst's contents are then
 // unspecified. *flen = the frame's length (with OK). Scratch as for encode_block. Never stores outside dst[0, room) and
-// the scratch.
-template <class P, class S = State>
-PBSZ_HD int encode_frame(S &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint64_t room, uint8_t *blk, uint8_t *lit,
-                         uint64_t *seqs, uint64_t *flen) {
+// the scratch. The long-range match finder (S = WState or WTState) also takes the window's log and its table, and the
+// content may lie in two parts (C = Src2).
+template <class P, class S = State, class C = const uint8_t *>
+PBSZ_HD int encode_frame(S &st, const C src, uint32_t n, uint8_t *dst, uint64_t room, uint8_t *blk, uint8_t *lit,
+                         uint64_t *seqs, uint64_t *flen, uint32_t window_log = 0, uint32_t *wtab = nullptr) {
     *flen = 0;
 #ifdef PBSGPU_ZSTD_COVERAGE
     g_dec_rep[0] = 1, g_dec_rep[1] = 4, g_dec_rep[2] = 8;  // a frame's decoder starts here
@@ -1006,15 +1086,25 @@ PBSZ_HD int encode_frame(S &st, const uint8_t *src, uint32_t n, uint8_t *dst, ui
     }
     for (uint32_t at = 0; at < n; at += kBlockMax) {
         const uint32_t bn = n - at < kBlockMax ? n - at : kBlockMax;
-        const uint32_t r = encode_block<P, S>(st, src + at, bn, blk, lit, seqs);
+        uint32_t r;
+        if constexpr (S::kWindow) {  // the history: what of the window lies in the chunk
+            const uint32_t hn = at < (1u << window_log) ? at : 1u << window_log;
+            if (hn < at) PBSZ_ECOV(E_W_BEYOND);
+            else if (at) PBSZ_ECOV(E_W_CHUNK_START);
+            r = encode_block<P, S>(st, from(src, at - hn), bn, blk, lit, seqs, hn, wtab);
+        } else {
+            r = encode_block<P, S>(st, from(src, at), bn, blk, lit, seqs);
+        }
         const uint32_t type = r & 3u, size = r >> 2;
         if (room - pos < (uint64_t)3 + size) return BAD_SIZE;
         if (P::lane() == 0) block_header(dst + pos, at + bn == n ? 1u : 0u, type, type == B_COMPRESSED ? size : bn);
         pos += 3;
         if (type == B_RLE) {
-            if (P::lane() == 0) dst[pos] = src[at];
+            if (P::lane() == 0) dst[pos] = enc::at(src, at);
+        } else if (type == B_RAW) {
+            for (uint32_t i = (uint32_t)P::lane(); i < size; i += (uint32_t)P::lanes()) dst[pos + i] = enc::at(src, at + i);
         } else {
-            copy_bytes<P>(dst + pos, type == B_RAW ? src + at : blk, size);
+            copy_bytes<P>(dst + pos, blk, size);
         }
         pos += size;
         P::sync();  // blk, lit and seqs go to the next block

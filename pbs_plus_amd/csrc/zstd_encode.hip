@@ -14,7 +14,9 @@
 //                    together later. Per block: type and size. A chunk may lie in two parts (a ring chunk in two pages):
 //                    the one block that holds the seam is put together in the workgroup's scratch first.
 //                    With pbsgpu_engine_options::zstd_seq_tables the same loop runs as k_zenc_tblocks, in a translation unit
-//                    of its own (zstd_encode_tables.hip), on a State that adds the per-block sequence tables.
+//                    of its own (zstd_encode_tables.hip), on a State that adds the per-block sequence tables. With
+//                    pbsgpu_engine_options::zstd_window_log either runs with the long-range match finder, as
+//                    k_zenc_wblocks or k_zenc_wtblocks (zstd_encode_window.hip).
 //   k_zenc_assemble  one workgroup of 256 per chunk: a prefix over its blocks' sizes (wave 0), then the frame header, the
 //                    block headers and the payloads (content for raw blocks, one byte for RLE, the compressed form) to
 //                    their places in the room. It records the frame's length and the status; for the blob call the
@@ -116,7 +118,9 @@ int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p) {
     p.res_bytes = pad64((size_t)n * 8);
     p.blkout_bytes = pad64((size_t)p.bp.most * pbsz::kBlockMax);
     p.bplace_bytes = pad64((size_t)p.bp.most * 12 + (p.bp.cuts.size() - 1) * 4);
-    p.work_bytes = (size_t)p.grid * ((two_parts ? 2 : 1) * (size_t)pbsz::kBlockMax + (size_t)ze::kSeqCap * 8);
+    p.window_log = e->opt.zstd_window_log;  // the engine's: a slot's size is stable
+    // the long-range match finder reads both parts in place and stages nothing; its table takes the staged block's place
+    p.work_bytes = (size_t)p.grid * (p.window_log ? kWindowWork : (two_parts ? 2 : 1) * (size_t)pbsz::kBlockMax + (size_t)ze::kSeqCap * 8);
     return PBSGPU_OK;
 }
 
@@ -144,7 +148,8 @@ int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, co
     pl.bres = reinterpret_cast<uint32_t *>(room.bplace + p.bp.most);
     pl.lit = room.work;
     pl.seqs = reinterpret_cast<uint64_t *>(room.work + (size_t)p.grid * pbsz::kBlockMax);
-    pl.stage = p.two_parts ? room.work + (size_t)p.grid * (pbsz::kBlockMax + (size_t)ze::kSeqCap * 8) : nullptr;
+    pl.stage = p.two_parts && !p.window_log ? room.work + (size_t)p.grid * (pbsz::kBlockMax + (size_t)ze::kSeqCap * 8) : nullptr;
+    pl.window_log = p.window_log;  // (the window kernels: kWindowWork bytes per workgroup from pl.lit on, nothing staged)
     pl.dst = dst;
     pl.res = room.res;
     pl.blob = blob ? 1u : 0u;
@@ -159,7 +164,9 @@ int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, co
         if (pl.c0 == pl.c1) continue;
         if (pl.b1 > pl.b0) {
             const uint32_t grid = std::min<uint32_t>(p.grid, pl.b1 - pl.b0);
-            if (e->opt.zstd_seq_tables) {  // the engine's option: per-block tables and repeat codes
+            if (p.window_log) {  // the engine's options: the long-range match finder, without or with tables
+                HIPCHK(launch_blocks_window(pl, grid, e->opt.zstd_seq_tables != 0, st));
+            } else if (e->opt.zstd_seq_tables) {  // per-block tables and repeat codes
                 HIPCHK(launch_blocks_tables(pl, grid, st));
             } else {
                 hipLaunchKernelGGL(k_zenc_blocks, dim3(grid), dim3(64), 0, st, pl);

@@ -68,8 +68,8 @@ class Engine:
     chunker + hasher built from the buzhash.Config (commit_orchestrate.go:137-149)."""
 
     def __init__(self, config: Config, device: int = 0, inflight: int = 2, **options):
-        """`options`: fields of pbsgpu_engine_options by name (sha_form=2, stream_ring_gib=8.0, zstd_seq_tables=1, ...); none =
-        the defaults."""
+        """`options`: fields of pbsgpu_engine_options by name (sha_form=2, stream_ring_gib=8.0, zstd_seq_tables=1,
+        zstd_window_log=17, ...); none = the defaults."""
         self._L = _lib.lib()
         self.config = config
         h = C.c_void_p()

@@ -3,6 +3,8 @@ GiB/s of CONTENT, beside what it is measured against:
 
 * with --seq-tables the same call on an engine created with zstd_seq_tables=1 (repeat offsets and per-block sequence
   tables): its rate and its bytes per content byte beside the default mode's;
+* with --window-log N (17, 18 or 19) the same call on an engine created with zstd_window_log=N (the long-range match
+  finder: a block's matches may start up to 2^N bytes in front of it), and with --seq-tables as well on one with both;
 * the plain pbsgpu_blob_encode_device of the same chunks (what the write side did before it could compress);
 * ZSTD_compress level 1 of the same chunks on 16 host threads, where libzstd.so.1 loads (ctypes releases the GIL); where it
   does not load, the leg says so and is left out.
@@ -14,7 +16,7 @@ the run. Each figure is the median of --reps synchronous calls timed with a host
 fastest and the slowest beside it. Not measured: the share of the serial lane (sequence and Huffman code), which needs a
 kernel variant or a trace, not a clock around the call.
 
-    python tools/zstd_encode_rate.py [--chunks 4096] [--reps 5] [--limit 600] [--seq-tables]
+    python tools/zstd_encode_rate.py [--chunks 4096] [--reps 5] [--limit 600] [--seq-tables] [--window-log N]
 """
 import argparse
 import ctypes as C
@@ -69,17 +71,18 @@ def _rates(total, t):
             "GiBps_fastest": round(gib / t[1], 3)}
 
 
-def leg_device(a, zstd, tables=False):
+def leg_device(a, zstd, tables=False, window_log=0):
     from pbs_plus_amd import Engine, buzhash
 
     host, ranges, kinds = _batch(a.chunks)
     total = int(ranges[:, 1].sum())
-    eng = Engine(buzhash.NewConfig(4 << 20), device=0, **({"zstd_seq_tables": 1} if tables else {}))
+    options = dict({"zstd_seq_tables": 1} if tables else {}, **({"zstd_window_log": window_log} if window_log else {}))
+    eng = Engine(buzhash.NewConfig(4 << 20), device=0, **options)
     dev = eng.alloc(host.size)
     dev.upload(host)
     dst = eng.alloc(total + 12 * a.chunks)
-    res = {"leg": ("encode2_zstd_seq_tables" if tables else "encode2_zstd") if zstd else "blob_encode_device", "chunks": a.chunks,
-           "content_bytes": total}
+    name = ("encode2_zstd_seq_tables" if tables else "encode2_zstd") + ("_window%d" % window_log if window_log else "")
+    res = {"leg": name if zstd else "blob_encode_device", "chunks": a.chunks, "content_bytes": total}
     if zstd:
         fn = lambda: eng.blob_encode2(dev, ranges, dst=dst, zstd=True)  # noqa: E731
         _, offs, lens, kd, crcs, stats = fn()
@@ -147,15 +150,22 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=600, help="seconds each leg may take")
     ap.add_argument("--seq-tables", action="store_true", help="also the zstd leg on an engine with zstd_seq_tables=1")
-    ap.add_argument("--leg", choices=("zstd", "tables", "plain", "host"), help="(internal) run one leg in this process")
+    ap.add_argument("--window-log", type=int, default=0, choices=(0, 17, 18, 19),
+                    help="also the zstd leg (with --seq-tables: both) on an engine with zstd_window_log=N")
+    ap.add_argument("--leg", choices=("zstd", "tables", "wzstd", "wtables", "plain", "host"), help="(internal) run one leg in this process")
     a = ap.parse_args()
     if a.leg:
         {"zstd": lambda: leg_device(a, True), "tables": lambda: leg_device(a, True, True), "plain": lambda: leg_device(a, False),
+         "wzstd": lambda: leg_device(a, True, False, a.window_log), "wtables": lambda: leg_device(a, True, True, a.window_log),
          "host": lambda: leg_host(a)}[a.leg]()
         return
-    legs = ("plain", "zstd", "tables", "host") if a.seq_tables else ("plain", "zstd", "host")
+    legs = ["plain", "zstd"] + (["tables"] if a.seq_tables else [])
+    if a.window_log:
+        legs += ["wzstd"] + (["wtables"] if a.seq_tables else [])
+    legs.append("host")
     for leg in legs:  # each in a fresh process under its own limit; the first that fails ends the run
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--chunks", str(a.chunks), "--reps", str(a.reps)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--chunks", str(a.chunks), "--reps", str(a.reps),
+               "--window-log", str(a.window_log)]
         try:
             r = subprocess.run(cmd, timeout=a.limit)
         except subprocess.TimeoutExpired:
