@@ -49,8 +49,10 @@ namespace pbsz {
 inline uint64_t g_cov = 0;
 }
 #define PBSZ_COV(bit) (::pbsz::g_cov |= 1ull << (bit))
+#define PBSZ_COV_IF(cond, bit) ((cond) ? (void)PBSZ_COV(bit) : (void)0)
 #else
 #define PBSZ_COV(bit) ((void)0)
+#define PBSZ_COV_IF(cond, bit) ((void)0)  // the condition is not compiled either: the kernel is what it was
 #endif
 
 namespace pbsz {
@@ -66,6 +68,12 @@ enum : int {  // coverage bits
     C_LL_PREDEF, C_LL_RLE, C_LL_FSE, C_LL_REPEAT, C_OF_PREDEF, C_OF_RLE, C_OF_FSE, C_OF_REPEAT,
     C_ML_PREDEF, C_ML_RLE, C_ML_FSE, C_ML_REPEAT,
     C_REP_1, C_REP_2, C_REP_3, C_REP_SHIFTED, C_REP_1_MINUS_1, C_MATCH_OVERLAP, C_MATCH_OFFSET_1, C_MATCH_ACROSS_BLOCKS,
+    // where the lanes of the kernel cooperate (the CPU build walks the same branches with one lane): a match that waits
+    // for the stores before it and one that does not, a source inside the match just before and inside the sequence's
+    // own literal run, a literal run copied by one lane and by all, a batch whose first match reads the last match of
+    // the batch before
+    C_MATCH_WAIT, C_MATCH_NO_WAIT, C_MATCH_SRC_IN_PREV_MATCH, C_MATCH_SRC_OWN_LITERALS, C_LIT_SHORT, C_LIT_LONG,
+    C_BATCH_FOLLOWS_BATCH,
     C_NBITS
 };
 
@@ -604,6 +612,9 @@ PBSZ_HD int decode_block(State &st, const uint8_t *b, uint32_t bs, uint8_t *dst,
             s_ml = br.read(st.ml_log);
             if (br.over) st.err = BAD_FRAME;
         }
+#ifdef PBSGPU_ZSTD_COVERAGE
+        uint32_t prev_end = 0, prev_ml = 0;
+#endif
         for (uint32_t done = 0; done < nseq;) {
             const uint32_t nb = nseq - done < (uint32_t)kBatch ? nseq - done : (uint32_t)kBatch;
             if (lane0 && !st.err) {  // the serial chain: states, extra bits, repeat offsets, and every bound
@@ -670,6 +681,8 @@ PBSZ_HD int decode_block(State &st, const uint8_t *b, uint32_t bs, uint8_t *dst,
             // literal runs: short ones one lane each, long ones by all lanes
             for (uint32_t k = (uint32_t)P::lane(); k < nb; k += (uint32_t)P::lanes()) {
                 const uint32_t ll = st.seq[k].ll;
+                PBSZ_COV_IF(ll > 0 && ll <= 16, C_LIT_SHORT);
+                PBSZ_COV_IF(ll > 16, C_LIT_LONG);
                 if (ll <= 16) {
                     uint8_t *d = dst + st.seq[k].out;
                     const uint8_t *s = litp + st.seq[k].lit;
@@ -686,10 +699,20 @@ PBSZ_HD int decode_block(State &st, const uint8_t *b, uint32_t bs, uint8_t *dst,
                 const uint32_t at = P::uni(st.seq[k].out + st.seq[k].ll);
                 const uint32_t ml = P::uni(st.seq[k].ml), off = P::uni(st.seq[k].off);
                 const uint32_t span = off < ml ? off : ml;
+                PBSZ_COV_IF(at - off + span > seen, C_MATCH_WAIT);
+                PBSZ_COV_IF(at - off + span <= seen, C_MATCH_NO_WAIT);
+                PBSZ_COV_IF(st.seq[k].ll > 0 && at - off + span > st.seq[k].out, C_MATCH_SRC_OWN_LITERALS);
+                // (prev_end: where the match before this one ended, in this batch or the one before; 0 = none in this block)
+                PBSZ_COV_IF(k > 0 && at - off < prev_end && at - off + span > prev_end - prev_ml, C_MATCH_SRC_IN_PREV_MATCH);
+                PBSZ_COV_IF(k == 0 && done > 0 && at - off < prev_end && at - off + span > prev_end - prev_ml, C_BATCH_FOLLOWS_BATCH);
                 if (at - off + span > seen) {
                     P::sync();
                     seen = at;
                 }
+#ifdef PBSGPU_ZSTD_COVERAGE
+                prev_end = at + ml;
+                prev_ml = ml;
+#endif
                 uint8_t *d = dst + at;
                 const uint8_t *s = d - off;
                 if (off >= ml)

@@ -27,7 +27,8 @@ BRANCHES = ("single_segment window_descriptor fcs_1 fcs_2 fcs_4 fcs_8 fcs_absent
             "huf_1stream huf_4stream_3 huf_4stream_4 huf_4stream_5 huf_treeless weights_direct weights_fse "
             "nseq_0 nseq_1 nseq_2 nseq_3 ll_predef ll_rle ll_fse ll_repeat of_predef of_rle of_fse of_repeat "
             "ml_predef ml_rle ml_fse ml_repeat rep_1 rep_2 rep_3 rep_shifted rep_1_minus_1 "
-            "match_overlap match_offset_1 match_across_blocks").split()
+            "match_overlap match_offset_1 match_across_blocks "
+            "match_wait match_no_wait match_src_in_prev_match match_src_own_literals lit_short lit_long batch_follows_batch").split()
 # branches that neither libzstd 1.4.8 nor a hand-assembled frame reaches: at most two, each explained in DESIGN.md §15
 UNREACHED = ()
 
