@@ -137,6 +137,13 @@ func (s *Stream) Finish() error                                              { r
 func (s *Stream) FinishBegin() error                                         { return ErrNotBuilt }
 func (s *Stream) Done() (bool, error)                                        { return false, ErrNotBuilt }
 func (s *Stream) Poll(int) ([]ChunkInfo, error)                              { return nil, ErrNotBuilt }
+func (s *Stream) Hold() error                                                { return ErrNotBuilt }
+func (s *Stream) Release(uint64) error                                       { return ErrNotBuilt }
+func (s *Stream) Held() (uint64, uint32, uint32, error)                      { return 0, 0, 0, ErrNotBuilt }
+func (s *Stream) UploadNew2(*KnownChunks, []ChunkInfo, bool, bool, unsafe.Pointer, uint64) (Uploaded2, error) {
+	return Uploaded2{}, ErrNotBuilt
+}
+func (s *Stream) Copy(uint64, uint64, unsafe.Pointer) error                  { return ErrNotBuilt }
 func (s *Stream) Close()                                                     {}
 
 func (c *Chunker) Scan([]byte) (int, error) { return 0, ErrNotBuilt }

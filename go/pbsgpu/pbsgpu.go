@@ -360,6 +360,26 @@ func ShouldReuse(idx []ChunkInfo, rangeStart, rangeEnd uint64, saved *ReuseChunk
 type Stream struct {
 	h   *C.pbsgpu_stream
 	eng *Engine // keeps the Go handle reachable while the stream lives
+	// OnBusy, for a stream that holds its pages (Hold): called when a call needs a page and only a Release can bring one.
+	// It polls, uploads and releases (Poll -> UploadNew2 -> Release); the call that met the full ring then goes on where
+	// it stood. With OnBusy nil such a call returns ErrBusy.
+	OnBusy func() error
+}
+
+// busy runs call until it no longer answers PBSGPU_E_BUSY, making room through OnBusy in between.
+func (s *Stream) busy(what string, call func() C.int) error {
+	for {
+		st := call()
+		if st != C.PBSGPU_E_BUSY {
+			return check(st, what)
+		}
+		if s.OnBusy == nil {
+			return ErrBusy
+		}
+		if err := s.OnBusy(); err != nil {
+			return err
+		}
+	}
 }
 
 func (e *Engine) NewStream(windowBytes uint64) (*Stream, error) {
@@ -379,9 +399,15 @@ func (s *Stream) Write(p []byte) (int, error) {
 	if len(p) == 0 {
 		return 0, nil
 	}
-	err := check(C.pbsgpu_stream_write(s.h, unsafe.Pointer(&p[0]), C.size_t(len(p))), "stream_write")
+	var w0, w1 C.uint64_t
+	C.pbsgpu_stream_bytes_written(s.h, &w0)
+	st := C.pbsgpu_stream_write(s.h, unsafe.Pointer(&p[0]), C.size_t(len(p)))
 	runtime.KeepAlive(p)
-	if err != nil {
+	if st == C.PBSGPU_E_BUSY { // a holding stream whose ring is full: a prefix was taken (io.Writer's n); Release, write the rest
+		C.pbsgpu_stream_bytes_written(s.h, &w1)
+		return int(w1 - w0), ErrBusy
+	}
+	if err := check(st, "stream_write"); err != nil {
 		return 0, err
 	}
 	return len(p), nil
@@ -395,7 +421,7 @@ func (s *Stream) ReadFrom(r io.Reader) (int64, error) {
 	for {
 		var buf unsafe.Pointer
 		var capacity C.size_t
-		if err := check(C.pbsgpu_stream_reserve(s.h, &buf, &capacity), "stream_reserve"); err != nil {
+		if err := s.busy("stream_reserve", func() C.int { return C.pbsgpu_stream_reserve(s.h, &buf, &capacity) }); err != nil {
 			return total, err
 		}
 		if capacity == 0 { // inside an entry whose announced size has been reached
@@ -403,10 +429,13 @@ func (s *Stream) ReadFrom(r io.Reader) (int64, error) {
 			return total, nil
 		}
 		n, rerr := io.ReadFull(r, unsafe.Slice((*byte)(buf), int(capacity)))
-		if err := check(C.pbsgpu_stream_commit(s.h, C.size_t(n)), "stream_commit"); err != nil {
+		if st := C.pbsgpu_stream_commit(s.h, C.size_t(n)); st == C.PBSGPU_E_BUSY {
+			total += int64(n) // a committed reservation is taken whole; the next reserve lands it once there is room
+		} else if err := check(st, "stream_commit"); err != nil {
 			return total, err
+		} else {
+			total += int64(n)
 		}
-		total += int64(n)
 		if rerr == io.EOF || rerr == io.ErrUnexpectedEOF {
 			return total, nil
 		}
@@ -423,7 +452,8 @@ func (s *Stream) ReadFrom(r io.Reader) (int64, error) {
 func (s *Stream) WriteEntryReader(r io.Reader, size uint64) (payloadOffset, fileIndex uint64, err error) {
 	defer runtime.KeepAlive(s) // the finalizer must not run Close while the C call is executing
 	var off, idx C.uint64_t
-	if err = check(C.pbsgpu_stream_begin_entry(s.h, nil, C.uint64_t(size), &off), "stream_begin_entry"); err != nil {
+	err = s.busy("stream_begin_entry", func() C.int { return C.pbsgpu_stream_begin_entry(s.h, nil, C.uint64_t(size), &off) })
+	if err != nil {
 		return 0, 0, err
 	}
 	n, err := s.ReadFrom(io.LimitReader(r, int64(size)))
@@ -476,13 +506,13 @@ func (s *Stream) WriteMarker(tail bool) error {
 	if tail {
 		t = 1
 	}
-	return check(C.pbsgpu_stream_write_marker(s.h, nil, t), "stream_write_marker")
+	return s.busy("stream_write_marker", func() C.int { return C.pbsgpu_stream_write_marker(s.h, nil, t) })
 }
 
 // Inject mirrors InjectChunks: forced cut, the payload position advances by the injected sizes.
 func (s *Stream) Inject(injectedBytes uint64) error {
 	defer runtime.KeepAlive(s) // the finalizer must not run Close while the C call is executing
-	return check(C.pbsgpu_stream_cut(s.h, C.uint64_t(injectedBytes)), "stream_cut")
+	return s.busy("stream_cut", func() C.int { return C.pbsgpu_stream_cut(s.h, C.uint64_t(injectedBytes)) })
 }
 
 // PayloadPosition is Encoder().PayloadPosition() (commit_reuse.go:265): written + injected bytes.
@@ -501,14 +531,14 @@ func (s *Stream) SuggestBoundary() error {
 
 func (s *Stream) Finish() error {
 	defer runtime.KeepAlive(s) // the finalizer must not run Close while the C call is executing
-	return check(C.pbsgpu_stream_finish(s.h), "stream_finish")
+	return s.busy("stream_finish", func() C.int { return C.pbsgpu_stream_finish(s.h) })
 }
 
 // FinishBegin closes the input without waiting for the last chunks' digests: the goroutine goes on with its next
 // archive while this one drains; Poll keeps delivering, Done reports when the last entry is out.
 func (s *Stream) FinishBegin() error {
 	defer runtime.KeepAlive(s)
-	return check(C.pbsgpu_stream_finish_begin(s.h), "stream_finish_begin")
+	return s.busy("stream_finish_begin", func() C.int { return C.pbsgpu_stream_finish_begin(s.h) })
 }
 
 // Done never blocks: true once every entry of a stream closed by Finish / FinishBegin can be polled.
@@ -532,6 +562,64 @@ func (s *Stream) Poll(max int) ([]ChunkInfo, error) {
 		return nil, err
 	}
 	return fromRecords(buf, int(n)), nil
+}
+
+// ---- held pages of a payload stream (PBSGPU_HAS_STREAM_UPLOAD) ------------------------------------------------------
+
+// Hold makes the stream keep its pages until Release: UploadNew2 then frames the new chunks of what Write was given
+// straight out of them, and the payload never leaves the device before it is known to be new. Only before the stream's
+// first byte, marker or cut. The writer's loop: Write -> Poll -> UploadNew2 -> upload the blobs -> Release(last End).
+// A call that needs a page calls OnBusy (or, without one, returns ErrBusy) instead of waiting for a page that only
+// Release can bring; no byte is lost
+// (Write reports the prefix it took; Inject, Finish, FinishBegin, WriteEntryReader's header and WriteMarker happen
+// entirely or not at all).
+func (s *Stream) Hold() error {
+	defer runtime.KeepAlive(s)
+	return check(C.pbsgpu_stream_hold(s.h), "stream_hold")
+}
+
+// Release says that the payload below position upto (at most the End of the last polled entry) is no longer needed.
+func (s *Stream) Release(upto uint64) error {
+	defer runtime.KeepAlive(s)
+	return check(C.pbsgpu_stream_release(s.h, C.uint64_t(upto)), "stream_release")
+}
+
+// Held returns the lowest payload position whose bytes are still available, the handed-back pages the stream holds and
+// the free pages of the engine's ring.
+func (s *Stream) Held() (firstPosition uint64, pages, ringPagesFree uint32, err error) {
+	defer runtime.KeepAlive(s)
+	var f C.uint64_t
+	var p, fr C.uint32_t
+	err = check(C.pbsgpu_stream_held(s.h, &f, &p, &fr), "stream_held")
+	return uint64(f), uint32(p), uint32(fr), err
+}
+
+// UploadNew2 is Ring.UploadNew2 for entries of this stream exactly as Poll returned them (End a payload position, Segment
+// the section number; a batch may span sections).
+func (s *Stream) UploadNew2(known *KnownChunks, recs []ChunkInfo, insert, zstd bool, dst unsafe.Pointer, dstCap uint64) (Uploaded2, error) {
+	defer runtime.KeepAlive(s)
+	defer runtime.KeepAlive(known)
+	if len(recs) == 0 || known == nil {
+		return Uploaded2{}, errors.New("pbsgpu: UploadNew2 needs entries and a known-chunk set")
+	}
+	cr := toRecords(recs)
+	o := newUpload2Out(len(recs))
+	ins := C.int(0)
+	if insert {
+		ins = 1
+	}
+	err := check(C.pbsgpu_stream_upload_new2_device(s.h, known.h, &cr[0], C.uint64_t(len(cr)), ins, encodeFlags(zstd), dst,
+		C.uint64_t(dstCap), &o.flags[0], (*C.uint64_t)(unsafe.Pointer(&o.offsets[0])), (*C.uint32_t)(unsafe.Pointer(&o.lens[0])),
+		(*C.uint8_t)(unsafe.Pointer(&o.kinds[0])), (*C.uint32_t)(unsafe.Pointer(&o.crcs[0])), &o.used, &o.st, &o.enc),
+		"stream_upload_new2_device")
+	return o.result(), err
+}
+
+// Copy writes the raw payload bytes [position, position + length) into device memory dst; the range lies in one section,
+// is covered by polled entries and no Release has passed it.
+func (s *Stream) Copy(position, length uint64, dst unsafe.Pointer) error {
+	defer runtime.KeepAlive(s)
+	return check(C.pbsgpu_stream_copy_device(s.h, C.uint64_t(position), C.uint64_t(length), dst), "stream_copy_device")
 }
 
 func (s *Stream) Close() {

@@ -508,6 +508,54 @@ int pbsgpu_ring_blob_encode_device(pbsgpu_ring *ring, uint32_t stream, const pbs
  * pbsgpu_ring_held reports (PBSGPU_E_STATE otherwise). */
 int pbsgpu_ring_copy_device(pbsgpu_ring *ring, uint32_t stream, uint64_t offset, uint64_t length, void *dst);
 
+/* ---- held pages of a payload stream: frame the new chunks of what pbsgpu_stream_write was given ------------------------
+ * A payload stream (pbsgpu_stream_*, above) is a client of the engine's own page ring, and a page of that ring is free the
+ * moment the SHA-256 services have read it: a writer whose bytes came from an io.Reader has nothing left to upload once
+ * poll and classify call a chunk new. A stream that HOLDS keeps its pages, like a stream of a PBSGPU_RING_F_HOLD_PAGES
+ * ring, until it releases them:
+ *   hold -> { write -> poll -> pbsgpu_stream_upload_new2_device -> upload the blobs -> pbsgpu_stream_release(last end) }
+ * Positions are payload positions — written plus injected bytes, the coordinates of pbsgpu_stream_position and of the
+ * polled records' `end`. The switch is per stream; the engine's other streams are not affected, their pages go back the
+ * moment the services hand them back, in the same order as before. On a stream that never called pbsgpu_stream_hold the
+ * other four calls return PBSGPU_E_STATE and change nothing.
+ * NEVER WAIT FOR YOURSELF. A stream call that needs a page waits, pumping, until the ring has one. A holding stream does
+ * not wait for a page that only a release can bring: when the ring has no free page and no page still with the services
+ * will become free as they hand it back (such a page belongs to a stream that does not hold, or lies below its stream's
+ * watermark), the call returns PBSGPU_E_BUSY instead. That status is not sticky and no byte is lost:
+ * pbsgpu_stream_write may have taken a prefix (pbsgpu_stream_bytes_written says how much; pass the rest again after a
+ * release); a committed reservation is library memory and is taken whole; cut, finish, finish_begin, begin_entry,
+ * end_entry and write_marker happen entirely or not at all. The arena (pbsgpu_engine_options::stream_ring_gib) must hold
+ * what lies between two releases, plus what is in flight. Same thread rule as every pbsgpu_stream_* call. */
+#define PBSGPU_HAS_STREAM_UPLOAD 1
+struct pbsgpu_known;
+struct pbsgpu_dedup_stats;
+struct pbsgpu_encode_stats;
+/* Only before the stream's first byte, marker or cut (PBSGPU_E_STATE later). A recycled stream context starts not
+ * holding. Destroying a holding stream gives everything back. */
+int pbsgpu_stream_hold(pbsgpu_stream *s);
+/* The caller is done with the payload below position `upto`: every page wholly below it goes back to the ring, at once or
+ * the moment the services hand it back. The watermark only moves forward (a lower value is a no-op) and may not pass the
+ * `end` of the last record pbsgpu_stream_poll has handed out (PBSGPU_E_INVALID). A position inside an injected gap counts
+ * as the end of the section in front of it. A section that lies wholly below the watermark gives back its ring slot and
+ * every page, its short last page included. */
+int pbsgpu_stream_release(pbsgpu_stream *s, uint64_t upto);
+/* *first_position: the lowest position whose bytes are still available; *pages_held: handed-back pages the stream is
+ * holding; *ring_pages_free (may be NULL): free pages of the engine's ring. */
+int pbsgpu_stream_held(pbsgpu_stream *s, uint64_t *first_position, uint32_t *pages_held, uint32_t *ring_pages_free);
+/* pbsgpu_ring_upload_new2_device (below: the fused calls) for records of this stream, word for word: flags 0 or
+ * PBSGPU_ENCODE_F_ZSTD, the slots of the uncompressed layout, the verdict rule, PBSGPU_E_CAPACITY leaving dst and the set
+ * untouched, the sizing call (dst = NULL, dst_cap = 0), one lease and one synchronisation. recs exactly as
+ * pbsgpu_stream_poll returned them (`end` a payload position, `segment` the section number); a batch may span sections.
+ * PBSGPU_E_STATE, nothing written: a record begins below *first_position or has not been polled yet. PBSGPU_E_INVALID: an
+ * unknown section, or size > end - base of its section. The engine's other streams keep writing while the call runs. */
+int pbsgpu_stream_upload_new2_device(pbsgpu_stream *s, struct pbsgpu_known *known, const pbsgpu_record *recs, uint64_t n,
+                                     int insert, uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *known_out,
+                                     uint64_t *blob_off, uint32_t *lens, uint8_t *kinds, uint32_t *crcs, uint64_t *used,
+                                     struct pbsgpu_dedup_stats *stats, struct pbsgpu_encode_stats *enc_stats);
+/* The raw bytes [position, position + length) into device memory dst. The range must lie in one section, be covered by
+ * polled records and begin at or above *first_position (PBSGPU_E_STATE otherwise: an injected gap has no bytes). */
+int pbsgpu_stream_copy_device(pbsgpu_stream *s, uint64_t position, uint64_t length, void *dst);
+
 /* ---- whole-stream SHA-256 batch ---------------------------------------------
  * verification.HashFile (internal/agent/verification/handler.go:36-68) and
  * extractFileHash (internal/server/verification/job.go:1273-1303) for many

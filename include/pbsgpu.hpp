@@ -667,6 +667,55 @@ class PayloadWriter {
         return r;
     }
 
+    // ---- held pages (PBSGPU_HAS_STREAM_UPLOAD) ----
+    // Hold: the writer keeps its pages until Release, so that UploadNewChunks can frame the new chunks of what it was given
+    // straight out of them. Only before the first byte, marker or cut. The loop: WriteEntry... -> TakePolled -> UploadNewChunks
+    // -> upload the blobs -> Release(last end). A call that needs a page then fails with PBSGPU_E_BUSY ("busy") instead of
+    // waiting for a page only Release can bring; no byte is lost (WriteEntry: BytesWritten() names the prefix taken).
+    std::string Hold() {
+        const int st = pbsgpu_stream_hold(s_);
+        if (st == PBSGPU_OK) holding_ = true;
+        return st == PBSGPU_OK ? std::string() : errorf("stream hold", st);
+    }
+    // the entries delivered to the sink since the last call, as pbsgpu_stream_poll returned them (a holding writer only)
+    std::vector<pbsgpu_record> TakePolled() {
+        std::vector<pbsgpu_record> out;
+        out.swap(polled_);
+        return out;
+    }
+    uint64_t BytesWritten() const {
+        uint64_t n = 0;
+        pbsgpu_stream_bytes_written(s_, &n);
+        return n;
+    }
+    // PageRing's fused call with the blob's kind decided on the device, for entries of this writer as TakePolled returned them
+    Result<datastore::Uploaded2> UploadNewChunks(datastore::KnownChunks &known, const std::vector<pbsgpu_record> &recs, bool insert,
+                                            bool zstd, void *dst, uint64_t dstCap) {
+        Result<datastore::Uploaded2> r;
+        datastore::Uploaded2 &v = r.value;
+        v.Resize(recs.size());
+        const int st = pbsgpu_stream_upload_new2_device(s_, known.Handle(), recs.data(), recs.size(), insert ? 1 : 0,
+                                                        zstd ? PBSGPU_ENCODE_F_ZSTD : 0u, dst, dstCap, v.known.data(),
+                                                        v.offsets.data(), v.lens.data(), v.kinds.data(), v.crcs.data(), &v.bytes,
+                                                        &v.stats, &v.encoded);
+        if (st != PBSGPU_OK) r.err = errorf("stream upload new2", st);
+        return r;
+    }
+    // the payload below position `upto` (at most the end of the last delivered entry) is no longer needed
+    std::string Release(uint64_t upto) {
+        const int st = pbsgpu_stream_release(s_, upto);
+        return st == PBSGPU_OK ? std::string() : errorf("stream release", st);
+    }
+    std::string Held(uint64_t *firstPosition, uint32_t *pagesHeld, uint32_t *ringPagesFree = nullptr) {
+        const int st = pbsgpu_stream_held(s_, firstPosition, pagesHeld, ringPagesFree);
+        return st == PBSGPU_OK ? std::string() : errorf("stream held", st);
+    }
+    // the raw payload bytes [position, position + length) into device buffer dst
+    std::string Copy(uint64_t position, uint64_t length, void *dst) {
+        const int st = pbsgpu_stream_copy_device(s_, position, length, dst);
+        return st == PBSGPU_OK ? std::string() : errorf("stream copy", st);
+    }
+
   private:
     PayloadWriter(std::shared_ptr<Engine> e, pbsgpu_stream *s, Sink sink) : eng_(std::move(e)), s_(s), sink_(std::move(sink)) {}
     std::string drain() {
@@ -681,12 +730,15 @@ class PayloadWriter {
                 std::memcpy(ci.Digest_.data(), buf[i].digest, 32);
                 sink_(ci, buf[i].size);
             }
+            if (holding_) polled_.insert(polled_.end(), buf, buf + n);
             if (n < 256) return {};
         }
     }
     std::shared_ptr<Engine> eng_;
     pbsgpu_stream *s_;
     Sink sink_;
+    bool holding_ = false;
+    std::vector<pbsgpu_record> polled_;
 };
 
 // Several archives at once on bytes that are (or arrive) in device memory: the page ring (pbsgpu_ring_*). One writer

@@ -217,6 +217,12 @@ SYMBOLS = {
     "pbsgpu_stream_position": (C.c_int, [_P, _U64P]),
     "pbsgpu_stream_bytes_written": (C.c_int, [_P, _U64P]),
     "pbsgpu_stream_suggest": (C.c_int, [_P, C.c_uint64]),
+    "pbsgpu_stream_hold": (C.c_int, [_P]),
+    "pbsgpu_stream_release": (C.c_int, [_P, C.c_uint64]),
+    "pbsgpu_stream_held": (C.c_int, [_P, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pbsgpu_stream_upload_new2_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P,
+                                                   _U64P, C.POINTER(DedupStats), C.POINTER(EncodeStats)]),
+    "pbsgpu_stream_copy_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
     "pbsgpu_stream_begin_file": (C.c_int, [_P]),
     "pbsgpu_stream_end_file": (C.c_int, [_P, _U64P]),
     "pbsgpu_stream_poll_files": (C.c_int, [_P, _P, C.c_uint64, _U64P]),

@@ -1,8 +1,10 @@
 // Held pages of a page ring created with PBSGPU_RING_F_HOLD_PAGES (ring.cpp): which stream and logical
 // page every physical page carries, which pages the services have handed back, and each stream's release watermark.
 // A page returns to the free list when BOTH hold: the services have handed it back, and it lies wholly below its
-// stream's watermark (or the stream was closed). Host-only, no HIP: tests/test_ring_upload_surface.py drives it against
-// a model.
+// stream's watermark (or the stream was closed). On the engine's ring streams that hold share the pages
+// with streams that do not: the latter's pages are nobody's (`unowned`) and free at hand-back, and
+// `frees_without_release` says whether a holder that waits for a page waits for itself. Host-only, no HIP:
+// tests/test_ring_upload_surface.py and tests/native/test_hold_streams.cpp drive it against models.
 #pragma once
 
 #include <cstdint>
@@ -16,6 +18,7 @@ public:
     void init(uint32_t npages, uint32_t nstreams, uint64_t page_bytes) {
         page_ = page_bytes;
         owner_.assign(npages, Owner{});
+        out_.assign(npages, 0);
         streams_.assign(nstreams, Stream{});
     }
     // a new stream takes the slot
@@ -30,11 +33,18 @@ public:
         if (s.pages.empty()) s.base_k = k;
         s.pages.push_back(Page{phys, kOut});
         owner_[phys] = Owner{slot, s.gen, k, true};
+        out_[phys] = 1;
+    }
+    // the page was committed for a stream that does not hold: nobody's page, free the moment it is handed back
+    void unowned(uint32_t phys) {
+        owner_[phys].valid = false;
+        out_[phys] = 1;
     }
     // the services are done with the page: held, or free at once when it is already released
     void handed_back(uint32_t phys, std::vector<uint32_t> &free_pages) {
         const Owner o = owner_[phys];
         owner_[phys].valid = false;
+        out_[phys] = 0;
         if (!o.valid || streams_[o.slot].gen != o.gen) {  // no stream's page (any more: closed)
             free_pages.push_back(phys);
             return;
@@ -76,6 +86,17 @@ public:
     uint64_t first_offset(uint32_t slot) const { return streams_[slot].below * page_; }
     uint64_t watermark(uint32_t slot) const { return streams_[slot].mark; }
     uint32_t pages_held(uint32_t slot) const { return streams_[slot].held; }
+    // Can a page reach the free list without a release or a close? Only a page that is still with the services and that
+    // handed_back will free: nobody's (its stream does not hold, or was closed) or wholly below its stream's watermark.
+    // When this is false and the free list is empty, a holding stream that waits for a page waits for itself.
+    bool frees_without_release() const {
+        for (size_t p = 0; p < out_.size(); ++p) {
+            if (!out_[p]) continue;
+            const Owner &o = owner_[p];
+            if (!o.valid || streams_[o.slot].gen != o.gen || o.k < streams_[o.slot].below) return true;
+        }
+        return false;
+    }
     // physical page of an available logical page, -1 when it is released or was never committed
     int64_t phys_of(uint32_t slot, uint64_t k) const {
         const Stream &s = streams_[slot];
@@ -111,6 +132,7 @@ private:
     }
     uint64_t page_ = 1;
     std::vector<Owner> owner_;
+    std::vector<uint8_t> out_;  // per physical page: committed and not handed back yet
     std::vector<Stream> streams_;
 };
 

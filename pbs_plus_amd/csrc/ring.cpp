@@ -789,13 +789,28 @@ int ring_commit_dep(pbsgpu_ring *r, uint32_t stream, uint64_t nbytes, int final,
     q.valid = (uint32_t)nbytes;
     q.final = final != 0;
     q.dep = dep;
-    if (r->hold) r->held.assign(stream, q.k, q.phys);
+    if (r->hold) {
+        if (s.holding) r->held.assign(stream, q.k, q.phys);
+        else r->held.unowned(q.phys);  // (a section of a payload stream that does not hold: free at hand-back, as without the flag)
+    }
     s.ready.push_back(q);
     r->ready_bytes += nbytes;
     s.reserved = -1;
     s.bytes_committed += nbytes;
     if (final) s.final_committed = true;
     return PBSGPU_OK;
+}
+
+int ring_open_hold(pbsgpu_ring *r, uint32_t *stream, bool hold) {
+    CHK(pbsgpu_ring_open(r, stream));
+    r->slots[*stream].holding = hold;
+    return PBSGPU_OK;
+}
+
+bool ring_page_needs_release(pbsgpu_ring *r) {
+    if (!r->hold) return false;
+    ring_reap_free(r);
+    return r->free_pages.empty() && !r->held.frees_without_release();
 }
 
 int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool hold_engine_ref, pbsgpu_ring **out,
@@ -1260,20 +1275,17 @@ int pbsgpu_ring_blob_encode_device(pbsgpu_ring *r, uint32_t stream, const pbsgpu
 // logical page of that span. A page inside [first available offset, last polled end) is always there — pages go only
 // below the release watermark, and nothing beyond a polled record is uncommitted — so the two range checks per record
 // refuse what the per-record page lookup of pbsgpu_ring_blob_encode_device refuses; the lookup per page stays as the proof.
-int pbsgpu_ring_upload_new2_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
-                                   int insert, uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *known_out,
-                                   uint64_t *blob_off, uint32_t *lens, uint8_t *kinds, uint32_t *crcs, uint64_t *used,
-                                   pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc_stats) {
-    if (flags & ~PBSGPU_ENCODE_F_ZSTD) return PBSGPU_E_INVALID;
-    if (!r || !k || !used || !stats || (n && (!recs || !blob_off)) || n >= (1ull << 32)) return PBSGPU_E_INVALID;
-    if (!dst && dst_cap) return PBSGPU_E_INVALID;
-    if (!r->hold) return PBSGPU_E_STATE;
-    if (known_engine(k) != r->eng) return PBSGPU_E_INVALID;
+// ring_upload_plan is the host's part (the payload-stream writer runs it under the ring's lock and the device work without
+// it; stream.cpp).
+}  // extern "C"
+
+int pbse::ring_upload_plan(pbsgpu_ring *r, uint32_t stream, const pbsgpu_record *recs, uint64_t n, UploadPlan *plan) {
     struct Span {
         uint64_t lo = ~0ull, hi = 0;  // stream bytes [lo, hi) hold every chunk of the batch
     };
     std::vector<Span> span(r->slots.size());
-    UploadSrc us;
+    UploadSrc &us = plan->us;
+    std::vector<uint64_t> &tabs = plan->tabs;
     uint64_t first = 0, polled = 0;
     uint32_t cur = PBSGPU_RING_ANY_STREAM;
     for (uint64_t i = 0; i < n; ++i) {
@@ -1294,7 +1306,7 @@ int pbsgpu_ring_upload_new2_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t str
         us.pieces_max += ((rc.size + (1ull << kBlobPieceLog) - 1) >> kBlobPieceLog) + 1;  // (+1: a chunk in two pages)
     }
     if (us.pieces_max >= (1ull << 32)) return PBSGPU_E_INVALID;
-    std::vector<uint64_t> tabs(2 * span.size(), 0);  // PageTabs, then the pages
+    tabs.assign(2 * span.size(), 0);  // PageTabs, then the pages
     for (uint32_t sid = 0; sid < span.size(); ++sid) {
         if (span[sid].lo >= span[sid].hi) continue;
         const uint64_t k0 = span[sid].lo / r->page_bytes, k1 = (span[sid].hi - 1) / r->page_bytes;
@@ -1306,12 +1318,6 @@ int pbsgpu_ring_upload_new2_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t str
             tabs.push_back((uint64_t)phys * r->stride + 128u);
         }
     }
-    *used = 0;
-    std::memset(stats, 0, sizeof(*stats));
-    if (enc_stats) std::memset(enc_stats, 0, sizeof(*enc_stats));
-    if (n == 0) return PBSGPU_OK;
-    CHK(set_device(r->eng));
-    if (dst && !is_device_pointer(dst)) return PBSGPU_E_INVALID;
     ring_heartbeat(r);
     us.base = r->arena.as<uint8_t>();
     us.tabs = tabs.data();
@@ -1319,7 +1325,39 @@ int pbsgpu_ring_upload_new2_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t str
     us.nslots = (uint32_t)span.size();
     us.stream = stream;
     us.page_bytes = r->page_bytes;
-    return upload_new(k, us, recs, n, insert != 0, flags, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, lens,
+    return PBSGPU_OK;
+}
+
+int pbse::ring_copy_plan(pbsgpu_ring *r, uint32_t stream, uint64_t offset, uint64_t length, std::vector<SrcPart> *parts) {
+    if (offset + length > r->slots[stream].polled_end || offset < r->held.first_offset(stream)) return PBSGPU_E_STATE;
+    parts->assign((size_t)(length / r->page_bytes) + 2, SrcPart{});
+    uint32_t np = 0;
+    if (!ring_parts_of(r, stream, offset, length, parts->data(), (uint32_t)parts->size(), &np)) return PBSGPU_E_STATE;
+    parts->resize(np);
+    ring_heartbeat(r);
+    return PBSGPU_OK;
+}
+
+extern "C" {
+
+int pbsgpu_ring_upload_new2_device(pbsgpu_ring *r, pbsgpu_known *k, uint32_t stream, const pbsgpu_record *recs, uint64_t n,
+                                   int insert, uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *known_out,
+                                   uint64_t *blob_off, uint32_t *lens, uint8_t *kinds, uint32_t *crcs, uint64_t *used,
+                                   pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc_stats) {
+    if (flags & ~PBSGPU_ENCODE_F_ZSTD) return PBSGPU_E_INVALID;
+    if (!r || !k || !used || !stats || (n && (!recs || !blob_off)) || n >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (!dst && dst_cap) return PBSGPU_E_INVALID;
+    if (!r->hold) return PBSGPU_E_STATE;
+    if (known_engine(k) != r->eng) return PBSGPU_E_INVALID;
+    UploadPlan plan;
+    CHK(ring_upload_plan(r, stream, recs, n, &plan));
+    *used = 0;
+    std::memset(stats, 0, sizeof(*stats));
+    if (enc_stats) std::memset(enc_stats, 0, sizeof(*enc_stats));
+    if (n == 0) return PBSGPU_OK;
+    CHK(set_device(r->eng));
+    if (dst && !is_device_pointer(dst)) return PBSGPU_E_INVALID;
+    return upload_new(k, plan.us, recs, n, insert != 0, flags, static_cast<uint8_t *>(dst), dst_cap, known_out, blob_off, lens,
                       kinds, crcs, used, stats, enc_stats);
 }
 
@@ -1336,13 +1374,11 @@ int pbsgpu_ring_copy_device(pbsgpu_ring *r, uint32_t stream, uint64_t offset, ui
     if (stream >= r->slots.size() || !r->slots[stream].open || offset + length < offset) return PBSGPU_E_INVALID;
     if (offset + length > r->slots[stream].polled_end || offset < r->held.first_offset(stream)) return PBSGPU_E_STATE;
     if (length == 0) return PBSGPU_OK;
-    std::vector<SrcPart> parts((size_t)(length / r->page_bytes) + 2);
-    uint32_t np = 0;
-    if (!ring_parts_of(r, stream, offset, length, parts.data(), (uint32_t)parts.size(), &np)) return PBSGPU_E_STATE;
+    std::vector<SrcPart> parts;
+    CHK(ring_copy_plan(r, stream, offset, length, &parts));
     CHK(set_device(r->eng));
     if (!is_device_pointer(dst)) return PBSGPU_E_INVALID;
-    ring_heartbeat(r);
-    return copy_parts(r->eng, r->arena.as<uint8_t>(), parts.data(), np, static_cast<uint8_t *>(dst));
+    return copy_parts(r->eng, r->arena.as<uint8_t>(), parts.data(), (uint32_t)parts.size(), static_cast<uint8_t *>(dst));
 }
 
 int pbsgpu_ring_reserve(pbsgpu_ring *r, uint32_t stream, void **dptr, uint64_t *cap) {

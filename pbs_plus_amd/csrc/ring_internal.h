@@ -54,6 +54,7 @@ struct StreamSlot {
     uint64_t origin = 0;                  // payload position of the stream's byte 0 (absolute reader grid of suggested boundaries)
     std::deque<uint64_t> sugg;            // suggested boundaries still of interest (stream offsets, ascending)
     void *owner = nullptr;                // the stream writer's section that feeds this slot (stream.cpp)
+    bool holding = true;                  // on a PBSGPU_RING_F_HOLD_PAGES ring: its pages wait for a release (ring_open_hold)
 };
 
 struct RoundInfo {
@@ -229,5 +230,20 @@ struct UploadSrc {
 int upload_new(pbsgpu_known *k, const UploadSrc &src, const pbsgpu_record *recs, uint64_t n, bool insert, uint32_t flags,
                uint8_t *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off, uint32_t *lens, uint8_t *kinds,
                uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc);
+
+// ---- the engine's ring holds pages for the payload streams that ask for it (pbsgpu_stream_hold) ----
+// pbsgpu_ring_open with the choice: a stream opened with hold = false on a PBSGPU_RING_F_HOLD_PAGES ring gets no page
+// assignments — its pages are nobody's and go to the free list the moment the services hand them back
+int ring_open_hold(pbsgpu_ring *r, uint32_t *stream, bool hold);
+// no page is free and none can become free without a release (hold.h: frees_without_release): waiting would never end
+bool ring_page_needs_release(pbsgpu_ring *r);
+// The host's part of pbsgpu_ring_upload_new2_device / pbsgpu_ring_copy_device: the range checks and the page lookup. The
+// caller holds ring->mu for THIS and runs the device work without it (only its own release could free those pages).
+struct UploadPlan {
+    UploadSrc us;
+    std::vector<uint64_t> tabs;
+};
+int ring_upload_plan(pbsgpu_ring *r, uint32_t stream, const pbsgpu_record *recs, uint64_t n, UploadPlan *plan);
+int ring_copy_plan(pbsgpu_ring *r, uint32_t stream, uint64_t offset, uint64_t length, std::vector<SrcPart> *parts);
 
 }  // namespace pbse

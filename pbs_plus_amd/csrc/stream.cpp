@@ -121,6 +121,9 @@ void parallel_memcpy(void *dst, const void *src, size_t n) {
 //     a new one; records carry the section as `segment` and payload positions (written + injected) as `end`;
 //   * suggested boundaries in payload coordinates, forwarded to the section they fall into;
 //   * the per-file XXH3-64 tee and the pxar payload entry headers, run on a page's bytes before the page is committed;
+//   * held pages (pbsgpu_stream_hold): a stream that asks for it keeps its pages until it releases them, frames its new
+//     chunks out of them (pbsgpu_stream_upload_new2_device) and gets PBSGPU_E_BUSY, never a wait, for a page only its own
+//     release can bring;
 //   * records and file hashes are collected by WHICHEVER stream of the engine calls next (one lock per ring), so a writer
 //     that sits in a blocking read never holds up the others.
 namespace {
@@ -130,7 +133,10 @@ struct Section {                         // the bytes between two forced cuts = 
     uint32_t index = 0;                  // section number: the records' `segment`
     uint64_t base = 0;                   // payload position of its first byte
     bool input_closed = false;           // its last page has been committed
-    bool ring_done = false;              // the ring has delivered its last record (slot closed)
+    bool ring_done = false;              // the ring has delivered its last record (slot closed, unless the section holds pages)
+    bool hold = false;                   // a section of a holding stream: its slot stays open, with its pages, until it is released
+    bool released = false;               // ... and it has been, as a whole (pbsgpu_stream_release / destroy)
+    uint64_t len = 0;                    // bytes committed to it so far
     std::deque<pbsgpu_record> recs;      // filled under ring->mu by whoever drains the ring
 };
 
@@ -186,6 +192,13 @@ struct pbsgpu_stream {
     std::deque<uint64_t> suggested;      // announced boundaries (payload positions, ascending) not yet behind the stream
     size_t sugg_fwd = 0;                 // how many of them the current section's ring stream already knows
     std::deque<pbsgpu_record> out;
+    // held pages (pbsgpu_stream_hold)
+    bool hold = false;
+    std::deque<std::unique_ptr<Section>> kept;  // sections whose records are all in `out` (or polled) and that still hold pages
+    uint64_t polled_end = 0;             // `end` of the last record pbsgpu_stream_poll handed out
+    uint64_t mark = 0;                   // release watermark (payload position)
+    int pend_k = 0;                      // a staged piece the ring had no page for (PBSGPU_E_BUSY): stage[pend_k][pend_off, pend_n)
+    size_t pend_off = 0, pend_n = 0;     // ... still has to land, before any other byte
     // per-file XXH3-64 tee
     std::deque<FileSpan> files;          // files not yet completely hashed, in stream order
     uint64_t next_file = 0;
@@ -244,6 +257,9 @@ int engine_ring_get(pbsgpu_engine *e, pbsgpu_ring **out) {
         // host-fed pages trickle in (3 per millisecond at 50 GiB/s) and a round is three launches: cut every 8 pages instead of
         // waiting for a quarter of a full round (64 pages = 20 ms more latency for every chunk, and for the archive's drain)
         o.min_round_pages = 8;
+        // with the held-pages bookkeeping: a stream that asks for it (pbsgpu_stream_hold) keeps its pages until it releases
+        // them; the pages of every other stream are nobody's and free at hand-back, as without the flag
+        o.flags |= PBSGPU_RING_F_HOLD_PAGES;
         pbsgpu_ring *r = nullptr;
         // ... for every chunk of at least half the maximum size: what an archive waits for at its end is then a 16 MiB chunk on
         // an express pair (0.36 s) rather than a 13 MiB one on a pair lane (0.40 s); 23 % of 50 GiB/s keep 4-5 express CUs busy
@@ -276,6 +292,7 @@ int ring_drain(pbsgpu_ring *r) {
         }
         if (sl.final_done && sl.cells.empty()) {
             if (sec) sec->ring_done = true;
+            if (sec && sec->hold && !sec->released) continue;  // its pages are still wanted: the release closes the slot
             sl.owner = nullptr;
             (void)pbsgpu_ring_close(r, si);
         }
@@ -297,6 +314,7 @@ void stream_collect(pbsgpu_stream *s) {
         sec->recs.clear();
         if (!sec->ring_done) break;  // records come out in stream order: later sections wait
         if (sec == s->cur) s->cur = nullptr;
+        if (sec->hold && !sec->released) s->kept.push_back(std::move(s->sections.front()));  // reachable by number while it holds pages
         s->sections.pop_front();
     }
 }
@@ -413,6 +431,15 @@ int stream_enqueue_tee(pbsgpu_stream *s, const uint8_t *base, uint64_t w0, uint6
 }
 
 // ---- pages -------------------------------------------------------------------------------------------------------------------
+// ring->mu held: every slot of the ring is kept open by a section that waits for its stream's release
+bool stream_slots_need_release(pbsgpu_ring *r) {
+    for (auto &sl : r->slots) {
+        const Section *sec = static_cast<const Section *>(sl.owner);
+        if (!sl.open || !sec || !sec->hold || sec->released) return false;
+    }
+    return true;
+}
+
 // a page to write into: opens the section's ring stream at its first byte; waits (pumping) while the ring has no page or
 // no stream slot free — back-pressure: the ingest outruns the SHA-256 service
 int stream_acquire_page(pbsgpu_stream *s) {
@@ -428,11 +455,12 @@ int stream_acquire_page(pbsgpu_stream *s) {
             bool ok = true;
             if (!s->cur) {
                 uint32_t rid = 0;
-                const int so = pbsgpu_ring_open(r, &rid);
+                const int so = ring_open_hold(r, &rid, s->hold);
                 if (so == PBSGPU_OK) {
                     std::unique_ptr<Section> sec(new (std::nothrow) Section());
                     if (!sec) return PBSGPU_E_NOMEM;
                     sec->rid = rid;
+                    sec->hold = s->hold;
                     sec->index = s->section_index;
                     sec->base = s->landed + s->inject_total;  // payload position of the next byte to land
                     r->slots[rid].owner = sec.get();
@@ -442,6 +470,7 @@ int stream_acquire_page(pbsgpu_stream *s) {
                     s->sugg_fwd = 0;
                 } else if (so == PBSGPU_E_BUSY) {
                     ok = false;  // every slot is taken by sections that are still being hashed
+                    if (s->hold && stream_slots_need_release(r)) return PBSGPU_E_BUSY;  // ... or all wait for a release: not sticky
                 } else {
                     return so;
                 }
@@ -460,6 +489,8 @@ int stream_acquire_page(pbsgpu_stream *s) {
                     return PBSGPU_OK;
                 }
                 if (sr != PBSGPU_E_BUSY) return s->error = sr;
+                // Never wait for yourself: no page is free and none comes back without a release. Not sticky, nothing is lost.
+                if (s->hold && ring_page_needs_release(r)) return PBSGPU_E_BUSY;
             }
         }
         (void)stream_harvest_tees(s, false);
@@ -523,6 +554,7 @@ int stream_commit_page(pbsgpu_stream *s, bool final) {
     const int st = ring_commit_dep(r, s->cur->rid, bytes ? s->page_fill : 0, final ? 1 : 0, bytes ? dep : nullptr);
     if (!bytes && dep) ring_event_put(r, dep);
     if (st != PBSGPU_OK) return s->error = st;
+    s->cur->len = r->slots[s->cur->rid].bytes_committed;
     s->have_page = false;
     s->page_fill = 0;
     if (final) {
@@ -537,13 +569,22 @@ int stream_commit_page(pbsgpu_stream *s, bool final) {
 
 // H2D of one staged piece of n bytes (stage[k][0..n)) into the stream's pages. `written` was advanced when the bytes were
 // accepted.
-int stream_push_piece(pbsgpu_stream *s, int k, size_t n) {
+// A holding stream may find the ring without a page that anything but its own release could free (PBSGPU_E_BUSY): the rest
+// of the piece stays in its staging buffer as the stream's PENDING piece, and the next call that moves bytes lands it first.
+int stream_land_pending(pbsgpu_stream *s) {
     pbsgpu_engine *e = s->eng;
+    const int k = s->pend_k;
+    const size_t n = s->pend_n;
     const uint8_t *src = s->stage[k].as<uint8_t>();
-    size_t off = 0;
-    s->stage_idx = (k + 1) % kStreamStages;
+    size_t off = s->pend_off;
     while (off < n) {
-        if (!s->have_page) CHK(stream_acquire_page(s));
+        if (!s->have_page) {
+            const int st = stream_acquire_page(s);
+            if (st != PBSGPU_OK) {
+                s->pend_off = off;
+                return st;
+            }
+        }
         const size_t m = (size_t)std::min<uint64_t>(n - off, s->page_cap - s->page_fill);
         hipStream_t cs = e->copy_streams[(size_t)s->page_cs];
         HIPCHK(hipMemcpyAsync(s->page_ptr + s->page_fill, src + off, m, hipMemcpyHostToDevice, cs));
@@ -552,13 +593,24 @@ int stream_push_piece(pbsgpu_stream *s, int k, size_t n) {
         s->page_fill += m;
         s->landed += m;
         off += m;
+        s->pend_off = off;
         if (s->page_fill == s->page_cap) CHK(stream_commit_page(s, false));
     }
+    s->pend_n = s->pend_off = 0;
     return PBSGPU_OK;
+}
+
+int stream_push_piece(pbsgpu_stream *s, int k, size_t n) {
+    s->stage_idx = (k + 1) % kStreamStages;
+    s->pend_k = k;
+    s->pend_off = 0;
+    s->pend_n = n;
+    return stream_land_pending(s);
 }
 
 // push whatever small writes have gathered in the current staging buffer (before a cut / finish / reserve)
 int stream_push_staged(pbsgpu_stream *s) {
+    if (s->pend_n) CHK(stream_land_pending(s));  // (an earlier piece the ring had no page for goes first)
     if (s->stage_fill == 0) return PBSGPU_OK;
     const size_t n = s->stage_fill;
     s->stage_fill = 0;
@@ -607,6 +659,67 @@ int stream_drain(pbsgpu_stream *s) {
     CHK(stream_harvest_tees(s, true));
     stream_maybe_park(s);
     return PBSGPU_OK;
+}
+
+// ---- held pages (pbsgpu_stream_hold) ---------------------------------------------------------------------------
+// ring->mu held: the section's pages are no longer wanted; its slot closes now when the ring is done with it, else when
+// it is (ring_drain)
+void section_release_whole(pbsgpu_stream *s, Section *sec) {
+    pbsgpu_ring *r = s->ring;
+    if (sec->released) return;
+    sec->released = true;
+    if (sec->rid >= r->slots.size() || r->slots[sec->rid].owner != sec) return;
+    r->held.release(sec->rid, ~0ull, r->free_pages);  // (pages still with the services go as they are handed back)
+    if (sec->ring_done) {
+        r->slots[sec->rid].owner = nullptr;
+        (void)pbsgpu_ring_close(r, sec->rid);
+    }
+}
+
+// ring->mu held
+void stream_release_all(pbsgpu_stream *s) {
+    for (auto &sec : s->kept) section_release_whole(s, sec.get());
+    s->kept.clear();
+    for (auto &sec : s->sections)
+        if (sec->hold) section_release_whole(s, sec.get());
+}
+
+// ring->mu held: the watermark moves to `upto` (payload position, <= polled_end)
+void stream_release_upto(pbsgpu_stream *s, uint64_t upto) {
+    pbsgpu_ring *r = s->ring;
+    if (upto <= s->mark) return;
+    s->mark = upto;
+    auto one = [&](Section *sec) {  // true: the section is gone as a whole
+        if (sec->released) return true;
+        if (upto <= sec->base) return false;
+        // a section whose input is closed ends at base + len: a position in the injected gap behind it counts as its end
+        if ((sec->input_closed || sec->ring_done) && upto - sec->base >= sec->len) {
+            section_release_whole(s, sec);
+            return true;
+        }
+        r->held.release(sec->rid, std::min(upto - sec->base, r->slots[sec->rid].polled_end), r->free_pages);
+        return false;
+    };
+    while (!s->kept.empty() && one(s->kept.front().get())) s->kept.pop_front();
+    for (auto &sec : s->sections)
+        if (!one(sec.get())) break;
+}
+
+// the section with this number among those that still hold pages (few: a linear walk)
+Section *stream_section(pbsgpu_stream *s, uint32_t index) {
+    for (auto &sec : s->kept)
+        if (sec->index == index) return sec->released ? nullptr : sec.get();
+    for (auto &sec : s->sections)
+        if (sec->index == index) return sec->released ? nullptr : sec.get();
+    return nullptr;
+}
+
+// ring->mu held: lowest payload position whose bytes are still available
+uint64_t stream_first_position(pbsgpu_stream *s) {
+    for (auto *list : {&s->kept, &s->sections})
+        for (auto &sec : *list)
+            if (!sec->released) return sec->base + s->ring->held.first_offset(sec->rid);
+    return s->landed + s->inject_total;  // nothing is: what lands next will be
 }
 
 }  // namespace
@@ -729,6 +842,11 @@ static void stream_reset_state(pbsgpu_stream *s) {
     s->suggested.clear();
     s->sugg_fwd = 0;
     s->out.clear();
+    s->hold = false;
+    s->kept.clear();
+    s->polled_end = s->mark = 0;
+    s->pend_k = 0;
+    s->pend_off = s->pend_n = 0;
     s->files.clear();
     s->next_file = 0;
     s->n_stateful = 0;
@@ -800,6 +918,13 @@ void pbsgpu_stream_destroy(pbsgpu_stream *s) {
     if (e) {
         (void)hipSetDevice(e->device);
         bool healthy = s->error == PBSGPU_OK;
+        if (s->ring && s->hold) {
+            // a holding stream gives everything back: what it still holds now, what the services still have as they hand it
+            // back. Bytes the ring had no page for are dropped — nobody will read their records.
+            if (!s->finished) s->pend_n = s->pend_off = s->stage_fill = 0;
+            std::lock_guard<std::mutex> lk(s->ring->mu);
+            stream_release_all(s);
+        }
         if (s->ring) {
             // An unfinished stream still has to END its ring streams (their pages and slots only come back through a final
             // round), and every section has to hand out its last record before its slot is free: the same wait as finish.
@@ -845,6 +970,7 @@ int pbsgpu_stream_write(pbsgpu_stream *s, const void *data, size_t len) {
     if (s->error != PBSGPU_OK) return s->error;
     if (s->in_entry && len > s->entry_left) return PBSGPU_E_INVALID;  // more bytes than the entry header announced
     if (len) CHK(set_device(s->eng));
+    if (len && s->pend_n) CHK(stream_land_pending(s));  // (PBSGPU_E_BUSY again: nothing of this call was taken)
     const uint8_t *p = static_cast<const uint8_t *>(data);
     while (len) {
         // caller bytes -> library-owned pinned staging -> device page (async). Writes are COALESCED in the staging
@@ -947,6 +1073,13 @@ static int stream_write_header(pbsgpu_stream *s, uint64_t type, uint64_t full_si
         h[i] = (uint8_t)(type >> (8 * i));
         h[8 + i] = (uint8_t)(full_size >> (8 * i));
     }
+    if (s->hold && s->error == PBSGPU_OK && !s->finished && s->reserved < 0) {
+        // a holding stream's push can end in PBSGPU_E_BUSY: push BEFORE the header when the header would fill the staging
+        // buffer, so that the header (and with it begin_entry / write_marker) happens entirely or not at all
+        CHK(set_device(s->eng));
+        if (s->pend_n) CHK(stream_land_pending(s));
+        if (kStreamStage - s->stage_fill <= 16) CHK(stream_push_staged(s));
+    }
     return pbsgpu_stream_write(s, h, 16);
 }
 
@@ -1043,6 +1176,7 @@ int pbsgpu_stream_poll(pbsgpu_stream *s, pbsgpu_record *out, uint64_t cap, uint6
         out[k++] = s->out.front();
         s->out.pop_front();
     }
+    if (k) s->polled_end = out[k - 1].end;
     *n = k;
     return (k == 0) ? st : PBSGPU_OK;  // what was cut before a failure is still delivered; the error follows
 }
@@ -1060,6 +1194,104 @@ int pbsgpu_stream_bytes_written(const pbsgpu_stream *s, uint64_t *bytes_written)
     if (!s || !bytes_written) return PBSGPU_E_INVALID;
     *bytes_written = s->written;
     return PBSGPU_OK;
+}
+
+// ---- held pages: the stream keeps its pages until it releases them, and frames its new chunks from them ----
+int pbsgpu_stream_hold(pbsgpu_stream *s) {
+    if (!s) return PBSGPU_E_INVALID;
+    if (s->hold) return PBSGPU_OK;
+    // before the first byte, marker or cut: every section of the stream holds, or none does
+    if (s->written || s->inject_total || s->section_index || s->finished || s->reserved >= 0 || s->file_open || s->cur ||
+        !s->sections.empty())
+        return PBSGPU_E_STATE;
+    if (s->error != PBSGPU_OK) return s->error;
+    s->hold = true;
+    return PBSGPU_OK;
+}
+
+int pbsgpu_stream_release(pbsgpu_stream *s, uint64_t upto) {
+    if (!s) return PBSGPU_E_INVALID;
+    if (!s->hold) return PBSGPU_E_STATE;
+    if (upto > s->polled_end) return PBSGPU_E_INVALID;  // only what poll has handed out can be done with
+    std::lock_guard<std::mutex> lk(s->ring->mu);
+    stream_release_upto(s, upto);
+    return PBSGPU_OK;
+}
+
+int pbsgpu_stream_held(pbsgpu_stream *s, uint64_t *first_position, uint32_t *pages_held, uint32_t *ring_pages_free) {
+    if (!s || !first_position || !pages_held) return PBSGPU_E_INVALID;
+    if (!s->hold) return PBSGPU_E_STATE;
+    pbsgpu_ring *r = s->ring;
+    std::lock_guard<std::mutex> lk(r->mu);
+    (void)ring_page_needs_release(r);  // (takes in what the services have handed back)
+    uint32_t held = 0;
+    for (auto *list : {&s->kept, &s->sections})
+        for (auto &sec : *list)
+            if (!sec->released) held += r->held.pages_held(sec->rid);
+    *first_position = stream_first_position(s);
+    *pages_held = held;
+    if (ring_pages_free) *ring_pages_free = (uint32_t)r->free_pages.size();
+    return PBSGPU_OK;
+}
+
+int pbsgpu_stream_upload_new2_device(pbsgpu_stream *s, pbsgpu_known *known, const pbsgpu_record *recs, uint64_t n, int insert,
+                                     uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *known_out, uint64_t *blob_off,
+                                     uint32_t *lens, uint8_t *kinds, uint32_t *crcs, uint64_t *used, pbsgpu_dedup_stats *stats,
+                                     pbsgpu_encode_stats *enc_stats) {
+    if (flags & ~PBSGPU_ENCODE_F_ZSTD) return PBSGPU_E_INVALID;
+    if (!s || !known || !used || !stats || (n && (!recs || !blob_off)) || n >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (!dst && dst_cap) return PBSGPU_E_INVALID;
+    if (!s->hold) return PBSGPU_E_STATE;
+    if (known_engine(known) != s->eng) return PBSGPU_E_INVALID;
+    pbsgpu_ring *r = s->ring;
+    std::vector<pbsgpu_record> local(recs, recs + n);  // ring coordinates: end from the section's first byte, segment = its slot
+    UploadPlan plan;
+    {
+        std::lock_guard<std::mutex> lk(r->mu);
+        const uint64_t first = stream_first_position(s);
+        Section *sec = nullptr;
+        for (uint64_t i = 0; i < n; ++i) {
+            pbsgpu_record &rc = local[(size_t)i];
+            if (rc.size > rc.end) return PBSGPU_E_INVALID;
+            if (rc.end - rc.size < first || rc.end > s->polled_end) return PBSGPU_E_STATE;  // released, or not polled yet
+            if (!sec || sec->index != rc.segment) sec = stream_section(s, rc.segment);
+            if (!sec || rc.end < sec->base || rc.size > rc.end - sec->base) return PBSGPU_E_INVALID;
+            rc.end -= sec->base;
+            rc.segment = sec->rid;
+        }
+        CHK(ring_upload_plan(r, PBSGPU_RING_ANY_STREAM, local.data(), n, &plan));
+    }
+    *used = 0;
+    std::memset(stats, 0, sizeof(*stats));
+    if (enc_stats) std::memset(enc_stats, 0, sizeof(*enc_stats));
+    if (n == 0) return PBSGPU_OK;
+    CHK(set_device(s->eng));
+    if (dst && !is_device_pointer(dst)) return PBSGPU_E_INVALID;
+    // the device work and its synchronisation run WITHOUT the ring's lock — the engine's other streams keep writing: only
+    // this stream's own release could free the pages of the plan, and a stream has one thread
+    return upload_new(known, plan.us, local.data(), n, insert != 0, flags, static_cast<uint8_t *>(dst), dst_cap, known_out,
+                      blob_off, lens, kinds, crcs, used, stats, enc_stats);
+}
+
+int pbsgpu_stream_copy_device(pbsgpu_stream *s, uint64_t position, uint64_t length, void *dst) {
+    if (!s || (length && !dst) || position + length < position) return PBSGPU_E_INVALID;
+    if (!s->hold) return PBSGPU_E_STATE;
+    if (position + length > s->polled_end) return PBSGPU_E_STATE;
+    if (length == 0) return PBSGPU_OK;
+    pbsgpu_ring *r = s->ring;
+    std::vector<SrcPart> parts;
+    {
+        std::lock_guard<std::mutex> lk(r->mu);
+        Section *in = nullptr;  // the range lies in ONE section: an injected gap has no bytes
+        for (auto *list : {&s->kept, &s->sections})
+            for (auto &sec : *list)
+                if (!sec->released && position >= sec->base && position - sec->base < sec->len) in = sec.get();
+        if (!in || length > in->len - (position - in->base)) return PBSGPU_E_STATE;
+        CHK(ring_copy_plan(r, in->rid, position - in->base, length, &parts));
+    }
+    CHK(set_device(s->eng));
+    if (!is_device_pointer(dst)) return PBSGPU_E_INVALID;
+    return copy_parts(s->eng, r->arena.as<uint8_t>(), parts.data(), (uint32_t)parts.size(), static_cast<uint8_t *>(dst));
 }
 
 // ---- chunker ----------------------------------------------------------------------------

@@ -783,12 +783,68 @@ class PayloadStream:
     """The payload-stream seam ``WriteEntryReader`` feeds (transfer.ArchiveWriter,
     internal/pxarmount/commit_test.go:33-67): append bytes, get (end, digest) records."""
 
-    def __init__(self, eng: Engine, window_bytes: int = 0):
+    def __init__(self, eng: Engine, window_bytes: int = 0, hold: bool = False):
+        """hold=True: the stream keeps its pages until release() (pbsgpu_stream_hold): upload_new2() frames the new chunks
+        of what write() was given straight out of them. A call that needs a page then raises PbsGpuError(E_BUSY) instead
+        of waiting for a page only a release can bring; write() may have taken a prefix (bytes_written())."""
         self._eng = eng
         self._L = eng._L
         h = C.c_void_p()
         check(self._L.pbsgpu_stream_create(eng._h, window_bytes, C.byref(h)), "stream_create")
         self._h = h
+        if hold:
+            try:
+                check(self._L.pbsgpu_stream_hold(self._h), "stream_hold")
+            except Exception:
+                self.close()
+                raise
+
+    # ---- held pages (hold=True) -------------------------------------------------------------------------------
+    def release(self, upto: int) -> None:
+        """The payload below position `upto` (at most the `end` of the last polled record) is no longer needed."""
+        check(self._L.pbsgpu_stream_release(self._h, int(upto)), "stream_release")
+
+    def held(self) -> tuple:
+        """(lowest position whose bytes are still available, handed-back pages the stream holds, free pages of the ring)"""
+        first, pages, free = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        check(self._L.pbsgpu_stream_held(self._h, C.byref(first), C.byref(pages), C.byref(free)), "stream_held")
+        return int(first.value), int(pages.value), int(free.value)
+
+    def upload_new2(self, known: "KnownChunks", recs: np.ndarray, insert: bool = True, zstd: bool = False,
+                    dst: DeviceBuffer | None = None):
+        """PageRing.upload_new2() for records of this stream, exactly as poll() returned them (a batch may span sections):
+        classified against `known`, the new ones framed out of the stream's held pages. Returns (buffer with .used, known
+        flags, offsets, lens, kinds, CRCs, stats, encode stats)."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        n = int(recs.size)
+        own = dst is None
+        if own:
+            dst = self._eng.alloc(max(int(recs["size"].astype(np.uint64).sum()) + 12 * n, 16))
+        o = _Upload2Out(n)
+        try:
+            check(self._L.pbsgpu_stream_upload_new2_device(self._h, known._h, recs.ctypes.data if n else None, n, int(insert),
+                                                           _lib.ENCODE_F_ZSTD if zstd else 0, dst.ptr, dst.nbytes, *o.args()),
+                  "stream_upload_new2_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return o.result(dst)
+
+    def copy(self, position: int, length: int, dst: DeviceBuffer | None = None) -> DeviceBuffer:
+        """The raw payload bytes [position, position + length) out of the held pages into dst (None: a new DeviceBuffer).
+        The range lies in one section, is covered by polled records and is not released."""
+        own = dst is None
+        if own:
+            dst = self._eng.alloc(max(int(length), 16))
+        try:
+            assert dst.nbytes >= int(length), "dst is too small"
+            check(self._L.pbsgpu_stream_copy_device(self._h, int(position), int(length), dst.ptr), "stream_copy_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return dst
 
     def write(self, data) -> None:
         a = _host_view(data)
