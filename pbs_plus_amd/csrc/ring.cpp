@@ -41,12 +41,6 @@ double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-uint32_t pow2_at_least(uint64_t v) {
-    uint32_t p = 1;
-    while (p < v && p < (1u << 31)) p <<= 1;
-    return p;
-}
-
 volatile uint32_t *hb_words(const pbsgpu_ring *r) { return r->heartbeat.as<volatile uint32_t>(); }
 
 // the service launched last is known to have ended: statistics, the service count, parked frees
@@ -66,7 +60,7 @@ void ring_service_ended(pbsgpu_ring *r) {
     hb[pbsk::kHbCommitted] = 0;
     // head := tail, stop := 0 — NOW, while nothing is published behind the service's back: its lanes may have left holding
     // claims beyond the tail, and rounds enqueued from here on (even before the next service starts: a lone stream's rounds
-    // are cut ahead at full chip width, ring_enqueue_round) must find the queue ready to be served from exactly this point
+    // are cut ahead at full chip width, pbsp::defer_decision) must find the queue ready to be served from exactly this point
     if (r->cs) {
         (void)pbsk::launch_ring_reset(r->ctl.as<pbsk::RingCtl>(), r->cs);
         (void)hipEventRecord(r->ev_reset, r->cs);
@@ -182,30 +176,19 @@ int ring_launch_services(pbsgpu_ring *r) {
     return PBSGPU_OK;
 }
 
-// The express form hashes a chunk 1.37x sooner at 0.70 of the pair form's throughput per CU (2.99 vs 4.28 GiB/s per CU,
-// DESIGN.md 5.6). For a share s of the bytes in long chunks both services are equally busy when the express service holds
-//   (s / 2.99) / (s / 2.99 + (1 - s) / 4.28)   of the services' CUs:
-// 7 % = 16 CUs for random data (s = 0.05: the default), 59 % = 112 CUs for a corpus with half its bytes in zero runs or
-// periodic files (BASELINE configs[2]: measured 429 GiB/s with 16 express CUs, 441 / 475 / 490 with 48 / 80 / 112 — every
-// page of such a file is held for the chain of a 16 MiB chunk, 0.49 s on a pair lane, 0.34 s on an express pair, and the
-// arena binds). Called when a service starts: the observation window is what was published since the last decision
-// (at least 8 GiB), halved afterwards so that the split follows the data with some memory.
+// The pair / express split follows the data (pbsp::adapt_xp_cus). Called when a service starts: the observation window is
+// what was published since the last decision (at least 8 GiB), halved afterwards so that the split follows the data with
+// some memory.
 void ring_adapt_split(pbsgpu_ring *r) {
     if (!r->split_auto || r->xs == nullptr || r->long_bytes == 0 || r->obs_bytes < 8.0 * 1073741824.0) return;
-    const double s = std::min(1.0, r->obs_long_bytes / r->obs_bytes);
-    const double fx = (s / 2.99) / (s / 2.99 + (1.0 - s) / 4.28);
-    // (x 0.9: the pair lanes help out with long chunks whenever every express pair is busy, the express pairs never take a
-    // short chunk — too few express CUs cost little, too many leave the pair service short: configs[2] measured 490 GiB/s at
-    // 112 express CUs, 469 at 120, 445 at 128)
-    int xp = (int)(0.9 * fx * (double)r->svc_cus / 8.0 + 0.5) * 8;  // whole XCD rows: other counts leave the XCDs unevenly loaded
-    xp = std::max(16, std::min(xp, (int)r->svc_cus - 32));
+    const uint32_t xp = pbsp::adapt_xp_cus(r->obs_long_bytes / r->obs_bytes, r->svc_cus, r->xp_cus);
     r->obs_bytes *= 0.5;
     r->obs_long_bytes *= 0.5;
-    if (std::abs(xp - (int)r->xp_cus) < 16) return;  // hysteresis
-    r->xp_cus = (uint32_t)xp;
+    if (xp == r->xp_cus) return;
+    r->xp_cus = xp;
     r->sha_cus = r->svc_cus - r->xp_cus - r->lanes_cus;
     r->st.sha_cus = r->sha_cus;
-    if (r->backlog_auto) r->backlog_limit = (uint64_t)(r->sha_cus + r->lanes_cus) << 27;  // (the gate is sized by the CUs that serve the main and the short queue)
+    if (r->backlog_auto) r->backlog_limit = pbsp::backlog_auto_bytes(r->sha_cus, r->lanes_cus);
 }
 
 // (`force`: quiesce / destroy — the caller is about to wait for the queue to drain, a service must run now)
@@ -256,102 +239,96 @@ int ring_start_service(pbsgpu_ring *r, bool force = false) {
     return PBSGPU_OK;
 }
 
-// build + enqueue one round from the committed pages; *did = false when there is nothing to do or no room
-int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
-    *did = false;
-    pbsgpu_engine *e = r->eng;
-    if (r->error != PBSGPU_OK) return r->error;
-    bool any = false, any_final = false;
-    size_t ready = 0;
-    for (auto &s : r->slots) {
-        if (!s.open) continue;
-        any |= !s.ready.empty() || s.zero_final;
-        any_final |= s.zero_final || (!s.ready.empty() && s.ready.back().final);
-        ready += s.ready.size();
-    }
-    if (!any) return PBSGPU_OK;
-    // A round costs a few dependent launches whatever it holds: while earlier rounds keep the device busy, wait until
-    // a quarter of a full round has gathered (pages come back from the SHA service one by one). A stream's end and an
-    // idle device go at once.
-    {
-        size_t inflight = 0;
-        for (auto &ri : r->rounds) inflight += ri.reaped ? 0 : 1;
-        if (inflight > 0 && !any_final && ready < r->min_round_pages) return PBSGPU_OK;
-        // ... and never queue rounds deep: a page that waits behind several queued rounds is resident without being
-        // worked on (measured: 16 rounds deep = ~80 ms of extra residency per page, a quarter of the whole)
-        if (inflight >= r->max_inflight) return PBSGPU_OK;
-    }
-    int in = -1;
-    for (uint32_t i = 0; i < kRingInputs; ++i)
-        if (!r->input_busy[i]) { in = (int)i; break; }
-    if (in < 0) return PBSGPU_OK;
-    // record cells: a round takes a contiguous (modulo the ring) range; wait while older rounds still own what the
-    // largest possible round would overwrite (only a caller that never polls gets here)
-    {
-        const uint64_t oldest = r->rounds.empty() ? r->cell_cursor : r->rounds.front().cell_base;
-        if (r->cell_cursor + r->rec_cap - oldest > r->ncells) return PBSGPU_OK;
-    }
-    pbsk::RingPage *pg = r->in_pages((uint32_t)in);
-    pbsk::RingSeg *sg = r->in_segs((uint32_t)in);
-    uint32_t *recbase = r->in_recbase((uint32_t)in);
-    uint32_t *suggidx = r->in_suggidx((uint32_t)in);
+// ---- one round, step by step (ring_enqueue_round; what each step DECIDES is in ring_plan.h) ----
+
+struct RoundBuild {                  // a round between the gate and the launch
+    uint32_t in = 0;                 // the set of input tables it is built in
+    bool any_final = false;          // a stream's end is waiting
     uint32_t np = 0, ns = 0, fill_pages = 0;
     uint64_t cells_needed = 0, new_bytes = 0;
+    uint64_t feed = 0;               // the engine's suggested-boundary feed when the round was gathered
+    const uint64_t *sugg_dev = nullptr;
+    uint32_t set = 0;                // scan set
     RoundInfo ri;
     std::vector<hipEvent_t> deps;
     std::vector<uint64_t> sugg;
+};
+
+// step 1, the gate: is there anything to cut, is it worth a round now, and is there an input table set and cell room for it?
+bool round_gate(pbsgpu_ring *r, RoundBuild &b) {
+    bool any = false;
+    size_t ready = 0, inflight = 0;
+    for (auto &s : r->slots) {
+        if (!s.open) continue;
+        any |= !s.ready.empty() || s.zero_final;
+        b.any_final |= s.zero_final || (!s.ready.empty() && s.ready.back().final);
+        ready += s.ready.size();
+    }
+    if (!any) return false;
+    for (auto &ri : r->rounds) inflight += ri.reaped ? 0 : 1;
+    if (!pbsp::round_gate(inflight, b.any_final, ready, r->min_round_pages, r->max_inflight)) return false;
+    int in = -1;
+    for (uint32_t i = 0; i < kRingInputs; ++i)
+        if (!r->input_busy[i]) { in = (int)i; break; }
+    if (in < 0) return false;
+    b.in = (uint32_t)in;
+    const uint64_t oldest = r->rounds.empty() ? r->cell_cursor : r->rounds.front().cell_base;
+    return pbsp::cells_have_room(r->cell_cursor, oldest, r->rec_cap, r->ncells);
+}
+
+// the ready page `q` of stream slot `si` as an entry of the round's page table, in segment `seg`
+pbsk::RingPage round_page(const pbsgpu_ring *r, StreamSlot &s, uint32_t si, uint32_t seg, const PageReq &q) {
+    pbsk::RingPage p{};
+    p.phys = q.phys;
+    p.phys_off = (uint64_t)q.phys * r->stride + 128u;
+    p.logical = ((uint64_t)si << pbsk::kRingOffBits) | (q.k * r->page_bytes);
+    p.valid = q.valid;
+    p.slot = si;
+    p.seg = seg;
+    p.do_fill = q.do_fill ? 1u : 0u;
+    p.fill_seed = q.seed;
+    p.fill_off = q.fill_off;
+    p.fill_kind = q.kind;
+    p.fill_tab = q.tab;
+    p.fill_ntab = q.ntab;
+    p.prev_phys = (q.k > 0 && s.last_phys >= 0) ? (uint32_t)s.last_phys : 0xffffffffu;
+    s.last_phys = (int64_t)q.phys;
+    return p;
+}
+
+// step 2: the page, segment, record-base and suggested-boundary tables from the stream slots — the only step that takes
+// pages and boundaries out of them. false: nothing was taken.
+bool round_gather(pbsgpu_ring *r, RoundBuild &b) {
+    pbsgpu_engine *e = r->eng;
+    pbsk::RingPage *pg = r->in_pages(b.in);
+    pbsk::RingSeg *sg = r->in_segs(b.in);
+    uint32_t *recbase = r->in_recbase(b.in);
+    uint32_t *suggidx = r->in_suggidx(b.in);
     const uint32_t minsz = std::min(e->effmin, e->cfg.min);
-    const uint64_t feed = e->sugg_feed.load(std::memory_order_relaxed);
-    const uint64_t look = feed > 1 ? (uint64_t)e->cfg.max : 0;  // reader-buffer rule: boundaries just beyond the bytes matter too
-    // While the services run the cut side has a quarter of the chip, and there a FULL round costs it 1.5x more per byte than a
-    // half one (the refill of round n + 1 then runs beside the scan of round n on the same CUs, and nothing of a 4.3 GB round
-    // is still in the last-level cache when the scan comes to it): measured with 184 + 8 service CUs, where every round was
-    // full, 680 GiB/s of feed phase at 256 pages per round, 763 at 128, 780 at 32 (profiles/r06_round_size_bistability.log).
-    // A ring that falls behind once grows its rounds, which makes it fall behind further: round 5's "unexplained" 184 + 8
-    // cliff and its few-large-rounds regime. So a round takes at most HALF the configured pages while a service runs; the
-    // whole-chip cut-ahead of an idle ring (no service yet: 64 GiB in ~20 ms) keeps full rounds.
-    // (Since the refill takes turns with the scan while a service runs — below — the cap no longer dodges their sharing; it stays
-    // because it was not measured again without it: profiles/ring_cut_partition.log.)
-    // (one stream alone is cut-bound on the cut side's quarter of the chip once its service has started, with most lanes
-    // idle: there the full round is the faster one — one file alone 407 vs 395 ms — and nothing can pile up behind it)
+    b.feed = e->sugg_feed.load(std::memory_order_relaxed);
+    const uint64_t look = b.feed > 1 ? (uint64_t)e->cfg.max : 0;  // reader-buffer rule: boundaries just beyond the bytes matter too
     uint32_t streams_waiting = 0;
     for (auto &s : r->slots) streams_waiting += (s.open && !s.ready.empty()) ? 1u : 0u;
-    const uint32_t round_cap = (r->svc == SvcState::Stopped || streams_waiting < 2)
-                                   ? r->round_pages
-                                   : std::max(std::min(r->round_pages, r->min_round_pages), r->round_pages / 2);
-    for (uint32_t si = 0; si < r->slots.size() && np < round_cap; ++si) {
+    const uint32_t round_cap = pbsp::round_cap(r->svc == SvcState::Stopped, streams_waiting, r->round_pages, r->min_round_pages);
+    for (uint32_t si = 0; si < r->slots.size() && b.np < round_cap; ++si) {
         StreamSlot &s = r->slots[si];
         if (!s.open || (s.ready.empty() && !s.zero_final)) continue;
         pbsk::RingSeg g{};
         g.slot = si;
-        g.first_page = np;
+        g.first_page = b.np;
         g.reset = s.fresh ? 1u : 0u;
         g.origin = s.origin;
         const uint64_t end_old = s.bytes_enqueued;
         uint64_t end = end_old;
         uint32_t take = 0;
-        while (!s.ready.empty() && take < kPagesPerStreamRound && np < round_cap) {
+        while (!s.ready.empty() && take < kPagesPerStreamRound && b.np < round_cap) {
             const PageReq &q = s.ready.front();
-            pbsk::RingPage p{};
-            p.phys = q.phys;
-            p.phys_off = (uint64_t)q.phys * r->stride + 128u;
-            p.logical = ((uint64_t)si << pbsk::kRingOffBits) | (q.k * r->page_bytes);
-            p.valid = q.valid;
-            p.slot = si;
-            p.seg = ns;
-            p.do_fill = q.do_fill ? 1u : 0u;
-            fill_pages += p.do_fill;
-            p.fill_seed = q.seed;
-            p.fill_off = q.fill_off;
-            p.fill_kind = q.kind;
-            p.fill_tab = q.tab;
-            p.fill_ntab = q.ntab;
-            p.prev_phys = (q.k > 0 && s.last_phys >= 0) ? (uint32_t)s.last_phys : 0xffffffffu;
-            s.last_phys = (int64_t)q.phys;
-            pg[np++] = p;
-            if (q.dep) deps.push_back(q.dep);
+            const pbsk::RingPage p = round_page(r, s, si, b.ns, q);
+            b.fill_pages += p.do_fill;
+            pg[b.np++] = p;
+            if (q.dep) b.deps.push_back(q.dep);
             end += q.valid;
-            new_bytes += q.valid;
+            b.new_bytes += q.valid;
             if (q.final) g.final = 1;
             s.ready.pop_front();
             ++take;
@@ -366,61 +343,60 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
         s.fresh = false;
         if (g.final) {
             s.final_enqueued = true;
-            ri.finals.push_back(si);
+            b.ri.finals.push_back(si);
         }
         // suggested boundaries that can still matter: behind the open chunk's start (>= end_old - max, the chunk is
         // shorter than max), up to the new end (+ one max chunk under the reader-buffer rule)
-        suggidx[ns] = (uint32_t)sugg.size();
+        suggidx[b.ns] = (uint32_t)b.sugg.size();
         {
             const uint64_t lower = end_old > e->cfg.max ? end_old - e->cfg.max : 0;
             while (!s.sugg.empty() && s.sugg.front() < lower) s.sugg.pop_front();
-            for (uint64_t b : s.sugg) {
-                if (b > end + look) break;
-                sugg.push_back(b);
+            for (uint64_t x : s.sugg) {
+                if (x > end + look) break;
+                b.sugg.push_back(x);
             }
         }
-        recbase[ns] = (uint32_t)cells_needed;
-        cells_needed += ((uint64_t)take * r->page_bytes + e->cfg.max) / minsz + 2;
-        sg[ns++] = g;
+        recbase[b.ns] = (uint32_t)b.cells_needed;
+        b.cells_needed += pbsp::seg_cell_bound(take, r->page_bytes, e->cfg.max, minsz);
+        sg[b.ns++] = g;
     }
-    if (ns == 0) return PBSGPU_OK;
-    suggidx[ns] = (uint32_t)sugg.size();
-    if (cells_needed > r->rec_cap) cells_needed = r->rec_cap;  // (the bound above is never larger: rec_cap is the same formula for a full round)
-    recbase[ns] = (uint32_t)cells_needed;
-    // From here on the popped pages and the streams' new lengths exist only in this round: any failure is the ring's (sticky).
-    auto fail = [&](int st) {
-        r->error = st;
-        for (hipEvent_t ev : deps) ring_event_put(r, ev);
-        return st;
-    };
-    const uint64_t *sugg_dev = nullptr;
-    if (!sugg.empty()) {
-        PinnedBuf &sb = r->sugg_in[in];
-        if (sb.ensure(std::max<size_t>(sugg.size() * 8, 4096)) != PBSGPU_OK) return fail(PBSGPU_E_NOMEM);
-        std::memcpy(sb.p, sugg.data(), sugg.size() * 8);
-        sugg_dev = sb.as<uint64_t>();
-    }
-    ri.cell_base = r->cell_cursor;
-    ri.cell_cap = (uint32_t)cells_needed;
-    r->cell_cursor += cells_needed;
-    uint8_t *cells = r->cells.as<uint8_t>();
-    for (uint64_t i = 0; i < cells_needed; ++i)
-        std::memset(cells + (size_t)((ri.cell_base + i) & (r->ncells - 1)) * pbsk::kCellBytes, 0, pbsk::kCellBytes);
-    ri.seq = r->next_seq++;
-    ri.input = (uint32_t)in;
-    pbsk::RingRoundStatus *hs = r->in_status((uint32_t)in);
-    hs->seq = 0;
-    // the service's self-stop handshake (kernels.hip): count and heartbeat first, THEN look at its intent flag
-    volatile uint32_t *hb = hb_words(r);
-    hb[pbsk::kHbRoundsEnq] = ++r->rounds_enq;
-    ring_heartbeat(r);
-    std::atomic_thread_fence(std::memory_order_seq_cst);
-    {
-        const int st = ring_service_check(r, true);
-        if (st != PBSGPU_OK) return fail(st);
-    }
+    if (b.ns == 0) return false;
+    suggidx[b.ns] = (uint32_t)b.sugg.size();
+    if (b.cells_needed > r->rec_cap) b.cells_needed = r->rec_cap;  // (the bound above is never larger: pbsp::round_rec_cap)
+    recbase[b.ns] = (uint32_t)b.cells_needed;
+    return true;
+}
 
-    pbsk::RingRound rr{};
+// From round_gather on the popped pages and the streams' new lengths exist only in the round: any failure is the ring's (sticky).
+int round_fail(pbsgpu_ring *r, RoundBuild &b, int st) {
+    r->error = st;
+    for (hipEvent_t ev : b.deps) ring_event_put(r, ev);
+    return st;
+}
+
+// the round's suggested boundaries where the device reads them, its record cells (cleared), its number and status block
+int round_claim(pbsgpu_ring *r, RoundBuild &b) {
+    if (!b.sugg.empty()) {
+        PinnedBuf &sb = r->sugg_in[b.in];
+        if (sb.ensure(std::max<size_t>(b.sugg.size() * 8, 4096)) != PBSGPU_OK) return PBSGPU_E_NOMEM;
+        std::memcpy(sb.p, b.sugg.data(), b.sugg.size() * 8);
+        b.sugg_dev = sb.as<uint64_t>();
+    }
+    b.ri.cell_base = r->cell_cursor;
+    b.ri.cell_cap = (uint32_t)b.cells_needed;
+    r->cell_cursor += b.cells_needed;
+    uint8_t *cells = r->cells.as<uint8_t>();
+    for (uint64_t i = 0; i < b.cells_needed; ++i)
+        std::memset(cells + (size_t)((b.ri.cell_base + i) & (r->ncells - 1)) * pbsk::kCellBytes, 0, pbsk::kCellBytes);
+    b.ri.seq = r->next_seq++;
+    b.ri.input = b.in;
+    r->in_status(b.in)->seq = 0;
+    return PBSGPU_OK;
+}
+
+// step 3: what the round's kernels are launched with
+void round_params(pbsgpu_ring *r, RoundBuild &b, pbsk::RingRound &rr) {
+    pbsgpu_engine *e = r->eng;
     rr.arena = r->arena.as<uint8_t>();
     rr.page_bytes = (uint32_t)r->page_bytes;
     rr.stride = (uint32_t)r->stride;
@@ -432,28 +408,27 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     rr.cap = r->cap;
     rr.thr = e->thr;
     rr.table_rot = e->d_table_rot;
-    rr.pages = pg;
-    rr.npages = np;
-    rr.segs_in = sg;
-    rr.nseg = ns;
-    rr.seq = ri.seq;
-    rr.cell_base = (uint32_t)(ri.cell_base & (r->ncells - 1));
-    rr.cell_cap = ri.cell_cap;
+    rr.pages = r->in_pages(b.in);
+    rr.npages = b.np;
+    rr.segs_in = r->in_segs(b.in);
+    rr.nseg = b.ns;
+    rr.seq = b.ri.seq;
+    rr.cell_base = (uint32_t)(b.ri.cell_base & (r->ncells - 1));
+    rr.cell_cap = b.ri.cell_cap;
     rr.cell_mask = r->ncells - 1;
-    rr.scan_blocks = (uint32_t)std::max(1, e->num_cus - (int)r->svc_cus);
-    rr.status = hs;
+    rr.status = r->in_status(b.in);
     rr.streams = r->streams.as<pbsk::RingStreamState>();
     rr.q = r->source();
     rr.desc_w = r->desc.as<uint4>();
     rr.ldesc_w = r->ldesc.as<uint4>();
     rr.sdesc_w = r->lanes_cus ? r->sdesc.as<uint4>() : nullptr;
-    const uint32_t set = r->ps ? r->scan_set : 0u;
+    b.set = r->ps ? r->scan_set : 0u;
     rr.scalars = r->scalars.as<uint32_t>();
-    rr.tile_queue = r->tileq.as<unsigned long long>() + set * 8u;
-    rr.fill_queue = r->tileq.as<unsigned long long>() + 16u + (uint32_t)in;
-    rr.tile_cnt = set ? r->tile_cnt2.as<uint32_t>() : r->tile_cnt.as<uint32_t>();
+    rr.tile_queue = r->tileq.as<unsigned long long>() + b.set * 8u;
+    rr.fill_queue = r->tileq.as<unsigned long long>() + 16u + b.in;
+    rr.tile_cnt = b.set ? r->tile_cnt2.as<uint32_t>() : r->tile_cnt.as<uint32_t>();
     rr.tile_off = r->tile_off.as<uint32_t>();
-    rr.tile_slots = set ? r->tile_slots2.as<uint32_t>() : r->tile_slots.as<uint32_t>();
+    rr.tile_slots = b.set ? r->tile_slots2.as<uint32_t>() : r->tile_slots.as<uint32_t>();
     rr.scan_tmp = r->scan_tmp.as<uint32_t>();
     rr.dense = r->dense.as<uint64_t>();
     rr.dense_cap = r->dense_cap;
@@ -466,115 +441,102 @@ int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
     rr.seg_open = r->seg_open.as<uint32_t>();
     rr.seg_ecand_in = r->seg_ecand_in.as<uint64_t>();
     rr.seg_ecand = r->seg_ecand.as<uint64_t>();
-    rr.sugg = sugg_dev;
-    rr.sugg_idx = sugg_dev ? suggidx : nullptr;
-    rr.sugg_feed = feed;
+    rr.sugg = b.sugg_dev;
+    rr.sugg_idx = b.sugg_dev ? r->in_suggidx(b.in) : nullptr;
+    rr.sugg_feed = b.feed;
     rr.sugg_abs = e->sugg_feed_abs.load(std::memory_order_relaxed);
-    rr.seg_rec_base = recbase;
-    std::atomic_thread_fence(std::memory_order_release);
-    // Start the service with this round — unless it is worth cutting AHEAD of it: a LONE stream that delivers pages in bulk
-    // (bytes already in device memory) cannot keep the service's lanes busy anyway (a 64 GiB file is 17 k chunks for 24 k
-    // lanes: it is bound by the chain of its longest chunk), but its scan can use the WHOLE chip while no service holds
-    // three quarters of it: 64 GiB are cut in ~20 ms at full width instead of ~75 ms on the cut side's quarter. The
-    // service starts when the stream's bytes are all in, when another stream shows up, or after lone_defer_ms — and
-    // finds every chunk queued (the queue was reset when the previous service ended, not now).
-    // The same holds for the first rounds of SEVERAL bulk streams on an idle ring: until the service's lanes could all be
-    // busy (lanes x average chunk size: ~96 GiB at avg 4 MiB) it only holds CUs the cut side could use — 96 GiB are cut in
-    // ~26 ms on the whole chip, ~105 ms on a quarter of it with lanes waiting all the while. A trickle of pages (host-fed
-    // streams: a few pages per pump) never defers: np is small there.
-    bool defer = r->defer_service;
-    if (!defer && r->svc == SvcState::Stopped && r->lone_defer_ms > 0 && !any_final &&
-        np >= std::max<uint32_t>(1, r->round_pages / 2)) {
-        const uint64_t lanes_worth = (uint64_t)r->sha_cus * (r->dense_service ? 256u : 128u) * (uint64_t)e->cfg.avg;
-        const double t = now_ms();
-        if (r->defer_t0 == 0) r->defer_t0 = t;
-        defer = t - r->defer_t0 < r->lone_defer_ms && r->deferred_bytes + new_bytes < lanes_worth;
-    }
-    if (!defer) {
-        const int st = ring_start_service(r);
-        if (st != PBSGPU_OK) return fail(st);
+    rr.seg_rec_base = r->in_recbase(b.in);
+}
+
+// step 4, second half: start the service with this round, or cut ahead of it (pbsp::defer_decision)
+int round_service(pbsgpu_ring *r, const RoundBuild &b, pbsk::RingRound &rr) {
+    const double t = now_ms();
+    const pbsp::DeferDecision d = pbsp::defer_decision(
+        r->defer_service, r->svc == SvcState::Stopped, r->lone_defer_ms, b.any_final, b.np, r->round_pages, r->sha_cus,
+        r->dense_service, r->eng->cfg.avg, r->deferred_bytes + b.new_bytes, r->defer_t0 == 0 ? 0.0 : t - r->defer_t0);
+    if (d.timed && r->defer_t0 == 0) r->defer_t0 = t;
+    if (!d.defer) {
+        CHK(ring_start_service(r));
         // the start may have moved the pair / express split (ring_adapt_split): this round publishes against the split it
         // will be served by, not the one before it (xp_pairs, long_spill, long_lo: heuristics only, records do not depend on them)
         rr.q = r->source();
     }
-    if (r->svc == SvcState::Stopped) r->deferred_bytes += new_bytes;  // cut ahead of the service (or the start waits for a graveyard flush)
-    if (fill_pages) r->rounds_since_fill = 0;
+    if (r->svc == SvcState::Stopped) r->deferred_bytes += b.new_bytes;  // cut ahead of the service (or the start waits for a graveyard flush)
+    return PBSGPU_OK;
+}
+
+// step 5: the cut side's partition, the waits, the staging of the tables and the launch
+int round_launch(pbsgpu_ring *r, RoundBuild &b, pbsk::RingRound &rr) {
+    if (b.fill_pages) r->rounds_since_fill = 0;
     else if (r->rounds_since_fill < 1000u) r->rounds_since_fill++;
-    // How the synthetic refill and the scan share the cut side.
-    // No service (the whole-chip cut-ahead of an idle ring, a lone file): both at full width, the refill on its own stream.
-    // A service runs: the cut side is shared IN TIME. The refill of round n + 1 goes in stream order behind the scan of round n,
-    // and each has every cut CU but the one left to the control kernel, which runs beside them on its own stream. Measured
-    // (profiles/ring_cut_partition.log): whenever the two run at the same time both get dearer per byte, on shared CUs
-    // (scan 82, refill 28 CU-ms per GiB) and on disjoint ones alike (58 and 22), against 42 and 16 in turn on small rounds: the refill
-    // is bound by what the memory system takes in beside the services' reads, not by its CUs, and the scan waits on the same
-    // memory. A ring that had fallen behind once then stayed behind (the large-round regime of round 6).
-    // fill_cus > 0 (experiments, tests): the partition IN SPACE instead — that many whole-CU refill workgroups on their own
-    // stream beside the scan, which gets the rest; a ring whose recent rounds had nothing to refill gives them to the scan.
-    bool fill_serial = r->fill_serial;
-    if (r->svc == SvcState::Stopped) {
-        rr.scan_blocks = (uint32_t)std::max(1, e->num_cus);
-        rr.fill_blocks = 2u * rr.scan_blocks;  // (two 1024-thread workgroups fill a CU's wave slots)
-        rr.fill_shared = 1;
-    } else {
-        constexpr uint32_t kFillRecent = 8;  // rounds
-        const int cut = std::max(1, e->num_cus - (int)r->svc_cus);
-        const int rest = cut - ((r->ps && cut > 8) ? 1 : 0);  // (one CU stays free for the control kernel)
-        if (r->opt_fill_cus && !fill_serial && rest >= 2) {
-            const int F = r->rounds_since_fill < kFillRecent ? (int)std::min<uint32_t>(r->opt_fill_cus, (uint32_t)rest - 1u) : 0;
-            rr.scan_blocks = (uint32_t)(rest - F);
-            rr.fill_blocks = (uint32_t)std::max(1, F);
-        } else {
-            fill_serial = true;
-            rr.scan_blocks = (uint32_t)std::max(1, rest);
-            rr.fill_blocks = 2u * rr.scan_blocks;
-            rr.fill_shared = 1;
-        }
-    }
+    const pbsp::CutPartition cp = pbsp::cut_partition(r->svc == SvcState::Stopped, r->eng->num_cus, r->svc_cus, r->ps != nullptr,
+                                                      r->opt_fill_cus, r->fill_serial, r->rounds_since_fill);
+    rr.scan_blocks = cp.scan_blocks;
+    rr.fill_blocks = cp.fill_blocks;
+    rr.fill_shared = cp.fill_shared ? 1u : 0u;
     hipStream_t scan_st = r->ps ? r->ps : r->cs;
-    for (hipEvent_t ev : deps)  // host-fed pages: the cut waits for their copies (device-side wait; the copies never wait for a kernel)
-        if (hipStreamWaitEvent(scan_st, ev, 0) != hipSuccess) return fail(PBSGPU_E_HIP);
-    for (hipEvent_t ev : deps) ring_event_put(r, ev);
-    deps.clear();
-    if (r->ps && r->ctl_used[set])  // this scan set's previous user must have been resolved before the scan overwrites it
-        if (hipStreamWaitEvent(r->ps, r->ev_ctl[set], 0) != hipSuccess) return fail(PBSGPU_E_HIP);
-    {
-        pbsk::RingStage stg{};
-        if (r->stage_inputs) {
-            const uint8_t *hb = r->in((uint32_t)in);
-            uint8_t *db = r->in_dev((uint32_t)in);
-            stg.src = hb;
-            stg.dst = db;
-            stg.off[0] = (uint32_t)r->in_pages_off;   stg.len[0] = np * (uint32_t)sizeof(pbsk::RingPage);
-            stg.off[1] = (uint32_t)r->in_segs_off;    stg.len[1] = ns * (uint32_t)sizeof(pbsk::RingSeg);
-            stg.off[2] = (uint32_t)r->in_recbase_off; stg.len[2] = (ns + 1u) * 4u;
-            stg.off[3] = (uint32_t)r->in_suggidx_off; stg.len[3] = rr.sugg_idx ? (ns + 1u) * 4u : 0u;
-            stg.pages_host = pg;
-            auto mirror = [&](const void *hp) { return db + (reinterpret_cast<const uint8_t *>(hp) - hb); };
-            rr.pages = reinterpret_cast<const pbsk::RingPage *>(mirror(pg));
-            rr.segs_in = reinterpret_cast<const pbsk::RingSeg *>(mirror(sg));
-            rr.seg_rec_base = reinterpret_cast<const uint32_t *>(mirror(recbase));
-            if (rr.sugg_idx) rr.sugg_idx = reinterpret_cast<const uint32_t *>(mirror(suggidx));
-        }
-        const hipError_t he = pbsk::launch_ring_round(rr, e->num_cus, r->cs, fill_serial ? nullptr : r->fs, r->ev_fill[in], r->ps,
-                                                      r->ps ? r->ev_scan[in] : nullptr, r->stage_inputs ? &stg : nullptr);
-        if (he != hipSuccess) {
-            g_last_hip_error.store((int)he);
-            return fail(PBSGPU_E_HIP);
-        }
+    for (hipEvent_t ev : b.deps)  // host-fed pages: the cut waits for their copies (device-side wait; the copies never wait for a kernel)
+        HIPCHK(hipStreamWaitEvent(scan_st, ev, 0));
+    for (hipEvent_t ev : b.deps) ring_event_put(r, ev);
+    b.deps.clear();
+    if (r->ps && r->ctl_used[b.set])  // this scan set's previous user must have been resolved before the scan overwrites it
+        HIPCHK(hipStreamWaitEvent(r->ps, r->ev_ctl[b.set], 0));
+    pbsk::RingStage stg{};
+    if (r->stage_inputs) {
+        const uint8_t *hb = r->in(b.in);
+        uint8_t *db = r->in_dev(b.in);
+        stg.src = hb;
+        stg.dst = db;
+        stg.off[0] = (uint32_t)r->in_pages_off;   stg.len[0] = b.np * (uint32_t)sizeof(pbsk::RingPage);
+        stg.off[1] = (uint32_t)r->in_segs_off;    stg.len[1] = b.ns * (uint32_t)sizeof(pbsk::RingSeg);
+        stg.off[2] = (uint32_t)r->in_recbase_off; stg.len[2] = (b.ns + 1u) * 4u;
+        stg.off[3] = (uint32_t)r->in_suggidx_off; stg.len[3] = rr.sugg_idx ? (b.ns + 1u) * 4u : 0u;
+        stg.pages_host = rr.pages;
+        auto mirror = [&](const void *hp) { return db + (reinterpret_cast<const uint8_t *>(hp) - hb); };
+        rr.pages = reinterpret_cast<const pbsk::RingPage *>(mirror(rr.pages));
+        rr.segs_in = reinterpret_cast<const pbsk::RingSeg *>(mirror(rr.segs_in));
+        rr.seg_rec_base = reinterpret_cast<const uint32_t *>(mirror(rr.seg_rec_base));
+        if (rr.sugg_idx) rr.sugg_idx = reinterpret_cast<const uint32_t *>(mirror(rr.sugg_idx));
     }
+    HIPCHK(pbsk::launch_ring_round(rr, r->eng->num_cus, r->cs, cp.fill_serial ? nullptr : r->fs, r->ev_fill[b.in], r->ps,
+                                   r->ps ? r->ev_scan[b.in] : nullptr, r->stage_inputs ? &stg : nullptr));
     if (r->ps) {
-        if (hipEventRecord(r->ev_ctl[set], r->cs) != hipSuccess) return fail(PBSGPU_E_HIP);
-        r->ctl_used[set] = true;
+        HIPCHK(hipEventRecord(r->ev_ctl[b.set], r->cs));
+        r->ctl_used[b.set] = true;
         r->scan_set ^= 1u;
     }
-    r->input_busy[in] = true;
-    ri.new_bytes = new_bytes;
-    r->ready_bytes -= new_bytes;
-    r->inflight_bytes += new_bytes;
-    r->rounds.push_back(std::move(ri));
+    return PBSGPU_OK;
+}
+
+// build + enqueue one round from the committed pages; *did = false when there is nothing to do or no room
+int ring_enqueue_round(pbsgpu_ring *r, bool *did) {
+    *did = false;
+    if (r->error != PBSGPU_OK) return r->error;
+    RoundBuild b;
+    if (!round_gate(r, b) || !round_gather(r, b)) return PBSGPU_OK;
+    int st = round_claim(r, b);
+    if (st != PBSGPU_OK) return round_fail(r, b, st);
+    // step 4, first half: the service's self-stop handshake (kernels.hip): count and heartbeat first, THEN look at its intent flag
+    hb_words(r)[pbsk::kHbRoundsEnq] = ++r->rounds_enq;
+    ring_heartbeat(r);
+    std::atomic_thread_fence(std::memory_order_seq_cst);
+    st = ring_service_check(r, true);
+    if (st != PBSGPU_OK) return round_fail(r, b, st);
+    pbsk::RingRound rr{};
+    round_params(r, b, rr);
+    std::atomic_thread_fence(std::memory_order_release);
+    st = round_service(r, b, rr);
+    if (st == PBSGPU_OK) st = round_launch(r, b, rr);
+    if (st != PBSGPU_OK) return round_fail(r, b, st);
+    // step 6: the bookkeeping
+    r->input_busy[b.in] = true;
+    b.ri.new_bytes = b.new_bytes;
+    r->ready_bytes -= b.new_bytes;
+    r->inflight_bytes += b.new_bytes;
+    r->rounds.push_back(std::move(b.ri));
     r->st.rounds++;
-    r->st.bytes_enqueued += new_bytes;
-    r->st.pages_enqueued += np;
+    r->st.bytes_enqueued += b.new_bytes;
+    r->st.pages_enqueued += b.np;
     *did = true;
     return PBSGPU_OK;
 }
@@ -662,48 +624,22 @@ pbsk::RingSource pbsgpu_ring::source() const {
     q.sdesc = sdesc.as<uint4>();
     q.smask = sslots ? sslots - 1 : 0;
     q.short_bytes = lanes_cus ? short_bytes : 0u;
-    // entries that may wait for the lanes service: its lanes take ~2 chunks per CU and round (256 lanes x 1.2 ms / ~0.15 s per
-    // chunk); 32 per CU rides out a dozen rounds and fills an idle service within ten
-    q.short_room = lanes_cus * (dense_lanes ? 64u : 32u);
     q.xp = xp_cus ? 1u : 0u;
-    // the pair lanes take a long chunk only while EVERY express pair is busy (RingCtl::xp_busy): random data keeps the express
-    // service just busy (2.6 long chunks per ms against the 2.8 it can take), a corpus whose files are mostly zero runs or
-    // periodic (configs[2]: half the bytes in 16 MiB chunks) swamps 16 CUs at once — and a long chunk that WAITS for an express
-    // pair (0.36 s + 0.36 s) finishes later than on a pair lane that is free now (0.49 s), holding its page all the while
-    // (measured with a queue-length rule instead: ring_manyfiles 441 -> 418 GiB/s, drain 0.50 -> 0.58 s)
-    q.long_spill = 0u;
-    q.xp_pairs = xp_cus * 64u;
-    // ... unless the express service is LARGE (the split has followed a corpus of long chunks, ring_adapt_split): with
-    // thousands of express pairs one comes free every few dozen microseconds (6 656 pairs x 0.34 s per 16 MiB chunk: one per
-    // 50 us), so a long chunk near the head of the queue is on an express pair — and done 0.15 s sooner than on a pair lane —
-    // almost at once. The pair lanes then only see what is queued beyond xp_pairs / 16 (<= 21 ms of waiting).
-    if (xp_cus >= 32) q.long_spill = q.xp_pairs / 16u;
-    // light load (fewer than 3/4 of the express pairs taken): chunks from 11/16 of the maximum on go express too — bulk rings
-    // only (the stream writer's ring already sends every chunk >= half the maximum express). One 64 GiB file alone: ~400 chunks
-    // >= 11 MiB for 1 024 pairs; its last record then waits for the express chain of a 16 MiB chunk (0.34 s), not for the pair
-    // chain of a 12.9 MiB one (0.37 s).
-    q.long_lo = (xp_cus && long_lo_auto) ? (uint32_t)((uint64_t)eng->cfg.max * 11 / 16) : 0u;
-    if (opt_long_lo) q.long_lo = (xp_cus && opt_long_lo != PBSGPU_RING_OFF) ? opt_long_lo : 0u;
-    if (q.long_lo >= q.long_bytes) q.long_lo = 0u;
-    if (opt_long_spill) q.long_spill = opt_long_spill;
+    const pbsp::QueuePolicy pol = pbsp::queue_policy({lanes_cus, xp_cus, dense_lanes, long_lo_auto, long_bytes, opt_long_lo,
+                                                      opt_long_spill, opt_poll_every, idle_timeout_s, eng->cfg.max,
+                                                      std::min(eng->effmin, eng->cfg.min)});
+    q.short_room = pol.short_room;
+    q.xp_pairs = pol.xp_pairs;
+    q.long_spill = pol.long_spill;
+    q.long_lo = pol.long_lo;
+    q.idle_ticks = pol.idle_ticks;
+    q.poll_mask = pol.poll_mask;
     q.ctl = ctl.as<pbsk::RingCtl>();
     q.cells = cells.as<uint8_t>();
     q.pending = pending.as<uint32_t>();
     q.free_fifo = free_fifo.as<unsigned long long>();
     q.free_mask = nfree - 1;
-    const double idle_s = idle_timeout_s > 0 ? std::max(0.05, idle_timeout_s) : 20.0;
-    q.idle_ticks = (unsigned long long)(idle_s * 100e6);  // wall_clock64 runs at 100 MHz
     q.heartbeat = heartbeat.as<uint32_t>();
-    {   // poll period of waves that carry work (power of two; 1 = every step, the behaviour before round 4)
-        // A free lane waits up to `every` block steps (1.75 us each) for its next look at the queue: kept below 0.4 % of the
-        // chain of a MINIMUM-size chunk — 8 for small chunkers (tests), 64 at the production average of 4 MiB (min 1 MiB =
-        // 16 384 steps). Measured on the driver's command: every 8th step 610.5 / 609.7, every 32nd 617.0 GiB/s, drain
-        // 0.430 -> 0.409 s (profiles/r05_ab_long_spill_and_poll.log; round 4: 1 -> 8: 606 -> 615).
-        const uint64_t min_steps = std::min<uint64_t>(eng->effmin, eng->cfg.min) / 64u;
-        int every = (int)std::min<uint64_t>(64, std::max<uint64_t>(8, pow2_at_least(min_steps / 256u + 1u) / 2u));
-        if (opt_poll_every) every = (int)opt_poll_every;
-        q.poll_mask = pow2_at_least((uint64_t)every) - 1u;
-    }
     return q;
 }
 
@@ -813,6 +749,121 @@ bool ring_page_needs_release(pbsgpu_ring *r) {
     return r->free_pages.empty() && !r->held.frees_without_release();
 }
 
+// creation step 1: the ring's shape (pbsp::shape_ring) and the options that are only carried along
+static int ring_shape(pbsgpu_ring *r, const pbsgpu_ring_options &o, uint32_t long_bytes_hint) {
+    pbsgpu_engine *e = r->eng;
+    size_t fr = 0, tot = 0;
+    if (o.arena_bytes == 0) HIPCHK(hipMemGetInfo(&fr, &tot));
+    CHK(pbsp::shape_ring(o, {e->cfg.min, e->effmin, e->cfg.avg, e->cfg.max, e->cfg.mask}, e->num_cus, fr, long_bytes_hint,
+                         kRingInputs, r));
+    r->autopark_ms = std::max(0.0, o.autopark_ms);
+    r->idle_timeout_s = o.idle_timeout_s;
+    r->opt_long_lo = o.long_lo_bytes;
+    r->opt_long_spill = o.long_spill;
+    r->opt_poll_every = o.poll_every;
+    r->opt_fill_cus = o.fill_cus;
+    // PBSGPU_RING_F_NO_STAGE: the round's kernels read their tables from mapped host memory (rounds 3-4), for A/B runs
+    r->stage_inputs = !(o.flags & PBSGPU_RING_F_NO_STAGE);
+    return PBSGPU_OK;
+}
+
+// creation step 2: every buffer of the shape, and the layout of the round input tables
+static int ring_allocate(pbsgpu_ring *r, bool overlap) {
+    const uint64_t ntiles = r->ntiles;
+    CHK(r->arena.ensure((size_t)r->npages * r->stride + 512));
+    CHK(r->ctl.ensure(256));
+    CHK(r->probe.ensure(128));
+    CHK(r->streams.ensure((size_t)r->max_streams * sizeof(pbsk::RingStreamState)));
+    CHK(r->pending.ensure((size_t)r->npages * 4 + 64));
+    CHK(r->desc.ensure((size_t)r->qslots * 32));
+    CHK(r->ldesc.ensure((size_t)r->lslots * 32));
+    CHK(r->sdesc.ensure((size_t)r->sslots * 32));
+    CHK(r->scalars.ensure(pbsk::kRsCount * 4 + 64));
+    CHK(r->tile_cnt.ensure((size_t)ntiles * 4 + 16));
+    CHK(r->tile_off.ensure((size_t)ntiles * 4 + 16));
+    CHK(r->tile_slots.ensure((size_t)ntiles * r->cap * 4 + 16));
+    CHK(r->tileq.ensure(128 + kRingInputs * 8));  // two tile counters (64 bytes apart), then one refill counter per round in flight
+    if (overlap) {
+        CHK(r->tile_cnt2.ensure((size_t)ntiles * 4 + 16));
+        CHK(r->tile_slots2.ensure((size_t)ntiles * r->cap * 4 + 16));
+    }
+    CHK(r->dense.ensure((size_t)r->dense_cap * 8 + 16));
+    CHK(r->scan_tmp.ensure(pbsk::scan_tmp_words(std::max<uint64_t>(ntiles, r->max_streams)) * 4 + 64));
+    CHK(r->segs.ensure((size_t)r->max_streams * sizeof(pbsgpu_segment)));
+    CHK(r->seg_cnt.ensure((size_t)r->max_streams * 4 + 16));
+    CHK(r->seg_off.ensure((size_t)r->max_streams * 4 + 16));
+    CHK(r->seg_newc.ensure((size_t)r->max_streams * 8 + 16));
+    CHK(r->seg_open.ensure((size_t)r->max_streams * 4 + 16));
+    CHK(r->seg_ecand_in.ensure((size_t)r->max_streams * 8 + 16));
+    CHK(r->seg_ecand.ensure((size_t)r->max_streams * 8 + 16));
+    CHK(r->recs.ensure((size_t)r->rec_cap * sizeof(pbsgpu_record) + 64));
+    CHK(r->cells.ensure((size_t)r->ncells * pbsk::kCellBytes));
+    CHK(r->heartbeat.ensure(256));
+    std::memset(r->heartbeat.p, 0, 256);
+    CHK(r->free_fifo.ensure((size_t)r->nfree * 8));
+    std::memset(r->free_fifo.p, 0, (size_t)r->nfree * 8);
+    auto al64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+    r->in_pages_off = 0;
+    r->in_segs_off = al64((size_t)r->round_pages * sizeof(pbsk::RingPage));
+    r->in_recbase_off = al64(r->in_segs_off + (size_t)r->max_streams * sizeof(pbsk::RingSeg));
+    r->in_suggidx_off = al64(r->in_recbase_off + ((size_t)r->max_streams + 1) * 4);
+    r->in_status_off = al64(r->in_suggidx_off + ((size_t)r->max_streams + 1) * 4);
+    r->input_stride = r->in_status_off + 128;
+    CHK(r->inputs.ensure(r->input_stride * kRingInputs));
+    if (r->stage_inputs) CHK(r->inputs_dev.ensure(r->input_stride * kRingInputs));
+    std::memset(r->inputs.p, 0, r->input_stride * kRingInputs);
+    return PBSGPU_OK;
+}
+
+// creation step 3: the ring's streams and events, and the device-side state cleared
+static int ring_streams_and_events(pbsgpu_ring *r, bool overlap, bool cut_prio) {
+    // Three priorities: the services highest (their own hardware-queue pool: nothing may queue behind a kernel that only
+    // ends on request), the CONTROL side of the rounds normal, the producers of bulk work — synthetic refill, scan —
+    // lowest: the one-workgroup control kernel and its prep launch find a CU as soon as one frees up instead of waiting
+    // behind the next round's scan workgroups (kernel trace of the driver's command: k_ring_prep 1.2 ms and
+    // k_ring_control 1.1 ms per launch for 10 us / 170 us of work; PBSGPU_RING_CUT_PRIO=0: all normal).
+    int prio_lo = 0, prio_hi = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+    r->bulk_prio = cut_prio ? prio_lo : 0;
+    HIPCHK(hipStreamCreateWithFlags(&r->cs, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithPriority(&r->fs, hipStreamNonBlocking, r->bulk_prio));
+    // The device-side state starts from zero — cleared ON THE CONTROL STREAM and waited for. A plain hipMemset is
+    // queued on the null stream and returns at once for device memory; the ring's streams are non-blocking, i.e. not
+    // ordered against the null stream: when the null stream was held up (it waits for every blocking stream's earlier
+    // work, e.g. the previous engine's last kernels) the clear arrived AFTER the first rounds had run and wiped queue
+    // tail, stream states and page reference counts — pages never came back, lanes waited at positions the tail had
+    // been reset below (the one-in-a-few-hundred hang of the small-ring tests).
+    HIPCHK(hipMemsetAsync(r->ctl.p, 0, 256, r->cs));
+    HIPCHK(hipMemsetAsync(r->probe.p, 0, 128, r->cs));
+    HIPCHK(hipMemsetAsync(r->streams.p, 0, (size_t)r->max_streams * sizeof(pbsk::RingStreamState), r->cs));
+    HIPCHK(hipMemsetAsync(r->pending.p, 0, (size_t)r->npages * 4 + 64, r->cs));
+    HIPCHK(hipMemsetAsync(r->scalars.p, 0, pbsk::kRsCount * 4 + 64, r->cs));
+    HIPCHK(hipMemsetAsync(r->tileq.p, 0, 128 + kRingInputs * 8, r->cs));
+    HIPCHK(hipStreamSynchronize(r->cs));
+    for (auto &ev : r->ev_fill) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (overlap) {
+        HIPCHK(hipStreamCreateWithPriority(&r->ps, hipStreamNonBlocking, r->bulk_prio));
+        for (auto &ev : r->ev_scan) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        for (auto &ev : r->ev_ctl) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    // the service must never share a hardware queue with a stream that enqueues behind it (packets of one queue
+    // run in order: work queued behind a kernel that only ends on request would never start). HIP keeps one queue
+    // pool per priority: the service gets the highest priority to itself.
+    HIPCHK(hipStreamCreateWithPriority(&r->ss, hipStreamNonBlocking, prio_hi));
+    if (r->xp_cus) {
+        HIPCHK(hipStreamCreateWithPriority(&r->xs, hipStreamNonBlocking, prio_hi));
+        HIPCHK(hipEventCreateWithFlags(&r->ev_xsvc1, hipEventDisableTiming));
+    }
+    if (r->lanes_cus) {
+        HIPCHK(hipStreamCreateWithPriority(&r->ls, hipStreamNonBlocking, prio_hi));
+        HIPCHK(hipEventCreateWithFlags(&r->ev_lsvc1, hipEventDisableTiming));
+    }
+    HIPCHK(hipEventCreateWithFlags(&r->ev_reset, hipEventDisableTiming));
+    HIPCHK(hipEventCreate(&r->ev_svc0));
+    HIPCHK(hipEventCreate(&r->ev_svc1));
+    return PBSGPU_OK;
+}
+
 int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool hold_engine_ref, pbsgpu_ring **out,
                          uint32_t long_bytes_hint) {
     if (!e || !out) return PBSGPU_E_INVALID;
@@ -826,224 +877,24 @@ int ring_create_internal(pbsgpu_engine *e, const pbsgpu_ring_options *opt, bool 
     r->holds_engine_ref = hold_engine_ref;
     if (hold_engine_ref) engine_ref(e);
     r->eng = e;
-    int st = [&]() -> int {
-        // page geometry: a whole number of scan tiles, >= the largest chunk (so a chunk touches at most two pages)
-        const uint32_t big = 64u * 34u * 128u, small = 64u * 4u * 128u;
-        uint64_t page = o.page_bytes;
-        if (page == 0) {
-            const uint32_t tile = e->cfg.max >= (1u << 20) ? big : small;
-            page = ((uint64_t)e->cfg.max + tile - 1) / tile * tile;
-            if (page < 2ull * tile && tile == small) page = 2ull * tile;
-        }
-        if (page % big == 0) r->tile_bytes = big;
-        else if (page % small == 0) r->tile_bytes = small;
-        else return PBSGPU_E_INVALID;
-        if (page < e->cfg.max || page >= (1ull << 31)) return PBSGPU_E_INVALID;
-        r->page_bytes = page;
-        r->tpp = (uint32_t)(page / r->tile_bytes);
-        r->stride = page + 256;
-        uint64_t arena_bytes = o.arena_bytes;
-        if (arena_bytes == 0) {
-            size_t fr = 0, tot = 0;
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-            arena_bytes = fr > (12ull << 30) ? fr - (8ull << 30) : fr / 2;
-        }
-        r->npages = (uint32_t)std::min<uint64_t>(arena_bytes / r->stride, 65534);  // 16-bit page ids in the queue descriptors
-        {   // the chunk FIFO and the record cells are sized for every chunk the arena can hold (arena / min chunk size):
-            // with small average chunk sizes that bound, not HBM, limits the arena (4 M resident chunks = 128 MB of
-            // descriptors + 1 GB of pinned record cells)
-            const uint64_t lim = (4ull << 20) * std::min(e->effmin, e->cfg.min) / r->page_bytes;
-            if (r->npages > lim) r->npages = (uint32_t)std::max<uint64_t>(lim, 4);
-        }
-        if (r->npages < 4) return PBSGPU_E_INVALID;
-        r->max_streams = o.max_streams ? o.max_streams : 64;
-        if (r->max_streams > 4096) return PBSGPU_E_INVALID;
-        // 3/4 of the chip hashes, 1/4 cuts: per GiB the cut rounds cost ~70 CU-ms (scan 52 + refill 18), the service
-        // ~233 CU-ms (128 chains per CU at 1.66-1.75 us per 64-byte block) — measured optimum 192 of 256 CUs
-        // (profiles/r03_ring_sweep_*.log: 184 -> 580, 192 -> 597, 200 -> 528, 208 -> 504 GiB/s)
-        int sha = o.sha_cus ? (int)o.sha_cus : std::max(1, e->num_cus - e->num_cus / 4);
-        // EXPRESS service: that many CUs run k_sha256_xpair — two lanes per chunk: the chain of a chunk 1.37x faster (1.28
-        // vs 1.75 us per block, profiles/r04_chain_time_pair_vs_express.log) at 0.65 of the throughput per CU — on the
-        // chunks of at least long_bytes. Bulk rings (default service share): 16 CUs for chunks >= 13/16 of the maximum
-        // (1.3 % of random data's chunks, 5 % of its bytes): the driver's line is unchanged within noise (the drain gets
-        // 0.08 s shorter, the feed phase 4 % slower: profiles/r04_ab_express_service.log), one file alone is 15 % sooner.
-        // The CUs come out of the pair service's share unless that was given explicitly.
-        int xp = o.express_cus == PBSGPU_RING_OFF ? 0 : (int)o.express_cus;
-        if (o.express_cus == 0 && !o.sha_cus && e->num_cus >= 128) xp = 16;
-        xp = std::min(xp, std::max(0, e->num_cus / 2));
-        if (xp && !o.sha_cus) sha = std::max(1, sha - xp);
-        // The cut side needs its share: with 13/16 of the chip (208 of 256 CUs) in service workgroups the driver's line falls
-        // to 525-545 GiB/s, with 216 the cut kernels barely find a CU (a warm-up of 5 files took 120 s:
-        // profiles/r04_ab_cu_split.log). Whatever was asked for, the services together get at most 3/4 of the chip + 8.
-        const int svc_max = std::max(2, e->num_cus - e->num_cus / 4 + (e->num_cus >= 64 ? 8 : 0));
-        if (sha + xp > svc_max) sha = std::max(1, svc_max - xp);
-        r->xp_cus = (uint32_t)xp;
-        r->sha_cus = (uint32_t)std::min(std::max(sha, 1), std::max(1, e->num_cus - 1 - xp));
-        // LANES service: out of the pair service's share (at most 3/4 of it)
-        r->lanes_cus = std::min<uint32_t>(o.lanes_cus, r->sha_cus * 3u / 4u);
-        r->sha_cus -= r->lanes_cus;
-        r->short_bytes = o.short_bytes ? (uint32_t)std::min<uint64_t>(o.short_bytes, e->cfg.max) : (uint32_t)((uint64_t)e->cfg.avg * 3 / 2);
-        r->svc_cus = r->sha_cus + r->xp_cus + r->lanes_cus;
-        r->split_auto = xp > 0 && !o.sha_cus && !o.express_cus && r->svc_cus >= 96 && !(o.flags & PBSGPU_RING_F_NO_SPLIT_AUTO);
-        r->round_pages = o.round_pages ? o.round_pages : 256;
-        r->round_pages = std::min(r->round_pages, r->npages);
-        r->min_round_pages = o.min_round_pages ? std::max(1u, std::min(o.min_round_pages, std::max(1u, r->round_pages / 4)))
-                                               : std::max(1u, r->round_pages / 4);
-        // ~30 ms of the service's throughput (4.3 GiB/s per CU measured) is plenty to ride out the gaps between rounds
-        r->backlog_limit = o.backlog_mib < 0 ? 0 : o.backlog_mib > 0 ? (uint64_t)(o.backlog_mib * 1048576.0)   : (uint64_t)(r->sha_cus + r->lanes_cus) << 27;
-        r->backlog_auto = o.backlog_mib == 0;
-        if (o.max_inflight) r->max_inflight = std::min<uint32_t>(std::max(1u, o.max_inflight), kRingInputs);
-        r->autopark_ms = std::max(0.0, o.autopark_ms);
-        r->defer_service = (o.flags & PBSGPU_RING_F_DEFER_SERVICE) != 0;
-        r->fill_serial = (o.flags & PBSGPU_RING_F_FILL_SERIAL) != 0;
-        r->dense_service = (o.flags & PBSGPU_RING_F_DENSE_SERVICE) != 0;
-        r->dense_lanes = (o.flags & PBSGPU_RING_F_DENSE_LANES) != 0;
-        r->tier_tag = (o.flags & PBSGPU_RING_F_TIER_TAG) != 0;
-        r->lone_defer_ms = o.lone_defer_ms < 0 ? 0.0 : o.lone_defer_ms > 0 ? o.lone_defer_ms : 25.0;
-        r->idle_timeout_s = o.idle_timeout_s;
-        r->opt_long_lo = o.long_lo_bytes;
-        r->opt_long_spill = o.long_spill;
-        r->opt_poll_every = o.poll_every;
-        r->opt_fill_cus = o.fill_cus;
-        // Candidate slots per scan tile. The batch path starts small and RE-RUNS a batch whose tile overflowed; a ring round
-        // cannot be re-run (later rounds continue from it), so the ring provisions for periodic data up front: one
-        // candidate per 128 bytes (a repeating block of >= 128 bytes whose every period holds a candidate — BASELINE
-        // configs[2]'s repeating 4 KiB files have one per 4 KiB). 12 bytes per slot: ~400 MB at the default round size.
-        // A tile beyond that (a crafted short period) keeps what fits and is re-scanned on demand by the resolve walk
-        // (DenseTiles, kernels.h): slower for that stretch, exact all the same.
-        const double lambda = 3.0 * r->tile_bytes / ((double)e->cfg.mask + 1.0);
-        uint32_t capv = 8;
-        while (capv < 4.0 * lambda + 16.0) capv <<= 1;
-        r->cap = std::min<uint32_t>(std::max<uint32_t>(capv * 2, r->tile_bytes / 128), r->tile_bytes);
-        const uint64_t ntiles = (uint64_t)r->round_pages * r->tpp;
-        if (ntiles * r->cap >= (1ull << 32)) return PBSGPU_E_INVALID;  // (round_pages far beyond anything an arena holds)
-        const uint32_t minsz = std::min(e->effmin, e->cfg.min);
-        r->dense_cap = ntiles * r->cap;
-        r->rec_cap = ((uint64_t)r->round_pages * r->page_bytes + (uint64_t)r->max_streams * e->cfg.max) / minsz +
-                     4ull * r->max_streams + 64;
-        const uint64_t resident_chunks = (uint64_t)r->npages * r->page_bytes / minsz + 2ull * r->npages + r->rec_cap;
-        r->qslots = pow2_at_least(2 * resident_chunks + 4096);
-        r->ncells = pow2_at_least(4 * resident_chunks + 4 * r->rec_cap);
-        r->nfree = pow2_at_least(4ull * r->npages + 64);
-
-        CHK(r->arena.ensure((size_t)r->npages * r->stride + 512));
-        CHK(r->ctl.ensure(256));
-        CHK(r->probe.ensure(128));
-        CHK(r->streams.ensure((size_t)r->max_streams * sizeof(pbsk::RingStreamState)));
-        CHK(r->pending.ensure((size_t)r->npages * 4 + 64));
-        CHK(r->desc.ensure((size_t)r->qslots * 32));
-        // optional long-chunk queue (PBSGPU_RING_LONG_BYTES, e.g. half the maximum chunk size = 8 % of the chunks, 30 % of the
-        // bytes of random data): idle lanes look at it first
-        // (OFF by default: measured +0.8 % on the bench line for +40 ms of single-file latency — the drain is not made of
-        // late-starting long chunks; kept as a switch)
-        r->long_bytes = r->xp_cus ? (long_bytes_hint ? long_bytes_hint : (uint32_t)((uint64_t)e->cfg.max * 13 / 16)) : 0;
-        r->long_lo_auto = long_bytes_hint == 0;  // (a ring with its own threshold — the stream writer's — keeps it)
-        if (o.long_bytes) r->long_bytes = o.long_bytes == PBSGPU_RING_OFF ? 0u : o.long_bytes;
-        if (r->xp_cus && r->long_bytes == 0) r->xp_cus = 0;  // (no long queue: nothing the express service could take)
-        r->lslots = pow2_at_least(2 * ((uint64_t)r->npages * r->page_bytes / std::max<uint32_t>(r->long_bytes, minsz) + r->rec_cap) + 1024);
-        CHK(r->ldesc.ensure((size_t)r->lslots * 32));
-        r->sslots = r->lanes_cus ? r->qslots : 2;
-        CHK(r->sdesc.ensure((size_t)r->sslots * 32));
-        CHK(r->scalars.ensure(pbsk::kRsCount * 4 + 64));
-        CHK(r->tile_cnt.ensure((size_t)ntiles * 4 + 16));
-        CHK(r->tile_off.ensure((size_t)ntiles * 4 + 16));
-        CHK(r->tile_slots.ensure((size_t)ntiles * r->cap * 4 + 16));
-        CHK(r->tileq.ensure(128 + kRingInputs * 8));  // two tile counters (64 bytes apart), then one refill counter per round in flight
-        const bool overlap = !(o.flags & PBSGPU_RING_F_NO_OVERLAP);
-        if (overlap) {
-            CHK(r->tile_cnt2.ensure((size_t)ntiles * 4 + 16));
-            CHK(r->tile_slots2.ensure((size_t)ntiles * r->cap * 4 + 16));
-        }
-        CHK(r->dense.ensure((size_t)r->dense_cap * 8 + 16));
-        CHK(r->scan_tmp.ensure(pbsk::scan_tmp_words(std::max<uint64_t>(ntiles, r->max_streams)) * 4 + 64));
-        CHK(r->segs.ensure((size_t)r->max_streams * sizeof(pbsgpu_segment)));
-        CHK(r->seg_cnt.ensure((size_t)r->max_streams * 4 + 16));
-        CHK(r->seg_off.ensure((size_t)r->max_streams * 4 + 16));
-        CHK(r->seg_newc.ensure((size_t)r->max_streams * 8 + 16));
-        CHK(r->seg_open.ensure((size_t)r->max_streams * 4 + 16));
-        CHK(r->seg_ecand_in.ensure((size_t)r->max_streams * 8 + 16));
-        CHK(r->seg_ecand.ensure((size_t)r->max_streams * 8 + 16));
-        CHK(r->recs.ensure((size_t)r->rec_cap * sizeof(pbsgpu_record) + 64));
-        CHK(r->cells.ensure((size_t)r->ncells * pbsk::kCellBytes));
-        CHK(r->heartbeat.ensure(256));
-        std::memset(r->heartbeat.p, 0, 256);
-        CHK(r->free_fifo.ensure((size_t)r->nfree * 8));
-        std::memset(r->free_fifo.p, 0, (size_t)r->nfree * 8);
-        auto al64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
-        r->in_pages_off = 0;
-        r->in_segs_off = al64((size_t)r->round_pages * sizeof(pbsk::RingPage));
-        r->in_recbase_off = al64(r->in_segs_off + (size_t)r->max_streams * sizeof(pbsk::RingSeg));
-        r->in_suggidx_off = al64(r->in_recbase_off + ((size_t)r->max_streams + 1) * 4);
-        r->in_status_off = al64(r->in_suggidx_off + ((size_t)r->max_streams + 1) * 4);
-        r->input_stride = r->in_status_off + 128;
-        CHK(r->inputs.ensure(r->input_stride * kRingInputs));
-        // PBSGPU_RING_F_NO_STAGE: the round's kernels read their tables from mapped host memory (rounds 3-4), for A/B runs
-        r->stage_inputs = !(o.flags & PBSGPU_RING_F_NO_STAGE);
-        if (r->stage_inputs) CHK(r->inputs_dev.ensure(r->input_stride * kRingInputs));
-        std::memset(r->inputs.p, 0, r->input_stride * kRingInputs);
-        // Three priorities: the services highest (their own hardware-queue pool: nothing may queue behind a kernel that only
-        // ends on request), the CONTROL side of the rounds normal, the producers of bulk work — synthetic refill, scan —
-        // lowest: the one-workgroup control kernel and its prep launch find a CU as soon as one frees up instead of waiting
-        // behind the next round's scan workgroups (kernel trace of the driver's command: k_ring_prep 1.2 ms and
-        // k_ring_control 1.1 ms per launch for 10 us / 170 us of work; PBSGPU_RING_CUT_PRIO=0: all normal).
-        int prio_lo = 0, prio_hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        const bool cut_prio = !(o.flags & PBSGPU_RING_F_NO_CUT_PRIO);
-        r->bulk_prio = cut_prio ? prio_lo : 0;
-        HIPCHK(hipStreamCreateWithFlags(&r->cs, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithPriority(&r->fs, hipStreamNonBlocking, r->bulk_prio));
-        // The device-side state starts from zero — cleared ON THE CONTROL STREAM and waited for. A plain hipMemset is
-        // queued on the null stream and returns at once for device memory; the ring's streams are non-blocking, i.e. not
-        // ordered against the null stream: when the null stream was held up (it waits for every blocking stream's earlier
-        // work, e.g. the previous engine's last kernels) the clear arrived AFTER the first rounds had run and wiped queue
-        // tail, stream states and page reference counts — pages never came back, lanes waited at positions the tail had
-        // been reset below (the one-in-a-few-hundred hang of the small-ring tests).
-        HIPCHK(hipMemsetAsync(r->ctl.p, 0, 256, r->cs));
-        HIPCHK(hipMemsetAsync(r->probe.p, 0, 128, r->cs));
-        HIPCHK(hipMemsetAsync(r->streams.p, 0, (size_t)r->max_streams * sizeof(pbsk::RingStreamState), r->cs));
-        HIPCHK(hipMemsetAsync(r->pending.p, 0, (size_t)r->npages * 4 + 64, r->cs));
-        HIPCHK(hipMemsetAsync(r->scalars.p, 0, pbsk::kRsCount * 4 + 64, r->cs));
-        HIPCHK(hipMemsetAsync(r->tileq.p, 0, 128 + kRingInputs * 8, r->cs));
-        HIPCHK(hipStreamSynchronize(r->cs));
-        for (auto &ev : r->ev_fill) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        if (overlap) {
-            HIPCHK(hipStreamCreateWithPriority(&r->ps, hipStreamNonBlocking, r->bulk_prio));
-            for (auto &ev : r->ev_scan) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            for (auto &ev : r->ev_ctl) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
-        // the service must never share a hardware queue with a stream that enqueues behind it (packets of one queue
-        // run in order: work queued behind a kernel that only ends on request would never start). HIP keeps one queue
-        // pool per priority: the service gets the highest priority to itself.
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&r->ss, hipStreamNonBlocking, hi));
-        if (r->xp_cus) {
-            HIPCHK(hipStreamCreateWithPriority(&r->xs, hipStreamNonBlocking, hi));
-            HIPCHK(hipEventCreateWithFlags(&r->ev_xsvc1, hipEventDisableTiming));
-        }
-        if (r->lanes_cus) {
-            HIPCHK(hipStreamCreateWithPriority(&r->ls, hipStreamNonBlocking, hi));
-            HIPCHK(hipEventCreateWithFlags(&r->ev_lsvc1, hipEventDisableTiming));
-        }
-        HIPCHK(hipEventCreateWithFlags(&r->ev_reset, hipEventDisableTiming));
-        HIPCHK(hipEventCreate(&r->ev_svc0));
-        HIPCHK(hipEventCreate(&r->ev_svc1));
-        r->slots.resize(r->max_streams);
-        r->piece_tab.resize(r->max_streams);
-        r->piece_n.assign(r->max_streams, 0);
-        r->free_pages.reserve(r->npages);
-        for (uint32_t p = r->npages; p-- > 0;) r->free_pages.push_back(p);  // page 0 is handed out first
-        r->hold = (o.flags & PBSGPU_RING_F_HOLD_PAGES) != 0;
-        if (r->hold) r->held.init(r->npages, r->max_streams, r->page_bytes);
-        r->st.pages_total = r->npages;
-        r->st.page_bytes = r->page_bytes;
-        r->st.sha_cus = r->sha_cus;
-        return PBSGPU_OK;
-    }();
+    const bool overlap = !(o.flags & PBSGPU_RING_F_NO_OVERLAP);
+    int st = ring_shape(r, o, long_bytes_hint);
+    if (st == PBSGPU_OK) st = ring_allocate(r, overlap);
+    if (st == PBSGPU_OK) st = ring_streams_and_events(r, overlap, !(o.flags & PBSGPU_RING_F_NO_CUT_PRIO));
     if (st != PBSGPU_OK) {
         pbsgpu_ring_destroy(r);
         return st;
     }
+    r->slots.resize(r->max_streams);
+    r->piece_tab.resize(r->max_streams);
+    r->piece_n.assign(r->max_streams, 0);
+    r->free_pages.reserve(r->npages);
+    for (uint32_t p = r->npages; p-- > 0;) r->free_pages.push_back(p);  // page 0 is handed out first
+    r->hold = (o.flags & PBSGPU_RING_F_HOLD_PAGES) != 0;
+    if (r->hold) r->held.init(r->npages, r->max_streams, r->page_bytes);
+    r->st.pages_total = r->npages;
+    r->st.page_bytes = r->page_bytes;
+    r->st.sha_cus = r->sha_cus;
     *out = r;
     return PBSGPU_OK;
 }
@@ -1085,7 +936,7 @@ int pbsgpu_ring_quiesce(pbsgpu_ring *r) {
         return r->error;
     }
     if (r->svc == SvcState::Stopped && r->deferred_bytes > 0) {
-        // rounds were cut AHEAD of the service (a lone bulk stream on an idle ring: ring_enqueue_round): their chunks sit in
+        // rounds were cut AHEAD of the service (a lone bulk stream on an idle ring: pbsp::defer_decision): their chunks sit in
         // the queue with no service to hash them. "Everything enqueued is hashed" needs one: start it, then stop it behind
         // what is published, like a running one (round 5; before that fill -> pump -> quiesce -> poll saw no records)
         CHK(ring_start_service(r, true));
@@ -1545,7 +1396,7 @@ int pbsgpu_ring_pump(pbsgpu_ring *r) {
         // the deferral has lasted long enough
         bool waiting = false;
         for (auto &s : r->slots) waiting |= s.open && !s.ready.empty();
-        const uint64_t lanes_worth = (uint64_t)r->sha_cus * (r->dense_service ? 256u : 128u) * (uint64_t)r->eng->cfg.avg;
+        const uint64_t lanes_worth = pbsp::lanes_worth(r->sha_cus, r->dense_service, r->eng->cfg.avg);
         // (Round 5 tried a 1 ms grace before "nothing waiting" ends the deferral — a feeder that commits a round's worth, pumps
         // and polls in a loop has nothing waiting after every pump, so its cut-ahead ends with the first poll: the file's last
         // bytes are cut ~7 ms sooner, its first chunks start ~25 ms later; one file alone 487-500 vs 496-502 ms on the same box,

@@ -9,13 +9,14 @@
 
 #include "engine_internal.h"
 #include "hold.h"
+#include "ring_plan.h"
 
 namespace pbse {
 
 constexpr uint32_t kRingInputs = 16;            // rounds whose host-written tables may be in flight
 constexpr uint32_t kPagesPerStreamRound = 256;  // < kRingPT - 2 (open chunk). It was 48 until a lone 64 GiB file turned out to
                                                 // go through 83 small rounds, none of them large enough for the cut-ahead at
-                                                // full chip width (ring_enqueue_round): a whole default round per stream now
+                                                // full chip width (pbsp::defer_decision): a whole default round per stream now
 
 struct PageReq {                          // a committed page waiting for its round
     uint32_t phys = 0;
@@ -72,38 +73,26 @@ enum class SvcState { Stopped, Running, Stopping };
 
 }  // namespace pbse
 
-struct pbsgpu_ring {
+struct pbsgpu_ring : pbsp::RingShape {  // (geometry, CU split, round and queue sizes: decided by pbsp::shape_ring at creation)
     pbsgpu_engine *eng = nullptr;
     bool holds_engine_ref = true;         // false for the engine's own ring (the engine owns it, not the reverse)
     std::mutex mu;                        // taken by the stream writer around every use (the C ABI's ring calls are
                                           // single-threaded by contract and do not lock)
-    // geometry
-    uint64_t page_bytes = 0, stride = 0;
-    uint32_t tile_bytes = 0, tpp = 0, npages = 0, max_streams = 0, sha_cus = 0, round_pages = 0, min_round_pages = 0, cap = 0;
-    uint32_t max_inflight = 3;
-    // backlog gate: no page is handed out while more than this many bytes wait in front of the service — committed pages
-    // not yet in a round, rounds in flight, published chunks no lane has claimed. A full arena of unhashed chunks feeds
-    // the service no faster than a short queue does; it only adds its length to every latency (and to the final drain).
-    uint64_t backlog_limit = 0;
+    // what the backlog gate (RingShape::backlog_limit) weighs
     uint64_t ready_bytes = 0, inflight_bytes = 0;
     uint32_t tail_seen = 0;               // queue tail after the last reaped round
     uint64_t pub_positions = 0, pub_bytes = 0;  // queue positions / stream bytes of all reaped rounds (average chunk size)
-    uint64_t rec_cap = 0, dense_cap = 0;
-    uint32_t qslots = 0, ncells = 0, nfree = 0;
     // device
     pbse::DevBuf arena, ctl, streams, pending, desc, ldesc, sdesc, probe;
     unsigned long long probe_seen[6] = {};  // the probe counters as the newest reaped round reported them (pbsgpu_ring_get_probe)
     bool probe_seen_valid = false;
     unsigned long long ctl_phase_ticks[2][5] = {};  // k_ring_control's phase times summed over the reaped rounds (small / large rounds)
     unsigned long long ctl_phase_rounds[2] = {};
-    uint32_t lslots = 0, long_bytes = 0;
-    uint32_t sslots = 0, short_bytes = 0, lanes_cus = 0;  // the LANES service and its short-chunk queue (kernels.h: RingSource::sdesc)
     pbse::DevBuf scalars, tile_cnt, tile_off, tile_slots, scan_tmp, dense, segs, seg_cnt, seg_off, recs, seg_newc, seg_open;
     pbse::DevBuf tile_cnt2, tile_slots2, tileq;  // second set of the scan side (rounds alternate) + the two tile-queue counters
     pbse::DevBuf seg_ecand_in, seg_ecand;
     pbse::DevBuf inputs_dev;  // device mirror of `inputs` (the round tables are staged once per round: k_ring_stage)
     bool stage_inputs = true;
-    bool long_lo_auto = false;  // RingSource::long_lo from the chunker's maximum (bulk rings)
     // mapped pinned
     pbse::PinnedBuf cells, free_fifo, inputs, heartbeat;
     std::vector<pbse::PinnedBuf> piece_tab;      // per stream slot: the piece table of a synthetic edited stream (fill_pieces)
@@ -120,14 +109,7 @@ struct pbsgpu_ring {
     bool ctl_used[2] = {false, false};
     uint32_t scan_set = 0;                // scan set of the next round
     int bulk_prio = 0;                    // HIP priority of the refill and scan streams (lowest: the control side goes first)
-    uint32_t xp_cus = 0;
-    // The split between the two services follows the DATA (round 5): the share of the published bytes that sits in long
-    // chunks (>= long_bytes) is observed as rounds are reaped, and every service START — the ring was idle, nothing is in
-    // flight, the change is free — picks the express share that balances the two services' CU-time for that share
-    // (ring_adapt_split). Only when neither the options nor the environment fixed the counts.
-    bool split_auto = false;
-    uint32_t svc_cus = 0;                 // CUs of both services together (constant)
-    double obs_bytes = 0, obs_long_bytes = 0;
+    double obs_bytes = 0, obs_long_bytes = 0;  // published bytes / those in long chunks since the last split decision (ring_adapt_split)
     hipEvent_t ev_reset = nullptr, ev_svc0 = nullptr, ev_svc1 = nullptr, ev_xsvc1 = nullptr, ev_lsvc1 = nullptr;
     hipEvent_t ev_fill[pbse::kRingInputs] = {};
     std::vector<hipEvent_t> ev_pool;      // page dependency events (ring_event_get / ring_event_put)
@@ -135,22 +117,15 @@ struct pbsgpu_ring {
     uint32_t rounds_enq = 0;              // mirrored into the heartbeat block for the service's self-stop handshake
     double autopark_ms = 0;               // > 0: stop the service when the ring has been idle this long (engine ring of the stream writer)
     double idle_since_ms = 0;
-    bool dense_service = false;           // PBSGPU_RING_F_DENSE_SERVICE
-    bool dense_lanes = false;             // PBSGPU_RING_F_DENSE_LANES
-    bool tier_tag = false;                // PBSGPU_RING_F_TIER_TAG
-    bool backlog_auto = true;             // backlog_limit derived from sha_cus (follows ring_adapt_split)
     uint32_t park_gen_seen = 0;           // last graveyard park request this ring honoured (engine_internal.h: dev_free)
     uint32_t park_grace_gen = 0;          // the park request this ring has already waited its grace period for (ring_start_service)
     double park_wait_t0 = 0;              // since when a start has been waiting for the other rings of the device to let go (ring_start_service)
     bool parked_for_flush = false;        // ... and its service was parked for it: the next start waits for that service's END
-    bool fill_serial = false;             // PBSGPU_RING_F_FILL_SERIAL
     bool hold = false;                    // PBSGPU_RING_F_HOLD_PAGES: handed-back pages wait in `held` for pbsgpu_ring_release
     pbse::HeldPages held;
     uint32_t opt_long_lo = 0, opt_long_spill = 0, opt_poll_every = 0;  // pbsgpu_ring_options (0 = the default rule)
-    uint32_t opt_fill_cus = 0;            // pbsgpu_ring_options::fill_cus (0 = the rule in ring_enqueue_round)
+    uint32_t opt_fill_cus = 0;            // pbsgpu_ring_options::fill_cus (0 = the rule in pbsp::cut_partition)
     uint32_t rounds_since_fill = 1000;    // rounds enqueued since the last one with pages for the synthetic refill
-    bool defer_service = false;           // PBSGPU_RING_F_DEFER_SERVICE (profiling): rounds only enqueue; quiesce runs the service ALONE
-    double lone_defer_ms = 25.0;          // a lone bulk stream's rounds are cut ahead of the service start for at most this long (0 = off)
     double defer_t0 = 0;                  // when the current deferral began (0 = none)
     uint64_t deferred_bytes = 0;          // bytes cut while no service was running (they are the next launch's work)
     double idle_timeout_s = 0;            // > 0: the service's own idle stop (pbsgpu_ring_options::idle_timeout_s; default 20 s)
