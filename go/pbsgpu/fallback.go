@@ -275,6 +275,40 @@ func (e *Engine) EncodeZstd(unsafe.Pointer, uint64, []uint64, []uint64, []uint64
 	return nil, nil, ErrNotBuilt
 }
 
+// ZstdBadChecksum is DecodeZstd2's status for a frame that decoded, but not to what its content checksum says.
+const ZstdBadChecksum = 4
+
+// Flags of DecodeZstd2 and EncodeZstd2.
+const (
+	ZstdFlagChecksum = 1
+	ZstdFlagStream   = 2
+)
+
+// ZstdStream is what the headers of a whole zstd stream declare.
+type ZstdStream struct {
+	Status         int
+	ContentSize    uint64
+	HasContentSize bool
+	Frames         uint32
+	Skippable      uint32
+	AnyChecksum    bool
+}
+
+func ZstdStreamInfo([]byte) (ZstdStream, error) { return ZstdStream{}, ErrNotBuilt }
+func (e *Engine) XXH64Device(unsafe.Pointer, uint64, []uint64, []uint64, uint64) ([]uint64, error) {
+	return nil, ErrNotBuilt
+}
+func (e *Engine) DecodeZstd2(unsafe.Pointer, uint64, []uint64, []uint64, []uint64, []uint64, unsafe.Pointer, uint64, uint32) ([]uint8, []uint64, error) {
+	return nil, nil, ErrNotBuilt
+}
+
+// ZstdEncodeBound2 is ZstdEncodeBound for EncodeZstd2 with the same flags.
+func ZstdEncodeBound2(n uint64, flags uint32) uint64 { return 0 }
+
+func (e *Engine) EncodeZstd2(unsafe.Pointer, uint64, []uint64, []uint64, []uint64, []uint64, unsafe.Pointer, uint64, uint32) ([]uint8, []uint64, error) {
+	return nil, nil, ErrNotBuilt
+}
+
 // EncodeStats counts what EncodeBlobs2 wrote, per kind (index 0 uncompressed, 1 compressed).
 type EncodeStats struct {
 	Blobs, BlobBytes, ChunkBytes [2]uint64

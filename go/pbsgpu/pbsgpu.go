@@ -1704,6 +1704,123 @@ func (e *Engine) EncodeZstd(dptr unsafe.Pointer, nbytes uint64, offsets, lengths
 	return status[:len(segs)], frameLen[:len(segs)], nil
 }
 
+// ZstdBadChecksum is DecodeZstd2's status for a frame that decoded, but not to what its content checksum says
+// (PBSGPU_ZSTD_BAD_CHECKSUM).
+const ZstdBadChecksum = 4
+
+// Flags of DecodeZstd2 and EncodeZstd2 (PBSGPU_ZSTD_F_*).
+const (
+	ZstdFlagChecksum = 1 // verify, or write, the frame's content checksum
+	ZstdFlagStream   = 2 // DecodeZstd2 only: every segment is a whole zstd stream
+)
+
+// ZstdStream is what the headers of a whole zstd stream declare. ContentSize, the sum over the frames, is valid when
+// HasContentSize is set: when every frame declares its size.
+type ZstdStream struct {
+	Status         int
+	ContentSize    uint64
+	HasContentSize bool
+	Frames         uint32
+	Skippable      uint32
+	AnyChecksum    bool
+}
+
+// ZstdStreamInfo walks the headers of the zstd stream in `stream` (host only): what a caller without an index sizes the
+// destination of DecodeZstd2 with ZstdFlagStream with.
+func ZstdStreamInfo(stream []byte) (ZstdStream, error) {
+	var size C.uint64_t
+	var nf, ns C.uint32_t
+	var ck C.int
+	var p *C.uint8_t
+	if len(stream) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&stream[0]))
+	}
+	st := C.pbsgpu_zstd_stream_info(p, C.uint64_t(len(stream)), &size, &nf, &ns, &ck)
+	if st < 0 {
+		return ZstdStream{}, check(st, "zstd_stream_info")
+	}
+	return ZstdStream{Status: int(st), ContentSize: uint64(size), HasContentSize: uint64(size) != ^uint64(0), Frames: uint32(nf),
+		Skippable: uint32(ns), AnyChecksum: ck != 0}, nil
+}
+
+// XXH64Device hashes the ranges (offsets, lengths) of a device buffer with XXH64 and `seed` in one call: what a zstd
+// frame's content checksum is the low 32 bits of (seed 0). Ranges may be empty, unaligned and overlapping.
+func (e *Engine) XXH64Device(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, seed uint64) ([]uint64, error) {
+	defer runtime.KeepAlive(e)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]uint64, len(segs)+1)
+	var sp *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp = &segs[0]
+	}
+	err = check(C.pbsgpu_xxh64_many_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), C.uint64_t(seed),
+		(*C.uint64_t)(unsafe.Pointer(&out[0]))), "xxh64_many_device")
+	if err != nil {
+		return nil, err
+	}
+	return out[:len(segs)], nil
+}
+
+// zstdBatch is what DecodeZstd2 and EncodeZstd2 share: the segments, one room each, the result arrays, the call.
+func zstdBatch(who string, offsets, lengths, outOffsets, outRooms []uint64,
+	call func(sp *C.pbsgpu_segment, n C.uint32_t, op *C.pbsgpu_segment, status *C.uint8_t, lens *C.uint64_t) C.int) ([]uint8, []uint64, error) {
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, nil, err
+	}
+	outs, err := toSegments(outOffsets, outRooms)
+	if err != nil {
+		return nil, nil, err
+	}
+	if len(outs) != len(segs) {
+		return nil, nil, errors.New("pbsgpu: " + who + " needs one destination per segment")
+	}
+	status := make([]uint8, len(segs)+1)
+	lens := make([]uint64, len(segs)+1)
+	var sp, op *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp, op = &segs[0], &outs[0]
+	}
+	if err := check(call(sp, C.uint32_t(len(segs)), op, (*C.uint8_t)(unsafe.Pointer(&status[0])), (*C.uint64_t)(unsafe.Pointer(&lens[0]))), who); err != nil {
+		return nil, nil, err
+	}
+	return status[:len(segs)], lens[:len(segs)], nil
+}
+
+// DecodeZstd2 is DecodeZstd with flags, for frames that are not blobs of an index (the same call sites:
+// internal/server/verification/job.go:931-966, internal/pxar/format.go:101-129). With ZstdFlagChecksum a frame that carries a
+// content checksum is checked against it (ZstdBadChecksum, 0 bytes decoded); with ZstdFlagStream every segment is a whole
+// zstd stream, decoded as ZSTD_decompress does it: frames one after the other, skippable frames skipped, an empty segment
+// ZstdOK with 0 bytes. With flags 0 it is DecodeZstd, output for output.
+func (e *Engine) DecodeZstd2(dptr unsafe.Pointer, nbytes uint64, offsets, lengths, outOffsets, outRooms []uint64, dst unsafe.Pointer,
+	dstCap uint64, flags uint32) ([]uint8, []uint64, error) {
+	defer runtime.KeepAlive(e)
+	return zstdBatch("zstd_decode2_device", offsets, lengths, outOffsets, outRooms,
+		func(sp *C.pbsgpu_segment, n C.uint32_t, op *C.pbsgpu_segment, status *C.uint8_t, lens *C.uint64_t) C.int {
+			return C.pbsgpu_zstd_decode2_device(e.h, dptr, C.uint64_t(nbytes), sp, n, op, dst, C.uint64_t(dstCap), status, lens, C.uint32_t(flags))
+		})
+}
+
+// ZstdEncodeBound2 is ZstdEncodeBound for EncodeZstd2 with the same flags: 4 bytes more with ZstdFlagChecksum (host only).
+func ZstdEncodeBound2(n uint64, flags uint32) uint64 {
+	return uint64(C.pbsgpu_zstd_encode_bound2(C.uint64_t(n), C.uint32_t(flags)))
+}
+
+// EncodeZstd2 is EncodeZstd with flags, for the same writers (internal/tapeio/converter.go:399, :410-435) when the frames are
+// kept outside a blob: with ZstdFlagChecksum every frame carries its content checksum, 4 bytes more (ZstdEncodeBound2). With
+// flags 0 it is EncodeZstd.
+func (e *Engine) EncodeZstd2(dptr unsafe.Pointer, nbytes uint64, offsets, lengths, outOffsets, outRooms []uint64, dst unsafe.Pointer,
+	dstCap uint64, flags uint32) ([]uint8, []uint64, error) {
+	defer runtime.KeepAlive(e)
+	return zstdBatch("zstd_encode2_device", offsets, lengths, outOffsets, outRooms,
+		func(sp *C.pbsgpu_segment, n C.uint32_t, op *C.pbsgpu_segment, status *C.uint8_t, lens *C.uint64_t) C.int {
+			return C.pbsgpu_zstd_encode2_device(e.h, dptr, C.uint64_t(nbytes), sp, n, op, dst, C.uint64_t(dstCap), status, lens, C.uint32_t(flags))
+		})
+}
+
 // EncodeStats counts what EncodeBlobs2 wrote, per kind (index 0 uncompressed, 1 compressed).
 type EncodeStats struct {
 	Blobs, BlobBytes, ChunkBytes [2]uint64

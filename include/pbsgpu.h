@@ -795,6 +795,47 @@ int pbsgpu_zstd_decode_device(pbsgpu_engine *eng, const void *src, uint64_t nbyt
                               void *dst, uint64_t dst_cap, uint8_t *status /* nframe */,
                               uint64_t *decoded /* nframe, may be NULL */);
 
+/* ---- zstd content checksums and whole streams ---------------------------------------------------------------------------
+ * For the same call sites as above (internal/server/verification/job.go:931-966, internal/pxar/format.go:101-129,
+ * internal/pxarmount/commit_orchestrate.go:356-368, internal/pxar/client.go:236) when a frame is NOT a blob of an index:
+ * there no CRC-32 and no digest cover it, and the frame's own content checksum (the low 32 bits of XXH64 of the content,
+ * seed 0) is all there is. pbsgpu_zstd_decode_device and pbsgpu_blob_decode2_device are unchanged: inside a restore the
+ * blob's CRC covers the frame and the index digest covers the content, so the restore still does not verify the frame's
+ * checksum. DESIGN.md §20. */
+#define PBSGPU_HAS_ZSTD_CHECKSUM 1
+#define PBSGPU_ZSTD_BAD_CHECKSUM 4 /* pbsgpu_zstd_decode2_device with F_CHECKSUM only: decoded, but not to what the frame's checksum says */
+#define PBSGPU_ZSTD_F_CHECKSUM 1u
+#define PBSGPU_ZSTD_F_STREAM 2u
+/* out[i] = XXH64 with `seed` of dptr[segs[i].offset .. +length): the sibling of pbsgpu_xxh3_many_device. Ranges may have any
+ * length (0 included) and alignment and may overlap. Argument checks as for pbsgpu_crc32_many_device and
+ * pbsgpu_xxh3_many_device. Four lanes per range (pbs_plus_amd/csrc/xxh64.h); one leased stream, ONE synchronisation. */
+int pbsgpu_xxh64_many_device(pbsgpu_engine *eng, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                             uint32_t nseg, uint64_t seed, uint64_t *out /* nseg, host */);
+/* pbsgpu_zstd_decode_device with flags. flags = 0 is that call, output for output. An unknown bit is PBSGPU_E_INVALID.
+ *   PBSGPU_ZSTD_F_CHECKSUM  a frame that carries a content checksum is checked against it after everything else about the
+ *       frame is OK (libzstd's order). A mismatch is PBSGPU_ZSTD_BAD_CHECKSUM with decoded[i] = 0; the contents of out[i]
+ *       are then unspecified and nothing outside it is written. A frame without a checksum is unaffected.
+ *   PBSGPU_ZSTD_F_STREAM    segment i is a whole zstd stream, decoded as ZSTD_decompress does it: its frames one after the
+ *       other into out[i]; skippable frames (magic 0x184D2A5?, a 4-byte length) skipped; an empty segment or skippable
+ *       frames alone are OK with 0 bytes. status[i] is that of the first frame that is not OK. A skippable frame cut short,
+ *       trailing bytes that are no frame and an unknown magic are BAD_FRAME; only a dictionary id stays UNSUPPORTED. An
+ *       offset may not reach in front of ITS OWN frame's first output byte: libzstd's one-shot call lets a later frame
+ *       reach into the output of the frame before it, this call answers BAD_FRAME. A deliberate difference.
+ *   With both, every frame's checksum is checked.
+ * Everything else as for pbsgpu_zstd_decode_device: the refusals, one wave per segment, one leased stream, ONE
+ * synchronisation, usable between the pumps of a running ring. The verdict is the device's. */
+int pbsgpu_zstd_decode2_device(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const pbsgpu_segment *frames,
+                               uint32_t nframe, const pbsgpu_segment *out /* nframe: offset and room inside dst */,
+                               void *dst, uint64_t dst_cap, uint8_t *status /* nframe */,
+                               uint64_t *decoded /* nframe, may be NULL */, uint32_t flags);
+/* What the headers of the stream at stream[0, nbytes) declare, for sizing a destination of pbsgpu_zstd_decode2_device with
+ * F_STREAM without an index; returns a PBSGPU_ZSTD_* status as the headers alone decide it (PBSGPU_E_INVALID for a NULL
+ * stream). *content_size = the sum over the frames, UINT64_MAX if any frame declares none; *nframes and *nskippable count
+ * what was walked (also up to a failure); *any_checksum = 1 if a frame carries a checksum. Frame and block headers are
+ * walked, nothing is decoded. Every out pointer may be NULL. Host only. */
+int pbsgpu_zstd_stream_info(const uint8_t *stream, uint64_t nbytes, uint64_t *content_size /* sum; UINT64_MAX if any frame declares none */,
+                            uint32_t *nframes, uint32_t *nskippable, int *any_checksum);
+
 /* Restore with the compressed blobs decoded: pbsgpu_blob_decode_device's arguments with `int check_digest` replaced by
  * flags, and statistics with two more fields. The same call sites (internal/server/verification/job.go:931-966,
  * internal/pxar/format.go:101-129, internal/pxarmount/commit_orchestrate.go:356-368, internal/pxar/client.go:236), now for
@@ -876,6 +917,18 @@ uint64_t pbsgpu_zstd_encode_bound(uint64_t n);
 int pbsgpu_zstd_encode_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *chunks,
                               uint32_t n, const pbsgpu_segment *out /* n: offset and room inside dst */, void *dst,
                               uint64_t dst_cap, uint8_t *status /* n */, uint64_t *frame_len /* n, may be NULL */);
+/* pbsgpu_zstd_encode_device with flags, for the same writers (internal/tapeio/converter.go:399, 410-435) when the frames are
+ * kept outside a blob. flags = 0 is that call. With PBSGPU_ZSTD_F_CHECKSUM the frame is that call's frame for the same
+ * engine (whatever zstd_seq_tables and zstd_window_log are) with bit 2 of the frame header descriptor (byte 4) set and the
+ * low 32 bits of XXH64(content, 0) behind the last block, little endian; frame_len[i] counts them, and a room of
+ * pbsgpu_zstd_encode_bound2(length, flags) always suffices. The checksum is taken from the chunk's source bytes on the same
+ * stream, before the frame is put together. Any other bit is PBSGPU_E_INVALID. The blob and fused upload calls write no
+ * checksum: a blob's CRC-32 covers its frame. */
+uint64_t pbsgpu_zstd_encode_bound2(uint64_t n, uint32_t flags);
+int pbsgpu_zstd_encode2_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *chunks,
+                               uint32_t n, const pbsgpu_segment *out /* n: offset and room inside dst */, void *dst,
+                               uint64_t dst_cap, uint8_t *status /* n */, uint64_t *frame_len /* n, may be NULL */,
+                               uint32_t flags);
 /* pbsgpu_blob_encode_device with the blob's kind decided on the device. Without PBSGPU_ENCODE_F_ZSTD it is that call output
  * for output (dst, offsets, crcs), with lens[i] = 12 + length and kinds[i] = PBSGPU_BLOB_UNCOMPRESSED. With it, blob i lies
  * in the same slot [offsets[i], offsets[i] + 12 + length) that the uncompressed layout gives it, and the verdict is the one

@@ -390,6 +390,67 @@ inline Result<ZstdEncoded> EncodeZstd(pbsgpu_engine *eng, const void *src, uint6
     return r;
 }
 
+// DecodeZstd with flags (PBSGPU_ZSTD_F_CHECKSUM: a frame's content checksum is verified, PBSGPU_ZSTD_BAD_CHECKSUM;
+// PBSGPU_ZSTD_F_STREAM: every segment is a whole zstd stream, decoded as ZSTD_decompress does it), for frames that are not
+// blobs of an index. flags = 0 is DecodeZstd, output for output.
+inline Result<ZstdDecoded> DecodeZstd2(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const std::vector<pbsgpu_segment> &frames,
+                                       const std::vector<pbsgpu_segment> &out, void *dst, uint64_t dstCap, uint32_t flags) {
+    Result<ZstdDecoded> r;
+    r.value.status.resize(frames.size() + 1);
+    r.value.decoded.resize(frames.size() + 1);
+    const int st = out.size() != frames.size() ? PBSGPU_E_INVALID
+                 : pbsgpu_zstd_decode2_device(eng, src, nbytes, frames.data(), (uint32_t)frames.size(), out.data(), dst, dstCap,
+                                              r.value.status.data(), r.value.decoded.data(), flags);
+    r.value.status.resize(frames.size());
+    r.value.decoded.resize(frames.size());
+    if (st != PBSGPU_OK) r.err = errorf("zstd decode2", st);
+    return r;
+}
+
+// EncodeZstd with flags (PBSGPU_ZSTD_F_CHECKSUM: every frame carries its content checksum, 4 bytes more; a room of
+// pbsgpu_zstd_encode_bound2(length, flags) always suffices). flags = 0 is EncodeZstd.
+inline Result<ZstdEncoded> EncodeZstd2(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const std::vector<pbsgpu_segment> &chunks,
+                                       const std::vector<pbsgpu_segment> &out, void *dst, uint64_t dstCap, uint32_t flags) {
+    Result<ZstdEncoded> r;
+    r.value.status.resize(chunks.size() + 1);
+    r.value.frameLen.resize(chunks.size() + 1);
+    const int st = out.size() != chunks.size() ? PBSGPU_E_INVALID
+                 : pbsgpu_zstd_encode2_device(eng, src, nbytes, chunks.data(), (uint32_t)chunks.size(), out.data(), dst, dstCap,
+                                              r.value.status.data(), r.value.frameLen.data(), flags);
+    r.value.status.resize(chunks.size());
+    r.value.frameLen.resize(chunks.size());
+    if (st != PBSGPU_OK) r.err = errorf("zstd encode2", st);
+    return r;
+}
+
+// XXH64 with `seed` of many ranges of a device buffer in one call: what a zstd frame's content checksum is the low 32 bits
+// of (seed 0).
+inline Result<std::vector<uint64_t>> XXH64Device(pbsgpu_engine *eng, const void *src, uint64_t nbytes,
+                                                 const std::vector<pbsgpu_segment> &segs, uint64_t seed = 0) {
+    Result<std::vector<uint64_t>> r;
+    r.value.resize(segs.size() + 1);
+    const int st = pbsgpu_xxh64_many_device(eng, src, nbytes, segs.data(), (uint32_t)segs.size(), seed, r.value.data());
+    r.value.resize(segs.size());
+    if (st != PBSGPU_OK) r.err = errorf("xxh64", st);
+    return r;
+}
+
+struct ZstdStream {
+    int status = 0;             // PBSGPU_ZSTD_* as the headers alone decide it
+    uint64_t contentSize = 0;   // the sum over the frames; UINT64_MAX if a frame declares none
+    uint32_t frames = 0, skippable = 0;
+    bool anyChecksum = false;
+};
+
+// what the headers of a whole zstd stream declare (host only): sizes the destination of DecodeZstd2 with PBSGPU_ZSTD_F_STREAM
+inline ZstdStream ZstdStreamInfo(const uint8_t *stream, uint64_t nbytes) {
+    ZstdStream s;
+    int any = 0;
+    s.status = pbsgpu_zstd_stream_info(stream, nbytes, &s.contentSize, &s.frames, &s.skippable, &any);
+    s.anyChecksum = any != 0;
+    return s;
+}
+
 struct Encoded2 {
     std::vector<uint64_t> offsets;  // segs.size() + 1: blob i lies at offsets[i], in the slot the uncompressed layout gives it
     std::vector<uint32_t> lens;     // the blob's length: what is sent

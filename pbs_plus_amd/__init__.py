@@ -16,6 +16,8 @@ pbs-plus reference uses for its pxar stream path:
 * ``Engine.zstd_decode`` / ``zstd_frame_info`` — the zstd frames behind the compressed blobs, decoded on the device
 * ``Engine.zstd_encode`` / ``blob_encode2`` / ``zstd_encode_bound`` — chunks compressed to zstd frames on the device and
   framed as blobs whose kind the device decides
+* ``Engine.zstd_decode2`` / ``zstd_encode2`` / ``xxh64_many`` / ``zstd_stream_info`` / ``zstd_encode_bound2`` — the frame's
+  content checksum verified and written, whole zstd streams decoded, for frames that are not blobs of an index
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
@@ -23,6 +25,8 @@ from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
 from .engine import Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
 from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine, zstd_encode_bound, zstd_frame_info  # noqa: F401
+from .engine import zstd_encode_bound2, zstd_stream_info  # noqa: F401
 
 __all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError",
-           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine", "zstd_encode_bound", "zstd_frame_info"]
+           "blob_index", "blob_magic", "chunk_ranges", "crc32_combine", "zstd_encode_bound", "zstd_frame_info",
+           "zstd_encode_bound2", "zstd_stream_info"]

@@ -152,6 +152,8 @@ class DecodeStats2(C.Structure):
 
 ZSTD_OK, ZSTD_BAD_FRAME, ZSTD_BAD_SIZE, ZSTD_UNSUPPORTED = range(4)
 ZSTD_STATUS_NAMES = ("ok", "bad_frame", "bad_size", "unsupported")
+ZSTD_BAD_CHECKSUM = 4  # zstd_decode2(checksum=True) only
+ZSTD_F_CHECKSUM, ZSTD_F_STREAM = 1, 2
 ENCODE_F_ZSTD = 1
 
 
@@ -280,6 +282,11 @@ SYMBOLS = {
     "pbsgpu_zstd_frame_info": (C.c_int, [_P, C.c_uint64, _U64P, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "pbsgpu_zstd_decode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
     "pbsgpu_zstd_encode_bound": (C.c_uint64, [C.c_uint64]),
+    "pbsgpu_xxh64_many_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint64, _P]),
+    "pbsgpu_zstd_decode2_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, C.c_uint32]),
+    "pbsgpu_zstd_stream_info": (C.c_int, [_P, C.c_uint64, _U64P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "pbsgpu_zstd_encode_bound2": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "pbsgpu_zstd_encode2_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P, C.c_uint32]),
     "pbsgpu_zstd_encode_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, _P, C.c_uint64, _P, _P]),
     "pbsgpu_blob_encode2_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P, _P]),
     "pbsgpu_ring_upload_new_device": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, _P, _P, _U64P,

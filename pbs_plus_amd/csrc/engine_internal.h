@@ -372,8 +372,10 @@ constexpr uint32_t kNoJob = 0xffffffffu;
 // blob = true: room is the chunk's length; PBSGPU_BLOB_COMPRESSED when the frame is strictly shorter than the chunk and
 // was written, PBSGPU_BLOB_UNCOMPRESSED (nothing written) otherwise. Takes its arrays from the slot's
 // scratch. jobs: src_off, dst_off, room and len from the caller, one part each; the rest is filled in here.
+// sums (device, n, may be nullptr): XXH64 of each chunk's content, made on the same stream before; every frame then
+// carries the content checksum (4 bytes more; pbsgpu_zstd_encode2_device).
 int enqueue(pbsgpu_engine *e, pbse::Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob,
-            uint64_t **res_dev);
+            uint64_t **res_dev, const uint64_t *sums = nullptr);
 // The same in three steps for a caller that has a kernel of its own fill in what only the device knows of a job (blob.hip's
 // fused upload): prepare() plans the blocks from the jobs' `len` and says how much room each array needs;
 // carve() takes that room from the slot's scratch and copies the jobs and the block table to it; launch() enqueues the
@@ -397,7 +399,8 @@ struct Prep {
 };
 int prepare(pbsgpu_engine *e, std::vector<Job> &jobs, bool two_parts, Prep &p);  // PBSGPU_E_INVALID: 2^32 blocks or more
 int carve(pbse::Slot *s, const Prep &p, const std::vector<Job> &jobs, Room &room);
-int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob);
+int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob,
+           const uint64_t *sums = nullptr);
 }  // namespace zenc
 }  // namespace pbsk
 namespace pbse {

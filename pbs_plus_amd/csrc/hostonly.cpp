@@ -6,6 +6,7 @@
 #include "../../include/pbsgpu.h"
 #include "zstd_decode.h"
 #include "zstd_encode.h"
+#include "zstd_stream.h"
 
 namespace {
 
@@ -139,6 +140,24 @@ int pbsgpu_zstd_frame_info(const uint8_t *frame, uint64_t nbytes, uint64_t *cont
 }
 
 uint64_t pbsgpu_zstd_encode_bound(uint64_t n) { return pbsz::enc::encode_bound(n); }
+
+uint64_t pbsgpu_zstd_encode_bound2(uint64_t n, uint32_t flags) {
+    return pbsz::enc::encode_bound2(n, (flags & PBSGPU_ZSTD_F_CHECKSUM) != 0);
+}
+
+int pbsgpu_zstd_stream_info(const uint8_t *stream, uint64_t nbytes, uint64_t *content_size, uint32_t *nframes,
+                            uint32_t *nskippable, int *any_checksum) {
+    if (!stream && nbytes) return PBSGPU_E_INVALID;
+    uint64_t content = 0;
+    uint32_t nf = 0, ns = 0;
+    int any = 0;
+    const int st = pbsz::stream_info(stream, nbytes, &content, &nf, &ns, &any);
+    if (content_size) *content_size = content;
+    if (nframes) *nframes = nf;
+    if (nskippable) *nskippable = ns;
+    if (any_checksum) *any_checksum = any;
+    return st;
+}
 
 int pbsgpu_payload_format_default(pbsgpu_payload_format *out) {
     if (!out) return PBSGPU_E_INVALID;

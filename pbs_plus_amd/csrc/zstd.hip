@@ -20,39 +20,14 @@
 #include <cstring>
 #include <vector>
 
-#include "engine_internal.h"
-#include "zstd_decode.h"
+#include "zstd_frames.h"
 
 using namespace pbse;
 
 namespace pbsk {
 namespace zstd {
 
-struct Desc {  // one frame: where it lies in src, and its room in dst (src_len = kSkip: no frame, the result says so)
-    uint64_t src_off, src_len, dst_off, room;
-};
-constexpr uint64_t kSkip = ~0ull;
-
-struct Plan {
-    const uint8_t *src;
-    const Desc *desc;  // nframe
-    uint8_t *dst;
-    uint8_t *lit;      // gridDim.x * kLitMax
-    uint64_t *res;     // nframe: status << 32 | bytes decoded
-    uint32_t nframe;
-    uint32_t stride;   // = gridDim.x
-};
-
-struct WaveLanes {
-    static __device__ __forceinline__ int lane() {
-        int x = (int)threadIdx.x;
-        asm volatile("" : "+v"(x));  // taken anew at every use: lane tests hoisted to the kernel's entry cost an SGPR pair each
-        return x;
-    }
-    static __device__ __forceinline__ int lanes() { return 64; }
-    static __device__ __forceinline__ void sync() { __syncthreads(); }
-    static __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-};
+// (Desc, Plan, WaveLanes: zstd_frames.h, shared with k_zstd_frames2 of zstd_checksum.hip)
 
 __global__ __launch_bounds__(64) void k_zstd_frames(Plan pl) {
     __shared__ pbsz::State st;
@@ -167,8 +142,8 @@ using pbsk::zstd::Desc;
 using pbsk::zstd::Plan;
 
 int zstd_decode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu_segment *frames, uint32_t nframe,
-                const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *decoded) {
-    if (!e) return PBSGPU_E_INVALID;
+                const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *decoded, uint32_t flags) {
+    if (!e || (flags & ~(uint32_t)(PBSGPU_ZSTD_F_CHECKSUM | PBSGPU_ZSTD_F_STREAM))) return PBSGPU_E_INVALID;
     if (nframe == 0) return PBSGPU_OK;
     if (!frames || !out || !status || (!src && nbytes) || (!dst && dst_cap)) return PBSGPU_E_INVALID;
     uint64_t lo = ~0ull, hi = 0;  // the part of dst the call may write
@@ -205,8 +180,12 @@ int zstd_decode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu
     pl.dst = static_cast<uint8_t *>(dst);
     pl.nframe = nframe;
     pl.stride = grid;
-    hipLaunchKernelGGL(pbsk::zstd::k_zstd_frames, dim3(grid), dim3(64), 0, s->stream, pl);
-    HIPCHK(hipGetLastError());
+    if (flags) {  // checksums verified, whole streams: k_zstd_frames2 (zstd_checksum.hip)
+        HIPCHK(pbsk::zstd::launch_frames2(pl, flags, s->stream));
+    } else {
+        hipLaunchKernelGGL(pbsk::zstd::k_zstd_frames, dim3(grid), dim3(64), 0, s->stream, pl);
+        HIPCHK(hipGetLastError());
+    }
     std::vector<uint64_t> back(nframe);
     CHK(fetch_result(s, back.data(), pl.res, (size_t)nframe * 8));  // the call's one synchronisation
     for (uint32_t i = 0; i < nframe; ++i) {
@@ -223,7 +202,13 @@ extern "C" {
 int pbsgpu_zstd_decode_device(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const pbsgpu_segment *frames,
                               uint32_t nframe, const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status,
                               uint64_t *decoded) {
-    return zstd_decode(eng, src, nbytes, frames, nframe, out, dst, dst_cap, status, decoded);
+    return zstd_decode(eng, src, nbytes, frames, nframe, out, dst, dst_cap, status, decoded, 0);
+}
+
+int pbsgpu_zstd_decode2_device(pbsgpu_engine *eng, const void *src, uint64_t nbytes, const pbsgpu_segment *frames,
+                               uint32_t nframe, const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status,
+                               uint64_t *decoded, uint32_t flags) {
+    return zstd_decode(eng, src, nbytes, frames, nframe, out, dst, dst_cap, status, decoded, flags);
 }
 
 }  // extern "C"

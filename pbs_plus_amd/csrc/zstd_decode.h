@@ -15,9 +15,11 @@
 // over the lanes; the four Huffman streams of a literals section run on four lanes.
 //
 // Decisions (include/pbsgpu.h):
-//   * The content checksum (XXH64, another serial chain per chunk) is parsed and accounted for, NOT verified: the blob's
-//     CRC-32 covers the compressed bytes and the index digest covers the content.
+//   * The content checksum (XXH64, another serial chain per chunk) is parsed and accounted for, NOT verified by
+//     decode_frame: the blob's CRC-32 covers the compressed bytes and the index digest covers the content. The
+//     stand-alone call that is asked to verifies it (zstd_stream.h, pbsgpu_zstd_decode2_device).
 //   * A nonzero dictionary id, a skippable frame, a second frame or trailing bytes are UNSUPPORTED: a blob is one frame.
+//     (Whole streams: zstd_stream.h, for the same stand-alone call.)
 //   * An offset is valid iff it does not reach before the frame's first output byte: the decoder writes straight into
 //     the destination, so the output so far is the window. A declared window size is read, not enforced, not allocated.
 //   * The decoder knows the room it may write and never stores outside it: a declared content size above the room is
@@ -733,12 +735,24 @@ PBSZ_HD int decode_block(State &st, const uint8_t *b, uint32_t bs, uint8_t *dst,
     return OK;
 }
 
-// Decodes the one frame src[0, n) into dst[0, room): both below 4 GiB (a chunk is 16 MiB at the most). lit: kLitMax bytes of scratch for this call. *decoded = bytes
-// produced (valid with OK). Never loads outside src[0, n), never stores outside dst[0, room) and lit[0, kLitMax).
-template <class P>
-PBSZ_HD int decode_frame(State &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t room, uint8_t *lit,
-                         uint32_t *decoded) {
+// What a decoded frame says of itself beyond its bytes: for a caller that walks a stream or verifies the checksum
+// (zstd_stream.h). decode_frame drops it.
+struct FrameEnd {
+    uint32_t used;          // the frame's own bytes, header to checksum; 0: the decoder did not get that far
+    uint32_t has_checksum;
+    uint32_t checksum;      // the stored low word of XXH64(content, 0)
+};
+
+// Decodes the frame that starts at src[0] into dst[0, room): n = the bytes that may be read, both below 4 GiB (a chunk is
+// 16 MiB at the most). kAlone: the frame must end at src + n, anything behind it is UNSUPPORTED (a blob is one frame);
+// otherwise the caller goes on at src + end.used, or decides itself that bytes are left over: end.used is set, with any
+// status, once the frame's last byte has been found, and 0 before. lit: kLitMax bytes of scratch for this call. *decoded = bytes produced
+// and `end` (both valid with OK). Never loads outside src[0, n), never stores outside dst[0, room) and lit[0, kLitMax).
+template <class P, bool kAlone>
+PBSZ_HD int decode_frame_at(State &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t room, uint8_t *lit,
+                            uint32_t *decoded, FrameEnd &end) {
     *decoded = 0;
+    end.used = end.has_checksum = end.checksum = 0;
     FrameHeader h;
     const int r = parse_frame_header<P>(src, n, h);
     if (r) return r;
@@ -789,14 +803,25 @@ PBSZ_HD int decode_frame(State &st, const uint8_t *src, uint32_t n, uint8_t *dst
         P::sync();  // the next block may match into this one, and reuses lit
         if (last) break;
     }
-    if (has_checksum) {  // XXH64 low word: accounted for, not verified (see the top)
+    if (has_checksum) {  // XXH64 low word: accounted for here, verified by the caller that was asked to (zstd_stream.h)
         if (n - pos < 4) return BAD_FRAME;
+        end.checksum = (uint32_t)load_le(src + pos, 4);  // (a plain load: dropped where `end` is)
         pos += 4;
     }
-    if (pos != n) return UNSUPPORTED;  // a second frame, a skippable frame, or garbage behind the frame
+    end.used = pos;
+    end.has_checksum = has_checksum;
+    if (kAlone && pos != n) return UNSUPPORTED;  // a second frame, a skippable frame, or garbage behind the frame
     if (sized && want != out) return BAD_SIZE;
     *decoded = out;
     return OK;
+}
+
+// Decodes the one frame src[0, n): the restore's call (k_zstd_frames) and pbsgpu_zstd_decode_device.
+template <class P>
+PBSZ_HD int decode_frame(State &st, const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t room, uint8_t *lit,
+                         uint32_t *decoded) {
+    FrameEnd end;
+    return decode_frame_at<P, true>(st, src, n, dst, room, lit, decoded, end);
 }
 
 

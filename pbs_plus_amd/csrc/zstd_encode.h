@@ -61,6 +61,7 @@
 //     compressed form that would pass the block's content length is abandoned where it would).
 #pragma once
 
+#include "xxh64.h"
 #include "zstd_decode.h"
 
 #ifdef PBSGPU_ZSTD_COVERAGE  // CPU test build only: one bit per branch (names: tests/test_zstd_encode_native.py)
@@ -189,14 +190,17 @@ PBSZ_HD uint64_t block_count(uint64_t n) { return n ? (n + kBlockMax - 1) / kBlo
 // no frame of n bytes of content is longer: the header, three bytes per block, the content
 PBSZ_HD uint64_t encode_bound(uint64_t n) { return header_bytes(n) + 3 * block_count(n) + n; }
 
-// the frame header of n < 4 GiB bytes of content into h[0, header_bytes(n))
-PBSZ_HD void frame_header(uint64_t n, uint8_t *h) {
+// ... and with a content checksum: the low word of XXH64(content, 0) behind the last block
+PBSZ_HD uint64_t encode_bound2(uint64_t n, bool checksum) { return encode_bound(n) + (checksum ? 4u : 0u); }
+
+// the frame header of n < 4 GiB bytes of content into h[0, header_bytes(n)); checksum: Content_Checksum_flag
+PBSZ_HD void frame_header(uint64_t n, uint8_t *h, bool checksum = false) {
     const uint32_t hb = header_bytes(n), fcs = hb - 5;
     h[0] = 0x28;
     h[1] = 0xb5;
     h[2] = 0x2f;
     h[3] = 0xfd;
-    h[4] = (uint8_t)((fcs == 1 ? 0u : fcs == 2 ? 1u : 2u) << 6 | 1u << 5);
+    h[4] = (uint8_t)((fcs == 1 ? 0u : fcs == 2 ? 1u : 2u) << 6 | 1u << 5 | (checksum ? 1u << 2 : 0u));
     const uint64_t v = fcs == 2 ? n - 256 : n;
     for (uint32_t i = 0; i < fcs; ++i) h[5 + i] = (uint8_t)(v >> (8 * i));
     PBSZ_ECOV(fcs == 1 ? E_FCS_1 : fcs == 2 ? E_FCS_2 : E_FCS_4);
@@ -1064,10 +1068,13 @@ PBSZ_HD uint32_t encode_block(S &st, const C src, uint32_t bn, uint8_t *blk, uin
 // The frame of src[0, n), n < 4 GiB, into dst[0, room): BAD_SIZE where it needs more, and dst's contents are then
 // unspecified. *flen = the frame's length (with OK). Scratch as for encode_block. Never stores outside dst[0, room) and
 // the scratch. The long-range match finder (S = WState or WTState) also takes the window's log and its table, and the
-// content may lie in two parts (C = Src2).
+// content may lie in two parts (C = Src2). sum: where the caller has put XXH64(content, 0) (xxh64.h; the kernels take it
+// from k_xxh64_ranges), and the frame then carries the content checksum: the flag in its header, the low word behind its
+// last block. nullptr: the frame without, byte for byte what it always was.
 template <class P, class S = State, class C = const uint8_t *>
 PBSZ_HD int encode_frame(S &st, const C src, uint32_t n, uint8_t *dst, uint64_t room, uint8_t *blk, uint8_t *lit,
-                         uint64_t *seqs, uint64_t *flen, uint32_t window_log = 0, uint32_t *wtab = nullptr) {
+                         uint64_t *seqs, uint64_t *flen, uint32_t window_log = 0, uint32_t *wtab = nullptr,
+                         const uint64_t *sum = nullptr) {
     *flen = 0;
 #ifdef PBSGPU_ZSTD_COVERAGE
     g_dec_rep[0] = 1, g_dec_rep[1] = 4, g_dec_rep[2] = 8;  // a frame's decoder starts here
@@ -1075,14 +1082,29 @@ PBSZ_HD int encode_frame(S &st, const C src, uint32_t n, uint8_t *dst, uint64_t 
     init_tables<P>(st);
     const uint32_t hb = header_bytes(n);
     if (room < (uint64_t)hb + 3) return BAD_SIZE;
-    if (P::lane() == 0) frame_header(n, dst);
+    if (P::lane() == 0) frame_header(n, dst, sum != nullptr);
     uint64_t pos = hb;
+    auto close = [&]() -> int {  // the checksum, if any, and the length
+        PBSZ_COV2(sum ? K_ENC_SUM : K_ENC_NO_SUM);
+        if (sum) {
+            if (room - pos < 4) {
+                PBSZ_COV2(K_ENC_SUM_NO_ROOM);
+                return BAD_SIZE;
+            }
+            if (P::lane() == 0)
+                for (uint32_t i = 0; i < 4; ++i) dst[pos + i] = (uint8_t)(*sum >> (8 * i));
+            pos += 4;
+            P::sync();
+        }
+        *flen = pos;
+        return OK;
+    };
     if (n == 0) {
         if (P::lane() == 0) block_header(dst + pos, 1, B_RAW, 0);
         PBSZ_ECOV(E_EMPTY_LAST_BLOCK);
         P::sync();
-        *flen = pos + 3;
-        return OK;
+        pos += 3;
+        return close();
     }
     for (uint32_t at = 0; at < n; at += kBlockMax) {
         const uint32_t bn = n - at < kBlockMax ? n - at : kBlockMax;
@@ -1109,8 +1131,7 @@ PBSZ_HD int encode_frame(S &st, const C src, uint32_t n, uint8_t *dst, uint64_t 
         pos += size;
         P::sync();  // blk, lit and seqs go to the next block
     }
-    *flen = pos;
-    return OK;
+    return close();
 }
 
 }  // namespace enc

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "zstd_encode_blocks.h"
+#include "zstd_frames.h"
 
 using namespace pbse;
 namespace ze = pbsz::enc;
@@ -68,15 +69,19 @@ __global__ __launch_bounds__(256) void k_zenc_assemble(Plan pl) {
             if (t == 0) s_total = nb ? carry : (uint64_t)hb + 3;
         }
         __syncthreads();
-        const uint64_t flen = s_total;
+        const uint64_t flen = s_total + (pl.sums ? 4u : 0u);  // with the content checksum behind the last block
         const bool write = pl.blob ? flen < j.len : flen <= j.room;
         const uint32_t status = pl.blob ? (write ? PBSGPU_BLOB_COMPRESSED : PBSGPU_BLOB_UNCOMPRESSED)
                                         : (write ? PBSGPU_ZSTD_OK : PBSGPU_ZSTD_BAD_SIZE);
         if (write) {
             uint8_t *d = pl.dst + j.dst_off;
             if (t == 0) {
-                ze::frame_header(j.len, d);
+                ze::frame_header(j.len, d, pl.sums != nullptr);
                 if (nb == 0) ze::block_header(d + hb, 1, ze::B_RAW, 0);
+                if (pl.sums) {
+                    const uint32_t low = (uint32_t)pl.sums[j.out];
+                    for (uint32_t i = 0; i < 4; ++i) d[flen - 4 + i] = (uint8_t)(low >> (8 * i));
+                }
             }
             for (uint32_t k = 0; k < nb; ++k) {
                 const uint32_t r = pl.bres[fb + k], type = r & 3u, size = r >> 2;
@@ -138,8 +143,10 @@ int carve(Slot *s, const Prep &p, const std::vector<Job> &jobs, Room &room) {
 }
 
 // the rounds, back to back on st; nothing synchronised
-int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob) {
+int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, const uint8_t *src, uint8_t *dst, bool blob,
+           const uint64_t *sums) {
     Plan pl{};
+    pl.sums = sums;
     pl.src = src;
     pl.jobs = room.jobs;
     pl.bchunk = room.bchunk;
@@ -181,7 +188,8 @@ int launch(pbsgpu_engine *e, hipStream_t st, const Prep &p, const Room &room, co
 
 // The frames of jobs[0, n), every one of them, enqueued on the slot's stream, nothing synchronised.
 // *res_dev = per chunk, frame length | status << 56 (blob: the kind, and nothing written unless compressed).
-int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob, uint64_t **res_dev) {
+int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::vector<Job> &jobs, bool blob, uint64_t **res_dev,
+            const uint64_t *sums) {
     for (uint32_t c = 0; c < jobs.size(); ++c) {
         jobs[c].src1_off = 0;
         jobs[c].a = jobs[c].len;
@@ -191,7 +199,7 @@ int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::ve
     CHK(prepare(e, jobs, false, p));
     Room room;
     CHK(carve(s, p, jobs, room));
-    CHK(launch(e, s->stream, p, room, src, dst, blob));
+    CHK(launch(e, s->stream, p, room, src, dst, blob, sums));
     *res_dev = room.res;
     return PBSGPU_OK;
 }
@@ -202,8 +210,8 @@ int enqueue(pbsgpu_engine *e, Slot *s, const uint8_t *src, uint8_t *dst, std::ve
 namespace {
 
 int zstd_encode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu_segment *chunks, uint32_t n,
-                const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *frame_len) {
-    if (!e) return PBSGPU_E_INVALID;
+                const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *frame_len, uint32_t flags) {
+    if (!e || (flags & ~(uint32_t)PBSGPU_ZSTD_F_CHECKSUM)) return PBSGPU_E_INVALID;
     if (n == 0) return PBSGPU_OK;
     if (!chunks || !out || !status || (!src && nbytes) || (!dst && dst_cap)) return PBSGPU_E_INVALID;
     uint64_t lo = ~0ull, hi = 0;  // the part of dst the call may write
@@ -230,8 +238,16 @@ int zstd_encode(pbsgpu_engine *e, const void *src, uint64_t nbytes, const pbsgpu
     Slot *s = lease.s;
     std::vector<pbsk::zenc::Job> jobs(n);
     for (uint32_t i = 0; i < n; ++i) jobs[i] = pbsk::zenc::Job{chunks[i].offset, 0, out[i].offset, out[i].length, (uint32_t)chunks[i].length, 0, 0, 0};
+    uint64_t *sums = nullptr;
+    if (flags & PBSGPU_ZSTD_F_CHECKSUM) {  // XXH64 of every chunk's source bytes, on the same stream, in front of the frames
+        const pbsgpu_segment *ranges = nullptr;
+        CHK(put_table(s, chunks, n, &ranges));
+        sums = s->take<uint64_t>(n);
+        CHK(s->taken());
+        HIPCHK(pbsk::zstd::launch_xxh64_ranges(static_cast<const uint8_t *>(src), ranges, n, 0, sums, e->num_cus, s->stream));
+    }
     uint64_t *res = nullptr;
-    CHK(pbsk::zenc::enqueue(e, s, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), jobs, false, &res));
+    CHK(pbsk::zenc::enqueue(e, s, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(dst), jobs, false, &res, sums));
     std::vector<uint64_t> back(n);
     CHK(fetch_result(s, back.data(), res, (size_t)n * 8));  // the call's one synchronisation
     for (uint32_t i = 0; i < n; ++i) {
@@ -247,7 +263,13 @@ extern "C" {
 
 int pbsgpu_zstd_encode_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *chunks, uint32_t n,
                               const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *frame_len) {
-    return zstd_encode(eng, src, src_bytes, chunks, n, out, dst, dst_cap, status, frame_len);
+    return zstd_encode(eng, src, src_bytes, chunks, n, out, dst, dst_cap, status, frame_len, 0);
+}
+
+int pbsgpu_zstd_encode2_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *chunks, uint32_t n,
+                               const pbsgpu_segment *out, void *dst, uint64_t dst_cap, uint8_t *status, uint64_t *frame_len,
+                               uint32_t flags) {
+    return zstd_encode(eng, src, src_bytes, chunks, n, out, dst, dst_cap, status, frame_len, flags);
 }
 
 }  // extern "C"

@@ -32,6 +32,8 @@ struct Plan {
     uint32_t blob;
     uint32_t window_log;     // the window kernels: pbsgpu_engine_options::zstd_window_log. Their scratch is one piece of
                              // kWindowWork bytes per workgroup from `lit` on: literals, sequences, the match finder's table
+    const uint64_t *sums;    // per Job::out: XXH64(content, 0), for k_zenc_assemble to close the frame with its low word
+                             // (pbsgpu_zstd_encode2_device with PBSGPU_ZSTD_F_CHECKSUM); nullptr: frames without a checksum
 };
 constexpr size_t kWindowWork = (size_t)pbsz::kBlockMax + (size_t)ze::kSeqCap * 8 + (sizeof(uint32_t) << ze::kWindowHashLog);
 

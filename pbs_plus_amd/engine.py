@@ -241,6 +241,16 @@ class Engine:
                                                 out.ctypes.data), "xxh3_many_host")
         return out[:nseg]
 
+    def xxh64_many(self, data, segments, seed: int = 0, nbytes: int | None = None) -> np.ndarray:
+        """XXH64 with `seed` of the ranges [(offset, length)] of the device buffer `data` (pbsgpu_xxh64_many_device): what
+        a zstd frame's content checksum is the low 32 bits of. Ranges may be empty, unaligned and overlapping."""
+        segs, nseg = _segs(segments)
+        out = np.zeros(max(nseg, 1), dtype=np.uint64)
+        ptr, n = self._dev(data, nbytes)
+        assert ptr is not None, "xxh64_many() wants device memory"
+        check(self._L.pbsgpu_xxh64_many_device(self._h, ptr, n, segs, nseg, int(seed), out.ctypes.data), "xxh64_many_device")
+        return out[:nseg]
+
     # ---- CRC-32 and data blobs (the upload step and the chunk check of the read side) -------------------
     def crc32_many(self, data, segments, nbytes: int | None = None) -> np.ndarray:
         """CRC-32 (zlib's crc32) of every (offset, length) range of device or host bytes."""
@@ -376,12 +386,26 @@ class Engine:
                      out_bytes=int(st.out_bytes), zstd_in_bytes=int(st.zstd_in_bytes), zstd_out_bytes=int(st.zstd_out_bytes))
         return dst, status[:n], stats
 
+    def zstd_decode2(self, data, frames, out=None, dst=None, nbytes: int | None = None, checksum=False, stream=False):
+        """zstd_decode() with flags (pbsgpu_zstd_decode2_device). checksum=True: a frame that carries a content checksum
+        is checked against it, a mismatch is status 4 (_lib.ZSTD_BAD_CHECKSUM) with 0 bytes decoded. stream=True: every
+        segment is a whole zstd stream (frames one behind the other, skippable frames skipped, an empty segment is ok
+        with 0 bytes), decoded as ZSTD_decompress does it; `out` must then be given (zstd_stream_info() sizes a stream
+        on the host). With neither it is zstd_decode(), output for output."""
+        flags = (_lib.ZSTD_F_CHECKSUM if checksum else 0) | (_lib.ZSTD_F_STREAM if stream else 0)
+        if stream and out is None:
+            raise ValueError("stream=True: pass out= (zstd_stream_info() gives a stream's content size)")
+        return self._zstd_decode(data, frames, out, dst, nbytes, flags)
+
     def zstd_decode(self, data, frames, out=None, dst=None, nbytes: int | None = None):
         """Decode the zstd frames [(offset, length)] of the device buffer `data` in one launch (pbsgpu_zstd_decode_device):
         frame i goes to dst at out[i] = (offset, room). out None lays the frames out back to back by the content size
         their headers declare (read back from the device; a frame that declares none is a ValueError); dst None allocates
         what `out` needs. Returns (dst, status per frame: 0 ok, 1 bad frame, 2 bad size, 3 unsupported, bytes decoded per
         frame, out as an (n, 2) array). On a status other than 0 the frame's own room holds unspecified bytes."""
+        return self._zstd_decode(data, frames, out, dst, nbytes, None)
+
+    def _zstd_decode(self, data, frames, out, dst, nbytes, flags):  # flags None: the call without flags
         dp, dn = self._dev(data, nbytes)
         assert dp is not None, "zstd_decode() wants device memory"
         fr = np.ascontiguousarray(frames, dtype=np.uint64).reshape(-1, 2)
@@ -413,26 +437,38 @@ class Engine:
         status = np.zeros(max(n, 1), dtype=np.uint8)
         decoded = np.zeros(max(n, 1), dtype=np.uint64)
         try:
-            check(self._L.pbsgpu_zstd_decode_device(self._h, dp, dn, fr.ctypes.data if n else None, n, oa.ctypes.data if n else None,
-                                                    dst.ptr, dst.nbytes, status.ctypes.data, decoded.ctypes.data),
-                  "zstd_decode_device")
+            args = (self._h, dp, dn, fr.ctypes.data if n else None, n, oa.ctypes.data if n else None, dst.ptr, dst.nbytes,
+                    status.ctypes.data, decoded.ctypes.data)
+            if flags is None:
+                check(self._L.pbsgpu_zstd_decode_device(*args), "zstd_decode_device")
+            else:
+                check(self._L.pbsgpu_zstd_decode2_device(*args, flags), "zstd_decode2_device")
         except Exception:
             if own:
                 dst.free()
             raise
         return dst, status[:n], decoded[:n], oa
 
+    def zstd_encode2(self, data, chunks, out=None, dst=None, nbytes: int | None = None, checksum=False):
+        """zstd_encode() with flags (pbsgpu_zstd_encode2_device). checksum=True: every frame carries the content checksum
+        (the flag in its header, the low 32 bits of XXH64(content, 0) behind its last block: 4 bytes more); out None then
+        lays out rooms of zstd_encode_bound2(length, checksum=True). Without it it is zstd_encode()."""
+        return self._zstd_encode(data, chunks, out, dst, nbytes, _lib.ZSTD_F_CHECKSUM if checksum else 0)
+
     def zstd_encode(self, data, chunks, out=None, dst=None, nbytes: int | None = None):
         """Compress the chunks [(offset, length)] of the device buffer `data` to one zstd frame each in one call
         (pbsgpu_zstd_encode_device): frame i goes to dst at out[i] = (offset, room). out None lays rooms of
         zstd_encode_bound(length) out back to back; dst None allocates what `out` needs. Returns (dst, status per chunk:
         0 ok, 2 the room is too small, frame length per chunk (0 unless ok), out as an (n, 2) array)."""
+        return self._zstd_encode(data, chunks, out, dst, nbytes, None)
+
+    def _zstd_encode(self, data, chunks, out, dst, nbytes, flags):  # flags None: the call without flags
         dp, dn = self._dev(data, nbytes)
         assert dp is not None, "zstd_encode() wants device memory"
         ch = np.ascontiguousarray(chunks, dtype=np.uint64).reshape(-1, 2)
         n = int(ch.shape[0])
         if out is None:
-            rooms = np.array([zstd_encode_bound(int(v)) for v in ch[:, 1]], dtype=np.uint64)
+            rooms = np.array([zstd_encode_bound2(int(v), bool(flags)) for v in ch[:, 1]], dtype=np.uint64)
             ends = np.cumsum(rooms)
             out = np.stack([ends - rooms, rooms], axis=1)
         oa = np.ascontiguousarray(out, dtype=np.uint64).reshape(-1, 2)
@@ -443,9 +479,12 @@ class Engine:
         status = np.zeros(max(n, 1), dtype=np.uint8)
         flen = np.zeros(max(n, 1), dtype=np.uint64)
         try:
-            check(self._L.pbsgpu_zstd_encode_device(self._h, dp, dn, ch.ctypes.data if n else None, n, oa.ctypes.data if n else None,
-                                                    dst.ptr, dst.nbytes, status.ctypes.data, flen.ctypes.data),
-                  "zstd_encode_device")
+            args = (self._h, dp, dn, ch.ctypes.data if n else None, n, oa.ctypes.data if n else None, dst.ptr, dst.nbytes,
+                    status.ctypes.data, flen.ctypes.data)
+            if flags is None:
+                check(self._L.pbsgpu_zstd_encode_device(*args), "zstd_encode_device")
+            else:
+                check(self._L.pbsgpu_zstd_encode2_device(*args, flags), "zstd_encode2_device")
         except Exception:
             if own:
                 dst.free()
@@ -589,6 +628,27 @@ class _Upload2Out:
 def zstd_encode_bound(n: int) -> int:
     """No zstd frame Engine.zstd_encode() writes for n bytes of content is longer (pbsgpu_zstd_encode_bound, host only)."""
     return int(_lib.lib().pbsgpu_zstd_encode_bound(int(n)))
+
+
+def zstd_encode_bound2(n: int, checksum: bool = False) -> int:
+    """zstd_encode_bound() for Engine.zstd_encode2(): 4 bytes more with checksum (pbsgpu_zstd_encode_bound2, host only)."""
+    return int(_lib.lib().pbsgpu_zstd_encode_bound2(int(n), _lib.ZSTD_F_CHECKSUM if checksum else 0))
+
+
+def zstd_stream_info(stream) -> dict:
+    """What the headers of a whole zstd stream declare (pbsgpu_zstd_stream_info, host only): status as the headers alone
+    decide it, content_size (the sum over the frames; None if a frame declares none), frames, skippable, any_checksum.
+    What a caller sizes the destination of Engine.zstd_decode2(stream=True) with."""
+    a = _host_view(stream)
+    size = C.c_uint64(0)
+    nf, ns = C.c_uint32(0), C.c_uint32(0)
+    ck = C.c_int(0)
+    st = _lib.lib().pbsgpu_zstd_stream_info(a.ctypes.data if a.size else None, a.size, C.byref(size), C.byref(nf), C.byref(ns),
+                                            C.byref(ck))
+    if st < 0:
+        raise _lib.PbsGpuError(st, "zstd_stream_info")
+    return dict(status=int(st), content_size=None if size.value == 2**64 - 1 else int(size.value), frames=int(nf.value),
+                skippable=int(ns.value), any_checksum=bool(ck.value))
 
 
 def zstd_frame_info(frame) -> dict:

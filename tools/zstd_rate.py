@@ -4,6 +4,11 @@ of DECODED bytes, beside what it is measured against:
 * blob_decode of the same chunks stored uncompressed (what the restore could do before it could decode);
 * ZSTD_decompress of the same frames on 16 host threads, where libzstd.so.1 loads (ctypes releases the GIL).
 
+And, on the same chunks compressed WITH a content checksum, the stand-alone calls: pbsgpu_zstd_decode_device, which
+verifies nothing, pbsgpu_zstd_decode2_device without flags (the same work by promise) and with F_CHECKSUM (XXH64 of every
+frame's output inside its wave), and pbsgpu_xxh64_many_device over the decoded chunks alone. For these the fastest and
+the slowest call are printed beside the median: the spread is what a difference has to be read against.
+
 Two batches, NewConfig(4 << 20)'s and NewConfig(4096)'s chunk sizes (fixed 4 MiB and 4 KiB chunks), each on data of two
 compressibilities (words over a small alphabet; skewed bytes over 220 values). The chunks are cut from an 8 MiB pool at
 scattered offsets and compressed here at level 3, the stock client's default, so the tool needs libzstd where it runs.
@@ -40,6 +45,17 @@ def _median_s(fn, reps):
         fn()
         ts.append(time.perf_counter() - t0)
     return statistics.median(ts)
+
+
+def _spread_ms(fn, reps):
+    """[fastest, median, slowest] of reps calls after one warm-up, in ms"""
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return [round(v * 1e3, 3) for v in (min(ts), statistics.median(ts), max(ts))]
 
 
 def _golden():
@@ -93,6 +109,24 @@ def main():
                     res["%s_%s_ms" % (name, "digest" if digest else "nodigest")] = round(t * 1e3, 3)
                     res["%s_%s_GBps" % (name, "digest" if digest else "nodigest")] = round(total / t / 1e9, 2)
                 dev.free()
+            # the stand-alone calls, on frames that carry a checksum
+            summed = list(pool16.map(lambda c: g.compress(z, c, level=3, checksum=True), chunks))
+            lens = np.array([len(f) for f in summed], dtype=np.uint64)
+            fr = np.stack([np.cumsum(lens) - lens, lens], axis=1)
+            out = np.stack([np.arange(count, dtype=np.uint64) * size, np.full(count, size, dtype=np.uint64)], axis=1)
+            dev = eng.alloc(int(lens.sum()))
+            dev.upload(np.frombuffer(b"".join(summed), np.uint8))
+            for name, fn in (("decode", lambda: eng.zstd_decode(dev, fr, out=out, dst=dst)),
+                             ("decode2", lambda: eng.zstd_decode2(dev, fr, out=out, dst=dst)),
+                             ("decode2_checksum", lambda: eng.zstd_decode2(dev, fr, out=out, dst=dst, checksum=True))):
+                assert not fn()[1].any(), name
+                ms = _spread_ms(fn, a.reps)
+                res[name + "_ms"] = ms
+                res[name + "_GBps"] = round(total / ms[1] / 1e6, 2)
+            ms = _spread_ms(lambda: eng.xxh64_many(dst, out), a.reps)
+            res["xxh64_many_ms"] = ms
+            res["xxh64_many_GBps"] = round(total / ms[1] / 1e6, 2)
+            dev.free()
             dst.free()
             bufs = [C.create_string_buffer(size) for _ in range(16)]
 
