@@ -1,5 +1,26 @@
-// Internal launch interface between the engine (host logic) and the gfx950 kernels.
-// Not part of the C ABI.
+// Internal launch interface between the engine (host logic) and the gfx950 (MI355X / CDNA4) kernels of the
+// content-defined chunker + SHA-256 engine. Not part of the C ABI.
+//
+// Hot path = the chunk loop behind transfer.ArchiveWriter.WriteEntryReader
+// (reference internal/pxarmount/commit_reuse.go:457, internal/tapeio/converter.go:836),
+// i.e. the Buzhash scan + per-chunk SHA-256 of github.com/pbs-plus/pxar v0.34.0
+// parameterised by buzhash.NewConfig (commit_orchestrate.go:143-149). Decomposition
+// (DESIGN.md): (1) candidate scan — every stream position's 64-byte window hash is a
+// pure function of those 64 bytes once chunk_size >= 64, so all positions are tested in
+// parallel, HBM-bound; (2) compaction + min/max resolution over the sparse candidate
+// list; (3) one SHA-256 lane per chunk, lanes pulling chunks from a queue, VALU-bound.
+// Integer/byte work only: no MFMA anywhere.
+//
+// One translation unit per subject. Every kernel is defined (a template: instantiated) in exactly one of them, and
+// another unit reaches it through a launch_* function declared here, never by naming the kernel:
+//   scan.hip          (1) k_scan3, the exclusive prefix scan, (2a) k_compact
+//   resolve.hip       (2b) k_resolve, k_resolve_par, k_par_*
+//   kernels.hip       (3) k_sha256, k_sha256_lanes, k_sha256_pair, k_sha256_xpair, k_order; the page ring's services
+//   ring_kernels.hip  k_ring_*: a page-ring cut round (which calls launch_scan), stop and reset of the services
+//   xxh3.hip          k_xxh3_sums, k_xxh3
+//   misc_kernels.hip  k_publish*, k_fill, k_pack
+// Device code that two units share lives in headers: resolve_walk.h (resolve.hip, k_ring_control), ring_queue.h
+// (kernels.hip, k_ring_control), fill_word.h (k_fill, k_ring_fill), kernel_util.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,7 +70,7 @@ hipError_t launch_compact(const uint32_t *tile_cnt, const uint32_t *tile_off, co
                           uint32_t cap, uint64_t ntiles, uint32_t lead, uint64_t nbytes, uint64_t *dense,
                           uint64_t dense_cap, uint32_t tile_bytes, hipStream_t st);
 
-// one long stream without suggested boundaries: the cut chain followed by pointer doubling (kernels.hip); `scratch` holds
+// one long stream without suggested boundaries: the cut chain followed by pointer doubling (resolve.hip); `scratch` holds
 // resolve_par_scratch_bytes(node_cap, levels); falls back to the serial walk when there are more candidates than node_cap - 1
 size_t resolve_par_scratch_bytes(uint32_t node_cap, uint32_t levels);
 hipError_t launch_resolve_single_par(const uint64_t *cands, const uint32_t *ncand, const pbsgpu_segment *segs, uint32_t effmin,
@@ -86,7 +107,7 @@ struct SuggFeed {
     uint64_t feed, origin;
     uint32_t absolute, open_end;
 };
-// Page-ring rounds (ring_kernels.inc): segments are the streams' open chunks + new pages in LOGICAL coordinates
+// Page-ring rounds (ring_kernels.hip): segments are the streams' open chunks + new pages in LOGICAL coordinates
 // ((slot << kRingOffBits) | offset), suggested offsets are relative to the stream's byte 0, a segment's end is the stream's end only
 // when its RingSeg says final, and the walk reports per segment what the round leaves behind (all null otherwise).
 // logical coordinates of a ring round: (stream slot << kRingOffBits) | offset. A ring has at most 4096 stream slots (12 bits),
@@ -98,7 +119,7 @@ struct RingPage;
 // Exact handling of candidate-DENSE scan tiles (periodic / crafted data). A tile records at most `cap` of its candidates; a
 // tile that found more (tile_cnt[t] > cap) leaves an arbitrary SUBSET in the dense list — every entry a true candidate, some
 // missing. The cut rule only ever needs ONE thing from such a tile: the first candidate at or behind a given position. So the
-// resolve walk re-scans on demand (kernels.hip: dense_refine / dense_first_hit): whenever the stretch it is about to skip —
+// resolve walk re-scans on demand (resolve_walk.h: dense_refine / dense_first_hit): whenever the stretch it is about to skip —
 // [s + effmin, first listed candidate) — touches an overflowed tile, one wave computes the window hashes of that part of the
 // tile (64 lanes x 64 positions per step, the scan's own pre-rotated table and threshold) and takes the first hit. Nothing
 // fails and nothing is re-run: the reference's writer never fails on byte content either
@@ -157,7 +178,7 @@ hipError_t launch_sha256_segments(const uint8_t *data, const pbsgpu_segment *seg
                                   uint8_t *digests, uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st);
 
 // XXH3-64 (seed 0) of whole segments: out[i] for segs[i]; `queue` zero at launch
-// XXH3-64 (seed 0), two phases (kernels.hip): every 1 KiB block of every input is summed by some wave of the grid
+// XXH3-64 (seed 0), two phases (xxh3.hip): every 1 KiB block of every input is summed by some wave of the grid
 // (k_xxh3_sums -> `sums`, 64 bytes per block), then one wave per input runs the short serial scramble chain + tail.
 // Work items: flags bit0 = first piece of its input, bit1 = last piece (both = a whole input); pieces of one input carry
 // state in states[state] and must be launched in order on one stream; the hash of a finished input lands in out[out].
@@ -179,7 +200,7 @@ size_t xxh3_state_bytes();
 hipError_t launch_xxh3_items(const XxhItem *items, uint32_t nitems, uint64_t total_blocks, void *states, uint64_t *sums,
                              uint64_t *out, uint32_t *queue, int num_cus, hipStream_t st);
 
-// device -> mapped pinned host memory by kernel// device -> mapped pinned host memory by kernel (never through the shared SDMA copy queues; see kernels.hip)
+// device -> mapped pinned host memory by kernel (never through the shared SDMA copy queues; see misc_kernels.hip)
 hipError_t launch_publish(void *dst_host_mapped, const void *src, uint64_t nbytes, hipStream_t st);
 hipError_t launch_publish_records(pbsgpu_record *dst_host_mapped, const pbsgpu_record *src, const uint32_t *nrec,
                                   uint64_t cap, hipStream_t st);

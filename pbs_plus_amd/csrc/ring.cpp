@@ -10,7 +10,7 @@
 // (internal/pxarmount/commit_reuse.go:457, internal/tapeio/converter.go:836):
 //   * device memory is an arena of fixed PAGES (>= max chunk, a whole number of scan tiles). A stream is a sequence
 //     of pages in logical order; physically they lie wherever a page was free;
-//   * newly filled pages of all streams are cut in ROUNDS (ring_kernels.inc): scan of the new pages only, multi-stream
+//   * newly filled pages of all streams are cut in ROUNDS (ring_kernels.hip): scan of the new pages only, multi-stream
 //     resolve continuing from each stream's open chunk (device-resident state: no host round trip between rounds);
 //   * every cut chunk goes into ONE device-resident FIFO that the SHA-256 SERVICE — a persistent kernel on a fixed set
 //     of CUs — drains: a lane takes the next chunk the moment it finishes one, across rounds and streams;

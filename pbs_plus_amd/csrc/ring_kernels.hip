@@ -1,5 +1,6 @@
-// Page ring: the kernels of one CUT ROUND and the control of the persistent SHA-256 service (included by kernels.hip,
-// namespace pbsk). Host side: ring.cpp. What a round does, in order (scan side and control side on their own HIP streams):
+// Page ring: the kernels of one CUT ROUND and the stop / reset of the persistent SHA-256 services (the services themselves
+// and their launchers: kernels.hip; the scan: scan.hip, through launch_scan). Host side: ring.cpp. What a round does, in
+// order (scan side and control side on their own HIP streams):
 //   k_ring_stage    the round's host-written tables -> device memory, once
 //   k_ring_fill     (bench / tests) the synthetic producer writes the round's new pages
 //   k_ring_prep_pages / ring_prep (the head of k_ring_control)   page tables, the 128-byte pads that make a page boundary
@@ -19,6 +20,16 @@
 // A scan tile that finds more candidates than it has slots (periodic / crafted input) is resolved EXACTLY all the same: the
 // walk asks such a tile for the first candidate behind a position by re-scanning the stretch on demand (DenseTiles, kernels.h).
 // No input fails a stream (rounds 3-5 failed the stream that owned the tile: PBSGPU_E_DENSITY, retired with ABI v5).
+
+#include <algorithm>
+
+#include "fill_word.h"
+#include "kernel_util.h"
+#include "kernels.h"
+#include "resolve_walk.h"
+#include "ring_queue.h"
+
+namespace pbsk {
 
 // a ticket for the short queue: true (and the entry written) while the round's allowance lasts. Tickets beyond it are simply
 // not used: the tail step publishes min(tickets, allowance) entries, and every ticket below the allowance has written its entry.
@@ -585,7 +596,7 @@ hipError_t launch_ring_round(const RingRound &r, int num_cus, hipStream_t st, hi
         p.ring_pages = r.pages;
         p.ring_tpp = r.tpp;
         p.max_blocks = r.scan_blocks;
-        hipError_t e = (r.tile_bytes == 64u * 34u * 128u) ? launch_scan3_any<34>(p, num_cus, sst) : launch_scan3_any<4>(p, num_cus, sst);
+        hipError_t e = launch_scan(p, num_cus, sst);  // (tile_bytes is one of the scan's two tile sizes: shape_ring, ring_plan.h)
         if (e != hipSuccess) return e;
     }
     if (sst != st) {
@@ -598,49 +609,4 @@ hipError_t launch_ring_round(const RingRound &r, int num_cus, hipStream_t st, hi
     return hipGetLastError();
 }
 
-// The EXPRESS service (k_sha256_xpair: two lanes per chunk, the long-chunk queue only) on its own CUs beside the pair
-// service: same LDS rule, same `stop`.
-hipError_t launch_ring_service_xp(const RingSource &q, unsigned workgroups, hipStream_t st) {
-    hipFuncAttributes fa{};
-    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_sha256_xpair<RingSource>));
-    if (e != hipSuccess) return e;
-    size_t pad = (160u << 10) > fa.sharedSizeBytes ? (160u << 10) - fa.sharedSizeBytes : 0;
-    pad &= ~(size_t)255;
-    e = allow_lds(&k_sha256_xpair<RingSource>, pad);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sha256_xpair<RingSource>), dim3(workgroups), dim3(256), pad, st, q, (const uint32_t *)nullptr, 0u,
-                       (uint32_t *)nullptr, (const uint32_t *)nullptr);
-    return hipGetLastError();
-}
-
-// The LANES service (k_sha256_lanes: one lane per chunk, the short-chunk queue only) on its own CUs: same LDS rule, same `stop`.
-// `dense` (PBSGPU_RING_F_DENSE_LANES): eight waves per workgroup, two per SIMD — 84 chain-blocks per us and CU against 77-81
-// (with two waves on a SIMD the two-operand adds and xors issue at twice the rate of the three-operand forms), every chain at
-// ~6 us per block (profiles/r06_sha_forms_full_lanes.log section 3)
-hipError_t launch_ring_service_lanes(const RingSource &q, unsigned workgroups, hipStream_t st, bool dense) {
-    const size_t pad = (size_t)(160u << 10) & ~(size_t)255;
-    hipError_t e = allow_lds(&k_sha256_lanes, pad);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sha256_lanes, dim3(workgroups), dim3(dense ? 512 : 256), pad, st, q);
-    return hipGetLastError();
-}
-
-template <bool DENSE>
-static hipError_t launch_ring_service_form(const RingSource &q, unsigned workgroups, hipStream_t st) {
-    // the whole LDS of the CU: one workgroup per CU (a co-resident wave on a chain's SIMD halves the chain's speed), and
-    // no room for any other kernel that asks for LDS (kRingLdsTag, the scan's table)
-    hipFuncAttributes fa{};
-    hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_sha256_pair<RingSource, DENSE>));
-    if (e != hipSuccess) return e;
-    size_t pad = (160u << 10) > fa.sharedSizeBytes ? (160u << 10) - fa.sharedSizeBytes : 0;
-    pad &= ~(size_t)255;
-    e = allow_lds(&k_sha256_pair<RingSource, DENSE>, pad);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sha256_pair<RingSource, DENSE>), dim3(workgroups), dim3(DENSE ? 512 : 256), pad, st, q,
-                       (const uint32_t *)nullptr, 0u, (uint32_t *)nullptr, (const uint32_t *)nullptr);
-    return hipGetLastError();
-}
-// dense (PBSGPU_RING_F_DENSE_SERVICE): four pairs per workgroup, two waves per SIMD — DESIGN.md 5.2 for what it buys and costs
-hipError_t launch_ring_service(const RingSource &q, unsigned workgroups, hipStream_t st, bool dense) {
-    return dense ? launch_ring_service_form<true>(q, workgroups, st) : launch_ring_service_form<false>(q, workgroups, st);
-}
+}  // namespace pbsk

@@ -8,7 +8,7 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def resolve_model(cands, seg_len, cmin, cmax):
-    """Python statement of kernels.hip k_resolve: given ascending candidate END offsets of one
+    """Python statement of resolve.hip k_resolve: given ascending candidate END offsets of one
     stream, apply the min/max rules. Must equal the serial chunker on every input."""
     effmin = max(cmin, 65)
     cands = np.asarray(cands, dtype=np.uint64)
@@ -114,7 +114,8 @@ def golden_records(case, dtype):
 
 
 def scan_lane_model(data, table, mask, break_min, strip=4352):
-    """numpy statement of kernels.hip k_scan2's per-lane algebra, for one buffer cut into lane strips:
+    """numpy statement of k_scan2's per-lane algebra (the scan's earlier register-streaming kernel, since removed;
+    described in docs/NOTES.md), for one buffer cut into lane strips:
       * prefix recurrence P(i) = rotl(P(i-1), 1) ^ T'[b[i]] restarted 64 bytes before every strip,
       * window hash h'(i) = P(i) ^ P(i-64)   (64 = 0 mod 32, so the leaving byte needs no rotation),
       * table pre-rotated by r = 32 - bits, candidate test h' >= break_min << r (one unsigned compare).
@@ -151,7 +152,7 @@ def scan_lane_model(data, table, mask, break_min, strip=4352):
 
 
 def scan_coop_model(data, table, mask, break_min, lines=4):
-    """numpy/python statement of kernels.hip k_scan3's dataflow for one buffer (no GPU):
+    """numpy/python statement of scan.hip k_scan3's dataflow for one buffer (no GPU):
       * wave tiles of 64 strips x (lines*128) bytes, a strip per lane, 64-byte half-lines;
       * quad-cooperative fetch: load j of a half-line gives lane (q, ql) piece ql (16 B) of strip 4q+j, zero outside
         the buffer; the per-wave stage [strip][piece] hands every lane its own 64 bytes back (the LDS transpose);

@@ -29,7 +29,7 @@ from helpers import describe_mismatch, records_equal  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 RING_OFF = 0xFFFFFFFF
-BIG_BATCH = 48 << 20                   # kernels.hip scan_tile_bytes: 272 KiB tiles from here on
+BIG_BATCH = 48 << 20                   # scan.hip scan_tile_bytes: 272 KiB tiles from here on
 TILE_BIG, TILE_SMALL = 64 * 34 * 128, 64 * 4 * 128
 ARENA_PAGES = 10
 

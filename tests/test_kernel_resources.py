@@ -15,10 +15,17 @@ LDS_PER_CU = 160 * 1024
 
 
 @pytest.fixture(scope="module")
-def usage():
+def usage_text():
+    """`make usage`: the compiler's resource report of the Makefile's KSRCS (kernels.hip = the SHA-256 kernels, scan.hip,
+    resolve.hip, xxh3.hip, misc_kernels.hip, ring_kernels.hip), one compile per file."""
     out = subprocess.run(["make", "-C", os.path.join(ROOT, "pbs_plus_amd", "csrc"), "-s", "usage"], capture_output=True,
                          text=True, timeout=600)
-    text = out.stdout + out.stderr
+    return out.stdout + out.stderr
+
+
+@pytest.fixture(scope="module")
+def usage(usage_text):
+    text = usage_text
     kernels = {}
     cur = None
     for line in text.splitlines():
@@ -42,6 +49,15 @@ def _find(kernels, *needles):
     hit = [k for k in kernels if all(n in k for n in needles)]
     assert hit, needles
     return hit
+
+
+def test_every_kernel_lives_in_one_translation_unit(usage_text):
+    """A kernel (or a kernel template's instance) that two of the kernel files define is compiled twice, and the copies can
+    drift apart: another file reaches a kernel through its launch_* function (kernels.h), never by naming it."""
+    names = re.findall(r"Function Name: (_ZN4pbsk\S+)", usage_text)
+    assert len(names) >= 25, (len(names), usage_text[-2000:])
+    twice = sorted({n for n in names if names.count(n) > 1})
+    assert not twice, twice
 
 
 def test_no_kernel_spills(usage):
@@ -95,7 +111,8 @@ def test_single_wave_sha_and_scan_register_budgets(usage):
 
 @pytest.fixture(scope="module")
 def sha_isa(tmp_path_factory):
-    """The device ISA of kernels.hip, one text per SHA-256 kernel (hipcc -S --offload-device-only; ~1 min)."""
+    """The device ISA of kernels.hip, the file that holds the SHA-256 kernels and nothing else, one text per kernel (hipcc -S
+    --offload-device-only)."""
     d = tmp_path_factory.mktemp("isa")
     src = os.path.join(ROOT, "pbs_plus_amd", "csrc", "kernels.hip")
     out = os.path.join(str(d), "kernels.s")

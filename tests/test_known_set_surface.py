@@ -1,6 +1,6 @@
 """The known-chunk set (pbsgpu_known_*) without a GPU: the C ABI, the Python / C++ / Go bindings and the argument checks
 that come before any device work, plus the build-quality guard for its kernels (known.hip is not part of the
-kernels.hip resource report of test_kernel_resources.py)."""
+`make usage` resource report of test_kernel_resources.py)."""
 import ctypes as C
 import os
 import re

@@ -102,7 +102,7 @@ def test_upstream_suggested_boundary_vector(O):
 @pytest.mark.parametrize("avg,n,kind", [(256, 60_000, 0), (4096, 900_000, 0), (4096, 500_000, 1), (4096, 700_000, 3),
                                         (65536, 5_000_000, 0)])
 def test_suggested_boundaries_as_a_second_candidate_list(O, avg, n, kind):
-    """The engine's formulation (tests/helpers.py::resolve_model_suggested = kernels.hip k_resolve) equals the serial
+    """The engine's formulation (tests/helpers.py::resolve_model_suggested = resolve.hip k_resolve) equals the serial
     payload chunker fed byte by byte, including boundaries closer than min (dropped), farther than max (left to the
     hash scan and re-examined from the next chunk), duplicates, and boundaries at / past the end."""
     from helpers import resolve_model_suggested
