@@ -76,6 +76,10 @@ enum : int {  // coverage bits
     // the batch before
     C_MATCH_WAIT, C_MATCH_NO_WAIT, C_MATCH_SRC_IN_PREV_MATCH, C_MATCH_SRC_OWN_LITERALS, C_LIT_SHORT, C_LIT_LONG,
     C_BATCH_FOLLOWS_BATCH,
+    // what only crafted Huffman literals and table descriptions reach (tests/zstd_huf_inputs.py): a stream that ends with
+    // spare bits, codes of kHufLogMax bits, a fourth stream shorter than the other three, the weights' FSE stream ending
+    // on its first and on its second state, a zero run in a table description that goes on after a count of 3
+    C_HUF_SPARE_BITS, C_HUF_LOG_MAX, C_HUF_SHORT_4TH, C_WEIGHTS_END_FIRST, C_WEIGHTS_END_SECOND, C_NORM_ZERO_RUN_CHAINED,
     C_NBITS
 };
 
@@ -299,6 +303,7 @@ PBSZ_HD int fse_read_norm(State &st, const uint8_t *p, uint32_t len, uint32_t ma
                     st.norm[sym++] = 0;
                 }
                 if (rep != 3) break;
+                PBSZ_COV(C_NORM_ZERO_RUN_CHAINED);
             }
         }
     }
@@ -376,6 +381,7 @@ PBSZ_HD int huf_read_table(State &st, const uint8_t *p, uint32_t len, uint32_t *
             s1 = st.wt[s1].next + br.read(st.wt[s1].nbits);
             if (br.over) {
                 st.weights[nw++] = st.wt[s2].sym;
+                PBSZ_COV((nw & 1) ? C_WEIGHTS_END_FIRST : C_WEIGHTS_END_SECOND);  // (the roles swapped nw - 1 times)
                 break;
             }
             const uint32_t t = s1;  // the roles swap
@@ -416,6 +422,7 @@ PBSZ_HD int huf_read_table(State &st, const uint8_t *p, uint32_t len, uint32_t *
         for (uint32_t i = 0; i < cnt; ++i) st.huf[at + i] = e;
         st.rank[w] = at + cnt;
     }
+    PBSZ_COV_IF(log == kHufLogMax, C_HUF_LOG_MAX);
     st.huf_log = log;
     st.huf_valid = 1;
     return OK;
@@ -433,6 +440,7 @@ PBSZ_HD int huf_stream(const State &st, const uint8_t *p, uint32_t len, uint8_t 
         if (br.over) return BAD_FRAME;
         out[i] = (uint8_t)e;
     }
+    PBSZ_COV_IF(br.pos > 0 && br.pos < (int32_t)log, C_HUF_SPARE_BITS);
     return br.pos < (int32_t)log ? OK : BAD_FRAME;
 }
 
@@ -561,6 +569,7 @@ PBSZ_HD int decode_block(State &st, const uint8_t *b, uint32_t bs, uint8_t *dst,
                 uint32_t so = 6, sl = c3;  // the stream's place from the jump table, read again by its own lane
                 for (uint32_t j = 0; j < s; ++j) so += (uint32_t)load_le(data + 2 * j, 2);
                 if (s < 3) sl = (uint32_t)load_le(data + 2 * s, 2);
+                PBSZ_COV_IF(s == 3 && regen - 3 * seg < seg, C_HUF_SHORT_4TH);
                 const int r = huf_stream(st, data + so, sl, lit + s * seg, s == 3 ? regen - 3 * seg : seg);
                 if (r) st.err = r;
             }

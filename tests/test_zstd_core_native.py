@@ -28,9 +28,13 @@ BRANCHES = ("single_segment window_descriptor fcs_1 fcs_2 fcs_4 fcs_8 fcs_absent
             "nseq_0 nseq_1 nseq_2 nseq_3 ll_predef ll_rle ll_fse ll_repeat of_predef of_rle of_fse of_repeat "
             "ml_predef ml_rle ml_fse ml_repeat rep_1 rep_2 rep_3 rep_shifted rep_1_minus_1 "
             "match_overlap match_offset_1 match_across_blocks "
-            "match_wait match_no_wait match_src_in_prev_match match_src_own_literals lit_short lit_long batch_follows_batch").split()
+            "match_wait match_no_wait match_src_in_prev_match match_src_own_literals lit_short lit_long batch_follows_batch "
+            "huf_spare_bits huf_log_max huf_short_4th weights_end_first weights_end_second norm_zero_run_chained").split()
 # branches that neither libzstd 1.4.8 nor a hand-assembled frame reaches: at most two, each explained in DESIGN.md §15
 UNREACHED = ()
+# the last six: branches that only the crafted frames of tests/zstd_huf_inputs.py are built for (libzstd leaves no spare bits
+# and no codes of 12 bits); tests/test_zstd_huf_native.py asserts them
+CRAFTED = tuple(BRANCHES[-6:])
 
 
 @pytest.fixture(scope="module")
@@ -101,7 +105,7 @@ def test_the_fixtures_reach_every_format_branch(run):
         word = [w for w in so.split() if w.startswith("0x")]
         assert word and "of %d bits" % len(BRANCHES) in so, so[-2000:]
         cov |= int(word[0], 16)
-    missing = [b for i, b in enumerate(BRANCHES) if not cov >> i & 1]
+    missing = [b for i, b in enumerate(BRANCHES) if not cov >> i & 1 and b not in CRAFTED]
     print("coverage", hex(cov), "missing", missing)
     assert len(UNREACHED) <= 2
     assert sorted(missing) == sorted(UNREACHED)

@@ -138,7 +138,10 @@ def _literals_section(lit, as_rle):
     return head + (lit[:1] if as_rle else lit)
 
 
-def _sequences_section(seqs, modes, pad):
+def _sequences_section(seqs, modes, pad, tables=None, desc=b""):
+    """tables: the (table, accuracy log) of literal lengths, offsets and match lengths that the sequences are coded under
+    (the predefined ones by default); desc: what stands between the modes byte and the bit stream (tests/zstd_huf_inputs.py)"""
+    (t_ll, l_ll), (t_of, l_of), (t_ml, l_ml) = tables or ((_LL, LL_LOG), (_OF, OF_LOG), (_ML, ML_LOG))
     n = len(seqs)
     if n == 0:
         return b"\x00"
@@ -151,10 +154,10 @@ def _sequences_section(seqs, modes, pad):
     ll = [_code(LL_BASE, s[0]) for s in seqs]
     ml = [_code(ML_BASE, s[1]) for s in seqs]
     of = [(s[2].bit_length() - 1, s[2] - (1 << (s[2].bit_length() - 1))) for s in seqs]
-    s_ll, b_ll = _states(_LL, [c for c, _ in ll])
-    s_of, b_of = _states(_OF, [c for c, _ in of])
-    s_ml, b_ml = _states(_ML, [c for c, _ in ml])
-    fields = [(s_ll[0], LL_LOG), (s_of[0], OF_LOG), (s_ml[0], ML_LOG)]  # in the order a decoder reads them
+    s_ll, b_ll = _states(t_ll, [c for c, _ in ll])
+    s_of, b_of = _states(t_of, [c for c, _ in of])
+    s_ml, b_ml = _states(t_ml, [c for c, _ in ml])
+    fields = [(s_ll[0], l_ll), (s_of[0], l_of), (s_ml[0], l_ml)]  # in the order a decoder reads them
     for i in range(n):
         fields += [(of[i][1], of[i][0]), (ml[i][1], ML_BITS[ml[i][0]]), (ll[i][1], LL_BITS[ll[i][0]])]
         if i + 1 < n:
@@ -166,7 +169,7 @@ def _sequences_section(seqs, modes, pad):
         total += nb
     v <<= pad
     total += pad
-    return head + bytes([modes]) + v.to_bytes(total // 8 + 1, "little")
+    return head + bytes([modes]) + desc + v.to_bytes(total // 8 + 1, "little")
 
 
 def frame(blocks, content_size=None):
@@ -183,8 +186,8 @@ def frame(blocks, content_size=None):
             assert b["regen"] < 1024 and len(b["stream"]) < 1024
             payload = struct.pack("<I", 3 | b["regen"] << 4 | len(b["stream"]) << 14)[:3] + b["stream"] + b"\x00"
             body.append(_block_header(2, len(payload), last) + payload)
-        else:
-            payload = _literals_section(b["lit"], b["rle"]) + _sequences_section(b["seqs"], b["modes"], b["pad"])
+        else:  # ("payload": the block's bytes as tests/zstd_huf_inputs.py wrote them, for the same literals and sequences)
+            payload = b.get("payload") or _literals_section(b["lit"], b["rle"]) + _sequences_section(b["seqs"], b["modes"], b["pad"])
             body.append(_block_header(2, len(payload), last) + payload)
     if content_size is None:
         content_size = len(execute(blocks))
