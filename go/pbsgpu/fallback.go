@@ -309,6 +309,22 @@ func (e *Engine) EncodeZstd2(unsafe.Pointer, uint64, []uint64, []uint64, []uint6
 	return nil, nil, ErrNotBuilt
 }
 
+// Statuses and flags of AesGcmMany.
+const (
+	AesOK          = 0
+	AesBadTag      = 1
+	AesFlagEncrypt = 1
+)
+
+// AesKey is an AES-256 key on the device.
+type AesKey struct{}
+
+func (e *Engine) NewAesKey([]byte) (*AesKey, error) { return nil, ErrNotBuilt }
+func (k *AesKey) Close()                            {}
+func (k *AesKey) AesGcmMany(unsafe.Pointer, uint64, []uint64, []uint64, []byte, uint32, []byte, []uint64, []uint64, unsafe.Pointer, uint64, uint32) ([]uint8, error) {
+	return nil, ErrNotBuilt
+}
+
 // EncodeStats counts what EncodeBlobs2 wrote, per kind (index 0 uncompressed, 1 compressed).
 type EncodeStats struct {
 	Blobs, BlobBytes, ChunkBytes [2]uint64
@@ -340,4 +356,19 @@ type DecodeStats2 struct {
 
 func (e *Engine) DecodeBlobs2(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, bool, unsafe.Pointer, uint64) ([]uint8, DecodeStats2, error) {
 	return nil, DecodeStats2{}, ErrNotBuilt
+}
+
+// BlobBadTag is DecodeBlobs3's status for an encrypted blob whose tag does not authenticate it.
+const BlobBadTag = 7
+
+// DecodeStats3 is DecodeStats2 with a count for BlobBadTag and the ciphertext bytes decrypted.
+type DecodeStats3 struct {
+	Count                                      [8]uint64
+	BlobBytes, CRCBytes, SHA256Bytes, OutBytes uint64
+	ZstdInBytes, ZstdOutBytes                  uint64
+	AesBytes                                   uint64
+}
+
+func (e *Engine) DecodeBlobs3(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, bool, *AesKey, unsafe.Pointer, uint64) ([]uint8, DecodeStats3, error) {
+	return nil, DecodeStats3{}, ErrNotBuilt
 }

@@ -1821,6 +1821,76 @@ func (e *Engine) EncodeZstd2(dptr unsafe.Pointer, nbytes uint64, offsets, length
 		})
 }
 
+// Statuses and flags of AesGcmMany (PBSGPU_AES_*).
+const (
+	AesOK          = 0
+	AesBadTag      = 1 // the tag does not authenticate the message: its output is zeroed
+	AesFlagEncrypt = 1
+)
+
+// AesKey is an AES-256 key on the device (pbsgpu_aes_key_*): round keys, hash key and multiplier tables. The 32 key bytes
+// are not kept on the host; Close zeroes the device copy. How to get the key out of a PBS key file: INTEGRATION.md §6.
+type AesKey struct {
+	h   *C.pbsgpu_aes_key
+	eng *Engine
+}
+
+// NewAesKey expands key (32 bytes) for the engine's device.
+func (e *Engine) NewAesKey(key []byte) (*AesKey, error) {
+	defer runtime.KeepAlive(e)
+	if len(key) != 32 {
+		return nil, errors.New("pbsgpu: an AES-256 key is 32 bytes")
+	}
+	k := &AesKey{eng: e}
+	if err := check(C.pbsgpu_aes_key_create(e.h, (*C.uint8_t)(unsafe.Pointer(&key[0])), &k.h), "aes_key_create"); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(k, (*AesKey).Close)
+	return k, nil
+}
+
+func (k *AesKey) Close() {
+	runtime.SetFinalizer(k, nil)
+	if k.h != nil {
+		C.pbsgpu_aes_key_destroy(k.h)
+		k.h = nil
+	}
+	k.eng = nil
+}
+
+// AesGcmMany decrypts (flags 0) or encrypts (AesFlagEncrypt) many messages of a device buffer in one call: AES-256-GCM with an
+// empty AAD, the cipher of the encrypted blob kinds the reference's pxar-mount cannot read (cmd/pxar-mount/main.go:43, :76
+// drop -keyfile). ivs holds ivLen (12 or 16) bytes per message, tags 16 per message: read when decrypting, written when
+// encrypting. Message i goes to dst at outOffsets[i], which has outRooms[i] >= lengths[i] bytes. Returns the status per
+// message; a message whose tag is bad (AesBadTag) has its output zeroed.
+func (k *AesKey) AesGcmMany(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, ivs []byte, ivLen uint32, tags []byte,
+	outOffsets, outRooms []uint64, dst unsafe.Pointer, dstCap uint64, flags uint32) ([]uint8, error) {
+	defer runtime.KeepAlive(k)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, err
+	}
+	outs, err := toSegments(outOffsets, outRooms)
+	if err != nil {
+		return nil, err
+	}
+	n := len(segs)
+	if len(outs) != n || len(ivs) != n*int(ivLen) || len(tags) != 16*n {
+		return nil, errors.New("pbsgpu: AesGcmMany: one room, one IV and one 16-byte tag per message")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	status := make([]uint8, n)
+	err = check(C.pbsgpu_aes_gcm_many_device(k.h, dptr, C.uint64_t(nbytes), &segs[0], C.uint32_t(n),
+		(*C.uint8_t)(unsafe.Pointer(&ivs[0])), C.uint32_t(ivLen), (*C.uint8_t)(unsafe.Pointer(&tags[0])), &outs[0], dst,
+		C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])), C.uint32_t(flags)), "aes_gcm_many_device")
+	if err != nil {
+		return nil, err
+	}
+	return status, nil
+}
+
 // EncodeStats counts what EncodeBlobs2 wrote, per kind (index 0 uncompressed, 1 compressed).
 type EncodeStats struct {
 	Blobs, BlobBytes, ChunkBytes [2]uint64
@@ -1933,5 +2003,76 @@ func (e *Engine) DecodeBlobs2(dptr unsafe.Pointer, nbytes uint64, offsets, lengt
 	}
 	out.BlobBytes, out.CRCBytes, out.SHA256Bytes = uint64(st.blob_bytes), uint64(st.crc_bytes), uint64(st.sha_bytes)
 	out.OutBytes, out.ZstdInBytes, out.ZstdOutBytes = uint64(st.out_bytes), uint64(st.zstd_in_bytes), uint64(st.zstd_out_bytes)
+	return status[:len(cr)], out, nil
+}
+
+// BlobBadTag is DecodeBlobs3's status for an encrypted blob whose tag does not authenticate it: a wrong key or a damaged blob.
+const BlobBadTag = 7
+
+// DecodeStats3 is DecodeStats2 with a count for BlobBadTag and the ciphertext bytes decrypted, once per distinct blob.
+type DecodeStats3 struct {
+	Count                                      [8]uint64
+	BlobBytes, CRCBytes, SHA256Bytes, OutBytes uint64
+	ZstdInBytes, ZstdOutBytes                  uint64
+	AesBytes                                   uint64
+}
+
+// DecodeBlobs3 is DecodeBlobs2 with the encrypted blobs decrypted on the device under key: the restore loop of a datastore a
+// stock client wrote with a key file, which the reference's pxar-mount cannot read (cmd/pxar-mount/main.go:43, :76 drop
+// -keyfile). An encrypted blob with a good CRC is decrypted to its entries' places; an encrypted-compressed one is then decoded
+// as a zstd frame if zstd is set and stays BlobCRCOnly if not. BlobBadTag: the entry's part of dst is zero where the blob was
+// decrypted in place and untouched otherwise. checkDigest is not applied to encrypted entries (their index digest is keyed).
+// With key nil every output is DecodeBlobs2's.
+func (e *Engine) DecodeBlobs3(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, idx []ChunkInfo, blobOf []uint32,
+	rangeStart, rangeEnd uint64, checkDigest, zstd bool, key *AesKey, dst unsafe.Pointer, dstCap uint64) ([]uint8, DecodeStats3, error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(key)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return nil, DecodeStats3{}, err
+	}
+	if blobOf != nil && len(blobOf) != len(idx) {
+		return nil, DecodeStats3{}, errors.New("pbsgpu: DecodeBlobs3 needs one blobOf per index entry")
+	}
+	cr := toRecords(idx)
+	var sp *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp = &segs[0]
+	}
+	var rp *C.pbsgpu_record
+	var bo *C.uint32_t
+	status := make([]uint8, len(cr)+1)
+	if len(cr) > 0 {
+		rp = &cr[0]
+		if blobOf != nil {
+			bo = (*C.uint32_t)(unsafe.Pointer(&blobOf[0]))
+		}
+	}
+	flags := C.uint32_t(0)
+	if checkDigest {
+		flags |= C.PBSGPU_DECODE_F_DIGEST
+	}
+	if zstd {
+		flags |= C.PBSGPU_DECODE_F_ZSTD
+	}
+	var kh *C.pbsgpu_aes_key
+	if key != nil {
+		flags |= C.PBSGPU_DECODE_F_AES
+		kh = key.h
+	}
+	var st C.pbsgpu_decode_stats3
+	err = check(C.pbsgpu_blob_decode3_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), rp, C.uint64_t(len(cr)), bo,
+		C.uint64_t(rangeStart), C.uint64_t(rangeEnd), flags, kh, dst, C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])),
+		&st), "blob_decode3_device")
+	if err != nil {
+		return nil, DecodeStats3{}, err
+	}
+	var out DecodeStats3
+	for i := range out.Count {
+		out.Count[i] = uint64(st.count[i])
+	}
+	out.BlobBytes, out.CRCBytes, out.SHA256Bytes = uint64(st.blob_bytes), uint64(st.crc_bytes), uint64(st.sha_bytes)
+	out.OutBytes, out.ZstdInBytes, out.ZstdOutBytes = uint64(st.out_bytes), uint64(st.zstd_in_bytes), uint64(st.zstd_out_bytes)
+	out.AesBytes = uint64(st.aes_bytes)
 	return status[:len(cr)], out, nil
 }

@@ -1020,6 +1020,92 @@ int pbsgpu_known_upload_new2_device(pbsgpu_known *known, const void *src, uint64
                                     uint8_t *known_out, uint64_t *blob_off, uint32_t *lens, uint8_t *kinds, uint32_t *crcs,
                                     uint64_t *used, pbsgpu_dedup_stats *stats, pbsgpu_encode_stats *enc_stats);
 
+/* ---- AES-256-GCM on the device --------------------------------------------------------------------------------------------
+ * The cipher of the two encrypted blob kinds ([EXTERNAL] PBS data_blob.rs / crypt_config.rs: magic 8 | CRC-32 LE 4 |
+ * IV 16 | tag 16 | ciphertext; AES-256-GCM, empty AAD, 16-byte tag, 16-byte IV). A datastore written by a stock
+ * proxmox-backup-client with a key file holds such blobs; the reference's pxar-mount takes -keyfile "for CLI compat" and
+ * drops it (cmd/pxar-mount/main.go:43, :76). With this call their payload is decrypted where it lies, on the device.
+ * The format core is pbs_plus_amd/csrc/aes_gcm.h (one source for the kernels and for the CPU build that runs under
+ * sanitizers); how a message is cut into pieces of 64 KiB and their partial hashes folded: DESIGN.md §21. Decisions:
+ *   - the AAD is always empty and the tag 16 bytes;
+ *   - an IV of 12 bytes gives J0 = IV || 0^31 1; one of 16 bytes gives J0 = GHASH(IV || 0^64 || [128]_64), whose low word is
+ *     arbitrary: the 32-bit counter may wrap inside a message and does so correctly;
+ *   - the tag is compared on the device over all 16 bytes without an early exit; a message whose tag is bad has the first
+ *     `length` bytes of its out range ZEROED before the call returns: unauthenticated plaintext is never handed out;
+ *   - the AES table is indexed by secret-dependent bytes: a timing channel that is NOT addressed here;
+ *   - the key never appears in options, environment, trace output or error strings. pbsgpu_aes_key_create expands it on
+ *     the host, copies the tables to device memory the key object owns, and wipes the host copy before it returns.
+ * Not here (NEXT.md): writing encrypted blobs (IV policy, framing), the keyed chunk digest SHA-256(content || id_key), the
+ * key-file KDF, pbsgpu_blob_verify_* with a key (they keep answering PBSGPU_BLOB_CRC_ONLY for encrypted
+ * blobs, as pbsgpu_blob_decode_device and pbsgpu_blob_decode2_device do), and a constant-time AES. */
+#define PBSGPU_HAS_AES_GCM 1
+typedef struct pbsgpu_aes_key pbsgpu_aes_key;
+/* The round keys, H = E_K(0) and the multiplier tables of `key` in device memory of eng's device. The key keeps the engine
+ * alive until it is destroyed. PBSGPU_E_INVALID for a NULL. */
+int pbsgpu_aes_key_create(pbsgpu_engine *eng, const uint8_t key[32], pbsgpu_aes_key **out);
+/* Zeroes the key's device memory, then frees it (the host holds no copy). No call may be using the key. NULL is allowed. */
+void pbsgpu_aes_key_destroy(pbsgpu_aes_key *k);
+#define PBSGPU_AES_OK 0
+#define PBSGPU_AES_BAD_TAG 1
+#define PBSGPU_AES_F_ENCRYPT 1u
+/* Decrypt (flags = 0) or encrypt (PBSGPU_AES_F_ENCRYPT) many messages in one call: message i =
+ * src[msgs[i].offset .. +length) with the IV ivs[i * iv_len .. +iv_len) goes to dst[out[i].offset .. +msgs[i].length); the
+ * rest of the room out[i] is never written. Decrypting reads tags[16 i .. +16) and sets status[i] = PBSGPU_AES_OK or
+ * PBSGPU_AES_BAD_TAG (output zeroed, see above); encrypting writes the tags and sets every status to OK. The caller
+ * supplies the IVs in both directions and answers for their uniqueness. Messages are independent: a bad tag, and whatever
+ * bytes a message holds, leave every other message and every byte outside its own out range as they were.
+ * Decided on the host before any device work, with dst untouched: PBSGPU_E_INVALID for a NULL where a value is needed,
+ * iv_len other than 12 or 16, an unknown flag bit, a message outside src, an out[i] outside dst_cap or shorter than its
+ * message, out ranges that overlap one another or the source, a host pointer for src or dst, a message or a room of
+ * 4 GiB or more. nmsg == 0 is PBSGPU_OK.
+ * One leased stream of the key's engine and ONE synchronisation of it, at the end; it waits only for that stream, so it is
+ * usable between the pumps of a running ring. */
+int pbsgpu_aes_gcm_many_device(pbsgpu_aes_key *k, const void *src, uint64_t nbytes,
+        const pbsgpu_segment *msgs, uint32_t nmsg,
+        const uint8_t *ivs /* host, iv_len * nmsg */, uint32_t iv_len /* 12 or 16 */,
+        uint8_t *tags /* host, 16 * nmsg: read when decrypting, written with F_ENCRYPT */,
+        const pbsgpu_segment *out /* nmsg: offset and room inside dst; room >= length */,
+        void *dst, uint64_t dst_cap, uint8_t *status /* nmsg */, uint32_t flags);
+
+/* Restore with the encrypted blobs decrypted: pbsgpu_blob_decode2_device plus a key, one flag, one status and one statistic.
+ * Without PBSGPU_DECODE_F_AES it is that call, output for output, and key may be NULL. With it (key NULL, or a key of another
+ * engine: PBSGPU_E_INVALID before any device work) a blob of the encrypted kind whose CRC is good is decrypted on the
+ * device under `key`; one of the encrypted-compressed kind as well, if PBSGPU_DECODE_F_ZSTD is set too (its plaintext is one
+ * zstd frame; without F_ZSTD such a blob stays PBSGPU_BLOB_CRC_ONLY). The checks of such a blob, in order: magic, header, CRC,
+ * tag, then for the compressed kind the frame, then the size:
+ *   - the CRC is bad: PBSGPU_BLOB_BAD_CRC, the blob is not decrypted and its part of dst stays untouched;
+ *   - the tag is bad (a wrong key, a damaged blob): PBSGPU_BLOB_BAD_TAG. The entry's part of dst is ZERO where the blob was
+ *     decrypted in place (the case in which pbsgpu_blob_decode2_device decodes a frame straight into dst: the blob's first
+ *     entry inside the range lies wholly inside it and is the largest entry naming the blob) and UNTOUCHED otherwise;
+ *     unauthenticated plaintext is never handed out;
+ *   - the frame is malformed or unsupported: PBSGPU_BLOB_BAD_DATA;
+ *   - the plaintext, or what its frame decodes to, is not exactly idx[i].size bytes: PBSGPU_BLOB_BAD_SIZE. (A plain encrypted
+ *     blob longer than the largest entry naming it still has its tag checked: GHASH reads the ciphertext only.)
+ * PBSGPU_DECODE_F_DIGEST is NOT applied to entries of the encrypted kinds: their index digest is the keyed
+ * SHA-256(content || id_key), which this library does not compute (NEXT.md), and the tag already authenticates the content.
+ * Everything pbsgpu_blob_decode2_device promises holds: the clipping at the range's ends, one decryption per distinct blob
+ * with a copy pass for the other entries, nothing written outside dst[0, range_end - range_start), every verdict on the
+ * device, ONE synchronisation. The plaintext of an encrypted-compressed blob lies in engine scratch, as large as the blobs
+ * of the call together. pbsgpu_blob_decode_device, pbsgpu_blob_decode2_device and pbsgpu_blob_verify_* keep answering
+ * PBSGPU_BLOB_CRC_ONLY for both kinds. Argument errors as for pbsgpu_blob_decode2_device with F_ZSTD, plus an unknown flag. */
+#define PBSGPU_DECODE_F_AES 4u
+#define PBSGPU_BLOB_BAD_TAG 7 /* pbsgpu_blob_decode3_device only: an encrypted blob whose tag does not authenticate it */
+typedef struct pbsgpu_decode_stats3 {
+    uint64_t count[8];       /* index entries per status (PBSGPU_BLOB_*, BAD_DATA and BAD_TAG included) */
+    uint64_t blob_bytes;     /* as pbsgpu_decode_stats2 */
+    uint64_t crc_bytes;
+    uint64_t sha_bytes;
+    uint64_t out_bytes;
+    uint64_t zstd_in_bytes;  /* also the frames of encrypted-compressed blobs with a good tag */
+    uint64_t zstd_out_bytes;
+    uint64_t aes_bytes;      /* ciphertext bytes decrypted: once per distinct encrypted blob with a good CRC */
+} pbsgpu_decode_stats3;
+int pbsgpu_blob_decode3_device(pbsgpu_engine *eng, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                               uint64_t range_start, uint64_t range_end, uint32_t flags, pbsgpu_aes_key *key /* may be NULL */,
+                               void *dst, uint64_t dst_cap, uint8_t *status /* nidx */,
+                               pbsgpu_decode_stats3 *stats /* may be NULL */);
+
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or
  * several engines in one process) ingests its own streams. The one exchange step is the digest-set reduce for cross-file

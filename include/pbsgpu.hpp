@@ -478,6 +478,81 @@ inline Result<Encoded2> Encode2(pbsgpu_engine *eng, const void *src, uint64_t sr
     return r;
 }
 
+// ---- AES-256-GCM (the cipher of the encrypted blob kinds), in batch on the device ----
+
+// An AES-256 key on the device: round keys, hash key and multiplier tables (pbsgpu_aes_key_*). The 32 key bytes are not
+// kept on the host; the destructor zeroes the device copy. Create() returns nullptr and sets *status on failure.
+class AesKey {
+public:
+    static std::unique_ptr<AesKey> Create(pbsgpu_engine *eng, const uint8_t key[32], int *status = nullptr) {
+        pbsgpu_aes_key *h = nullptr;
+        const int st = pbsgpu_aes_key_create(eng, key, &h);
+        if (status) *status = st;
+        if (st != PBSGPU_OK) return nullptr;
+        return std::unique_ptr<AesKey>(new AesKey(h));
+    }
+    ~AesKey() { pbsgpu_aes_key_destroy(h_); }
+    AesKey(const AesKey &) = delete;
+    AesKey &operator=(const AesKey &) = delete;
+    pbsgpu_aes_key *handle() const { return h_; }
+
+private:
+    explicit AesKey(pbsgpu_aes_key *h) : h_(h) {}
+    pbsgpu_aes_key *h_;
+};
+
+struct AesResult {
+    std::vector<uint8_t> status;  // PBSGPU_AES_OK or PBSGPU_AES_BAD_TAG (output zeroed)
+    std::vector<uint8_t> tags;    // 16 per message: as given when decrypting, as computed when encrypting
+};
+
+// Decrypt (flags 0; tags: 16 bytes per message) or encrypt (PBSGPU_AES_F_ENCRYPT; tags ignored, returned) many messages
+// of a device buffer in one call. ivs: ivLen (12 or 16) bytes per message, the caller's in both directions.
+inline Result<AesResult> AesGcmMany(const AesKey &key, const void *src, uint64_t nbytes, const std::vector<pbsgpu_segment> &msgs,
+                                    const std::vector<uint8_t> &ivs, uint32_t ivLen, const std::vector<uint8_t> &tags,
+                                    const std::vector<pbsgpu_segment> &out, void *dst, uint64_t dstCap, uint32_t flags) {
+    Result<AesResult> r;
+    const size_t n = msgs.size();
+    r.value.status.resize(n + 1);
+    r.value.tags.assign(16 * n + 16, 0);
+    const bool enc = (flags & PBSGPU_AES_F_ENCRYPT) != 0;
+    int st = PBSGPU_E_INVALID;
+    if (out.size() == n && ivs.size() == (size_t)ivLen * n && (enc || tags.size() == 16 * n)) {
+        if (!enc) std::copy(tags.begin(), tags.end(), r.value.tags.begin());
+        st = pbsgpu_aes_gcm_many_device(key.handle(), src, nbytes, msgs.data(), (uint32_t)n, ivs.data(), ivLen, r.value.tags.data(),
+                                        out.data(), dst, dstCap, r.value.status.data(), flags);
+    }
+    r.value.status.resize(n);
+    r.value.tags.resize(16 * n);
+    if (st != PBSGPU_OK) r.err = errorf("aes gcm", st);
+    return r;
+}
+
+struct Decoded3 {
+    std::vector<uint8_t> status;  // PBSGPU_BLOB_* per index entry, PBSGPU_BLOB_BAD_TAG included
+    pbsgpu_decode_stats3 stats{};
+};
+
+// Decode2 with the encrypted blobs decrypted on the device under `key` (PBSGPU_DECODE_F_AES; key nullptr: Decode2, output
+// for output): the restore loop of a datastore written with a key file. An encrypted-compressed blob needs zstd = true as
+// well; PBSGPU_BLOB_BAD_TAG is a wrong key or a damaged blob. checkDigest is not applied to encrypted entries.
+inline Result<Decoded3> Decode3(pbsgpu_engine *eng, const void *blobsDev, uint64_t nbytes,
+                                const std::vector<pbsgpu_segment> &blobs, const std::vector<pbsgpu_record> &idx,
+                                const std::vector<uint32_t> &blobOf, uint64_t rangeStart, uint64_t rangeEnd, bool checkDigest,
+                                bool zstd, const AesKey *key, void *dst, uint64_t dstCap) {
+    Result<Decoded3> r;
+    r.value.status.resize(idx.size() + 1);
+    const uint32_t flags = (checkDigest ? PBSGPU_DECODE_F_DIGEST : 0u) | (zstd ? PBSGPU_DECODE_F_ZSTD : 0u) |
+                           (key ? PBSGPU_DECODE_F_AES : 0u);
+    const int st = pbsgpu_blob_decode3_device(eng, blobsDev, nbytes, blobs.data(), (uint32_t)blobs.size(), idx.data(),
+                                              idx.size(), blobOf.empty() ? nullptr : blobOf.data(), rangeStart, rangeEnd,
+                                              flags, key ? key->handle() : nullptr, dst, dstCap, r.value.status.data(),
+                                              &r.value.stats);
+    r.value.status.resize(idx.size());
+    if (st != PBSGPU_OK) r.err = errorf("blob decode3", st);
+    return r;
+}
+
 }  // namespace blob
 
 // datastore.DynamicIndexReader

@@ -150,11 +150,22 @@ class DecodeStats2(C.Structure):
                 ("out_bytes", C.c_uint64), ("zstd_in_bytes", C.c_uint64), ("zstd_out_bytes", C.c_uint64)]
 
 
+BLOB_BAD_TAG = 7  # blob_decode3 only
+BLOB_STATUS_NAMES3 = BLOB_STATUS_NAMES2 + ("bad_tag",)
+DECODE_F_AES = 4
+
+
+class DecodeStats3(C.Structure):
+    _fields_ = DecodeStats2._fields_ + [("aes_bytes", C.c_uint64)]
+
+
 ZSTD_OK, ZSTD_BAD_FRAME, ZSTD_BAD_SIZE, ZSTD_UNSUPPORTED = range(4)
 ZSTD_STATUS_NAMES = ("ok", "bad_frame", "bad_size", "unsupported")
 ZSTD_BAD_CHECKSUM = 4  # zstd_decode2(checksum=True) only
 ZSTD_F_CHECKSUM, ZSTD_F_STREAM = 1, 2
 ENCODE_F_ZSTD = 1
+AES_OK, AES_BAD_TAG = 0, 1
+AES_F_ENCRYPT = 1
 
 
 class EncodeStats(C.Structure):
@@ -297,6 +308,12 @@ SYMBOLS = {
                                                  _P, _P, _U64P, C.POINTER(DedupStats), C.POINTER(EncodeStats)]),
     "pbsgpu_known_upload_new2_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_int, C.c_uint32, _P, C.c_uint64, _P,
                                                   _P, _P, _P, _P, _U64P, C.POINTER(DedupStats), C.POINTER(EncodeStats)]),
+    "pbsgpu_aes_key_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
+    "pbsgpu_aes_key_destroy": (None, [_P]),
+    "pbsgpu_aes_gcm_many_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint64, _P,
+                                             C.c_uint32]),
+    "pbsgpu_blob_decode3_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
+                                             C.c_uint32, _P, _P, C.c_uint64, _P, C.POINTER(DecodeStats3)]),
     "pbsgpu_comm_unique_id": (C.c_int, [_P]),
     "pbsgpu_comm_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "pbsgpu_comm_destroy": (None, [_P]),

@@ -1337,7 +1337,9 @@ int enqueue_restore(pbsgpu_engine *e, Slot *s, const Restore &r, const void *bpt
 // The zstd leg (zstd.hip), behind the statuses above on the same stream: the frames of the compressed blobs with a good
 // CRC into the rooms the plan gave them, the copies out of scratch, the digests of the decoded bytes, and the statuses
 // of the decoded blobs' entries. zres: the frames' results in the block that goes back.
-int enqueue_restore_zstd(pbsgpu_engine *e, Slot *s, Restore &r, const DecPlan &pl, uint64_t *zres) {
+// run = false: rooms, copies and scratch are laid out and *plan filled in for the AES leg, nothing of the zstd leg is launched.
+int enqueue_restore_zstd(pbsgpu_engine *e, Slot *s, Restore &r, const DecPlan &pl, uint64_t *zres, bool run,
+                         pbsk::zstd::RestorePlan *plan) {
     namespace pz = pbsk::zstd;
     const uint32_t nu = r.nu();
     uint8_t *scratch = s->bulk((size_t)r.scratch_bytes);
@@ -1371,6 +1373,8 @@ int enqueue_restore_zstd(pbsgpu_engine *e, Slot *s, Restore &r, const DecPlan &p
     zp.ncopy = (uint32_t)r.zcopies.size();
     zp.nidx = pl.nidx;
     zp.stride = r.lit_groups;
+    if (plan) *plan = zp;
+    if (!run) return PBSGPU_OK;
     HIPCHK(pz::launch_restore_frames(zp, w + zw.desc, s->stream));
     if (zp.ncopy) HIPCHK(pz::launch_restore_copy(zp, r.longest_zcopy, e->num_cus, s->stream));
     if (pl.recs) {
@@ -1383,8 +1387,8 @@ int enqueue_restore_zstd(pbsgpu_engine *e, Slot *s, Restore &r, const DecPlan &p
 }
 
 // the statistics of a restore from the block that came back
-void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bool check_digest, bool zstd,
-                   const uint8_t *status, pbsgpu_decode_stats2 *stats) {
+void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bool check_digest, bool zstd, bool aes,
+                   const uint8_t *status, pbsgpu_decode_stats3 *stats) {
     const uint32_t nu = r.nu();
     const size_t nidx = r.ents.size();
     const DecInfo *info = reinterpret_cast<const DecInfo *>(back + ob.info);
@@ -1399,6 +1403,22 @@ void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bo
         const uint32_t u = r.ents[i].u;
         if (info[u].hk == PBSGPU_BLOB_HEADER_SIZE && r.ub[u].length - PBSGPU_BLOB_HEADER_SIZE == r.ents[i].size)
             stats->out_bytes += r.clip[i];
+    }
+    if (aes) {  // the AES leg's results: once per distinct blob it decrypted
+        const uint64_t *ares = reinterpret_cast<const uint64_t *>(back + ob.ares);
+        for (uint32_t u = 0; u < nu; ++u) {
+            const uint32_t code = (uint32_t)(ares[u] >> 32);
+            if (code == pbsk::zstd::kNotDecoded) continue;
+            const uint64_t len = r.ub[u].length - PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE;
+            stats->aes_bytes += len;
+            if (code == pbsk::aes::kResBadTag || !(code & pbsk::aes::kResFrame)) continue;
+            stats->zstd_in_bytes += len;  // a good tag over a frame: it went to the decoder
+            if (code == (pbsk::aes::kResFrame | PBSGPU_ZSTD_OK)) stats->zstd_out_bytes += (uint32_t)ares[u];
+        }
+        for (size_t i = 0; i < nidx; ++i) {
+            const uint64_t a = ares[r.ents[i].u];
+            if ((a & ~((uint64_t)pbsk::aes::kResFrame << 32)) == (uint64_t)r.ents[i].size) stats->out_bytes += r.clip[i];
+        }
     }
     if (!zstd) return;
     const uint64_t *zres = reinterpret_cast<const uint64_t *>(back + ob.zres);
@@ -1418,27 +1438,36 @@ void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bo
 // length, CRC, digest, the frames) is decided on the device.
 int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
                 const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re,
-                uint32_t flags, void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats2 *stats) {
+                uint32_t flags, const pbsgpu_aes_key *key, void *dst, uint64_t dst_cap, uint8_t *status,
+                pbsgpu_decode_stats3 *stats) {
     const bool check_digest = (flags & PBSGPU_DECODE_F_DIGEST) != 0;
     const bool zstd = (flags & PBSGPU_DECODE_F_ZSTD) != 0;
+    const bool aes = (flags & PBSGPU_DECODE_F_AES) != 0;
     if (!e || nidx >= (1ull << 32)) return PBSGPU_E_INVALID;
+    if (aes && (!key || pbsk::aes::key_engine(key) != e)) return PBSGPU_E_INVALID;
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (nidx == 0) return PBSGPU_OK;
     if (!status) return PBSGPU_E_INVALID;
-    CHK(check_decode(e, bptr, nbytes, blobs, nblob, idx, nidx, blob_of, rs, re, zstd, dst, dst_cap));
-    Restore r;
-    if (!plan_restore(blobs, nblob, idx, nidx, blob_of, rs, re, zstd, (uint64_t)e->num_cus * 4, r)) return PBSGPU_E_INVALID;
+    CHK(check_decode(e, bptr, nbytes, blobs, nblob, idx, nidx, blob_of, rs, re, zstd || aes, dst, dst_cap));
+    Restore r;  // (the rooms and copies of a transformed blob are the same for either leg)
+    if (!plan_restore(blobs, nblob, idx, nidx, blob_of, rs, re, zstd || aes, (uint64_t)e->num_cus * 4, r)) return PBSGPU_E_INVALID;
     AuxLease lease(e);
     Slot *s = lease.s;
-    const DecBlock ob(r.nu(), (size_t)nidx, zstd);
+    const DecBlock ob(r.nu(), (size_t)nidx, zstd, aes);
     uint8_t *out = nullptr;
     DecPlan pl;
     CHK(enqueue_restore(e, s, r, bptr, nbytes, idx, check_digest, static_cast<uint8_t *>(dst), ob, &out, pl));
-    if (zstd) CHK(enqueue_restore_zstd(e, s, r, pl, reinterpret_cast<uint64_t *>(out + ob.zres)));
+    if (zstd || aes) {
+        pbsk::zstd::RestorePlan zp{};
+        CHK(enqueue_restore_zstd(e, s, r, pl, reinterpret_cast<uint64_t *>(out + ob.zres), zstd, &zp));
+        if (aes)
+            CHK(pbsk::aes::enqueue_restore(e, s, key, zp, r.ub.data(), zstd, r.longest_zcopy,
+                                           reinterpret_cast<uint64_t *>(out + ob.ares)));
+    }
     std::vector<uint8_t> back(ob.total);
     CHK(fetch_result(s, back.data(), out, ob.total));  // the call's one synchronisation
     std::memcpy(status, back.data() + ob.status, (size_t)nidx);
-    if (stats) restore_stats(r, back.data(), ob, check_digest, zstd, status, stats);
+    if (stats) restore_stats(r, back.data(), ob, check_digest, zstd, aes, status, stats);
     return PBSGPU_OK;
 }
 
@@ -1819,9 +1848,9 @@ int pbsgpu_blob_decode_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_t
                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
                               uint64_t range_start, uint64_t range_end, int check_digest, void *dst, uint64_t dst_cap,
                               uint8_t *status, pbsgpu_decode_stats *stats) {
-    pbsgpu_decode_stats2 st2{};
+    pbsgpu_decode_stats3 st2{};
     const int r = blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end,
-                              check_digest ? PBSGPU_DECODE_F_DIGEST : 0u, dst, dst_cap, status, &st2);
+                              check_digest ? PBSGPU_DECODE_F_DIGEST : 0u, nullptr, dst, dst_cap, status, &st2);
     if (stats && e && nidx < (1ull << 32)) {  // (past those two checks the statistics are cleared first, as they always were)
         for (int k = 0; k < PBSGPU_BLOB_NSTATUS; ++k) stats->count[k] = st2.count[k];
         stats->blob_bytes = st2.blob_bytes;
@@ -1837,7 +1866,20 @@ int pbsgpu_blob_decode2_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_
                                uint64_t range_start, uint64_t range_end, uint32_t flags, void *dst, uint64_t dst_cap,
                                uint8_t *status, pbsgpu_decode_stats2 *stats) {
     if (flags & ~(PBSGPU_DECODE_F_DIGEST | PBSGPU_DECODE_F_ZSTD)) return PBSGPU_E_INVALID;
-    return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, flags, dst, dst_cap,
+    pbsgpu_decode_stats3 st3{};
+    const int r = blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, flags, nullptr, dst,
+                              dst_cap, status, stats ? &st3 : nullptr);
+    static_assert(sizeof(pbsgpu_decode_stats3) == sizeof(pbsgpu_decode_stats2) + 8, "stats3 is stats2 and one field more");
+    if (stats && e && nidx < (1ull << 32)) std::memcpy(stats, &st3, sizeof(*stats));  // (cleared past those two checks, as ever)
+    return r;
+}
+
+int pbsgpu_blob_decode3_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                               uint64_t range_start, uint64_t range_end, uint32_t flags, pbsgpu_aes_key *key, void *dst,
+                               uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats3 *stats) {
+    if (flags & ~(PBSGPU_DECODE_F_DIGEST | PBSGPU_DECODE_F_ZSTD | PBSGPU_DECODE_F_AES)) return PBSGPU_E_INVALID;
+    return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, flags, key, dst, dst_cap,
                        status, stats);
 }
 

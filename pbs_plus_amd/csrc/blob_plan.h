@@ -170,11 +170,12 @@ struct DecTables {  // the restore's upload: pbase u64[nu + 1] | prim[nu] | copi
         : pbase(p.add((nu + 1) * 8, 8)), prim(p.add(nu * sizeof(DecStore), 8)), copies(p.add(ncopy * sizeof(DecStore), 8)),
           ents(p.add(nidx * sizeof(DecEntry), 4)), pseg(p.add(np * 4, 4)), total(p.total) {}
 };
-struct DecBlock {  // the restore's return block: info[nu] | status u8[nidx] | with F_ZSTD: the frames' results u64[nu]
-    Packer p;
-    size_t info, status, zres, total;
-    DecBlock(size_t nu, size_t nidx, bool zstd)
-        : info(p.add(nu * sizeof(DecInfo), 4)), status(p.add(nidx, 1)), zres(zstd ? p.add(nu * 8, 8) : 0), total(p.total) {}
+struct DecBlock {  // the restore's return block: info[nu] | status u8[nidx] | with F_ZSTD: the frames' results u64[nu] | with
+    Packer p;      // F_AES: the AES leg's results u64[nu]
+    size_t info, status, zres, ares, total;
+    DecBlock(size_t nu, size_t nidx, bool zstd, bool aes = false)
+        : info(p.add(nu * sizeof(DecInfo), 4)), status(p.add(nidx, 1)), zres(zstd ? p.add(nu * 8, 8) : 0),
+          ares(aes ? p.add(nu * 8, 8) : 0), total(p.total) {}
 };
 struct ZTables {  // the zstd leg's upload: jobs[nu] | copies[ncopy]
     Packer p;

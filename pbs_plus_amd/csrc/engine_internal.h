@@ -356,6 +356,21 @@ hipError_t launch_restore_copy(const RestorePlan &pl, uint32_t longest, int num_
 hipError_t launch_restore_status(const RestorePlan &pl, hipStream_t st);
 }  // namespace zstd
 }  // namespace pbsk
+// aes_gcm.hip: the AES leg of pbsgpu_blob_decode3_device, behind the restore's own kernels and the zstd leg on the same
+// stream. zp is the zstd leg's plan (src, blobs, info, crcs, jobs, copies, ents, status, dst, lit, stride: the rooms and
+// the copies are the same whatever transforms a blob). An encrypted blob with a good CRC is decrypted, a plain one to its
+// room, a compressed one to scratch and from there through the frame decoder (with zstd); its entries' statuses are
+// rewritten. ub: the distinct blobs (host). res (device, nu): per blob kNotDecoded << 32 when the leg left it alone, else
+// status << 32 | bytes with 0xfe = bad tag and bit 0x80 = its plaintext was a frame.
+struct pbsgpu_aes_key;
+namespace pbsk {
+namespace aes {
+int enqueue_restore(pbsgpu_engine *e, pbse::Slot *s, const pbsgpu_aes_key *key, const pbsk::zstd::RestorePlan &zp,
+                    const pbsgpu_segment *ub, bool zstd, uint32_t longest_copy, uint64_t *res);
+pbsgpu_engine *key_engine(const pbsgpu_aes_key *k);
+constexpr uint32_t kResBadTag = 0xfe, kResFrame = 0x80;
+}  // namespace aes
+}  // namespace pbsk
 // zstd_encode.hip: the frames of many chunks, enqueued on a slot's stream (pbsgpu_zstd_encode_device, and the zstd leg of
 // pbsgpu_blob_encode2_device, which blob.hip follows with its CRC and header kernels on the same stream).
 namespace pbsk {

@@ -122,6 +122,11 @@ hipError_t launch_restore_frames(const RestorePlan &pl, void *desc, hipStream_t 
     return hipGetLastError();
 }
 
+hipError_t launch_frames(const Plan &pl, hipStream_t st) {
+    hipLaunchKernelGGL(k_zstd_frames, dim3(pl.stride), dim3(64), 0, st, pl);
+    return hipGetLastError();
+}
+
 hipError_t launch_restore_copy(const RestorePlan &pl, uint32_t longest, int num_cus, hipStream_t st) {
     const uint32_t gx = std::max<uint32_t>(1, std::min<uint32_t>((longest + 4095) / 4096, (uint32_t)num_cus * 8));
     hipLaunchKernelGGL(k_zr_copy, dim3(gx, std::min<uint32_t>(pl.ncopy, 1024)), dim3(256), 0, st, pl);

@@ -34,6 +34,9 @@ struct WaveLanes {
     static __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 };
 
+// zstd.hip: pl.stride workgroups of k_zstd_frames over descriptors the caller has made on the device (the AES leg of the
+// restore, aes_gcm.hip: the frames of the encrypted-compressed blobs, decrypted into scratch)
+hipError_t launch_frames(const Plan &pl, hipStream_t st);
 // zstd_checksum.hip: pl.stride workgroups of k_zstd_frames2 with `flags` (PBSGPU_ZSTD_F_*, not 0)
 hipError_t launch_frames2(const Plan &pl, uint32_t flags, hipStream_t st);
 // zstd_checksum.hip: XXH64(base + ranges[i], seed) into out[i], i < n; ranges and out on the device. Enqueued, nothing

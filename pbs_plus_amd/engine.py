@@ -386,6 +386,50 @@ class Engine:
                      out_bytes=int(st.out_bytes), zstd_in_bytes=int(st.zstd_in_bytes), zstd_out_bytes=int(st.zstd_out_bytes))
         return dst, status[:n], stats
 
+    def blob_decode3(self, data, blobs, idx, blob_of=None, start=None, end=None, check_digest=True, dst=None,
+                     nbytes: int | None = None, zstd=True, key=None, aes=None):
+        """blob_decode2() with the encrypted blobs decrypted on the device under `key`, an AesKey of this engine
+        (pbsgpu_blob_decode3_device). aes defaults to "a key was given"; aes=True without a key raises PbsGpuError
+        (E_INVALID). An encrypted blob whose CRC is good is decrypted to its entries' places; an encrypted-compressed one is
+        then decoded as a frame if zstd is set, and stays 5 (crc_only) if not. Status 7 (bad_tag): a wrong key or a damaged
+        blob, the entry's part of dst is zero where the blob was decrypted in place and untouched otherwise. check_digest is
+        not applied to encrypted entries. Without aes every output is blob_decode2()'s. The stats dict has a count per status
+        name ("bad_tag" included) and aes_bytes beside blob_decode2()'s byte counts."""
+        recs = np.ascontiguousarray(idx, dtype=RECORD_DTYPE).reshape(-1)
+        n = int(recs.size)
+        segs, nblob = _segs(blobs)
+        bp, bn = self._dev(data, nbytes)
+        assert bp is not None, "blob_decode3() wants device memory"
+        bo = None if blob_of is None else np.ascontiguousarray(blob_of, dtype=np.uint32).reshape(-1)
+        assert bo is None or bo.size == n
+        if start is None:
+            start = int(recs["end"][0]) - int(recs["size"][0]) if n else 0
+        if end is None:
+            end = int(recs["end"][-1]) if n else start
+        own = dst is None
+        if own:
+            dst = self.alloc(max(int(end) - int(start), 16))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        st = _lib.DecodeStats3()
+        if aes is None:
+            aes = key is not None
+        flags = (_lib.DECODE_F_DIGEST if check_digest else 0) | (_lib.DECODE_F_ZSTD if zstd else 0) | (_lib.DECODE_F_AES if aes else 0)
+        try:
+            check(self._L.pbsgpu_blob_decode3_device(self._h, bp, bn, segs, nblob, recs.ctypes.data if n else None, n,
+                                                     bo.ctypes.data if bo is not None and n else None, int(start), int(end),
+                                                     flags, key._h if key is not None else None, dst.ptr, dst.nbytes,
+                                                     status.ctypes.data, C.byref(st)),
+                  "blob_decode3_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        stats = {name: int(st.count[k]) for k, name in enumerate(_lib.BLOB_STATUS_NAMES3)}
+        stats.update(blob_bytes=int(st.blob_bytes), crc_bytes=int(st.crc_bytes), sha_bytes=int(st.sha_bytes),
+                     out_bytes=int(st.out_bytes), zstd_in_bytes=int(st.zstd_in_bytes), zstd_out_bytes=int(st.zstd_out_bytes),
+                     aes_bytes=int(st.aes_bytes))
+        return dst, status[:n], stats
+
     def zstd_decode2(self, data, frames, out=None, dst=None, nbytes: int | None = None, checksum=False, stream=False):
         """zstd_decode() with flags (pbsgpu_zstd_decode2_device). checksum=True: a frame that carries a content checksum
         is checked against it, a mismatch is status 4 (_lib.ZSTD_BAD_CHECKSUM) with 0 bytes decoded. stream=True: every
@@ -448,6 +492,55 @@ class Engine:
                 dst.free()
             raise
         return dst, status[:n], decoded[:n], oa
+
+    def aes_gcm_many(self, key, data, messages, ivs, tags=None, out=None, dst=None, nbytes: int | None = None, encrypt=False):
+        """AES-256-GCM (empty AAD, 16-byte tags) over the messages [(offset, length)] of the device buffer `data` in one
+        call (pbsgpu_aes_gcm_many_device) under `key`, an AesKey of this engine. ivs: one IV of 12 or 16 bytes per message
+        (bytes each, or an (n, iv_len) uint8 array). Decrypting wants tags, an (n, 16) uint8 array; encrypt=True returns
+        them. Message i goes to dst at out[i] = (offset, room >= length); out None lays the messages out back to back,
+        dst None allocates what `out` needs. Returns (dst, status per message: 0 ok, 1 bad tag, tags as an (n, 16) array,
+        out as an (n, 2) array). A message whose tag is bad has its output zeroed."""
+        dp, dn = self._dev(data, nbytes)
+        assert dp is not None, "aes_gcm_many() wants device memory"
+        ms = np.ascontiguousarray(messages, dtype=np.uint64).reshape(-1, 2)
+        n = int(ms.shape[0])
+        def flat(items):  # an array as it is, else one bytes-like per message
+            if isinstance(items, np.ndarray):
+                return np.ascontiguousarray(items, dtype=np.uint8).reshape(-1)
+            return np.frombuffer(b"".join(bytes(v) for v in items), dtype=np.uint8)
+
+        iva = flat(ivs) if n else np.zeros(0, np.uint8)
+        iv_len = iva.size // n if n else 16
+        if n and (iva.size != n * iv_len or iv_len not in (12, 16)):
+            raise ValueError("one IV of 12 or 16 bytes per message, all of one length")
+        if encrypt:
+            ta = np.zeros((max(n, 1), 16), dtype=np.uint8)
+        else:
+            if tags is None:
+                raise ValueError("decrypting wants tags=")
+            ta = flat(tags).reshape(-1, 16).copy()
+            assert ta.shape[0] == n, "one 16-byte tag per message"
+            if n == 0:
+                ta = np.zeros((1, 16), dtype=np.uint8)
+        if out is None:
+            ends = np.cumsum(ms[:, 1])
+            out = np.stack([ends - ms[:, 1], ms[:, 1]], axis=1)
+        oa = np.ascontiguousarray(out, dtype=np.uint64).reshape(-1, 2)
+        assert oa.shape[0] == n, "one (offset, room) per message"
+        own = dst is None
+        if own:
+            dst = self.alloc(max(int((oa[:, 0] + oa[:, 1]).max()) if n else 0, 16))
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        try:
+            check(self._L.pbsgpu_aes_gcm_many_device(key._h, dp, dn, ms.ctypes.data if n else None, n, iva.ctypes.data if n else None,
+                                                     iv_len, ta.ctypes.data, oa.ctypes.data if n else None, dst.ptr, dst.nbytes,
+                                                     status.ctypes.data, _lib.AES_F_ENCRYPT if encrypt else 0),
+                  "aes_gcm_many_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        return dst, status[:n], ta[:n], oa
 
     def zstd_encode2(self, data, chunks, out=None, dst=None, nbytes: int | None = None, checksum=False):
         """zstd_encode() with flags (pbsgpu_zstd_encode2_device). checksum=True: every frame carries the content checksum
@@ -707,6 +800,45 @@ def chunk_ranges(records: np.ndarray, segments=None, known=None) -> np.ndarray:
     out[:, 0] = base + recs["end"] - size
     out[:, 1] = size
     return out
+
+
+class AesKey:
+    """An AES-256 key on the device (pbsgpu_aes_key_*): its round keys, hash key and multiplier tables, for
+    Engine.aes_gcm_many. The 32 key bytes are expanded once and not kept on the host; close() zeroes the device copy. The
+    key keeps its engine alive."""
+
+    def __init__(self, eng: "Engine", key: bytes):
+        if len(key) != 32:
+            raise ValueError("an AES-256 key is 32 bytes")
+        self._eng = eng
+        self._L = eng._L
+        h = C.c_void_p()
+        buf = (C.c_uint8 * 32).from_buffer_copy(bytes(key))
+        try:
+            check(self._L.pbsgpu_aes_key_create(eng._h, buf, C.byref(h)), "aes_key_create")
+        finally:
+            C.memset(buf, 0, 32)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pbsgpu_aes_key_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __repr__(self):  # (never the key)
+        return "AesKey(<32 bytes>)"
 
 
 class KnownChunks:
