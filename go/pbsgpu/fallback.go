@@ -372,3 +372,23 @@ type DecodeStats3 struct {
 func (e *Engine) DecodeBlobs3(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, bool, *AesKey, unsafe.Pointer, uint64) ([]uint8, DecodeStats3, error) {
 	return nil, DecodeStats3{}, ErrNotBuilt
 }
+
+// EncodeStats3 is EncodeStats over all four kinds, with the plaintext bytes encrypted.
+type EncodeStats3 struct {
+	Blobs, BlobBytes, ChunkBytes   [4]uint64
+	FrameBytes, CRCBytes, AesBytes uint64
+}
+
+// Encoded3 is what EncodeBlobs3 returns.
+type Encoded3 struct {
+	Offsets []uint64
+	Lens    []uint32
+	Kinds   []uint8
+	CRCs    []uint32
+	IVs     []byte
+	Stats   EncodeStats3
+}
+
+func (e *Engine) EncodeBlobs3(unsafe.Pointer, uint64, []uint64, []uint64, bool, *AesKey, []byte, unsafe.Pointer, uint64) (Encoded3, error) {
+	return Encoded3{}, ErrNotBuilt
+}

@@ -22,6 +22,7 @@ package pbsgpu
 import "C"
 
 import (
+	"crypto/rand"
 	"errors"
 	"fmt"
 	"io"
@@ -2075,4 +2076,79 @@ func (e *Engine) DecodeBlobs3(dptr unsafe.Pointer, nbytes uint64, offsets, lengt
 	out.OutBytes, out.ZstdInBytes, out.ZstdOutBytes = uint64(st.out_bytes), uint64(st.zstd_in_bytes), uint64(st.zstd_out_bytes)
 	out.AesBytes = uint64(st.aes_bytes)
 	return status[:len(cr)], out, nil
+}
+
+// EncodeStats3 is EncodeStats over all four kinds (index 2 encrypted, 3 encrypted-compressed), with the plaintext bytes
+// encrypted.
+type EncodeStats3 struct {
+	Blobs, BlobBytes, ChunkBytes   [4]uint64
+	FrameBytes, CRCBytes, AesBytes uint64
+}
+
+// Encoded3 is what EncodeBlobs3 returns: Encoded2 with Kinds up to 3 and the IVs the blobs were written with, 16 bytes each.
+type Encoded3 struct {
+	Offsets []uint64
+	Lens    []uint32
+	Kinds   []uint8
+	CRCs    []uint32
+	IVs     []byte
+	Stats   EncodeStats3
+}
+
+// EncodeBlobs3 is EncodeBlobs2 with the blobs encrypted on the device under key (AES-256-GCM, empty AAD): blob i lies in the
+// slot [Offsets[i], Offsets[i] + 44 + length) as magic, CRC-32 of the ciphertext, IV, tag, ciphertext. Kind 2 holds the chunk,
+// kind 3 (zstd true and the frame strictly shorter than the chunk) its frame. ivs holds 16 bytes per chunk; nil draws them
+// from crypto/rand. Two equal IVs in one call are refused; uniqueness across calls under one key is the caller's to answer
+// for. With key nil every output is EncodeBlobs2's and no IV is used.
+func (e *Engine) EncodeBlobs3(src unsafe.Pointer, srcBytes uint64, offsets, lengths []uint64, zstd bool, key *AesKey, ivs []byte,
+	dst unsafe.Pointer, dstCap uint64) (Encoded3, error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(key)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return Encoded3{}, err
+	}
+	n := len(segs)
+	out := Encoded3{Offsets: make([]uint64, n+1), Lens: make([]uint32, n+1), Kinds: make([]uint8, n+1), CRCs: make([]uint32, n+1)}
+	var sp *C.pbsgpu_segment
+	if n > 0 {
+		sp = &segs[0]
+	}
+	flags := C.uint32_t(0)
+	if zstd {
+		flags |= C.PBSGPU_ENCODE_F_ZSTD
+	}
+	var kh *C.pbsgpu_aes_key
+	var ip *C.uint8_t
+	if key != nil {
+		flags |= C.PBSGPU_ENCODE_F_AES
+		kh = key.h
+		if ivs == nil {
+			ivs = make([]byte, 16*n)
+			if _, err := rand.Read(ivs); err != nil {
+				return Encoded3{}, err
+			}
+		}
+		if len(ivs) != 16*n {
+			return Encoded3{}, errors.New("pbsgpu: EncodeBlobs3 needs one 16-byte IV per chunk")
+		}
+		if n > 0 {
+			ip = (*C.uint8_t)(unsafe.Pointer(&ivs[0]))
+		}
+		out.IVs = ivs
+	}
+	var st C.pbsgpu_encode_stats3
+	err = check(C.pbsgpu_blob_encode3_device(e.h, src, C.uint64_t(srcBytes), sp, C.uint32_t(n), flags, kh, ip, dst, C.uint64_t(dstCap),
+		(*C.uint64_t)(unsafe.Pointer(&out.Offsets[0])), (*C.uint32_t)(unsafe.Pointer(&out.Lens[0])),
+		(*C.uint8_t)(unsafe.Pointer(&out.Kinds[0])), (*C.uint32_t)(unsafe.Pointer(&out.CRCs[0])), &st), "blob_encode3_device")
+	if err != nil {
+		return Encoded3{}, err
+	}
+	out.Lens, out.Kinds, out.CRCs = out.Lens[:n], out.Kinds[:n], out.CRCs[:n]
+	for k := 0; k < 4; k++ {
+		out.Stats.Blobs[k], out.Stats.BlobBytes[k] = uint64(st.blobs[k]), uint64(st.blob_bytes[k])
+		out.Stats.ChunkBytes[k] = uint64(st.chunk_bytes[k])
+	}
+	out.Stats.FrameBytes, out.Stats.CRCBytes, out.Stats.AesBytes = uint64(st.frame_bytes), uint64(st.crc_bytes), uint64(st.aes_bytes)
+	return out, nil
 }

@@ -1035,9 +1035,10 @@ int pbsgpu_known_upload_new2_device(pbsgpu_known *known, const void *src, uint64
  *   - the AES table is indexed by secret-dependent bytes: a timing channel that is NOT addressed here;
  *   - the key never appears in options, environment, trace output or error strings. pbsgpu_aes_key_create expands it on
  *     the host, copies the tables to device memory the key object owns, and wipes the host copy before it returns.
- * Not here (NEXT.md): writing encrypted blobs (IV policy, framing), the keyed chunk digest SHA-256(content || id_key), the
- * key-file KDF, pbsgpu_blob_verify_* with a key (they keep answering PBSGPU_BLOB_CRC_ONLY for encrypted
- * blobs, as pbsgpu_blob_decode_device and pbsgpu_blob_decode2_device do), and a constant-time AES. */
+ * Writing encrypted blobs: pbsgpu_blob_encode3_device, below. Not here (NEXT.md): the keyed chunk digest
+ * SHA-256(content || id_key), the key-file KDF, pbsgpu_blob_verify_* with a key (they keep answering
+ * PBSGPU_BLOB_CRC_ONLY for encrypted blobs, as pbsgpu_blob_decode_device and pbsgpu_blob_decode2_device do), and a
+ * constant-time AES. */
 #define PBSGPU_HAS_AES_GCM 1
 typedef struct pbsgpu_aes_key pbsgpu_aes_key;
 /* The round keys, H = E_K(0) and the multiplier tables of `key` in device memory of eng's device. The key keeps the engine
@@ -1105,6 +1106,51 @@ int pbsgpu_blob_decode3_device(pbsgpu_engine *eng, const void *blobs_dptr, uint6
                                uint64_t range_start, uint64_t range_end, uint32_t flags, pbsgpu_aes_key *key /* may be NULL */,
                                void *dst, uint64_t dst_cap, uint8_t *status /* nidx */,
                                pbsgpu_decode_stats3 *stats /* may be NULL */);
+
+/* ---- encrypted data blobs written on the device ----------------------------------------------------------------------------
+ * The writer's side of the two encrypted kinds: pbsgpu_blob_encode2_device plus a key, the IVs and one flag. A caller that
+ * backs up with a key file gets [magic 8 | CRC-32 LE 4 | IV 16 | tag 16 | ciphertext] per chunk without the host in between:
+ * cipher, tag, CRC and header are made on one stream, from lengths only the device knows.
+ * Without PBSGPU_ENCODE_F_AES the call is pbsgpu_blob_encode2_device, output for output; key and ivs are not looked at.
+ * With PBSGPU_ENCODE_F_AES alone, blob i lies in the slot [offsets[i], offsets[i] + 44 + length), the slots back to back:
+ * encrypted magic | CRC | ivs[16 i .. +16) | tag | AES-256-GCM(chunk) under `key`, empty AAD. The CRC covers the CIPHERTEXT
+ * only (what pbsgpu_blob_decode3_device checks). lens[i] = 44 + length, kinds[i] = PBSGPU_BLOB_ENCRYPTED.
+ * With PBSGPU_ENCODE_F_AES | PBSGPU_ENCODE_F_ZSTD the slots are the same; the chunk is compressed exactly as
+ * pbsgpu_blob_encode2_device compresses it (the frame is byte for byte pbsgpu_zstd_encode_device's on the same engine), and
+ * when the frame is strictly shorter than the chunk the blob is encrypted-compressed magic | CRC | IV | tag | E(frame),
+ * lens[i] = 44 + the frame's length, kinds[i] = PBSGPU_BLOB_ENCRYPTED_COMPRESSED; otherwise it is the plain encrypted blob
+ * of the chunk. Slots are not compacted; the bytes of a slot behind lens[i] are unspecified.
+ * IVs. The caller supplies them, 16 bytes per blob, as the stock client's form has it and as pbsgpu_aes_gcm_many_device
+ * takes them. The library keeps NO counter: a counter would not survive a session, and two sessions share one key. It does
+ * refuse a call in which two of the nseg IVs are equal (PBSGPU_E_INVALID, decided on the host by a sort). Uniqueness
+ * ACROSS calls under one key is the caller's to answer for: a repeated IV gives away the xor of two plaintexts and the
+ * hash key. The bindings supply the default: Python draws os.urandom(16 n) for ivs=None, Go draws from crypto/rand for nil.
+ * Decided on the host before any device work, with dst untouched: every refusal of pbsgpu_blob_encode2_device; an unknown
+ * flag bit; with F_AES a NULL key or a key of another engine, NULL ivs, two equal IVs, a dst that overlaps src, a chunk of
+ * 4 GiB - 44 or more. PBSGPU_E_CAPACITY when dst_cap is below offsets[nseg]; offsets is filled in first, as in the plain
+ * call. pbsgpu_blob_encoded_size3 is that sum for either layout, host only.
+ * One leased stream and ONE synchronisation, at the end. The key never appears in a trace or an error string. The AES
+ * table is indexed by secret-dependent bytes: the timing channel of the section above is NOT addressed here either.
+ * Still left (NEXT.md): the keyed chunk digest SHA-256(content || id_key), the key-file KDF, encryption inside the fused
+ * upload calls (pbsgpu_*_upload_new2_device) and the ring (pbsgpu_ring_blob_encode_device), pbsgpu_blob_verify_* with a key. */
+#define PBSGPU_HAS_BLOB_ENCRYPT 1
+#define PBSGPU_ENCODE_F_AES 2u
+typedef struct pbsgpu_encode_stats3 {
+    uint64_t blobs[4];       /* blobs per kind, PBSGPU_BLOB_UNCOMPRESSED .. PBSGPU_BLOB_ENCRYPTED_COMPRESSED */
+    uint64_t blob_bytes[4];  /* sum of lens per kind */
+    uint64_t chunk_bytes[4]; /* sum of the chunk lengths per kind */
+    uint64_t frame_bytes;    /* frame bytes of the two compressed kinds */
+    uint64_t crc_bytes;      /* bytes the CRC was computed over: the payload of every blob */
+    uint64_t aes_bytes;      /* plaintext bytes encrypted */
+} pbsgpu_encode_stats3;
+/* host only: the bytes dst needs for these chunks, 12 + length each without PBSGPU_ENCODE_F_AES in flags, 44 + length with */
+int pbsgpu_blob_encoded_size3(const pbsgpu_segment *segs, uint32_t nseg, uint32_t flags, uint64_t *nbytes);
+int pbsgpu_blob_encode3_device(pbsgpu_engine *eng, const void *src, uint64_t src_bytes, const pbsgpu_segment *segs,
+                               uint32_t nseg, uint32_t flags, pbsgpu_aes_key *key /* may be NULL without F_AES */,
+                               const uint8_t *ivs /* host, 16 * nseg; may be NULL without F_AES */, void *dst,
+                               uint64_t dst_cap, uint64_t *offsets /* nseg + 1 */, uint32_t *lens /* nseg */,
+                               uint8_t *kinds /* nseg */, uint32_t *crcs /* nseg */,
+                               pbsgpu_encode_stats3 *stats /* may be NULL */);
 
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or

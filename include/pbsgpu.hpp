@@ -553,6 +553,40 @@ inline Result<Decoded3> Decode3(pbsgpu_engine *eng, const void *blobsDev, uint64
     return r;
 }
 
+struct Encoded3 {
+    std::vector<uint64_t> offsets;  // segs.size() + 1: blob i lies at offsets[i], in a slot of 44 + length bytes with a key
+    std::vector<uint32_t> lens;     // the blob's length: what is sent
+    std::vector<uint8_t> kinds;     // PBSGPU_BLOB_UNCOMPRESSED .. PBSGPU_BLOB_ENCRYPTED_COMPRESSED
+    std::vector<uint32_t> crcs;
+    pbsgpu_encode_stats3 stats{};
+};
+
+// Encode2 with the blobs encrypted on the device under `key` (PBSGPU_ENCODE_F_AES; key nullptr: Encode2, output for output,
+// ivs not looked at). ivs: 16 bytes per chunk, the caller's (pbsgpu_blob_encode3_device: two equal ones in a call are
+// refused, uniqueness across calls is the caller's to answer for). Kind 2 holds the chunk, kind 3 (zstd = true and the frame
+// strictly shorter than the chunk) its frame; the CRC covers the ciphertext.
+inline Result<Encoded3> Encode3(pbsgpu_engine *eng, const void *src, uint64_t srcBytes, const std::vector<pbsgpu_segment> &segs,
+                                bool zstd, const AesKey *key, const std::vector<uint8_t> &ivs, void *dst, uint64_t dstCap) {
+    Result<Encoded3> r;
+    const size_t n = segs.size();
+    r.value.offsets.resize(n + 1);
+    r.value.lens.resize(n + 1);
+    r.value.kinds.resize(n + 1);
+    r.value.crcs.resize(n + 1);
+    int st = PBSGPU_E_INVALID;
+    if (!key || ivs.size() == 16 * n) {
+        const uint32_t flags = (zstd ? PBSGPU_ENCODE_F_ZSTD : 0u) | (key ? PBSGPU_ENCODE_F_AES : 0u);
+        st = pbsgpu_blob_encode3_device(eng, src, srcBytes, segs.data(), (uint32_t)n, flags, key ? key->handle() : nullptr,
+                                        key && n ? ivs.data() : nullptr, dst, dstCap, r.value.offsets.data(), r.value.lens.data(),
+                                        r.value.kinds.data(), r.value.crcs.data(), &r.value.stats);
+    }
+    r.value.lens.resize(n);
+    r.value.kinds.resize(n);
+    r.value.crcs.resize(n);
+    if (st != PBSGPU_OK) r.err = errorf("blob encode3", st);
+    return r;
+}
+
 }  // namespace blob
 
 // datastore.DynamicIndexReader

@@ -173,6 +173,14 @@ class EncodeStats(C.Structure):
                 ("frame_bytes", C.c_uint64), ("crc_bytes", C.c_uint64)]
 
 
+ENCODE_F_AES = 2  # blob_encode3 only
+
+
+class EncodeStats3(C.Structure):
+    _fields_ = [("blobs", C.c_uint64 * 4), ("blob_bytes", C.c_uint64 * 4), ("chunk_bytes", C.c_uint64 * 4),
+                ("frame_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("aes_bytes", C.c_uint64)]
+
+
 class BlobStats(C.Structure):
     _fields_ = [("count", C.c_uint64 * 6), ("blob_bytes", C.c_uint64), ("crc_bytes", C.c_uint64), ("sha_bytes", C.c_uint64)]
 
@@ -314,6 +322,9 @@ SYMBOLS = {
                                              C.c_uint32]),
     "pbsgpu_blob_decode3_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
                                              C.c_uint32, _P, _P, C.c_uint64, _P, C.POINTER(DecodeStats3)]),
+    "pbsgpu_blob_encoded_size3": (C.c_int, [_P, C.c_uint32, C.c_uint32, _U64P]),
+    "pbsgpu_blob_encode3_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
+                                             C.POINTER(EncodeStats3)]),
     "pbsgpu_comm_unique_id": (C.c_int, [_P]),
     "pbsgpu_comm_create": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
     "pbsgpu_comm_destroy": (None, [_P]),

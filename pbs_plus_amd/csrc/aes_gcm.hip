@@ -352,6 +352,7 @@ int enqueue_restore(pbsgpu_engine *e, Slot *s, const pbsgpu_aes_key *key, const 
 }
 
 pbsgpu_engine *key_engine(const pbsgpu_aes_key *k) { return k->eng; }
+const void *key_tables(const pbsgpu_aes_key *k) { return k->tables.p; }
 
 }  // namespace aes
 }  // namespace pbsk

@@ -423,6 +423,68 @@ __global__ __launch_bounds__(256) void k_enc2_fold(Enc2Plan pl) {
     }
 }
 
+// ---- the encrypted kinds (pbsgpu_blob_encode3_device with PBSGPU_ENCODE_F_AES) -----------------------------
+// aes_encode.hip has left, per blob, IV, tag and ciphertext behind the 12 header bytes; the CRC covers the ciphertext where
+// it lies, so the walk stores nothing. With F_ZSTD the ciphertext is as long as the frame when the frame won (res, as
+// above), else as long as the chunk; the pieces are planned for the chunk's length and the ones past the end do nothing.
+struct Enc3Plan {
+    Plan p;               // p.src is not read; p.magic_*: the encrypted kind's
+    const uint64_t *res;  // nseg: frame length | kind << 56, or nullptr: nothing was compressed
+    uint32_t *lens;       // nseg: the blob's length
+    uint8_t *kinds;       // nseg
+    uint32_t zmagic_lo, zmagic_hi;  // the encrypted-compressed kind's magic
+};
+
+// the ciphertext's length of blob i, and whether it holds a frame
+__device__ __forceinline__ uint64_t enc3_len(const Enc3Plan &pl, uint32_t i, bool *comp) {
+    const uint64_t chunk = ((gquad_ptr)pl.p.segs)[2 * i + 1];
+    const uint64_t res = pl.res ? ((gquad_ptr)pl.res)[i] : 0;
+    *comp = (res >> 56) == PBSGPU_BLOB_COMPRESSED;
+    const uint64_t flen = res & ((1ull << 56) - 1);
+    return *comp && flen < chunk ? flen : chunk;  // (a frame that won is shorter than the chunk)
+}
+
+__global__ __launch_bounds__(256) void k_enc3_pieces(Enc3Plan pl) {
+    __shared__ uint32_t tab[17][256];
+    build_tables(tab);
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t nw = (uint64_t)gridDim.x * 4;
+    for (uint64_t p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pl.p.npieces; p += nw) {
+        const uint32_t i = ((gword_ptr)pl.p.pseg)[p];
+        const uint64_t b0 = ((gquad_ptr)pl.p.pbase)[i];
+        bool comp;
+        const uint64_t len = enc3_len(pl, i, &comp);
+        const uint64_t m = (len + kPiece - 1) >> kPieceLog;
+        if (p - b0 >= m) continue;  // (wave-uniform)
+        const uint64_t hi = len - (m - 1 - (p - b0)) * kPiece;
+        const uint64_t lo = hi > kPiece ? hi - kPiece : 0;
+        const uint8_t *data = pl.p.dst + ((gquad_ptr)pl.p.doff)[i] + PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE;
+        const uint32_t inv = (len >= 4 && lo < 4) ? (uint32_t)((hi < 4 ? hi : 4) - lo) : 0u;
+        const uint32_t v = piece_raw(tab, data + lo, (uint32_t)(hi - lo), inv, lane, PutIf{nullptr});
+        if (lane == 0) ((gword_out)pl.p.praw)[p] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_enc3_fold(Enc3Plan pl) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nw = gridDim.x * 4;
+    for (uint32_t i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); i < pl.p.nseg; i += nw) {
+        const uint64_t b0 = ((gquad_ptr)pl.p.pbase)[i];
+        bool comp;
+        const uint64_t len = enc3_len(pl, i, &comp);
+        const uint32_t m = (uint32_t)((len + kPiece - 1) >> kPieceLog);
+        const uint32_t acc = m ? fold_part((gword_ptr)pl.p.praw + b0, m, lane) : 0u;
+        const uint32_t crc = finish(acc, len);
+        if (lane == 0) {
+            ((gword_out)pl.p.crcs)[i] = crc;
+            ((gword_out)pl.lens)[i] = (uint32_t)(len + PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE);
+            ((gbyte_out)pl.kinds)[i] = comp ? PBSGPU_BLOB_ENCRYPTED_COMPRESSED : PBSGPU_BLOB_ENCRYPTED;
+        }
+        store_header(pl.p.dst + ((gquad_ptr)pl.p.doff)[i], lane, comp ? pl.zmagic_lo : pl.p.magic_lo,
+                     comp ? pl.zmagic_hi : pl.p.magic_hi, crc);
+    }
+}
+
 // the first min(len, 12) bytes of every blob (verify_device: the host parses the headers)
 __global__ __launch_bounds__(256) void k_blob_heads(const uint8_t *src, const pbsgpu_segment *blobs, uint32_t n,
                                                     uint8_t *heads) {
@@ -1140,6 +1202,56 @@ int blob_encode_zstd(pbsgpu_engine *e, const uint8_t *src, const pbsgpu_segment 
     return PBSGPU_OK;
 }
 
+// pbsgpu_blob_encode3_device with PBSGPU_ENCODE_F_AES: with zstd the frames at their blobs' data positions (byte 44), then
+// the AES leg (aes_encode.hip: IV, ciphertext, tag), then the CRC pair over the ciphertexts where they lie, all on the
+// slot's stream; one read-back of crcs, lens and kinds at the end. One piece table, for the slots' capacities, serves the
+// cipher and the CRC.
+int blob_encode_aes(pbsgpu_engine *e, const pbsgpu_aes_key *key, const uint8_t *ivs, bool zstd, const uint8_t *src,
+                    const pbsgpu_segment *segs, uint32_t nseg, uint8_t *dst, const uint64_t *offs, uint64_t src_bytes,
+                    uint32_t *lens, uint8_t *kinds, uint32_t *crcs) {
+    AuxLease lease(e);
+    Slot *s = lease.s;
+    const uint8_t *d = nullptr;
+    CHK(stage_ranges(e, s, src, false, src_bytes, segs, nseg, &d));
+    uint64_t *res = nullptr;
+    if (zstd) {
+        std::vector<pbsk::zenc::Job> jobs(nseg);
+        for (uint32_t i = 0; i < nseg; ++i)
+            jobs[i] = pbsk::zenc::Job{segs[i].offset, 0, offs[i] + PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE, segs[i].length,
+                                      (uint32_t)segs[i].length, 0, 0, 0};
+        CHK(pbsk::zenc::enqueue(e, s, d, dst, jobs, true, &res));
+    }
+    PieceTable t;
+    if (!capacity_pieces(segs, nseg, t)) return PBSGPU_E_INVALID;
+    const Enc3Block ob(nseg);
+    Enc3Plan pl{};
+    pl.p.src = d;
+    pl.p.segs = s->segs.as<pbsgpu_segment>();
+    pl.p.nseg = nseg;
+    CHK(put_pieces(s, t, pl.p));
+    CHK(put_table(s, offs, (size_t)nseg + 1, &pl.p.doff));
+    uint8_t *out = s->take<uint8_t>(ob.total);
+    CHK(s->taken());
+    pl.p.crcs = reinterpret_cast<uint32_t *>(out + ob.crcs);
+    pl.p.dst = dst;
+    pl.p.magic_lo = le32(kMagic[PBSGPU_BLOB_ENCRYPTED]);
+    pl.p.magic_hi = le32(kMagic[PBSGPU_BLOB_ENCRYPTED] + 4);
+    pl.res = res;
+    pl.lens = reinterpret_cast<uint32_t *>(out + ob.lens);
+    pl.kinds = out + ob.kinds;
+    pl.zmagic_lo = le32(kMagic[PBSGPU_BLOB_ENCRYPTED_COMPRESSED]);
+    pl.zmagic_hi = le32(kMagic[PBSGPU_BLOB_ENCRYPTED_COMPRESSED] + 4);
+    const pbsk::aese::Job job{d, dst, pl.p.segs, pl.p.doff, res, pl.p.pbase, pl.p.pseg, nseg, (uint32_t)t.np};
+    CHK(pbsk::aese::enqueue(e, s, key, job, ivs));
+    CHK(launch_pair(e, s->stream, k_enc3_pieces, k_enc3_fold, pl, t.np, nseg));
+    std::vector<uint8_t> back(ob.total);
+    CHK(fetch_result(s, back.data(), out, ob.total));  // the call's one synchronisation
+    std::memcpy(crcs, back.data() + ob.crcs, (size_t)nseg * 4);
+    std::memcpy(lens, back.data() + ob.lens, (size_t)nseg * 4);
+    std::memcpy(kinds, back.data() + ob.kinds, nseg);
+    return PBSGPU_OK;
+}
+
 // the first PBSGPU_BLOB_HEADER_SIZE bytes of every blob (zero-padded when it is shorter) to the host
 int read_heads(pbsgpu_engine *e, Slot *s, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t n,
                std::vector<uint8_t> &heads) {
@@ -1829,6 +1941,61 @@ int pbsgpu_blob_encode2_device(pbsgpu_engine *e, const void *src, uint64_t src_b
     if (lens && nseg) std::memcpy(lens, vlens.data(), (size_t)nseg * 4);
     if (kinds && nseg) std::memcpy(kinds, vkinds.data(), nseg);
     if (crcs && nseg) std::memcpy(crcs, vcrcs.data(), (size_t)nseg * 4);
+    return PBSGPU_OK;
+}
+
+int pbsgpu_blob_encoded_size3(const pbsgpu_segment *segs, uint32_t nseg, uint32_t flags, uint64_t *nbytes) {
+    if (!nbytes || (nseg && !segs) || (flags & ~(PBSGPU_ENCODE_F_ZSTD | PBSGPU_ENCODE_F_AES))) return PBSGPU_E_INVALID;
+    const uint32_t hdr = (flags & PBSGPU_ENCODE_F_AES) ? PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE : PBSGPU_BLOB_HEADER_SIZE;
+    return slot_offsets(segs, nseg, hdr, nullptr, nbytes) ? PBSGPU_OK : PBSGPU_E_INVALID;
+}
+
+int pbsgpu_blob_encode3_device(pbsgpu_engine *e, const void *src, uint64_t src_bytes, const pbsgpu_segment *segs,
+                               uint32_t nseg, uint32_t flags, pbsgpu_aes_key *key, const uint8_t *ivs, void *dst,
+                               uint64_t dst_cap, uint64_t *offsets, uint32_t *lens, uint8_t *kinds, uint32_t *crcs,
+                               pbsgpu_encode_stats3 *stats) {
+    if (flags & ~(PBSGPU_ENCODE_F_ZSTD | PBSGPU_ENCODE_F_AES)) return PBSGPU_E_INVALID;
+    if (!(flags & PBSGPU_ENCODE_F_AES)) {  // the older call, output for output; key and ivs are not looked at
+        pbsgpu_encode_stats st2{};
+        CHK(pbsgpu_blob_encode2_device(e, src, src_bytes, segs, nseg, flags, dst, dst_cap, offsets, lens, kinds, crcs,
+                                       stats ? &st2 : nullptr));
+        if (stats) {
+            std::memset(stats, 0, sizeof(*stats));
+            for (int k = 0; k < 2; ++k) {
+                stats->blobs[k] = st2.blobs[k];
+                stats->blob_bytes[k] = st2.blob_bytes[k];
+                stats->chunk_bytes[k] = st2.chunk_bytes[k];
+            }
+            stats->frame_bytes = st2.frame_bytes;
+            stats->crc_bytes = st2.crc_bytes;
+        }
+        return PBSGPU_OK;
+    }
+    if (!e || (!src && src_bytes) || (nseg && !segs)) return PBSGPU_E_INVALID;
+    if (!ranges_ok(segs, nseg, src_bytes)) return PBSGPU_E_INVALID;
+    for (uint32_t i = 0; i < nseg; ++i)
+        if ((segs[i].length + PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE) >> 32) return PBSGPU_E_INVALID;  // lens is 32 bits wide
+    if (!key || pbsk::aes::key_engine(key) != e || (nseg && !ivs)) return PBSGPU_E_INVALID;
+    if (!ivs_distinct(ivs, nseg)) return PBSGPU_E_INVALID;
+    std::vector<uint64_t> offs((size_t)nseg + 1);
+    uint64_t total = 0;
+    if (!slot_offsets(segs, nseg, PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE, offs.data(), &total)) return PBSGPU_E_INVALID;
+    if (offsets) std::memcpy(offsets, offs.data(), offs.size() * sizeof(uint64_t));  // (also what a caller sizes dst with)
+    if (total > dst_cap) return PBSGPU_E_CAPACITY;
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (nseg == 0) return PBSGPU_OK;
+    if (!dst || overlaps(dst, total, src, src_bytes)) return PBSGPU_E_INVALID;  // a frame is encrypted where it lies
+    CHK(set_device(e));
+    if (!is_device_pointer(dst) || (src_bytes && !is_device_pointer(src))) return PBSGPU_E_INVALID;
+    std::vector<uint32_t> vlens(nseg), vcrcs(nseg);
+    std::vector<uint8_t> vkinds(nseg);
+    CHK(blob_encode_aes(e, key, ivs, (flags & PBSGPU_ENCODE_F_ZSTD) != 0, static_cast<const uint8_t *>(src), segs, nseg,
+                        static_cast<uint8_t *>(dst), offs.data(), src_bytes, vlens.data(), vkinds.data(), vcrcs.data()));
+    if (stats)
+        for (uint32_t i = 0; i < nseg; ++i) count_blob3(*stats, vkinds[i], vlens[i], segs[i].length);
+    if (lens) std::memcpy(lens, vlens.data(), (size_t)nseg * 4);
+    if (kinds) std::memcpy(kinds, vkinds.data(), nseg);
+    if (crcs) std::memcpy(crcs, vcrcs.data(), (size_t)nseg * 4);
     return PBSGPU_OK;
 }
 

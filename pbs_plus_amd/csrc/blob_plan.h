@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/pbsgpu.h"
@@ -100,6 +101,50 @@ inline void count_blob(pbsgpu_encode_stats &st, int kind, uint32_t len, uint64_t
     st.crc_bytes += len - PBSGPU_BLOB_HEADER_SIZE;
 }
 
+// the same for pbsgpu_blob_encode3_device: four kinds, and the plaintext bytes that were encrypted
+inline uint32_t header_of(int kind) {
+    return kind >= PBSGPU_BLOB_ENCRYPTED ? PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE : PBSGPU_BLOB_HEADER_SIZE;
+}
+inline void count_blob3(pbsgpu_encode_stats3 &st, int kind, uint32_t len, uint64_t chunk_len) {
+    const uint32_t body = len - header_of(kind);
+    st.blobs[kind]++;
+    st.blob_bytes[kind] += len;
+    st.chunk_bytes[kind] += chunk_len;
+    if (kind == PBSGPU_BLOB_COMPRESSED || kind == PBSGPU_BLOB_ENCRYPTED_COMPRESSED) st.frame_bytes += body;
+    if (kind >= PBSGPU_BLOB_ENCRYPTED) st.aes_bytes += body;
+    st.crc_bytes += body;
+}
+
+// The slots of an encode call, back to back: slot i = [offsets[i], offsets[i] + header + segs[i].length), offsets[nseg] =
+// *total = the bytes dst needs. header = 12 (the plain kinds) or 44 (the encrypted ones); offsets may be nullptr.
+// false: the sum does not fit 64 bits.
+inline bool slot_offsets(const pbsgpu_segment *segs, uint32_t nseg, uint32_t header, uint64_t *offsets, uint64_t *total) {
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < nseg; ++i) {
+        if (offsets) offsets[i] = at;
+        const uint64_t b = segs[i].length + header;
+        if (b < segs[i].length || at + b < at) return false;
+        at += b;
+    }
+    if (offsets) offsets[nseg] = at;
+    *total = at;
+    return true;
+}
+
+// no two of the n 16-byte IVs of a call are equal (pbsgpu_blob_encode3_device refuses a call that repeats one: under one
+// key a repeated IV gives away the xor of two plaintexts and the hash key). A sort of the IVs as pairs of words.
+inline bool ivs_distinct(const uint8_t *ivs, uint32_t n) {
+    struct Iv {
+        uint64_t a, b;
+    };
+    std::vector<Iv> v(n);
+    for (uint32_t i = 0; i < n; ++i) std::memcpy(&v[i], ivs + 16 * (size_t)i, 16);
+    std::sort(v.begin(), v.end(), [](const Iv &x, const Iv &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    for (uint32_t i = 1; i < n; ++i)
+        if (v[i].a == v[i - 1].a && v[i].b == v[i - 1].b) return false;
+    return true;
+}
+
 // ---- the piece table ---------------------------------------------------------------------------------------------------
 // Every range is cut into pieces of kPiece bytes. pbase[i] = the index of range i's first piece, pbase[n] = the piece
 // count; false: 2^32 pieces or more (256 TiB in one call).
@@ -136,6 +181,11 @@ bool piece_table(uint64_t n, LenOf len_of, PieceTable &t) {
     fill_owners(t.pbase, t.owner.data());
     return true;
 }
+// the table of an encode call whose blobs' lengths only the device knows (F_ZSTD, F_AES | F_ZSTD): planned for each slot's
+// capacity, the chunk's length; a kernel leaves the planned pieces at or beyond the real length's count alone
+inline bool capacity_pieces(const pbsgpu_segment *segs, uint32_t nseg, PieceTable &t) {
+    return piece_table(nseg, [&](uint64_t i) { return segs[i].length; }, t);
+}
 
 // ---- packed blocks ----------------------------------------------------------------------------------------------------
 // Several arrays in one device buffer, so that one copy brings them over or back. A block's struct is built once and
@@ -163,6 +213,7 @@ struct Enc2Block {  // blob_encode_zstd's return block
     size_t crcs, lens, kinds, total;
     explicit Enc2Block(size_t n) : crcs(p.add(n * 4, 4)), lens(p.add(n * 4, 4)), kinds(p.add(n, 1)), total(p.total) {}
 };
+using Enc3Block = Enc2Block;  // pbsgpu_blob_encode3_device's return block: the same three arrays
 struct DecTables {  // the restore's upload: pbase u64[nu + 1] | prim[nu] | copies[ncopy] | ents[nidx] | pseg u32[np]
     Packer p;
     size_t pbase, prim, copies, ents, pseg, total;

@@ -368,8 +368,27 @@ namespace aes {
 int enqueue_restore(pbsgpu_engine *e, pbse::Slot *s, const pbsgpu_aes_key *key, const pbsk::zstd::RestorePlan &zp,
                     const pbsgpu_segment *ub, bool zstd, uint32_t longest_copy, uint64_t *res);
 pbsgpu_engine *key_engine(const pbsgpu_aes_key *k);
+const void *key_tables(const pbsgpu_aes_key *k);  // the key's pbsa::KeyTables in device memory
 constexpr uint32_t kResBadTag = 0xfe, kResFrame = 0x80;
 }  // namespace aes
+// aes_encode.hip: the AES leg of pbsgpu_blob_encode3_device, on the slot's stream between the encoder's rounds and blob.hip's
+// CRC pair. Blob i's message is the frame at dst + doff[i] + 44 when res says it won (res[i] >> 56 == PBSGPU_BLOB_COMPRESSED,
+// length in the low bits: encrypted where it lies), else the chunk segs[i] of src (res == nullptr: every chunk). The IV goes
+// to bytes 12-27 of the blob, the ciphertext behind byte 44, the tag to bytes 28-43. The pieces are blob.hip's table for
+// the slots' capacities (pbase, pseg: device); ivs is the host's array, 16 bytes per blob. Enqueued, nothing synchronised.
+namespace aese {
+struct Job {
+    const uint8_t *src;
+    uint8_t *dst;
+    const pbsgpu_segment *segs;  // nseg (device)
+    const uint64_t *doff;        // nseg + 1 (device)
+    const uint64_t *res;         // nseg (device), or nullptr
+    const uint64_t *pbase;       // nseg + 1 (device)
+    const uint32_t *pseg;        // npieces (device)
+    uint32_t nseg, npieces;
+};
+int enqueue(pbsgpu_engine *e, pbse::Slot *s, const pbsgpu_aes_key *key, const Job &job, const uint8_t *ivs);
+}  // namespace aese
 }  // namespace pbsk
 // zstd_encode.hip: the frames of many chunks, enqueued on a slot's stream (pbsgpu_zstd_encode_device, and the zstd leg of
 // pbsgpu_blob_encode2_device, which blob.hip follows with its CRC and header kernels on the same stream).

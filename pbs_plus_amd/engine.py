@@ -7,6 +7,7 @@ buffers (bytes / numpy); torch is plumbing only and is never imported here.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -612,6 +613,54 @@ class Engine:
                 dst.free()
             raise
         return dst, offs, lens[:n], kinds[:n], crcs[:n], _encode_stats(st)
+
+    def blob_encode3(self, src, chunks, key=None, ivs=None, dst=None, nbytes: int | None = None, zstd=True, aes=None):
+        """blob_encode2() with the blobs encrypted on the device under `key`, an AesKey of this engine
+        (pbsgpu_blob_encode3_device). aes defaults to "a key was given"; aes=True without a key raises PbsGpuError
+        (E_INVALID). With aes, blob i lies in the slot [offsets[i], offsets[i] + 44 + length): magic, CRC of the ciphertext,
+        IV, tag, ciphertext; kind 2 (encrypted) holds the chunk, kind 3 (encrypted-compressed, zstd=True and the frame
+        strictly shorter than the chunk) its frame. ivs: one 16-byte IV per chunk (bytes each, or an (n, 16) uint8 array);
+        None draws os.urandom(16 * n). Two equal IVs in one call are refused; uniqueness across calls under one key is the
+        caller's. Without aes every output is blob_encode2()'s and the IVs come back empty.
+        Returns (buffer, offsets (n + 1), lens (n), kinds (n), CRCs (n), stats dict with aes_bytes, IVs used as (n, 16))."""
+        segs, n = _segs(chunks)
+        sp, sn = self._dev(src, nbytes)
+        assert sp is not None, "blob_encode3() wants device memory"
+        if aes is None:
+            aes = key is not None
+        flags = (_lib.ENCODE_F_ZSTD if zstd else 0) | (_lib.ENCODE_F_AES if aes else 0)
+        if not aes:
+            iva = np.zeros((0, 16), dtype=np.uint8)
+        elif ivs is None:
+            iva = np.frombuffer(os.urandom(16 * n), dtype=np.uint8).reshape(n, 16).copy()
+        elif isinstance(ivs, np.ndarray):
+            iva = np.ascontiguousarray(ivs, dtype=np.uint8).reshape(-1, 16)
+        else:
+            iva = np.frombuffer(b"".join(bytes(v) for v in ivs), dtype=np.uint8).reshape(-1, 16).copy()
+        if aes and iva.shape[0] != n:
+            raise ValueError("one 16-byte IV per chunk")
+        own = dst is None
+        if own:
+            total = C.c_uint64()
+            check(self._L.pbsgpu_blob_encoded_size3(segs, n, flags, C.byref(total)), "blob_encoded_size3")
+            dst = self.alloc(max(total.value, 16))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        kinds = np.zeros(max(n, 1), dtype=np.uint8)
+        crcs = np.zeros(max(n, 1), dtype=np.uint32)
+        st = _lib.EncodeStats3()
+        try:
+            check(self._L.pbsgpu_blob_encode3_device(self._h, sp, sn, segs, n, flags, key._h if key is not None else None,
+                                                     iva.ctypes.data if aes and n else None, dst.ptr, dst.nbytes,
+                                                     offs.ctypes.data, lens.ctypes.data, kinds.ctypes.data, crcs.ctypes.data,
+                                                     C.byref(st)), "blob_encode3_device")
+        except Exception:
+            if own:
+                dst.free()
+            raise
+        stats = _encode_stats(st)
+        stats["aes_bytes"] = int(st.aes_bytes)
+        return dst, offs, lens[:n], kinds[:n], crcs[:n], stats, iva
 
     # ---- payload-stream assembly (.ppxar layout: markers + 16-byte headers + file bodies) ----------
     def payload_pack(self, src, files, dst, with_start: bool = True, with_tail: bool = True):
