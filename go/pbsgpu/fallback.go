@@ -389,6 +389,26 @@ type Encoded3 struct {
 	Stats   EncodeStats3
 }
 
+func (e *Engine) DecodeBlobs4(unsafe.Pointer, uint64, []uint64, []uint64, []ChunkInfo, []uint32, uint64, uint64, bool, bool, *AesKey, *IdKey, unsafe.Pointer, uint64) ([]uint8, DecodeStats3, error) {
+	return nil, DecodeStats3{}, ErrNotBuilt
+}
+
+// IdKey is the id key of keyed chunk digests on the device.
+type IdKey struct{}
+
+func (e *Engine) NewIdKey([]byte) (*IdKey, error) { return nil, ErrNotBuilt }
+func (k *IdKey) Close()                          {}
+func (k *IdKey) HashChunksKeyed([]byte, []uint64, []uint64) ([][32]byte, error) {
+	return nil, ErrNotBuilt
+}
+func (k *IdKey) HashChunksKeyedDevice(unsafe.Pointer, uint64, []uint64, []uint64) ([][32]byte, error) {
+	return nil, ErrNotBuilt
+}
+func (e *Engine) SubmitKeyed(*IdKey, []byte, []uint64, []uint64) (Ticket, error) { return 0, ErrNotBuilt }
+func (e *Engine) SubmitKeyedDevice(*IdKey, unsafe.Pointer, uint64, []uint64, []uint64) (Ticket, error) {
+	return 0, ErrNotBuilt
+}
+
 func (e *Engine) EncodeBlobs3(unsafe.Pointer, uint64, []uint64, []uint64, bool, *AesKey, []byte, unsafe.Pointer, uint64) (Encoded3, error) {
 	return Encoded3{}, ErrNotBuilt
 }

@@ -2026,8 +2026,23 @@ type DecodeStats3 struct {
 // With key nil every output is DecodeBlobs2's.
 func (e *Engine) DecodeBlobs3(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, idx []ChunkInfo, blobOf []uint32,
 	rangeStart, rangeEnd uint64, checkDigest, zstd bool, key *AesKey, dst unsafe.Pointer, dstCap uint64) ([]uint8, DecodeStats3, error) {
+	return e.decodeBlobs(false, dptr, nbytes, offsets, lengths, idx, blobOf, rangeStart, rangeEnd, checkDigest, zstd, key, nil, dst, dstCap)
+}
+
+// DecodeBlobs4 is DecodeBlobs3 with the keyed digest check (pbsgpu_blob_decode4_device): with a key, checkDigest and idKey, an
+// entry of an encrypted kind that passed tag, frame and size is compared with SHA-256(plaintext || id_key), the digest a
+// session with a key file puts into its index; BlobBadDigest on a mismatch, the bytes already stored stay. Entries of the plain
+// kinds keep the plain digest. With idKey nil every output is DecodeBlobs3's.
+func (e *Engine) DecodeBlobs4(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, idx []ChunkInfo, blobOf []uint32,
+	rangeStart, rangeEnd uint64, checkDigest, zstd bool, key *AesKey, idKey *IdKey, dst unsafe.Pointer, dstCap uint64) ([]uint8, DecodeStats3, error) {
+	return e.decodeBlobs(true, dptr, nbytes, offsets, lengths, idx, blobOf, rangeStart, rangeEnd, checkDigest, zstd, key, idKey, dst, dstCap)
+}
+
+func (e *Engine) decodeBlobs(four bool, dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64, idx []ChunkInfo, blobOf []uint32,
+	rangeStart, rangeEnd uint64, checkDigest, zstd bool, key *AesKey, idKey *IdKey, dst unsafe.Pointer, dstCap uint64) ([]uint8, DecodeStats3, error) {
 	defer runtime.KeepAlive(e)
 	defer runtime.KeepAlive(key)
+	defer runtime.KeepAlive(idKey)
 	segs, err := toSegments(offsets, lengths)
 	if err != nil {
 		return nil, DecodeStats3{}, err
@@ -2062,9 +2077,19 @@ func (e *Engine) DecodeBlobs3(dptr unsafe.Pointer, nbytes uint64, offsets, lengt
 		kh = key.h
 	}
 	var st C.pbsgpu_decode_stats3
-	err = check(C.pbsgpu_blob_decode3_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), rp, C.uint64_t(len(cr)), bo,
-		C.uint64_t(rangeStart), C.uint64_t(rangeEnd), flags, kh, dst, C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])),
-		&st), "blob_decode3_device")
+	if four {
+		var ik *C.pbsgpu_id_key
+		if idKey != nil {
+			ik = idKey.h
+		}
+		err = check(C.pbsgpu_blob_decode4_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), rp, C.uint64_t(len(cr)), bo,
+			C.uint64_t(rangeStart), C.uint64_t(rangeEnd), flags, kh, ik, dst, C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])),
+			&st), "blob_decode4_device")
+	} else {
+		err = check(C.pbsgpu_blob_decode3_device(e.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), rp, C.uint64_t(len(cr)), bo,
+			C.uint64_t(rangeStart), C.uint64_t(rangeEnd), flags, kh, dst, C.uint64_t(dstCap), (*C.uint8_t)(unsafe.Pointer(&status[0])),
+			&st), "blob_decode3_device")
+	}
 	if err != nil {
 		return nil, DecodeStats3{}, err
 	}
@@ -2076,6 +2101,123 @@ func (e *Engine) DecodeBlobs3(dptr unsafe.Pointer, nbytes uint64, offsets, lengt
 	out.OutBytes, out.ZstdInBytes, out.ZstdOutBytes = uint64(st.out_bytes), uint64(st.zstd_in_bytes), uint64(st.zstd_out_bytes)
 	out.AesBytes = uint64(st.aes_bytes)
 	return status[:len(cr)], out, nil
+}
+
+// ---- keyed chunk digests: SHA-256(content || id_key) -------------------------------------------------------------------
+
+// IdKey is the 32-byte id key of keyed chunk digests on the device (pbsgpu_id_key_*). A session with a key file names a chunk
+// in its index by SHA-256(content || id_key), not SHA-256(content). The bytes are not kept on the host; Close zeroes the
+// device copy. Nothing is derived here: where the 32 bytes come from is the caller's (INTEGRATION.md §6).
+type IdKey struct {
+	h   *C.pbsgpu_id_key
+	eng *Engine
+}
+
+// NewIdKey puts idKey (32 bytes) onto the engine's device.
+func (e *Engine) NewIdKey(idKey []byte) (*IdKey, error) {
+	defer runtime.KeepAlive(e)
+	if len(idKey) != 32 {
+		return nil, errors.New("pbsgpu: an id key is 32 bytes")
+	}
+	k := &IdKey{eng: e}
+	if err := check(C.pbsgpu_id_key_create(e.h, (*C.uint8_t)(unsafe.Pointer(&idKey[0])), &k.h), "id_key_create"); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(k, (*IdKey).Close)
+	return k, nil
+}
+
+// Close zeroes and frees the device copy. No call may be using the key and no ticket submitted with it may be uncollected.
+func (k *IdKey) Close() {
+	runtime.SetFinalizer(k, nil)
+	if k.h != nil {
+		C.pbsgpu_id_key_destroy(k.h)
+		k.h = nil
+	}
+	k.eng = nil
+}
+
+// HashChunksKeyed is HashFilesForced with the key: digests[i] = SHA-256(buf[offsets[i] : offsets[i]+lengths[i]] || id_key).
+func (k *IdKey) HashChunksKeyed(buf []byte, offsets, lengths []uint64) ([][32]byte, error) {
+	defer runtime.KeepAlive(k)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 {
+		return nil, errors.New("pbsgpu: HashChunksKeyed needs matching, non-empty offsets/lengths")
+	}
+	out := make([][32]byte, len(segs))
+	var base unsafe.Pointer
+	if len(buf) > 0 {
+		base = unsafe.Pointer(&buf[0])
+	}
+	err = check(C.pbsgpu_sha256_keyed_many_host(k.h, base, C.uint64_t(len(buf)), &segs[0], C.uint32_t(len(segs)),
+		(*C.uint8_t)(unsafe.Pointer(&out[0][0]))), "sha256_keyed_many_host")
+	runtime.KeepAlive(buf)
+	return out, err
+}
+
+// HashChunksKeyedDevice is HashChunksKeyed over ranges of a device buffer.
+func (k *IdKey) HashChunksKeyedDevice(dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64) ([][32]byte, error) {
+	defer runtime.KeepAlive(k)
+	segs, err := toSegments(offsets, lengths)
+	if err != nil || len(segs) == 0 {
+		return nil, errors.New("pbsgpu: HashChunksKeyedDevice needs matching, non-empty offsets/lengths")
+	}
+	out := make([][32]byte, len(segs))
+	err = check(C.pbsgpu_sha256_keyed_many_device(k.h, dptr, C.uint64_t(nbytes), &segs[0], C.uint32_t(len(segs)),
+		(*C.uint8_t)(unsafe.Pointer(&out[0][0]))), "sha256_keyed_many_device")
+	return out, err
+}
+
+// SubmitKeyed is Submit (without suggested boundaries) with every record's digest keyed: the cut points are the same, the
+// digest is SHA-256(chunk || id_key). Keep the key open until the ticket is collected.
+func (e *Engine) SubmitKeyed(key *IdKey, buf []byte, offsets, lengths []uint64) (Ticket, error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(key)
+	if key == nil {
+		return 0, errors.New("pbsgpu: SubmitKeyed needs an id key")
+	}
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return 0, err
+	}
+	var base unsafe.Pointer
+	if len(buf) > 0 {
+		base = unsafe.Pointer(&buf[0])
+	}
+	var sp *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp = &segs[0]
+	}
+	var t C.uint64_t
+	st := C.pbsgpu_submit_host_keyed(e.h, key.h, base, C.uint64_t(len(buf)), sp, C.uint32_t(len(segs)), &t)
+	runtime.KeepAlive(buf)
+	if st == C.PBSGPU_E_BUSY {
+		return 0, ErrBusy
+	}
+	return Ticket(t), check(st, "submit_host_keyed")
+}
+
+// SubmitKeyedDevice is SubmitKeyed over a device buffer, which must stay as it is until the ticket is collected.
+func (e *Engine) SubmitKeyedDevice(key *IdKey, dptr unsafe.Pointer, nbytes uint64, offsets, lengths []uint64) (Ticket, error) {
+	defer runtime.KeepAlive(e)
+	defer runtime.KeepAlive(key)
+	if key == nil {
+		return 0, errors.New("pbsgpu: SubmitKeyedDevice needs an id key")
+	}
+	segs, err := toSegments(offsets, lengths)
+	if err != nil {
+		return 0, err
+	}
+	var sp *C.pbsgpu_segment
+	if len(segs) > 0 {
+		sp = &segs[0]
+	}
+	var t C.uint64_t
+	st := C.pbsgpu_submit_device_keyed(e.h, key.h, dptr, C.uint64_t(nbytes), sp, C.uint32_t(len(segs)), &t)
+	if st == C.PBSGPU_E_BUSY {
+		return 0, ErrBusy
+	}
+	return Ticket(t), check(st, "submit_device_keyed")
 }
 
 // EncodeStats3 is EncodeStats over all four kinds (index 2 encrypted, 3 encrypted-compressed), with the plaintext bytes

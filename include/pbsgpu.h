@@ -1088,7 +1088,9 @@ int pbsgpu_aes_gcm_many_device(pbsgpu_aes_key *k, const void *src, uint64_t nbyt
  * with a copy pass for the other entries, nothing written outside dst[0, range_end - range_start), every verdict on the
  * device, ONE synchronisation. The plaintext of an encrypted-compressed blob lies in engine scratch, as large as the blobs
  * of the call together. pbsgpu_blob_decode_device, pbsgpu_blob_decode2_device and pbsgpu_blob_verify_* keep answering
- * PBSGPU_BLOB_CRC_ONLY for both kinds. Argument errors as for pbsgpu_blob_decode2_device with F_ZSTD, plus an unknown flag. */
+ * PBSGPU_BLOB_CRC_ONLY for both kinds. Argument errors as for pbsgpu_blob_decode2_device with F_ZSTD, plus an unknown flag.
+ * (Since PBSGPU_HAS_KEYED_DIGEST: pbsgpu_blob_decode4_device, below, is this call plus the id key, and with it the keyed
+ * digest of the encrypted entries IS computed and checked. This call stays as described.) */
 #define PBSGPU_DECODE_F_AES 4u
 #define PBSGPU_BLOB_BAD_TAG 7 /* pbsgpu_blob_decode3_device only: an encrypted blob whose tag does not authenticate it */
 typedef struct pbsgpu_decode_stats3 {
@@ -1151,6 +1153,58 @@ int pbsgpu_blob_encode3_device(pbsgpu_engine *eng, const void *src, uint64_t src
                                uint64_t dst_cap, uint64_t *offsets /* nseg + 1 */, uint32_t *lens /* nseg */,
                                uint8_t *kinds /* nseg */, uint32_t *crcs /* nseg */,
                                pbsgpu_encode_stats3 *stats /* may be NULL */);
+
+/* ---- keyed chunk digests: SHA-256(content || id_key) -------------------------------------------------------------------------
+ * A backup made with a key file names a chunk in its index by SHA-256(content || id_key): 32 secret bytes appended behind the
+ * content, NOT SHA-256(content) ([EXTERNAL], recalled from the stock client's CryptConfig::compute_digest).
+ * These entry points make the digest at both ends of an encrypted session the keyed one: the batch path and the whole-range
+ * hash with a key, and the restore's digest check for the encrypted kinds. The hot path is the batch SHA-256 kernels
+ * themselves, instantiated a second time for keyed sources: only the tail block(s) of a chunk differ (last data bytes | key |
+ * 0x80 | zeros | bit length of len + 32; pbs_plus_amd/csrc/sha256_suffix.h, one function for the kernels and for the CPU
+ * build that runs under sanitizers). The plain kernels are not touched.
+ * The library takes the 32 bytes and derives nothing. Where they come from is UNVERIFIED [EXTERNAL]: the last 32 bytes of a
+ * 64-byte key-file payload by one reading, PBKDF2-HMAC-SHA256 of the 32-byte encryption key (salt "_id_key", 10 iterations)
+ * by another; the key-file KDF stays with the caller.
+ * Not here (NEXT.md): keyed digests from the page ring's services and so from pbsgpu_stream_* and pbsgpu_ring_*, keyed
+ * _suggested submits, pbsgpu_blob_verify_* with keys, the key-file KDF, the encrypted kinds inside the fused upload calls. */
+#define PBSGPU_HAS_KEYED_DIGEST 1
+typedef struct pbsgpu_id_key pbsgpu_id_key;
+/* The 32 bytes of `id_key` in device memory of eng's device that the object owns; the host copy the call makes is wiped before it
+ * returns. The key keeps the engine alive until it is destroyed, and never appears in options, the environment, trace output
+ * or error strings. PBSGPU_E_INVALID for a NULL. */
+int pbsgpu_id_key_create(pbsgpu_engine *eng, const uint8_t id_key[32], pbsgpu_id_key **out);
+/* Zeroes the key's device memory, then frees it. No call may be using the key, and no ticket submitted with it may be
+ * uncollected. NULL is allowed. */
+void pbsgpu_id_key_destroy(pbsgpu_id_key *key);
+/* pbsgpu_sha256_many_device / _host with the key: digests[32 i] = SHA-256(range i || id_key); an empty range gives the digest
+ * of the key alone. The same argument checks (plus PBSGPU_E_INVALID for a NULL key), the same kernel form and dense selection
+ * from the options of the key's engine, one leased stream and ONE synchronisation. */
+int pbsgpu_sha256_keyed_many_device(pbsgpu_id_key *key, const void *dptr, uint64_t nbytes,
+        const pbsgpu_segment *segs, uint32_t nseg, uint8_t *digests /* host, 32*nseg */);
+int pbsgpu_sha256_keyed_many_host(pbsgpu_id_key *key, const void *hptr, uint64_t nbytes,
+        const pbsgpu_segment *segs, uint32_t nseg, uint8_t *digests);
+/* pbsgpu_submit_device / _host with every record's digest keyed. Cut points, `end`, `size` and `segment` are exactly those of
+ * the plain call; only `digest` differs. The key is fixed per ticket at submit time (the re-run of a batch whose scan tiles
+ * overflowed hashes with the same key); the caller keeps it alive until the ticket is collected. Plain and keyed tickets may
+ * be in flight together on one engine. PBSGPU_E_INVALID for a NULL key or a key of another engine. */
+int pbsgpu_submit_device_keyed(pbsgpu_engine *eng, pbsgpu_id_key *key, const void *dptr, uint64_t nbytes,
+                               const pbsgpu_segment *segs, uint32_t nseg, uint64_t *ticket);
+int pbsgpu_submit_host_keyed(pbsgpu_engine *eng, pbsgpu_id_key *key, const void *hptr, uint64_t nbytes,
+                             const pbsgpu_segment *segs, uint32_t nseg, uint64_t *ticket);
+/* pbsgpu_blob_decode3_device plus the id key. With idkey == NULL it is that call, output for output; an idkey without
+ * PBSGPU_DECODE_F_AES, or without PBSGPU_DECODE_F_DIGEST, is ignored. With F_AES | F_DIGEST and an id key (of another engine:
+ * PBSGPU_E_INVALID before any device work), an entry whose blob is of an encrypted kind and has passed magic, header, CRC, tag,
+ * frame and size is checked against idx[i].digest == SHA-256(plaintext content || id_key); a mismatch gives
+ * PBSGPU_BLOB_BAD_DIGEST, so the order of the checks becomes magic, header, CRC, tag, frame, size, digest. As with every other
+ * digest verdict of the restore the bytes already stored stay: the caller reads the status. Entries of the two plain kinds
+ * keep the plain digest. The keyed hash runs once per distinct encrypted blob over the plaintext where the AES leg or its
+ * frame decode left it, the comparison is made on the device, stats->sha_bytes counts these bytes, and there is still ONE
+ * synchronisation. */
+int pbsgpu_blob_decode4_device(pbsgpu_engine *eng, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                               uint64_t range_start, uint64_t range_end, uint32_t flags, pbsgpu_aes_key *key /* may be NULL */,
+                               pbsgpu_id_key *idkey /* may be NULL */, void *dst, uint64_t dst_cap, uint8_t *status /* nidx */,
+                               pbsgpu_decode_stats3 *stats /* may be NULL */);
 
 /* ---- multi-GPU digest-set reduce (RCCL over xGMI) ----------------------------------
  * The path shards at file / archive granularity with no data-path collective: one engine per GPU (one process per GPU, or

@@ -587,6 +587,71 @@ inline Result<Encoded3> Encode3(pbsgpu_engine *eng, const void *src, uint64_t sr
     return r;
 }
 
+// ---- keyed chunk digests, SHA-256(content || id_key): what an encrypted backup's index calls a chunk ----
+
+// The 32-byte id key on the device (pbsgpu_id_key_*). The bytes are not kept on the host; the destructor zeroes the device
+// copy. Nothing is derived: the caller brings the 32 bytes. Create() returns nullptr and sets *status on failure.
+class IdKey {
+public:
+    static std::unique_ptr<IdKey> Create(pbsgpu_engine *eng, const uint8_t idKey[32], int *status = nullptr) {
+        pbsgpu_id_key *h = nullptr;
+        const int st = pbsgpu_id_key_create(eng, idKey, &h);
+        if (status) *status = st;
+        if (st != PBSGPU_OK) return nullptr;
+        return std::unique_ptr<IdKey>(new IdKey(h));
+    }
+    ~IdKey() { pbsgpu_id_key_destroy(h_); }
+    IdKey(const IdKey &) = delete;
+    IdKey &operator=(const IdKey &) = delete;
+    pbsgpu_id_key *handle() const { return h_; }
+
+private:
+    explicit IdKey(pbsgpu_id_key *h) : h_(h) {}
+    pbsgpu_id_key *h_;
+};
+
+// SHA-256(range || id_key) of many ranges of a device buffer in one call: 32 bytes per range
+inline Result<std::vector<uint8_t>> Sha256KeyedMany(const IdKey &key, const void *dptr, uint64_t nbytes,
+                                                    const std::vector<pbsgpu_segment> &segs) {
+    Result<std::vector<uint8_t>> r;
+    r.value.resize(32 * segs.size() + 32);
+    const int st = pbsgpu_sha256_keyed_many_device(key.handle(), dptr, nbytes, segs.data(), (uint32_t)segs.size(), r.value.data());
+    r.value.resize(32 * segs.size());
+    if (st != PBSGPU_OK) r.err = errorf("sha256 keyed many", st);
+    return r;
+}
+
+// The batch path with every record's digest keyed: a ticket for pbsgpu_collect. Cut points are those of the plain submit; keep
+// the key alive until the ticket is collected.
+inline Result<uint64_t> SubmitDeviceKeyed(pbsgpu_engine *eng, const IdKey &key, const void *dptr, uint64_t nbytes,
+                                          const std::vector<pbsgpu_segment> &segs) {
+    Result<uint64_t> r;
+    const int st = pbsgpu_submit_device_keyed(eng, key.handle(), dptr, nbytes, segs.empty() ? nullptr : segs.data(),
+                                              (uint32_t)segs.size(), &r.value);
+    if (st != PBSGPU_OK) r.err = errorf("submit device keyed", st);
+    return r;
+}
+
+// Decode3 with the keyed digest check: with a key, checkDigest and idKey, an entry of an encrypted kind that passed tag, frame
+// and size is compared with SHA-256(plaintext || id_key); PBSGPU_BLOB_BAD_DIGEST on a mismatch, its bytes stay restored.
+// idKey nullptr: Decode3, output for output.
+inline Result<Decoded3> Decode4(pbsgpu_engine *eng, const void *blobsDev, uint64_t nbytes,
+                                const std::vector<pbsgpu_segment> &blobs, const std::vector<pbsgpu_record> &idx,
+                                const std::vector<uint32_t> &blobOf, uint64_t rangeStart, uint64_t rangeEnd, bool checkDigest,
+                                bool zstd, const AesKey *key, const IdKey *idKey, void *dst, uint64_t dstCap) {
+    Result<Decoded3> r;
+    r.value.status.resize(idx.size() + 1);
+    const uint32_t flags = (checkDigest ? PBSGPU_DECODE_F_DIGEST : 0u) | (zstd ? PBSGPU_DECODE_F_ZSTD : 0u) |
+                           (key ? PBSGPU_DECODE_F_AES : 0u);
+    const int st = pbsgpu_blob_decode4_device(eng, blobsDev, nbytes, blobs.data(), (uint32_t)blobs.size(), idx.data(),
+                                              idx.size(), blobOf.empty() ? nullptr : blobOf.data(), rangeStart, rangeEnd,
+                                              flags, key ? key->handle() : nullptr, idKey ? idKey->handle() : nullptr, dst,
+                                              dstCap, r.value.status.data(), &r.value.stats);
+    r.value.status.resize(idx.size());
+    if (st != PBSGPU_OK) r.err = errorf("blob decode4", st);
+    return r;
+}
+
 }  // namespace blob
 
 // datastore.DynamicIndexReader

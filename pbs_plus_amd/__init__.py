@@ -20,15 +20,17 @@ pbs-plus reference uses for its pxar stream path:
   content checksum verified and written, whole zstd streams decoded, for frames that are not blobs of an index
 * ``AesKey`` / ``Engine.aes_gcm_many`` / ``Engine.blob_decode3`` — AES-256-GCM, the cipher of the encrypted blob kinds, on
   the device: in batch in both directions, and inside the restore
+* ``IdKey`` / ``Engine.sha256_keyed_many`` / ``Engine.chunk_and_digest(id_key=)`` / ``Engine.blob_decode4`` — the keyed chunk
+  digest SHA-256(content || id_key) of an encrypted backup's index: in batch, on the batch path, and checked in the restore
 
 Everything executes in the gfx950 kernels of ``lib/libpbsgpu.so``; there is no CPU path.
 """
 from . import buzhash  # noqa: F401
 from ._lib import RECORD_DTYPE, PbsGpuError  # noqa: F401
-from .engine import AesKey, Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
+from .engine import AesKey, IdKey, Chunker, Comm, Engine, KnownChunks, PageRing, PayloadStream  # noqa: F401
 from .engine import blob_index, blob_magic, chunk_ranges, crc32_combine, zstd_encode_bound, zstd_frame_info  # noqa: F401
 from .engine import zstd_encode_bound2, zstd_stream_info  # noqa: F401
 
 __all__ = ["buzhash", "Engine", "PayloadStream", "PageRing", "Chunker", "Comm", "KnownChunks", "RECORD_DTYPE", "PbsGpuError",
            "blob_index", "blob_magic", "chunk_ranges", "crc32_combine", "zstd_encode_bound", "zstd_frame_info",
-           "zstd_encode_bound2", "zstd_stream_info", "AesKey"]
+           "zstd_encode_bound2", "zstd_stream_info", "AesKey", "IdKey"]

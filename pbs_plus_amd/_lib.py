@@ -322,6 +322,14 @@ SYMBOLS = {
                                              C.c_uint32]),
     "pbsgpu_blob_decode3_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
                                              C.c_uint32, _P, _P, C.c_uint64, _P, C.POINTER(DecodeStats3)]),
+    "pbsgpu_id_key_create": (C.c_int, [_P, _P, C.POINTER(_P)]),
+    "pbsgpu_id_key_destroy": (None, [_P]),
+    "pbsgpu_sha256_keyed_many_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "pbsgpu_sha256_keyed_many_host": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P]),
+    "pbsgpu_submit_device_keyed": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _U64P]),
+    "pbsgpu_submit_host_keyed": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint32, _U64P]),
+    "pbsgpu_blob_decode4_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64,
+                                             C.c_uint32, _P, _P, _P, C.c_uint64, _P, C.POINTER(DecodeStats3)]),
     "pbsgpu_blob_encoded_size3": (C.c_int, [_P, C.c_uint32, C.c_uint32, _U64P]),
     "pbsgpu_blob_encode3_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                              C.POINTER(EncodeStats3)]),

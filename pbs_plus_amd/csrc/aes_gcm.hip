@@ -16,8 +16,9 @@
 //   k_aesr_select per distinct blob: an encrypted blob with a good CRC becomes a message (IV and tag where the blob has them)
 //   k_aesr_frames per distinct blob, behind the verdicts: the plaintext of an encrypted-compressed blob becomes a frame for
 //                 k_zstd_frames (zstd.hip); every other blob's result is final
-//   k_aesr_merge  per distinct blob, behind the frames: one result word for the host and one for the copy pass
-//   k_aesr_status per entry of a blob the leg handled: tag, frame, size
+//   k_aesr_merge  per distinct blob, behind the frames: one result word for the host and one for the copy pass; with an id
+//                 key (pbsgpu_blob_decode4_device) also the range of plaintext that the keyed SHA-256 pass hashes
+//   k_aesr_status per entry of a blob the leg handled: tag, frame, size, and with an id key the keyed digest
 // Memory instructions: global_* and ds_* only, no scratch (tests/test_aes_surface.py). Every pointer a kernel dereferences
 // comes from its arguments.
 #include <algorithm>
@@ -185,6 +186,8 @@ struct Leg {
     pbsk::zstd::Desc *desc;      // nu
     uint64_t *zres;              // nu: the frames' results
     uint64_t *res, *fin;         // nu each
+    pbsgpu_segment *ksha;        // nu, with an id key: what the keyed SHA-256 pass hashes, relative to dst
+    const uint8_t *kdigs;        // nu * 32: SHA-256(plaintext || id_key); nullptr: no id key, the digest is not checked
     uint32_t zstd;
 };
 
@@ -246,7 +249,13 @@ __global__ __launch_bounds__(256) void k_aesr_merge(Leg lg) {
     }
     lg.res[u] = res;
     lg.fin[u] = fin;
+    // with an id key: the plaintext of a blob the leg restored lies at its job's place, whichever way it got there (decrypted
+    // in place, or decoded from its frame). That and the result's length is what the keyed SHA-256 pass hashes, as
+    // k_zr_ranges has it for the zstd leg; an empty range for every other blob
+    if (lg.ksha) lg.ksha[u] = pbsgpu_segment{lg.zp.jobs[u].place, (fin >> 32) == PBSGPU_ZSTD_OK ? (uint32_t)fin : 0u};
 }
+
+typedef const __attribute__((address_space(1))) uint32_t *aword_ptr;
 
 __global__ __launch_bounds__(256) void k_aesr_status(Leg lg) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -265,13 +274,22 @@ __global__ __launch_bounds__(256) void k_aesr_status(Leg lg) {
         r = PBSGPU_BLOB_BAD_SIZE;
     } else {
         r = PBSGPU_BLOB_OK;  // (no digest: an encrypted chunk's index digest is keyed, and the tag has vouched for the content)
+        if (lg.kdigs) {      // ... unless the call has the id key: the keyed digest of the plaintext against the record's
+            const aword_ptr want = (aword_ptr)(lg.zp.recs + 48ull * i + 8), got = (aword_ptr)(lg.kdigs + 32ull * u);
+            uint32_t diff = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) diff |= want[j] ^ got[j];
+            if (diff) r = PBSGPU_BLOB_BAD_DIGEST;
+        }
     }
     lg.zp.status[i] = r;
 }
 
 int enqueue_restore(pbsgpu_engine *e, Slot *s, const pbsgpu_aes_key *key, const pbsk::zstd::RestorePlan &zp,
-                    const pbsgpu_segment *ub, bool zstd, uint32_t longest_copy, uint64_t *res) {
+                    const pbsgpu_segment *ub, bool zstd, uint32_t longest_copy, uint64_t *res, const uint32_t *idkey,
+                    const pbsp::ShaWork *sha) {
     const uint32_t nu = zp.nu;
+    const bool keyed = idkey && zp.recs && sha;
     // what the host can know: every distinct blob might be encrypted, so each gets its pieces and, with zstd, room for a
     // plaintext frame in scratch
     std::vector<uint32_t> pfirst(nu);
@@ -305,7 +323,11 @@ int enqueue_restore(pbsgpu_engine *e, Slot *s, const pbsgpu_aes_key *key, const 
     lg.fin = s->take<uint64_t>(nu);
     Blk *heads = s->take<Blk>((size_t)nu * 2);
     Blk *partials = s->take<Blk>(refs.size() + 1);
+    uint8_t *kdigs = keyed ? s->take<uint8_t>((size_t)nu * 32) : nullptr;
+    uint32_t *kqueue = keyed ? s->take<uint32_t>(16) : nullptr;
+    lg.ksha = keyed ? s->take<pbsgpu_segment>(nu) : nullptr;
     CHK(s->taken());
+    lg.kdigs = kdigs;
     lg.verdict = verdict;
     lg.res = res;
     const dim3 per_blob((nu + 255) / 256);
@@ -345,6 +367,10 @@ int enqueue_restore(pbsgpu_engine *e, Slot *s, const pbsgpu_aes_key *key, const 
         pbsk::zstd::RestorePlan cp = zp;
         cp.res = lg.fin;
         HIPCHK(pbsk::zstd::launch_restore_copy(cp, longest_copy, e->num_cus, s->stream));
+    }
+    if (keyed) {  // once per distinct blob, over the plaintext where the leg left it; the copies above only read it
+        HIPCHK(hipMemsetAsync(kqueue, 0, 64, s->stream));
+        CHK(enqueue_sha256(e, s->stream, zp.dst, lg.ksha, nu, kdigs, kqueue, *sha, idkey));
     }
     hipLaunchKernelGGL(k_aesr_status, dim3((zp.nidx + 255) / 256), dim3(256), 0, s->stream, lg);
     HIPCHK(hipGetLastError());

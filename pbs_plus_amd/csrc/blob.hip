@@ -1500,7 +1500,7 @@ int enqueue_restore_zstd(pbsgpu_engine *e, Slot *s, Restore &r, const DecPlan &p
 
 // the statistics of a restore from the block that came back
 void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bool check_digest, bool zstd, bool aes,
-                   const uint8_t *status, pbsgpu_decode_stats3 *stats) {
+                   const uint8_t *status, pbsgpu_decode_stats3 *stats, bool keyed = false) {
     const uint32_t nu = r.nu();
     const size_t nidx = r.ents.size();
     const DecInfo *info = reinterpret_cast<const DecInfo *>(back + ob.info);
@@ -1523,6 +1523,8 @@ void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bo
             if (code == pbsk::zstd::kNotDecoded) continue;
             const uint64_t len = r.ub[u].length - PBSGPU_BLOB_ENCRYPTED_HEADER_SIZE;
             stats->aes_bytes += len;
+            // with the id key: the plaintext of every blob the leg restored was hashed once, keyed
+            if (keyed && (code & ~pbsk::aes::kResFrame) == PBSGPU_ZSTD_OK) stats->sha_bytes += (uint32_t)ares[u];
             if (code == pbsk::aes::kResBadTag || !(code & pbsk::aes::kResFrame)) continue;
             stats->zstd_in_bytes += len;  // a good tag over a frame: it went to the decoder
             if (code == (pbsk::aes::kResFrame | PBSGPU_ZSTD_OK)) stats->zstd_out_bytes += (uint32_t)ares[u];
@@ -1551,12 +1553,14 @@ void restore_stats(const Restore &r, const uint8_t *back, const DecBlock &ob, bo
 int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgpu_segment *blobs, uint32_t nblob,
                 const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of, uint64_t rs, uint64_t re,
                 uint32_t flags, const pbsgpu_aes_key *key, void *dst, uint64_t dst_cap, uint8_t *status,
-                pbsgpu_decode_stats3 *stats) {
+                pbsgpu_decode_stats3 *stats, const pbsgpu_id_key *idkey = nullptr) {
     const bool check_digest = (flags & PBSGPU_DECODE_F_DIGEST) != 0;
     const bool zstd = (flags & PBSGPU_DECODE_F_ZSTD) != 0;
     const bool aes = (flags & PBSGPU_DECODE_F_AES) != 0;
     if (!e || nidx >= (1ull << 32)) return PBSGPU_E_INVALID;
     if (aes && (!key || pbsk::aes::key_engine(key) != e)) return PBSGPU_E_INVALID;
+    if (idkey && idkey->eng != e) return PBSGPU_E_INVALID;
+    const bool keyed = idkey && aes && check_digest;  // (an id key without F_AES or without F_DIGEST is ignored)
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (nidx == 0) return PBSGPU_OK;
     if (!status) return PBSGPU_E_INVALID;
@@ -1574,12 +1578,12 @@ int blob_decode(pbsgpu_engine *e, const void *bptr, uint64_t nbytes, const pbsgp
         CHK(enqueue_restore_zstd(e, s, r, pl, reinterpret_cast<uint64_t *>(out + ob.zres), zstd, &zp));
         if (aes)
             CHK(pbsk::aes::enqueue_restore(e, s, key, zp, r.ub.data(), zstd, r.longest_zcopy,
-                                           reinterpret_cast<uint64_t *>(out + ob.ares)));
+                                           reinterpret_cast<uint64_t *>(out + ob.ares), keyed ? idkey->dev() : nullptr, &r.zsha));
     }
     std::vector<uint8_t> back(ob.total);
     CHK(fetch_result(s, back.data(), out, ob.total));  // the call's one synchronisation
     std::memcpy(status, back.data() + ob.status, (size_t)nidx);
-    if (stats) restore_stats(r, back.data(), ob, check_digest, zstd, aes, status, stats);
+    if (stats) restore_stats(r, back.data(), ob, check_digest, zstd, aes, status, stats, keyed);
     return PBSGPU_OK;
 }
 
@@ -2048,6 +2052,15 @@ int pbsgpu_blob_decode3_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_
     if (flags & ~(PBSGPU_DECODE_F_DIGEST | PBSGPU_DECODE_F_ZSTD | PBSGPU_DECODE_F_AES)) return PBSGPU_E_INVALID;
     return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, flags, key, dst, dst_cap,
                        status, stats);
+}
+
+int pbsgpu_blob_decode4_device(pbsgpu_engine *e, const void *blobs_dptr, uint64_t nbytes, const pbsgpu_segment *blobs,
+                               uint32_t nblob, const pbsgpu_record *idx, uint64_t nidx, const uint32_t *blob_of,
+                               uint64_t range_start, uint64_t range_end, uint32_t flags, pbsgpu_aes_key *key, pbsgpu_id_key *idkey,
+                               void *dst, uint64_t dst_cap, uint8_t *status, pbsgpu_decode_stats3 *stats) {
+    if (flags & ~(PBSGPU_DECODE_F_DIGEST | PBSGPU_DECODE_F_ZSTD | PBSGPU_DECODE_F_AES)) return PBSGPU_E_INVALID;
+    return blob_decode(e, blobs_dptr, nbytes, blobs, nblob, idx, nidx, blob_of, range_start, range_end, flags, key, dst, dst_cap,
+                       status, stats, idkey);
 }
 
 int pbsgpu_known_upload_new2_device(pbsgpu_known *k, const void *src, uint64_t src_bytes, const pbsgpu_record *recs,

@@ -6,9 +6,12 @@
 // path launches the HIP kernels; without a device the engine cannot be created.
 #include <chrono>
 #include "engine_internal.h"
+#include "sha256_suffix.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <new>
 
 // The engine runs up to 16 batches on separate HIP streams; ROCm maps them onto the hardware queues the process may open.
 // That count is the host's setting (GPU_MAX_HW_QUEUES): the library never changes it.
@@ -450,7 +453,7 @@ static int enqueue_hash(pbsgpu_engine *e, Slot &s) {
     const uint64_t longest = std::min<uint64_t>(e->cfg.max, std::max<uint64_t>(s.nbytes, 1)) / 64 + 1;
     const bool dense = pbsk::sha256_dense_pays(s.nbytes / 64, longest, e->num_cus, e->opt.sha_dense_pct);
     HIPCHK(pbsk::launch_sha256_records(s.recs.as<pbsgpu_record>(), sc + SC_NREC, sc + SC_QUEUE, s.order.as<uint4>(),
-                                       sc + SC_WGLIMIT, e->num_cus, dense, (int)e->opt.sha_form, s.stream));
+                                       sc + SC_WGLIMIT, e->num_cus, dense, (int)e->opt.sha_form, s.stream, s.id_key));
     HIPCHK(hipEventRecord(s.ev[EV_SHA1], s.stream));
     return PBSGPU_OK;
 }
@@ -590,8 +593,9 @@ bool is_device_pointer(const void *p) {
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || attr.type == hipMemoryTypeUnified;
 }
 
+// (`idkey`: every digest of the ticket is the keyed one; it stays with the slot, so a density retry hashes with the same key)
 static int submit_common(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs,
-                         uint32_t nseg, const SuggestedHost *sg, uint64_t *ticket) {
+                         uint32_t nseg, const SuggestedHost *sg, uint64_t *ticket, const pbsgpu_id_key *idkey = nullptr) {
     if (!e || !ticket || (!ptr && nbytes)) return PBSGPU_E_INVALID;
     CHK(set_device(e));
     if (!host && nbytes && !is_device_pointer(ptr)) return PBSGPU_E_INVALID;
@@ -615,6 +619,7 @@ static int submit_common(pbsgpu_engine *e, const void *ptr, bool host, uint64_t 
             s->host_submit = host;
             s->retries = 0;
             s->synced = false;
+            s->id_key = idkey ? idkey->dev() : nullptr;
             return enqueue_pipeline(e, *s, default_cap(e, s->nbytes));
         }();
         if (st != PBSGPU_OK) (void)hipStreamSynchronize(s->stream);
@@ -928,6 +933,18 @@ int pbsgpu_submit_host_suggested(pbsgpu_engine *e, const void *hptr, uint64_t nb
     return submit_common(e, hptr, true, nbytes, segs, nseg, &sg, ticket);
 }
 
+int pbsgpu_submit_device_keyed(pbsgpu_engine *e, pbsgpu_id_key *key, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                               uint32_t nseg, uint64_t *ticket) {
+    if (!e || !key || key->eng != e) return PBSGPU_E_INVALID;
+    return submit_common(e, dptr, false, nbytes, segs, nseg, nullptr, ticket, key);
+}
+
+int pbsgpu_submit_host_keyed(pbsgpu_engine *e, pbsgpu_id_key *key, const void *hptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                             uint32_t nseg, uint64_t *ticket) {
+    if (!e || !key || key->eng != e) return PBSGPU_E_INVALID;
+    return submit_common(e, hptr, true, nbytes, segs, nseg, nullptr, ticket, key);
+}
+
 int pbsgpu_wait(pbsgpu_engine *e, uint64_t ticket, uint64_t *nrecords) {
     if (!e) return PBSGPU_E_INVALID;
     return with_ticket(e, ticket, [&](Slot &s) -> int {
@@ -1112,10 +1129,10 @@ int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes) {
 }
 
 int enqueue_sha256(pbsgpu_engine *e, hipStream_t st, const uint8_t *base, const pbsgpu_segment *ranges_dev, uint32_t n,
-                   uint8_t *digs, uint32_t *queue, const pbsp::ShaWork &work) {
+                   uint8_t *digs, uint32_t *queue, const pbsp::ShaWork &work, const uint32_t *key) {
     HIPCHK(pbsk::launch_sha256_segments(base, ranges_dev, n, digs, queue, e->num_cus,
                                         pbsk::sha256_dense_pays(work.total_blocks, work.longest, e->num_cus, e->opt.sha_dense_pct),
-                                        (int)e->opt.sha_form, st));
+                                        (int)e->opt.sha_form, st, key));
     return PBSGPU_OK;
 }
 
@@ -1124,7 +1141,7 @@ int enqueue_sha256(pbsgpu_engine *e, hipStream_t st, const uint8_t *base, const 
 extern "C" {
 
 static int sha256_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nbytes, const pbsgpu_segment *segs,
-                       uint32_t nseg, uint8_t *digests) {
+                       uint32_t nseg, uint8_t *digests, const uint32_t *key = nullptr) {
     if (!e || (!ptr && nbytes) || (nseg && (!segs || !digests))) return PBSGPU_E_INVALID;
     if (nseg == 0) return PBSGPU_OK;
     if (!pbsp::ranges_ok(segs, nseg, nbytes)) return PBSGPU_E_INVALID;
@@ -1137,8 +1154,68 @@ static int sha256_many(pbsgpu_engine *e, const void *ptr, bool host, uint64_t nb
     CHK(s->taken());
     pbsp::ShaWork work;
     for (uint32_t i = 0; i < nseg; ++i) work.add(segs[i].length);
-    CHK(enqueue_sha256(e, s->stream, d, s->segs.as<pbsgpu_segment>(), nseg, digs, s->scalars.as<uint32_t>() + SC_QUEUE, work));
+    CHK(enqueue_sha256(e, s->stream, d, s->segs.as<pbsgpu_segment>(), nseg, digs, s->scalars.as<uint32_t>() + SC_QUEUE, work, key));
     return fetch_result(s, digests, digs, (size_t)nseg * 32);
+}
+
+// ---- keyed chunk digests, SHA-256(content || id_key) (include/pbsgpu.h) --------------------------------------
+static void wipe_bytes(void *p, size_t n) {  // a memset the optimiser may not drop
+    volatile uint8_t *v = static_cast<volatile uint8_t *>(p);
+    for (size_t i = 0; i < n; ++i) v[i] = 0;
+}
+
+int pbsgpu_id_key_create(pbsgpu_engine *e, const uint8_t *id_key, pbsgpu_id_key **out) {
+    if (!e || !id_key || !out) return PBSGPU_E_INVALID;
+    *out = nullptr;
+    CHK(set_device(e));
+    pbsgpu_id_key *k = new (std::nothrow) pbsgpu_id_key();
+    int st = k ? k->words.ensure(pbss::kSuffixBytes) : PBSGPU_E_NOMEM;
+    if (st == PBSGPU_OK) {
+        // through one aligned block of this frame, not through a slot's pinned staging: no second copy outlives the call
+        alignas(16) uint8_t copy[pbss::kSuffixBytes];
+        std::memcpy(copy, id_key, sizeof(copy));
+        if (hipMemcpy(k->words.p, copy, sizeof(copy), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            st = PBSGPU_E_HIP;
+        }
+        wipe_bytes(copy, sizeof(copy));
+    }
+    if (st != PBSGPU_OK) {
+        if (k) k->words.release();
+        delete k;
+        return st;
+    }
+    engine_ref(e);
+    k->eng = e;
+    *out = k;
+    return PBSGPU_OK;
+}
+
+void pbsgpu_id_key_destroy(pbsgpu_id_key *k) {
+    if (!k) return;
+    pbsgpu_engine *e = k->eng;
+    if (e) (void)set_device(e);
+    if (k->words.p) {
+        AuxLease lease(e);  // (calls that use the key hold a lease or a ticket until they have synchronised: none is running now)
+        if (hipMemsetAsync(k->words.p, 0, pbss::kSuffixBytes, lease.s->stream) != hipSuccess ||
+            hipStreamSynchronize(lease.s->stream) != hipSuccess)
+            (void)hipGetLastError();
+    }
+    k->words.release();
+    delete k;
+    if (e) engine_unref(e);
+}
+
+int pbsgpu_sha256_keyed_many_device(pbsgpu_id_key *key, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                                    uint32_t nseg, uint8_t *digests) {
+    if (!key) return PBSGPU_E_INVALID;
+    return sha256_many(key->eng, dptr, false, nbytes, segs, nseg, digests, key->dev());
+}
+
+int pbsgpu_sha256_keyed_many_host(pbsgpu_id_key *key, const void *hptr, uint64_t nbytes, const pbsgpu_segment *segs,
+                                  uint32_t nseg, uint8_t *digests) {
+    if (!key) return PBSGPU_E_INVALID;
+    return sha256_many(key->eng, hptr, true, nbytes, segs, nseg, digests, key->dev());
 }
 
 int pbsgpu_sha256_many_device(pbsgpu_engine *e, const void *dptr, uint64_t nbytes, const pbsgpu_segment *segs,

@@ -207,6 +207,8 @@ struct Slot {
     bool sugg_open_end = false;
     bool host_submit = false;
     uint32_t retries = 0;
+    const uint32_t *id_key = nullptr;  // a keyed ticket (pbsgpu_submit_*_keyed): the key's eight words on the device, fixed at
+                                       // submit time for every run of the batch; nullptr = plain digests
     bool dense_mode = false;  // scanned at the capacity limit: the resolve walks re-scan overflowed tiles on demand (DenseTiles)
     uint64_t nrec = 0, ncand = 0;
 
@@ -266,6 +268,13 @@ struct pbsgpu_engine {
     int refs = 1;                // owner + live streams / chunkers (under mu); freed when it drops to 0
     bool destroyed = false;      // pbsgpu_engine_destroy was called (children may still be alive)
 };
+// the id key of keyed chunk digests, SHA-256(content || id_key) (engine.cpp): 32 bytes of device memory, the only copy the
+// library keeps
+struct pbsgpu_id_key {
+    pbsgpu_engine *eng = nullptr;
+    pbse::DevBuf words;
+    const uint32_t *dev() const { return words.as<const uint32_t>(); }
+};
 
 namespace pbse {
 
@@ -321,7 +330,8 @@ int fetch_result(Slot *s, void *dst, const void *src_dev, size_t nbytes);
 // SHA-256 of n device ranges of `base` into digs (32 bytes each), with the dense-form policy of pbsgpu_sha256_many_device
 // applied to `work`, the sums over the lengths the host knows; queue: a zeroed counter. Enqueued, nothing synchronised.
 int enqueue_sha256(pbsgpu_engine *e, hipStream_t st, const uint8_t *base, const pbsgpu_segment *ranges_dev, uint32_t n,
-                   uint8_t *digs, uint32_t *queue, const pbsp::ShaWork &work);
+                   uint8_t *digs, uint32_t *queue, const pbsp::ShaWork &work, const uint32_t *key = nullptr);
+// (`key`: the device words of a pbsgpu_id_key: keyed digests. `work` counts plain blocks either way: a budget, not a result)
 // synchronous helper for the upstream-style chunker (the caller owns the slot)
 int candidates_sync(pbsgpu_engine *e, Slot &s, const uint8_t *dptr, uint64_t nbytes, uint64_t *count);
 // Caller bytes -> pinned staging. One thread copies ~12 GB/s, the H2D engine moves 57 GB/s: a single writer (the
@@ -365,8 +375,12 @@ hipError_t launch_restore_status(const RestorePlan &pl, hipStream_t st);
 struct pbsgpu_aes_key;
 namespace pbsk {
 namespace aes {
+// idkey (pbsgpu_blob_decode4_device, with zp.recs set): the device words of the id key. Every blob the leg restored is then
+// hashed once, keyed, where its plaintext lies (job.place, the length of its result), and an entry that passed tag, frame and
+// size is compared with its record's digest on the device: PBSGPU_BLOB_BAD_DIGEST. sha: the budget over the rooms.
 int enqueue_restore(pbsgpu_engine *e, pbse::Slot *s, const pbsgpu_aes_key *key, const pbsk::zstd::RestorePlan &zp,
-                    const pbsgpu_segment *ub, bool zstd, uint32_t longest_copy, uint64_t *res);
+                    const pbsgpu_segment *ub, bool zstd, uint32_t longest_copy, uint64_t *res, const uint32_t *idkey = nullptr,
+                    const pbsp::ShaWork *sha = nullptr);
 pbsgpu_engine *key_engine(const pbsgpu_aes_key *k);
 const void *key_tables(const pbsgpu_aes_key *k);  // the key's pbsa::KeyTables in device memory
 constexpr uint32_t kResBadTag = 0xfe, kResFrame = 0x80;

@@ -161,8 +161,11 @@ hipError_t launch_resolve_single(const uint64_t *cands, const uint32_t *ncand, c
 // SHA-256 of every record's chunk: one lane per chunk, lanes pull records from a shared queue.
 // `queue` is a device uint32 that must be zero at launch.
 // (`form`: pbsgpu_engine_options::sha_form — 0 wave pairs, 1 single-wave lanes, 2 express)
+// (`key`: the eight words of a pbsgpu_id_key in device memory — every digest is the KEYED one, SHA-256(chunk || key), from the
+// keyed instances of the same kernels; null = the plain digest. The page ring's services have no keyed form.)
 hipError_t launch_sha256_records(pbsgpu_record *recs, const uint32_t *nrec, uint32_t *queue, const uint4 *qdesc,
-                                 const uint32_t *wg_limit, int num_cus, bool dense, int form, hipStream_t st);
+                                 const uint32_t *wg_limit, int num_cus, bool dense, int form, hipStream_t st,
+                                 const uint32_t *key = nullptr);
 // longest-first queue order (counting sort by size class) + workgroup budget for the SHA kernel:
 // lanes = (1 + slack_pct/100) x total blocks / longest chunk's blocks
 // (writes the queue as 16-byte descriptors {address lo, hi, size, record index}: kQueueDescBytes per record)
@@ -175,7 +178,8 @@ hipError_t launch_order(const uint8_t *data, const pbsgpu_segment *segs, const p
 bool sha256_dense_pays(uint64_t total_blocks, uint64_t longest_blocks, int num_cus, uint32_t dense_pct);
 // SHA-256 of whole segments (verification path): digests[32*i] for segs[i]
 hipError_t launch_sha256_segments(const uint8_t *data, const pbsgpu_segment *segs, uint32_t nseg,
-                                  uint8_t *digests, uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st);
+                                  uint8_t *digests, uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st,
+                                  const uint32_t *key = nullptr);
 
 // XXH3-64 (seed 0) of whole segments: out[i] for segs[i]; `queue` zero at launch
 // XXH3-64 (seed 0), two phases (xxh3.hip): every 1 KiB block of every input is summed by some wave of the grid

@@ -5,6 +5,9 @@
 #include "kernel_util.h"
 #include "kernels.h"
 #include "ring_queue.h"
+#include "sha256_suffix.h"
+
+#include <type_traits>
 
 namespace pbsk {
 
@@ -162,6 +165,60 @@ struct SegmentSource {
     }
 };
 
+// KEYED digests, SHA-256(content || id_key): the index digest of an encrypted backup's chunk. The keyed twins
+// of the two batch sources carry the key's eight words (device memory of a pbsgpu_id_key, never written while a kernel runs:
+// read through the constant address space, i.e. with scalar loads, inside the tail branch only) and the compile-time count of
+// suffix bytes. A source WITHOUT kSuffixBytes (RecordSource, SegmentSource, RingSource: not edited) has none, and every
+// `if constexpr` below then leaves exactly the code there was: the plain kernels' ISA does not change.
+template <typename S, typename = void>
+struct SuffixOf {
+    static constexpr uint32_t kBytes = 0;
+};
+template <typename S>
+struct SuffixOf<S, std::void_t<decltype(S::kSuffixBytes)>> {
+    static constexpr uint32_t kBytes = S::kSuffixBytes;
+};
+struct KeyedRecordSource : RecordSource {
+    static constexpr uint32_t kSuffixBytes = pbss::kSuffixBytes;
+    const uint32_t *key;
+};
+struct KeyedSegmentSource : SegmentSource {
+    static constexpr uint32_t kSuffixBytes = pbss::kSuffixBytes;
+    const uint32_t *key;
+};
+typedef const __attribute__((address_space(4))) uint32_t *kword_ptr;
+
+// sha256_tail_words for a keyed chunk: the same clamped dword loads and funnel shift for the data words, then
+// pbss::sha256_suffix_block (sha256_suffix.h: registers only, the CPU test runs the same function) decides what every byte
+// of the block is. At most two such blocks per chunk (63 + 32 + 9 < 128).
+__device__ __forceinline__ void sha256_tail_words_keyed(const uint8_t *base, uint64_t len, uint64_t off, bool last, const uint32_t *key,
+                                                        uint32_t (&R)[17]) {
+    const int64_t rem = (int64_t)len - (int64_t)off;                // data bytes from `off` on: < 64 here, <= 0 = none
+    const uint32_t valid = rem <= 0 ? 0u : (uint32_t)rem;
+    uint32_t q[17];
+#pragma unroll
+    for (int j = 0; j < 17; ++j) q[j] = 0;
+    uint32_t o = 0;
+    if (valid) {
+        const uint8_t *p = base + off;
+        o = (uint32_t)((uintptr_t)p & 3u);
+        const gword_ptr a = (gword_ptr)(p - o);
+        const uint32_t jmax = (o + valid - 1u) >> 2;               // last dword that holds a valid byte
+#pragma unroll
+        for (int j = 0; j < 17; ++j) q[j] = a[min((uint32_t)j, jmax)];
+    }
+    const uint32_t sh = o * 8u;
+    uint32_t d[16], k[pbss::kSuffixWords], out[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) d[j] = sh ? ((q[j] >> sh) | (q[j + 1] << (32u - sh))) : q[j];
+#pragma unroll
+    for (int j = 0; j < (int)pbss::kSuffixWords; ++j) k[j] = ((kword_ptr)key)[j];
+    pbss::sha256_suffix_block(d, valid, len, off, k, last, out);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) R[j] = out[j];
+    R[16] = 0;
+}
+
 // The page ring's SHA-256 SERVICE (ring.cpp): one persistent launch whose lanes pull chunk descriptors from a
 // device-resident FIFO that the cut rounds of ALL streams append to (k_ring_order / k_ring_publish), so a chunk starts
 // hashing the moment it has been cut, whichever round, stream or page it came from, and every lane that finishes a chunk
@@ -237,7 +294,10 @@ __global__ __launch_bounds__(64) void k_sha256(Source src, const uint32_t *nitem
     sha256_iv(H);
 
     // loads block `blk` of (base,len) into R (raw) and sets sel
-    auto load_block = [&]() {
+    // (`key`: empty for a plain source, the key's words for a keyed one. An argument, not `src.key`: with `src` named inside
+    // this lambda, even in a branch an instance discards, the plain instances compiled to ISA with a few instructions and
+    // registers swapped; with the argument pack their ISA text is what it was, byte for byte — DESIGN.md §23)
+    auto load_block = [&](auto... key) {
         const uint64_t off = blk * 64;
         if (off + 64 <= len) {  // pure data block: aligned dword loads + per-lane funnel selector
             const uint8_t *p = base + off;
@@ -251,7 +311,8 @@ __global__ __launch_bounds__(64) void k_sha256(Source src, const uint32_t *nitem
             R[16] = o ? ((gword_ptr)(p - o))[16] : 0u;
             sel = ((o) << 24) | ((o + 1) << 16) | ((o + 2) << 8) | (o + 3);
         } else {  // tail / padding block (at most two per range)
-            sha256_tail_words(base, len, off, blk + 1 == nblk, R);
+            if constexpr (sizeof...(key) != 0) sha256_tail_words_keyed(base, len, off, blk + 1 == nblk, key..., R);
+            else sha256_tail_words(base, len, off, blk + 1 == nblk, R);
             sel = 0x00010203u;
         }
     };
@@ -266,7 +327,8 @@ __global__ __launch_bounds__(64) void k_sha256(Source src, const uint32_t *nitem
             if (i < nitems) {
                 src.get(i, base, len, dst);
                 blk = 0;
-                nblk = (len + 8) / 64 + 1;
+                if constexpr (SuffixOf<Source>::kBytes != 0) nblk = pbss::sha256_blocks(len, SuffixOf<Source>::kBytes);
+                else nblk = (len + 8) / 64 + 1;
                 have = true;
             } else {
                 exhausted = true;
@@ -276,7 +338,10 @@ __global__ __launch_bounds__(64) void k_sha256(Source src, const uint32_t *nitem
     };
 
     acquire(true);
-    if (have) load_block();
+    if (have) {
+        if constexpr (SuffixOf<Source>::kBytes != 0) load_block(src.key);
+        else load_block();
+    }
 
     while (__any(have)) {
         // current block = R; convert to big-endian message words
@@ -292,7 +357,10 @@ __global__ __launch_bounds__(64) void k_sha256(Source src, const uint32_t *nitem
             if (!cur_last) ++blk; else have = false;
         }
         acquire(!have && !exhausted);
-        if (have) load_block();
+        if (have) {
+            if constexpr (SuffixOf<Source>::kBytes != 0) load_block(src.key);
+            else load_block();
+        }
 
         if (cur) sha256_compress(H, W);
 
@@ -620,7 +688,8 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                 if (i < nitems) {
                     if constexpr (!Source::kRing) src.get(i, base, len, dst);
                     blk = 0;
-                    nblk = (len + 8) / 64 + 1;
+                    if constexpr (SuffixOf<Source>::kBytes != 0) nblk = pbss::sha256_blocks(len, SuffixOf<Source>::kBytes);
+                    else nblk = (len + 8) / 64 + 1;
                     have = true;
                 } else {
                     exhausted = true;
@@ -637,8 +706,8 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                 }
             }
         };
-        // request the lane's next block into FIFO slot s (compile-time s)
-        auto prep = [&](const int s) {
+        // request the lane's next block into FIFO slot s (compile-time s); `key`: as for k_sha256's load_block
+        auto prep = [&](const int s, auto... key) {
             acquire(!have && !exhausted);
             uint32_t c = 0;
             const uint8_t *p = reinterpret_cast<const uint8_t *>(kIdleBlock);
@@ -658,14 +727,18 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
             }
             sha256_request_block(p, R[s], selv[s]);
             if (tail) {
-                sha256_tail_words(bb, len, off, last, R[s]);
+                if constexpr (sizeof...(key) != 0) sha256_tail_words_keyed(bb, len, off, last, key..., R[s]);
+                else sha256_tail_words(bb, len, off, last, R[s]);
                 selv[s] = 0x00010203u;
             }
             cflag[s] = c;
         };
 
 #pragma unroll
-        for (int s = 0; s < D; ++s) prep(s);
+        for (int s = 0; s < D; ++s) {
+            if constexpr (SuffixOf<Source>::kBytes != 0) prep(s, src.key);
+            else prep(s);
+        }
         // ONE exit, behind the last slot's step. Every path from a slot's requests back to the perm that consumes them then
         // passes the other slot's five requests, and the slot is awaited with vmcnt(5). (An exit in the middle — a test of
         // `running` per slot, or a return — is routed through the loop's latch by the structuriser: an edge from slot 0's
@@ -703,7 +776,9 @@ __global__ __launch_bounds__(DENSE ? 512 : 256) void k_sha256_pair(Source src, c
                         // its whole 0.46 s either way; configs[2] through the ring 412 vs 422 GiB/s. Removed again.)
                         if (c & 2u) ring_release_pages(src, pagesv[s]);
                     }
-                    prep(s);  // refill the slot: the block D iterations ahead
+                    // refill the slot: the block D iterations ahead
+                    if constexpr (SuffixOf<Source>::kBytes != 0) prep(s, src.key);
+                    else prep(s);
                     const bool any_cur = __any(c & 1u);
                     if (any_cur) {
 #pragma unroll
@@ -1044,13 +1119,14 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
                     }
                 }
                 if (pgot) {
-                    nblk = (len + 8) / 64 + 1;
+                    if constexpr (SuffixOf<Source>::kBytes != 0) nblk = pbss::sha256_blocks(len, SuffixOf<Source>::kBytes);
+                    else nblk = (len + 8) / 64 + 1;
                     blk = roleB ? 1ull : 0ull;
                     have = blk < nblk;
                 }
             }
         };
-        auto prep = [&](const int s) {
+        auto prep = [&](const int s, auto... key) {
             const unsigned long long hm = __ballot(have);
             const bool pair_busy = ((hm >> (lane & ~1)) & 3ull) != 0ull;
             acquire(!roleB && !pair_busy && !exhausted);
@@ -1073,7 +1149,8 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
             }
             sha256_request_block(p, R[s], selv[s]);
             if (tail) {
-                sha256_tail_words(bb, len, off, last, R[s]);
+                if constexpr (sizeof...(key) != 0) sha256_tail_words_keyed(bb, len, off, last, key..., R[s]);
+                else sha256_tail_words(bb, len, off, last, R[s]);
                 selv[s] = 0x00010203u;
             }
             cflag[s] = c;
@@ -1082,7 +1159,10 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
         const int wrow = lane & ~1, wplane = lane & 1;
 
 #pragma unroll
-        for (int s = 0; s < D; ++s) prep(s);
+        for (int s = 0; s < D; ++s) {
+            if constexpr (SuffixOf<Source>::kBytes != 0) prep(s, src.key);
+            else prep(s);
+        }
         bool drained = false;  // (one exit behind the last slot: k_sha256_pair)
         [[maybe_unused]] bool wg_busy = false;
         [[maybe_unused]] RingProbe probe;
@@ -1115,7 +1195,8 @@ __global__ __launch_bounds__(256) void k_sha256_xpair(Source src, const uint32_t
                         }
                         if (c & 2u) ring_release_pages(src, pagesv[s]);
                     }
-                    prep(s);
+                    if constexpr (SuffixOf<Source>::kBytes != 0) prep(s, src.key);
+                    else prep(s);
                     const bool any_cur = __any(c & 1u);
                     if (any_cur) {
 #pragma unroll
@@ -1332,8 +1413,17 @@ static hipError_t launch_pair(unsigned grid, bool dense, hipStream_t st, Source 
     return hipGetLastError();
 }
 
+// the keyed twins of the two launchers below (at the end of this file: the keyed instances are the LAST ones this unit
+// instantiates, so every kernel that was here before them keeps its place in the object and its ISA text, labels included)
+static hipError_t launch_sha256_records_keyed(pbsgpu_record *recs, const uint32_t *nrec, uint32_t *queue, const uint4 *qdesc,
+                                              const uint32_t *wg_limit, int num_cus, bool dense, int form, hipStream_t st,
+                                              const uint32_t *key);
+static hipError_t launch_sha256_segments_keyed(const uint8_t *data, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *digests,
+                                               uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st, const uint32_t *key);
+
 hipError_t launch_sha256_records(pbsgpu_record *recs, const uint32_t *nrec, uint32_t *queue, const uint4 *qdesc,
-                                 const uint32_t *wg_limit, int num_cus, bool dense, int form, hipStream_t st) {
+                                 const uint32_t *wg_limit, int num_cus, bool dense, int form, hipStream_t st, const uint32_t *key) {
+    if (key) return launch_sha256_records_keyed(recs, nrec, queue, qdesc, wg_limit, num_cus, dense, form, st, key);
     RecordSource src{recs, qdesc};
     if (form == 2) {
         hipLaunchKernelGGL((k_sha256_xpair<RecordSource>), dim3((unsigned)num_cus), dim3(256), 0, st, src, nrec, 0u, queue,
@@ -1358,8 +1448,9 @@ hipError_t launch_sha256_records(pbsgpu_record *recs, const uint32_t *nrec, uint
 }
 
 hipError_t launch_sha256_segments(const uint8_t *data, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *digests,
-                                  uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st) {
+                                  uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st, const uint32_t *key) {
     if (nseg == 0) return hipSuccess;
+    if (key) return launch_sha256_segments_keyed(data, segs, nseg, digests, queue, num_cus, dense, form, st, key);
     SegmentSource src{data, segs, digests};
     if (form != 1) {
         unsigned g2 = (unsigned)num_cus;
@@ -1427,6 +1518,54 @@ static hipError_t launch_ring_service_form(const RingSource &q, unsigned workgro
 // dense (PBSGPU_RING_F_DENSE_SERVICE): four pairs per workgroup, two waves per SIMD — DESIGN.md 5.2 for what it buys and costs
 hipError_t launch_ring_service(const RingSource &q, unsigned workgroups, hipStream_t st, bool dense) {
     return dense ? launch_ring_service_form<true>(q, workgroups, st) : launch_ring_service_form<false>(q, workgroups, st);
+}
+
+// ---- keyed digests (KeyedRecordSource, KeyedSegmentSource): the same launches as launch_sha256_records and
+// launch_sha256_segments, over the keyed instances --------------------------------------------------------------------------
+static hipError_t launch_sha256_records_keyed(pbsgpu_record *recs, const uint32_t *nrec, uint32_t *queue, const uint4 *qdesc,
+                                              const uint32_t *wg_limit, int num_cus, bool dense, int form, hipStream_t st,
+                                              const uint32_t *key) {
+    KeyedRecordSource src{{recs, qdesc}, key};
+    if (form == 2) {
+        hipLaunchKernelGGL((k_sha256_xpair<KeyedRecordSource>), dim3((unsigned)num_cus), dim3(256), 0, st, src, nrec, 0u, queue,
+                           wg_limit);
+    } else if (form == 0) {
+        if (dense) {
+            hipLaunchKernelGGL((k_sha256_pair<KeyedRecordSource, true>), dim3((unsigned)num_cus), dim3(512), 0, st, src, nrec,
+                               0u, queue, wg_limit);
+        } else {
+            hipError_t e = allow_lds(&k_sha256_pair<KeyedRecordSource, false>, kPairLdsPad);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL((k_sha256_pair<KeyedRecordSource, false>), dim3((unsigned)num_cus), dim3(256), kPairLdsPad, st, src,
+                               nrec, 0u, queue, wg_limit);
+        }
+    } else {
+        hipError_t e = allow_lds(&k_sha256<KeyedRecordSource>, kLaneLdsPad);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_sha256<KeyedRecordSource>), dim3((unsigned)num_cus * 4u), dim3(64), kLaneLdsPad, st, src, nrec, 0u,
+                           queue, wg_limit, 0u);
+    }
+    return hipGetLastError();
+}
+
+static hipError_t launch_sha256_segments_keyed(const uint8_t *data, const pbsgpu_segment *segs, uint32_t nseg, uint8_t *digests,
+                                               uint32_t *queue, int num_cus, bool dense, int form, hipStream_t st, const uint32_t *key) {
+    KeyedSegmentSource src{{data, segs, digests}, key};
+    if (form != 1) {
+        unsigned g2 = (unsigned)num_cus;
+        const unsigned need2 = (nseg + (dense ? 255u : 127u)) / (dense ? 256u : 128u);
+        if (g2 > need2) g2 = need2;
+        return launch_pair(g2, dense, st, src, nseg, queue, form);
+    }
+    hipError_t e = allow_lds(&k_sha256<KeyedSegmentSource>, kLaneLdsPad);
+    if (e != hipSuccess) return e;
+    const size_t pad = dense ? kLaneLdsPad / 2 : kLaneLdsPad;  // (launch_sha256_segments: eight single-wave workgroups per CU)
+    unsigned grid = (unsigned)num_cus * (dense ? 8u : 4u);
+    const unsigned need = (nseg + 63) / 64;
+    if (grid > need) grid = need;
+    hipLaunchKernelGGL((k_sha256<KeyedSegmentSource>), dim3(grid), dim3(64), pad, st, src, (const uint32_t *)nullptr,
+                       nseg, queue, (const uint32_t *)nullptr, 0u);
+    return hipGetLastError();
 }
 
 }  // namespace pbsk

@@ -126,12 +126,24 @@ class Engine:
         return None, None
 
     # ---- batch path ------------------------------------------------------------------------------
-    def submit(self, data, segments=None, nbytes: int | None = None, suggested=None) -> int:
+    def submit(self, data, segments=None, nbytes: int | None = None, suggested=None, id_key=None) -> int:
         """Enqueue cut + digest of every segment; returns a ticket. `suggested` = one ascending list of suggested
-        boundaries per segment (relative to the segment start; payload-chunker rule, see pbsgpu.h)."""
+        boundaries per segment (relative to the segment start; payload-chunker rule, see pbsgpu.h). `id_key` = an IdKey of
+        this engine: every record's digest is the keyed SHA-256(chunk || id_key) (pbsgpu_submit_*_keyed; not together with
+        `suggested`); keep the key open until the ticket is collected."""
         segs, nseg = _segs(segments)
         t = C.c_uint64()
         ptr, n = self._dev(data, nbytes)
+        if id_key is not None:
+            if suggested is not None:
+                raise ValueError("there is no keyed submit with suggested boundaries")
+            if ptr is not None:
+                check(self._L.pbsgpu_submit_device_keyed(self._h, id_key._h, ptr, n, segs, nseg, C.byref(t)), "submit_device_keyed")
+            else:
+                a = _host_view(data)
+                check(self._L.pbsgpu_submit_host_keyed(self._h, id_key._h, a.ctypes.data, a.size, segs, nseg, C.byref(t)),
+                      "submit_host_keyed")
+            return t.value
         if suggested is not None:
             ns = max(nseg, 1)
             assert len(suggested) == ns, "one suggested-boundary list per segment"
@@ -185,8 +197,8 @@ class Engine:
         check(self._L.pbsgpu_collect(self._h, ticket, out.ctypes.data, n, C.byref(got)), "collect")
         return out[: got.value]
 
-    def chunk_and_digest(self, data, segments=None, nbytes: int | None = None, suggested=None) -> np.ndarray:
-        return self.collect(self.submit(data, segments, nbytes, suggested))
+    def chunk_and_digest(self, data, segments=None, nbytes: int | None = None, suggested=None, id_key=None) -> np.ndarray:
+        return self.collect(self.submit(data, segments, nbytes, suggested, id_key))
 
     def candidates(self, data, nbytes: int | None = None) -> np.ndarray:
         """Raw Buzhash candidates (ascending END offsets) of a device byte range."""
@@ -227,6 +239,22 @@ class Engine:
             a = _host_view(data)
             check(self._L.pbsgpu_sha256_many_host(self._h, a.ctypes.data if a.size else None, a.size, segs, nseg,
                                                   out.ctypes.data), "sha256_many_host")
+        return out[:nseg]
+
+    def sha256_keyed_many(self, key: "IdKey", data, segments, nbytes: int | None = None) -> np.ndarray:
+        """sha256_many() with an id key: row i = SHA-256(range i || id_key), the index digest of a chunk of an encrypted
+        backup (pbsgpu_sha256_keyed_many_*). The key's engine does the work; a key of another engine is refused here."""
+        if key._eng is not self:
+            raise _lib.PbsGpuError(_lib.E_INVALID, "sha256_keyed_many: the key belongs to another engine")
+        segs, nseg = _segs(segments)
+        out = np.zeros((max(nseg, 1), 32), dtype=np.uint8)
+        ptr, n = self._dev(data, nbytes)
+        if ptr is not None:
+            check(self._L.pbsgpu_sha256_keyed_many_device(key._h, ptr, n, segs, nseg, out.ctypes.data), "sha256_keyed_many_device")
+        else:
+            a = _host_view(data)
+            check(self._L.pbsgpu_sha256_keyed_many_host(key._h, a.ctypes.data if a.size else None, a.size, segs, nseg,
+                                                        out.ctypes.data), "sha256_keyed_many_host")
         return out[:nseg]
 
     # ---- whole-stream XXH3-64 (the xxh3.New() tee of writeBackedFile / verifyBackedFileHashes) -------
@@ -387,8 +415,18 @@ class Engine:
                      out_bytes=int(st.out_bytes), zstd_in_bytes=int(st.zstd_in_bytes), zstd_out_bytes=int(st.zstd_out_bytes))
         return dst, status[:n], stats
 
+    def blob_decode4(self, data, blobs, idx, blob_of=None, start=None, end=None, check_digest=True, dst=None,
+                     nbytes: int | None = None, zstd=True, key=None, aes=None, id_key=None):
+        """blob_decode3() with the keyed digest check (pbsgpu_blob_decode4_device): with aes, check_digest and `id_key`, an
+        IdKey of this engine, an entry of an encrypted kind that passed tag, frame and size is checked against
+        SHA-256(plaintext || id_key) and gets status 3 (bad_digest) on a mismatch; its bytes stay restored. Entries of the
+        plain kinds keep the plain digest. sha_bytes counts the plaintext of each distinct encrypted blob once. With
+        id_key=None every output is blob_decode3()'s."""
+        return self.blob_decode3(data, blobs, idx, blob_of, start, end, check_digest, dst, nbytes, zstd, key, aes,
+                                 _id_key=id_key, _four=True)
+
     def blob_decode3(self, data, blobs, idx, blob_of=None, start=None, end=None, check_digest=True, dst=None,
-                     nbytes: int | None = None, zstd=True, key=None, aes=None):
+                     nbytes: int | None = None, zstd=True, key=None, aes=None, _id_key=None, _four=False):
         """blob_decode2() with the encrypted blobs decrypted on the device under `key`, an AesKey of this engine
         (pbsgpu_blob_decode3_device). aes defaults to "a key was given"; aes=True without a key raises PbsGpuError
         (E_INVALID). An encrypted blob whose CRC is good is decrypted to its entries' places; an encrypted-compressed one is
@@ -416,11 +454,19 @@ class Engine:
             aes = key is not None
         flags = (_lib.DECODE_F_DIGEST if check_digest else 0) | (_lib.DECODE_F_ZSTD if zstd else 0) | (_lib.DECODE_F_AES if aes else 0)
         try:
-            check(self._L.pbsgpu_blob_decode3_device(self._h, bp, bn, segs, nblob, recs.ctypes.data if n else None, n,
-                                                     bo.ctypes.data if bo is not None and n else None, int(start), int(end),
-                                                     flags, key._h if key is not None else None, dst.ptr, dst.nbytes,
-                                                     status.ctypes.data, C.byref(st)),
-                  "blob_decode3_device")
+            if _four:
+                check(self._L.pbsgpu_blob_decode4_device(self._h, bp, bn, segs, nblob, recs.ctypes.data if n else None, n,
+                                                         bo.ctypes.data if bo is not None and n else None, int(start), int(end),
+                                                         flags, key._h if key is not None else None,
+                                                         _id_key._h if _id_key is not None else None, dst.ptr, dst.nbytes,
+                                                         status.ctypes.data, C.byref(st)),
+                      "blob_decode4_device")
+            else:
+                check(self._L.pbsgpu_blob_decode3_device(self._h, bp, bn, segs, nblob, recs.ctypes.data if n else None, n,
+                                                         bo.ctypes.data if bo is not None and n else None, int(start), int(end),
+                                                         flags, key._h if key is not None else None, dst.ptr, dst.nbytes,
+                                                         status.ctypes.data, C.byref(st)),
+                      "blob_decode3_device")
         except Exception:
             if own:
                 dst.free()
@@ -888,6 +934,46 @@ class AesKey:
 
     def __repr__(self):  # (never the key)
         return "AesKey(<32 bytes>)"
+
+
+class IdKey:
+    """The 32-byte id key of keyed chunk digests on the device (pbsgpu_id_key_*), for Engine.sha256_keyed_many,
+    Engine.chunk_and_digest(id_key=) and Engine.blob_decode4(id_key=): SHA-256(content || id_key) is what an encrypted
+    backup's index calls a chunk. The bytes are not kept on the host; close() zeroes the device copy. The key keeps its engine
+    alive. Nothing is derived here: the caller brings the 32 bytes."""
+
+    def __init__(self, eng: "Engine", id_key: bytes):
+        if len(id_key) != 32:
+            raise ValueError("an id key is 32 bytes")
+        self._eng = eng
+        self._L = eng._L
+        h = C.c_void_p()
+        buf = (C.c_uint8 * 32).from_buffer_copy(bytes(id_key))
+        try:
+            check(self._L.pbsgpu_id_key_create(eng._h, buf, C.byref(h)), "id_key_create")
+        finally:
+            C.memset(buf, 0, 32)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pbsgpu_id_key_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __repr__(self):  # (never the key)
+        return "IdKey(<32 bytes>)"
 
 
 class KnownChunks:
